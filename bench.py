@@ -2,6 +2,16 @@
 """bench.py — OSC control steps/sec on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f64|mixed] [--batch B] [--layout k13|k7|k12_admit]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints ONE JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds per timed step, config).  Everything else the line can carry runs only with --full: the CPU baseline,
+the parity samples against the oracle, the other storage variant and the synthetic-records run, the sustained long leg, the
+per-kernel / untraced roofline timings, the path from joint coordinates, the end-to-end legs and the per-rank output checksums
+(the --no-* switches below then turn single legs off).  --dump-outputs DIR writes what the timed path computed in its last step,
+the torques u[B, n] and flags[B] a caller of irlosc_step_resident + irlosc_download receives, as DIR/u.npy and DIR/flags.npy
+(float64, or float32 for float32 records; flags as float64); over 64 MB in all, a fixed seeded sample of the instances, whose
+ids are DIR/index.npy.  The inputs depend on the arguments only, so two builds can be compared output for output.
 
 A "step" is one pass of the OSC hot path over one resident batch of B synthetic Dual-UR5 instances per GPU
 (default: B = 65 536, n = 25 joints, layout k13 = both arms xyz+abg and the base yaw, gravity and null-space
@@ -87,6 +97,28 @@ ROOFLINE_FIRST = ["bound", "achieved", "peak", "unit", "frac", "traffic", "frac_
                   "untraced_kernel_span_us", "untraced_period_us", "frac_from_kernel_span", "frac_from_period", "sclk_mhz", "kernel_ms",
                   "step_ms_events", "steps_per_launch", "whole_step_achieved", "algorithmic_bytes_per_launch",
                   "algorithmic_bytes_per_step_per_instance", "untraced_trains", "traffic_source", "rocprof_source", "kernel"]
+
+
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20241008
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write per-instance arrays (leading axis = instance) as out_dir/<name>.npy, float32 kept, everything else as float64.  When
+    they hold more than `max_bytes`, a fixed seeded sample of the instances is written instead, with their ids as index.npy.
+    -> the names written."""
+    conv = {k: np.asarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    B = next(iter(conv.values())).shape[0]
+    per_instance = sum(v[0].nbytes if B else 0 for v in conv.values())
+    if B and B * per_instance > max_bytes:
+        keep = max(1, max_bytes // (per_instance + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=keep, replace=False))
+        conv = {k: v[idx] for k, v in conv.items()}
+        conv["index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in conv.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(conv)
 
 
 def ordered_first(d, first):
@@ -582,6 +614,11 @@ def main():
     ap.add_argument("--no-from-q", action="store_true", help="skip the joint-coordinates path (front end + step)")
     ap.add_argument("--workload", default="physical", choices=["physical", "synthetic"],
                     help="physical: records of random joint states from the front end (tree zeros); synthetic: random dense SPD M")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: CPU baseline, parity samples, secondary modes, sustained leg, roofline "
+                         "timings, joint-coordinates path, end-to-end legs, output checksums")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step (u, flags) as DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--mint-physical", default=None, help=argparse.SUPPRESS)   # internal: write slot 0 of the physical workload to this directory
     ap.add_argument("--as-rank", type=int, default=-1, help=argparse.SUPPRESS)  # internal: seed the data like this rank (the minting child of rank 0)
     args = ap.parse_args()
@@ -613,10 +650,10 @@ def main():
         arr_ = {k: np.concatenate([p_[2][k] for p_ in parts], axis=0) for k in parts[0][2]} if S > 1 else parts[0][2]
         return lay_, gains_, arr_
 
-    def fill_physical(osc, lay, dt, s, model):
+    def fill_physical(osc, lay, dt, s, model, keep_slot0=True):
         """Slot s of the physical workload: random joint states -> front end (records stay in HBM) -> targets around the end
         effectors it found (-> wrench for the admittance layout, which only arrives with an upload of records).  Returns
-        slot 0's records as host arrays (what the oracle legs are run on), None for the other slots."""
+        slot 0's records as host arrays (what the oracle legs are run on), None for the other slots and when not keep_slot0."""
         rngs = [np.random.default_rng(20241008 + 1000 * 2 + 17 * s + 101 * vrank(j) + 500000) for j in range(S)]
         st = [model.random_state(r_, Bs) for r_ in rngs]
         qpos, qvel = np.concatenate([x_[0] for x_ in st]), np.concatenate([x_[1] for x_ in st])
@@ -627,20 +664,20 @@ def main():
         wrench = (np.concatenate([rngs[j].normal(0.0, 5.0, size=(Bs, lay.ndev, 6)) for j in range(S)]).astype(dt)
                   if lay.admittance else None)
         rec = None
-        if wrench is not None or s == 0:
+        if wrench is not None or (s == 0 and keep_slot0):
             rec = osc.download_records(s)
         if wrench is not None:
             osc.upload(rec["M"], rec["J"], rec["dq"], rec["bias"], rec["ee_pose"], wrench, slot=s)
         osc.set_targets(tgt, None, slot=s)
-        if s != 0:
+        if s != 0 or not keep_slot0:
             return None
         rec["tgt_pose"] = tgt
         if wrench is not None:
             rec["wrench"] = wrench
         return rec
 
-    def fill_slots(osc, lay, mode, workload):
-        """-> (gains, slot 0 as host arrays)."""
+    def fill_slots(osc, lay, mode, workload, keep_slot0=True):
+        """-> (gains, slot 0 as host arrays; None for the physical workload when not keep_slot0)."""
         dt = MODES[mode][0]
         slot0 = None
         if workload == "physical":
@@ -650,7 +687,7 @@ def main():
             _, gains, _ = synth.make_batch(args.layout, 2, seed=1, dtype=dt)       # the YAML gain set of the layout
             osc.set_gains(gains["kp"], gains["kv"], gains["ko"], gains["k"], gains["d"], gains["max_vel"], gains["null_kv"])
             for s in range(args.slots):
-                r = fill_physical(osc, lay, dt, s, model)
+                r = fill_physical(osc, lay, dt, s, model, keep_slot0)
                 slot0 = r if s == 0 else slot0
             return gains, slot0
         for s in range(args.slots):
@@ -678,14 +715,16 @@ def main():
             np.save(os.path.join(args.mint_physical, k2 + ".npy"), v)
         return
 
-    def measure(mode, steps, warmup, preroll, workload, long_leg=True):
+    def measure(mode, steps, warmup, preroll, workload, long_leg=True, full=True, dump_dir=None):
+        """full=False: the headline alone (set-up, preroll, warm-up, the timed steps, the dump) -> res without roofline / sustained /
+        checksums, and no host copy of slot 0."""
         dt, arith, kern = MODES[mode]
         if args.kernel >= 0:
             kern = args.kernel
         esz = np.dtype(dt).itemsize
         lay = synth.make_layout(args.layout)
         osc = BatchedOSC(lay, B, dtype=dt, hip_device=local_rank, n_slots=args.slots, kernel=kern)
-        gains, slot0 = fill_slots(osc, lay, mode, workload)
+        gains, slot0 = fill_slots(osc, lay, mode, workload, keep_slot0=full)
         if preroll > 0:                                          # untimed: lets the clocks settle after the idle set-up
             osc.step_resident(preroll)
         if warmup > 0:
@@ -701,6 +740,17 @@ def main():
             comm.barrier()
         elapsed = time.perf_counter() - t0
         total_steps, elapsed, rate = sharding.reduce_throughput(B * steps, elapsed, comm)
+        if dump_dir is not None and rank == 0:        # irlosc_download yields the outputs of the LAST step of the timed region
+            u_last, fl_last = osc.download(B)
+            dump_outputs(dump_dir, {"u": u_last, "flags": fl_last})
+            del u_last, fl_last
+        if not full:
+            tree = all(osc.slot_structure(sl) for sl in range(args.slots))
+            res = dict(value=rate, ms_per_step=elapsed / steps * 1e3, kernel=osc.kernel_name + ("+tree" if tree else ""), mode=mode,
+                       arith=arith, records="float64" if esz == 8 else "float32", layout=lay, workload=workload,
+                       steps_per_launch=osc.steps_per_launch)
+            osc.close()
+            return res, (lay, gains, slot0, None, None)
         # the same bracket over a LONG run (the driver's command times 20 steps = 2 ms; this is the figure that does not depend on
         # how the first milliseconds went): not `value`, reported beside it
         sustained = None
@@ -775,7 +825,8 @@ def main():
                         frac_rocprof=roof["committed_profile"]["frac_rocprof"],
                         rocprof_source="profiles/hbm_traffic.json (committed kernel trace of this command on another box; not measured in this run)")
         res = dict(value=rate, ms_per_step=elapsed / steps * 1e3, kernel=kname, mode=mode, arith=arith,
-                   records="float64" if esz == 8 else "float32", layout=lay, roofline=roof, workload=workload, sustained=sustained)
+                   records="float64" if esz == 8 else "float32", layout=lay, roofline=roof, workload=workload, sustained=sustained,
+                   steps_per_launch=spl)
         osc.step(slot=0)
         u, fl = osc.download(B)
         res["giveups"] = int(osc.giveup_counts()[0])
@@ -786,10 +837,10 @@ def main():
 
     # CPU legs first: their worker processes are forked before this process has initialised the HIP runtime
     cb = ref = ref_idx = fq_state = fq_ref = None
-    others = [m for m in ("f64", "mixed") if m != args.dtype] if (world == 1 and not args.no_secondary) else []
+    others = [m for m in ("f64", "mixed") if m != args.dtype] if (world == 1 and args.full and not args.no_secondary) else []
     NSEC = 4096                       # instances of slot 0 the secondary modes are checked on (oracle in this process)
     minted_crc = None
-    if rank == 0 and not args.no_cpu_baseline:          # N > 1 too: rank 0's host cores, rank 0's shard (the other ranks wait in make_comm)
+    if args.full and rank == 0 and not args.no_cpu_baseline:     # N > 1 too: rank 0's host cores, rank 0's shard (the other ranks wait in make_comm)
         if args.workload == "physical":
             # The records of the physical workload come from the GPU front end, and the CPU legs fork their workers before
             # THIS process touches the HIP runtime: a child process computes slot 0 (same seeds, same kernel: the same bits,
@@ -844,7 +895,8 @@ def main():
                 print(f"bench.py: --require-rccl, but the ranks fell back: {comm_note}", file=sys.stderr, flush=True)
             comm.close()
             sys.exit(3)
-    primary, chk = measure(args.dtype, args.steps, args.warmup, preroll=args.preroll, workload=args.workload)
+    primary, chk = measure(args.dtype, args.steps, args.warmup, preroll=args.preroll, workload=args.workload, full=args.full,
+                           dump_dir=args.dump_outputs)
     if minted_crc is not None and sharding.checksum_u64(chk[2]["M"]) != minted_crc:
         raise RuntimeError("slot 0 of the physical workload differs between the minting process and this one")
     lay = primary.pop("layout")
@@ -867,21 +919,22 @@ def main():
                    "instances_per_gpu": B, "layout": args.layout, "k": lay.k, "ndev": lay.ndev,
                    "admittance": bool(lay.admittance), "records": primary["records"], "arithmetic": primary["arith"],
                    "kernel": primary["kernel"], "records_from": args.workload, "preroll_steps": args.preroll,
-                   "steps_per_launch": primary["roofline"]["steps_per_launch"],
+                   "steps_per_launch": primary["steps_per_launch"], "full": args.full,
                    "sharding": f"{world} x independent shards, no data-path collective; barrier and final sum(steps) / "
                                f"max(elapsed) reduction: {comm_note}",
                    "rccl_ranks": (world if isinstance(comm, sharding.RcclComm) else 0) if world > 1 else None,
                    "slices_per_rank": S},
-        "roofline": primary["roofline"],
-        "sustained": primary["sustained"],
     }
-    # per-rank checksum of one step's outputs on slot 0 (rank r's data depend on r only, so its checksum must be the
-    # same in the 1-, 2-, 4- and 8-GPU runs: sharding changes no bit)
-    out["rank_checksums"] = [f"{v:016x}" for v in (comm.allgather_u64(primary["checksum"]) if comm else [primary["checksum"]])]
-    # slice_checksums[r][j] = sub-batch j ("virtual rank" r * S + j) of rank r: equal across every way of cutting the same total batch
-    cols = [(comm.allgather_u64(c_) if comm else [c_]) for c_ in primary["slice_checksums"]]
-    out["slice_checksums"] = [[f"{cols[j][r]:016x}" for j in range(S)] for r in range(world)]
-    if rank == 0:
+    if args.full:
+        out["roofline"] = primary["roofline"]
+        out["sustained"] = primary["sustained"]
+        # per-rank checksum of one step's outputs on slot 0 (rank r's data depend on r only, so its checksum must be the
+        # same in the 1-, 2-, 4- and 8-GPU runs: sharding changes no bit)
+        out["rank_checksums"] = [f"{v:016x}" for v in (comm.allgather_u64(primary["checksum"]) if comm else [primary["checksum"]])]
+        # slice_checksums[r][j] = sub-batch j ("virtual rank" r * S + j) of rank r: equal across every way of cutting the same total batch
+        cols = [(comm.allgather_u64(c_) if comm else [c_]) for c_ in primary["slice_checksums"]]
+        out["slice_checksums"] = [[f"{cols[j][r]:016x}" for j in range(S)] for r in range(world)]
+    if args.full and rank == 0:
         lay_, gains, arr, u, fl = chk
         out["flags"] = {"eigen_path_frac": float(((fl & 4) != 0).mean()), "pinv_branch_frac": float(((fl & 2) != 0).mean()),
                         "truncated_frac": float(((fl & 8) != 0).mean()), "nonfinite_frac": float(((fl & 64) != 0).mean()),
@@ -923,9 +976,9 @@ def main():
             out["synthetic_dense_records"] = {"metric": "OSC control steps/sec on synthetic dense records (random SPD M without the tree's zeros)",
                                               "value": e_["value"], "ms_per_step": e_["ms_per_step"], "kernel": e_["kernel"],
                                               "roofline_frac": e_["roofline"]["frac"]}
-    if world == 1 and not args.no_from_q:
+    if world == 1 and args.full and not args.no_from_q:
         out["from_q"] = measure_from_q(BatchedOSC, synth, args, B, local_rank, fq_state, fq_ref)
-    if world == 1 and rank == 0 and not args.no_end_to_end:
+    if world == 1 and rank == 0 and args.full and not args.no_end_to_end:
         lay_, gains_, arr_ = chk[0], chk[1], chk[2]
         out["end_to_end"] = measure_end_to_end(BatchedOSC, lay_, gains_, arr_, MODES[args.dtype][0],
                                                args.kernel if args.kernel >= 0 else MODES[args.dtype][2], local_rank)
@@ -970,7 +1023,8 @@ def main():
     # The driver's record keeps the first 24 keys of `config` and of `roofline`: the evidence scalars go first, the prose last
     # (tests/test_bench_host.py::test_evidence_scalars_lead_the_line).
     out["config"] = ordered_first(cfgd, CONFIG_FIRST)
-    out["roofline"] = ordered_first(out["roofline"], ROOFLINE_FIRST)
+    if "roofline" in out:
+        out["roofline"] = ordered_first(out["roofline"], ROOFLINE_FIRST)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if comm:

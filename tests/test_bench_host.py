@@ -111,3 +111,31 @@ def test_evidence_scalars_lead_the_line():
     for must in ("bound", "achieved", "peak", "unit", "frac", "traffic", "frac_rocprof", "untraced_kernel_span_us", "untraced_period_us"):
         assert got.index(must) < 24, must
     assert got.index("untraced") >= len(bench.ROOFLINE_FIRST)            # the nested dicts trail
+
+
+def test_dump_outputs_dtypes_and_the_64_mb_cap(tmp_path):
+    """--dump-outputs: float32 stays float32, everything else (float64 torques, uint32 flags) is written as float64; over the cap a
+    fixed seeded sample of the instances is written, the same one every time, with the instance ids as index.npy."""
+    rng = np.random.default_rng(3)
+    u, fl, u32 = rng.normal(size=(1000, 25)), rng.integers(0, 64, 1000).astype(np.uint32), rng.normal(size=(1000, 25)).astype(np.float32)
+    assert bench.dump_outputs(tmp_path / "a", {"u": u, "flags": fl}) == ["flags", "u"]
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in ("u", "flags")}
+    assert a["u"].dtype == np.float64 and np.array_equal(a["u"], u) and a["flags"].dtype == np.float64 and np.array_equal(a["flags"], fl)
+    bench.dump_outputs(tmp_path / "b", {"u": u32})
+    assert np.load(tmp_path / "b" / "u.npy").dtype == np.float32
+    cap = 100 * (25 * 8 + 8 + 8)                                     # room for 100 instances of u + flags + their ids
+    for d in ("c", "d"):
+        assert bench.dump_outputs(tmp_path / d, {"u": u, "flags": fl}, max_bytes=cap) == ["flags", "index", "u"]
+    c = {k: np.load(tmp_path / "c" / (k + ".npy")) for k in ("u", "flags", "index")}
+    assert sum(v.nbytes for v in c.values()) <= cap and c["u"].shape == (100, 25) and c["index"].dtype == np.float64
+    idx = c["index"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(c["u"], u[idx]) and np.array_equal(c["flags"], fl[idx])
+    assert np.array_equal(np.load(tmp_path / "d" / "index.npy"), c["index"])
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+
+
+def test_plain_run_options():
+    """--full (off by default) and --dump-outputs are on the command line; --help needs no GPU."""
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

@@ -689,7 +689,7 @@ def _bench_line(extra_args, env_extra, launcher):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["bench.py", "--steps", "16", "--warmup", "8", "--preroll", "0", "--batch", "2048", "--no-cpu-baseline",
+    args = ["bench.py", "--full", "--steps", "16", "--warmup", "8", "--preroll", "0", "--batch", "2048", "--no-cpu-baseline",
             "--no-secondary", "--no-from-q", "--sustained-steps", "4000"] + extra_args
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(env_extra)
@@ -738,7 +738,7 @@ def test_bench_line_with_the_cpu_legs_on_the_physical_workload(fail_hand_over):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     if fail_hand_over:
         env["IRLOSC_BENCH_FAIL_MINT"] = "1"
-    cmd = [sys.executable, "bench.py", "--steps", "16", "--warmup", "8", "--preroll", "0", "--batch", "4096", "--cpu-seconds", "0.5",
+    cmd = [sys.executable, "bench.py", "--full", "--steps", "16", "--warmup", "8", "--preroll", "0", "--batch", "4096", "--cpu-seconds", "0.5",
            "--no-secondary", "--no-from-q", "--sustained-steps", "4000"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -1710,8 +1710,9 @@ def test_time_trains_spans_and_periods_are_consistent():
     osc.close()
 
 
-def _bench_run(args, env_extra, timeout=1500):
-    """bench.py in a child process with exactly `args` -> (return code, parsed JSON line or None, number of JSON lines, stderr)."""
+def _bench_run(args, env_extra, timeout=1500, full=True):
+    """bench.py in a child process with `args` (+ --full unless full=False) -> (return code, parsed JSON line or None, number of JSON
+    lines, stderr)."""
     import json
     import os
     import subprocess
@@ -1719,11 +1720,46 @@ def _bench_run(args, env_extra, timeout=1500):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env.update(env_extra)
-    if "--sustained-steps" not in args:      # (bench.py's default long leg is ~10 s at the headline batch: the tests ask for a short one)
-        args = list(args) + ["--sustained-steps", "8000"]
+    if full:
+        args = ["--full"] + list(args)
+        if "--sustained-steps" not in args:      # (bench.py's default long leg is ~10 s at the headline batch: the tests ask for a short one)
+            args = list(args) + ["--sustained-steps", "8000"]
     p = subprocess.run([sys.executable, "bench.py"] + args, cwd=root, env=env, capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     return p.returncode, (json.loads(lines[-1]) if lines else None), len(lines), p.stderr
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run is the headline alone: the timed steps and one line with metric / value / unit / higher_is_better / dtype /
+    ms_per_step, none of the --full legs.  --dump-outputs writes the outputs of the LAST timed step: the same bits from a --full run
+    with the same arguments, and (synthetic records, 2 slots, 16 steps: the last step ran on slot 1) the oracle's torques on slot 1's
+    inputs."""
+    import os
+    common = ["--steps", "16", "--warmup", "8", "--preroll", "0", "--batch", "2048", "--slots", "2", "--workload", "synthetic"]
+    rc, plain, n, err = _bench_run(common + ["--dump-outputs", str(tmp_path / "plain")], {}, full=False)
+    assert rc == 0 and n == 1, err[-2000:]
+    assert plain["metric"] == "OSC control steps/sec" and plain["unit"] == "steps/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "f64" and plain["steps"] == 16 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert abs(plain["value"] * plain["ms_per_step"] * 1e-3 - 2048) < 1e-6 * 2048        # value = B / (ms_per_step in s)
+    assert plain["config"]["full"] is False and plain["config"]["steps_per_launch"] >= 1
+    for leg in ("roofline", "sustained", "cpu_baseline", "parity_sample", "secondary", "from_q", "end_to_end", "rank_checksums"):
+        assert leg not in plain, leg
+    rc, full, n, err = _bench_run(common + ["--dump-outputs", str(tmp_path / "full"), "--sustained-steps", "0", "--no-cpu-baseline",
+                                            "--no-secondary", "--no-from-q", "--no-end-to-end"], {})
+    assert rc == 0 and n == 1, err[-2000:]
+    assert full["config"]["full"] is True and "roofline" in full and "rank_checksums" in full
+    got = {d: {f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))} for d in ("plain", "full")}
+    assert sorted(got["plain"]) == ["flags", "u"] and got["plain"]["u"].shape == (2048, 25) and got["plain"]["flags"].shape == (2048,)
+    assert got["plain"]["u"].dtype == np.float64 and got["plain"]["flags"].dtype == np.float64
+    for k in ("u", "flags"):
+        assert np.array_equal(got["plain"][k], got["full"][k]), k
+    lay, gains, g = synth.make_batch("k13", 2048, seed=20241008 + 2000 + 17 * 1)        # bench.py's synthetic slot 1 of rank 0
+    n = 256
+    g = {k: (v[:n] if isinstance(v, np.ndarray) else v) for k, v in g.items()}
+    ref = osc_oracle.generate_batch(lay.as_oracle_dict(), gains, g["M"], g["J"], g["dq"], g["bias"], g["ee_pose"], g["tgt_pose"],
+                                    g.get("wrench"), g.get("tgt_vel"))
+    dom = np.array([in_parity_domain(*osc_oracle.task_inertia(g["J"][b], g["M"][b])[2:]) for b in range(n)])
+    assert dom.sum() > n // 2 and rel_err(got["plain"]["u"][:n], ref)[dom].max() <= TOL64
 
 
 def test_bench_config3_eight_ranks_dry_run_on_one_device():
