@@ -39,27 +39,18 @@ struct irlosc_ctx {
     std::vector<int> has_wrench, has_tvel;
     std::vector<int> uploaded, targeted;    // instances of the slot that hold state / targets (0 = nothing yet, -1 = an empty batch)
     std::vector<int> fused_away;            // 1: the slot's dense records were invalidated by a fused step from joint coordinates (error text only)
-    // Output sets (u, flags): step i of a row16 train writes set i; the generic path only ever uses set 0.
-    static constexpr int NSETS_MAX = R16_TRAIN;
-    int nsets = 1;
+    int nsets = 1;                     // output sets of bank 0: step i of a row16 train writes set i; the generic path only ever uses set 0
     int train = 1;                     // steps per launch in irlosc_step_resident
-    void* du_set[NSETS_MAX] = {};
-    uint32_t* dflags_set[NSETS_MAX] = {};
-    int cur = 0;                       // output set written by the most recent step
     hipEvent_t tev_begin = nullptr, tev_end = nullptr;   // timing events handed to the next train launch (or null)
     unsigned long long* dspan = nullptr;   // irlosc_time_trains: [ntrains][2] wall-clock stamps written by the kernels
     int dspan_cap = 0;
     unsigned long long* span_next = nullptr;   // the pair the next train launch stamps (or null)
     std::vector<hipEvent_t> tev_pool;
-    void* du = nullptr;                // = du_set[cur]
-    uint32_t* dflags = nullptr;        // = dflags_set[cur]
+    void* du = nullptr;                // output set written by the most recent step
+    uint32_t* dflags = nullptr;
     void* draw = nullptr;     // staging for irlosc_upload_raw (raw simulator arrays), grown on demand
     size_t draw_bytes = 0;
-    // fp64 row16 path: zero page for the padding lanes, worklist of the instances handed to the generic kernel, and
-    // two counters used alternately (the worklist pass of a step zeroes the counter of the next one)
-    void* dzeros = nullptr;
-    int32_t* dr16_list[R16_TRAIN] = {};    // give-up list of each step of a train
-    int32_t* dr16_count = nullptr;         // [R16_TRAIN] give-up counters, zeroed in front of every train
+    void* dzeros = nullptr;            // fp64 row16 path: zero page for the padding lanes
     // rigid-body front end (irlosc_set_model): device copy of the tables, resident joint coordinates per slot
     FeModel* dmodel = nullptr;
     size_t fe_smem = 0;
@@ -70,44 +61,40 @@ struct irlosc_ctx {
     // buffer and one buffer per step of a train
     FeCompactTables* dtables = nullptr;
     size_t fe_xentries = 0;
-    double* fe_xside[R16_TRAIN] = {};
-    double* dtrows[R16_TRAIN] = {};        // row16 path on dense records: task rows of each step of a train (osc_task_rows_dense_kernel);
-                                           // allocated by the first train that needs them (ensure_trows)
     int task_pass = 1;                     // IRLOSC_TASK_PASS=0: part 1 of the task signal in the row16 kernel (A/B, tests)
     int fused = 0;
-    int fused_train = R16_TRAIN;
-    // the OSC step of the fused path in lane-per-robot form (osc_lane.hpp): the instantiation that holds the layout (-1: none: the row16
-    // FROMQ kernel stays), its row map, the records + counters of the eigen pass behind it (allocated by the first fused step)
-    // Consecutive trains of irlosc_step_resident_from_q rotate over BANKS of buffers (exchange buffers, eigen-pass records, counters,
-    // give-up lists, output sets), each on a stream of its own: the walk and the lane kernel run one wave per SIMD, eight waves deep per
-    // train, so every kernel boundary leaves SIMDs idle for up to a wave's lifetime (~50 us) -- measured as a fixed ~126 us per train of
-    // 990 us (trains of 8 / 4 / 2 steps: 124 / 140 / 163 us per step).  With the NEXT trains independent and on other streams their first
-    // waves fill those tails (two banks: 60 us of the 126 left; three: ~45).  Bank 0 = the buffers above on `stream`; the others are
-    // allocated by the first call that chains that many trains.
+    // Consecutive trains of irlosc_step_resident_from_q / irlosc_step_resident rotate over BANKS of buffers, each on a stream of its own:
+    // the walk and the lane kernel run one wave per SIMD, eight waves deep per train, so every kernel boundary leaves SIMDs idle for up to
+    // a wave's lifetime (~50 us) -- measured as a fixed ~126 us per train of 990 us (trains of 8 / 4 / 2 steps: 124 / 140 / 163 us per
+    // step).  With the NEXT trains independent and on other streams their first waves fill those tails (two banks: 60 us of the 126
+    // left; three: ~45).  Bank 0 is the context's own, on `stream`: its output sets, give-up lists and counters come with the context
+    // (create_impl) and serve single steps too.  The other banks, and every bank's per-step buffers of the task pass, the fused path's
+    // exchange buffers and the lane form's records, are allocated by the first call that needs them (ensure_bank).
     struct Bank {
         hipStream_t st = nullptr;
         hipEvent_t done = nullptr;
-        double* xside[R16_TRAIN] = {};
-        double* lane_rec[R16_TRAIN] = {};
-        int32_t* lane_count = nullptr;
-        int32_t* list[R16_TRAIN] = {};
-        int32_t* count = nullptr;
-        void* u[R16_TRAIN] = {};
+        void* u[R16_TRAIN] = {};           // output sets
         uint32_t* flags[R16_TRAIN] = {};
-        double* trows[R16_TRAIN] = {};     // (dense-record trains: rows of the task pass)
+        int32_t* list[R16_TRAIN] = {};     // give-up list of each step of a train
+        int32_t* count = nullptr;          // [R16_TRAIN] give-up counters, zeroed in front of every train
+        double* trows[R16_TRAIN] = {};     // dense-record trains: task rows of each step (osc_task_rows_dense_kernel)
+        double* xside[R16_TRAIN] = {};     // fused path: compact exchange buffer of each step ...
+        size_t xentries = 0;               // ... sized for this many entries
+        double* lane_rec[R16_TRAIN] = {};  // lane form of the fused path: eigen-pass records of each step, and their counters
+        int32_t* lane_count = nullptr;
     };
-    static constexpr int MAX_XBANKS = 3;   // banks beside the context's own: trains of the fused path rotate over 1 + fq_xbanks of them
-    Bank xb[MAX_XBANKS];
-    int fq_xbanks = 2;                     // IRLOSC_FQ_BANKS = 2 .. 4 banks in all (default 3: k13 6.88 -> 7.00e8, four: 7.03e8, +2.4 GB each); the dense-record trains use xb[0] only
+    static constexpr int FQ_BANKS = 3;     // banks of the fused path's trains (k13 6.88 -> 7.00e8 against two; four: 7.03e8, +2.4 GB each)
+    static constexpr int R16_BANKS = 2;    // banks of the dense-record trains (a third was a cache artefact of a four-slot bench)
+    static constexpr int MAX_XBANKS = FQ_BANKS - 1;
+    Bank bank[1 + MAX_XBANKS];
     hipEvent_t ev_join = nullptr;
     int fq_overlap = 1;                    // IRLOSC_FQ_OVERLAP=0: one bank, one stream (A/B measurements, tests)
     int r16_overlap = 1;                   // IRLOSC_R16_OVERLAP=0: the same switch for the trains of irlosc_step_resident on dense records
-    int r16_xbanks = 1;                    // IRLOSC_R16_BANKS = 2 .. 4 banks in all for those trains (default 2)
     int32_t* count_cur = nullptr;          // give-up counters of the most recent train (irlosc_giveup_counts)
+    // the OSC step of the fused path in lane-per-robot form (osc_lane.hpp): the instantiation that holds the layout (-1: none: the row16
+    // FROMQ kernel stays) and its row map
     int lane_tier = -1;
     lane::RowMap lane_map{};
-    double* lane_rec[R16_TRAIN] = {};
-    int32_t* dlane_count = nullptr;        // [R16_TRAIN]
     std::vector<double*> dqpos, dqvel;
     std::vector<double*> dqt;          // per slot: the same coordinates in the fused walk's layout [wave][2 n][64 robots] (irlosc_upload_q writes both)
     std::vector<int> has_q;
@@ -203,36 +190,35 @@ static int validate(const irlosc_cfg* c, int* k_out) {
     return IRLOSC_OK;
 }
 
+// What a train needs of its bank beside the output sets, give-up lists and counters (irlosc_ctx::Bank, ensure_bank)
+enum : unsigned { NEED_ROWS = 1, NEED_X = 2, NEED_LANE = 4, BANK_ALL = ~0u };
+
+// Frees the buffers of `b` that `what` names (BANK_ALL: every buffer of the bank; its stream and event stay).
+static void free_bank(irlosc_ctx::Bank& b, unsigned what) {
+    auto fr = [](auto*& p) { if (p) (void)hipFree(p); p = nullptr; };
+    for (int i = 0; i < R16_TRAIN; ++i) {
+        if (what & NEED_ROWS) fr(b.trows[i]);
+        if (what & NEED_X) fr(b.xside[i]);
+        if (what & NEED_LANE) fr(b.lane_rec[i]);
+        if (what == BANK_ALL) { fr(b.u[i]); fr(b.flags[i]); fr(b.list[i]); }
+    }
+    if (what & NEED_LANE) fr(b.lane_count);
+    if (what == BANK_ALL) fr(b.count);
+}
+
 static void free_all(irlosc_ctx* c) {
     auto fr = [](std::vector<void*>& v) { for (void* p : v) if (p) (void)hipFree(p); v.clear(); };
     fr(c->dM); fr(c->dJ); fr(c->ddq); fr(c->dbias); fr(c->dee); fr(c->dwrench); fr(c->dtgt); fr(c->dtvel);
-    for (int k = 0; k < irlosc_ctx::NSETS_MAX; ++k) {
-        if (c->du_set[k]) (void)hipFree(c->du_set[k]);
-        if (c->dflags_set[k]) (void)hipFree(c->dflags_set[k]);
-    }
     if (c->draw) (void)hipFree(c->draw);
     if (c->dmodel) (void)hipFree(c->dmodel);
     if (c->fe_side) (void)hipFree(c->fe_side);
     if (c->dtables) (void)hipFree(c->dtables);
-    for (int k = 0; k < R16_TRAIN; ++k) if (c->fe_xside[k]) (void)hipFree(c->fe_xside[k]);
-    for (int k = 0; k < R16_TRAIN; ++k) if (c->dtrows[k]) (void)hipFree(c->dtrows[k]);
-    for (int k = 0; k < R16_TRAIN; ++k) if (c->lane_rec[k]) (void)hipFree(c->lane_rec[k]);
-    for (irlosc_ctx::Bank& bk : c->xb) {
-        for (int k = 0; k < R16_TRAIN; ++k) {
-            if (bk.xside[k]) (void)hipFree(bk.xside[k]);
-            if (bk.lane_rec[k]) (void)hipFree(bk.lane_rec[k]);
-            if (bk.list[k]) (void)hipFree(bk.list[k]);
-            if (bk.u[k]) (void)hipFree(bk.u[k]);
-            if (bk.flags[k]) (void)hipFree(bk.flags[k]);
-            if (bk.trows[k]) (void)hipFree(bk.trows[k]);
-        }
-        if (bk.lane_count) (void)hipFree(bk.lane_count);
-        if (bk.count) (void)hipFree(bk.count);
+    for (irlosc_ctx::Bank& bk : c->bank) {
+        free_bank(bk, BANK_ALL);
         if (bk.done) (void)hipEventDestroy(bk.done);
-        if (bk.st) (void)hipStreamDestroy(bk.st);
+        if (bk.st && bk.st != c->stream) (void)hipStreamDestroy(bk.st);
     }
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->dlane_count) (void)hipFree(c->dlane_count);
     for (double* p : c->dqpos) if (p) (void)hipFree(p);
     for (double* p : c->dqvel) if (p) (void)hipFree(p);
     for (double* p : c->dqt) if (p) (void)hipFree(p);
@@ -241,8 +227,6 @@ static void free_all(irlosc_ctx* c) {
     if (c->tick_hout) (void)hipHostFree(c->tick_hout);
     if (c->tick_dout) (void)hipFree(c->tick_dout);
     if (c->dzeros) (void)hipFree(c->dzeros);
-    for (int k = 0; k < R16_TRAIN; ++k) if (c->dr16_list[k]) (void)hipFree(c->dr16_list[k]);
-    if (c->dr16_count) (void)hipFree(c->dr16_count);
     if (c->dsym) (void)hipFree(c->dsym);
     if (c->dspan) (void)hipFree(c->dspan);
     if (c->dstruct) (void)hipFree(c->dstruct);
@@ -286,30 +270,31 @@ static int create_impl(irlosc_ctx* c) {
         c->train = R16_TRAIN;
         c->nsets = R16_TRAIN;               // a train completes (give-up pass included) before the next one starts
     }
+    irlosc_ctx::Bank& b0 = c->bank[0];
+    b0.st = c->stream;
     for (int k2 = 0; k2 < c->nsets; ++k2) {
-        HIPCHK(nullptr, hipMalloc(&c->du_set[k2], B * n * e));
-        HIPCHK(nullptr, hipMalloc((void**)&c->dflags_set[k2], B * sizeof(uint32_t)));
-        HIPCHK(nullptr, hipMemsetAsync(c->dflags_set[k2], 0, B * sizeof(uint32_t), c->stream));
+        HIPCHK(nullptr, hipMalloc(&b0.u[k2], B * n * e));
+        HIPCHK(nullptr, hipMalloc((void**)&b0.flags[k2], B * sizeof(uint32_t)));
+        HIPCHK(nullptr, hipMemsetAsync(b0.flags[k2], 0, B * sizeof(uint32_t), c->stream));
     }
     if (c->kernel == IRLOSC_KERNEL_ROW16) {
         constexpr size_t ZB = 64 * 1024;
         HIPCHK(nullptr, hipMalloc(&c->dzeros, ZB));
         HIPCHK(nullptr, hipMemsetAsync(c->dzeros, 0, ZB, c->stream));
-        for (int k2 = 0; k2 < R16_TRAIN; ++k2) HIPCHK(nullptr, hipMalloc((void**)&c->dr16_list[k2], B * sizeof(int32_t)));
-        HIPCHK(nullptr, hipMalloc((void**)&c->dr16_count, R16_TRAIN * sizeof(int32_t)));
+        for (int k2 = 0; k2 < R16_TRAIN; ++k2) HIPCHK(nullptr, hipMalloc((void**)&b0.list[k2], B * sizeof(int32_t)));
+        HIPCHK(nullptr, hipMalloc((void**)&b0.count, R16_TRAIN * sizeof(int32_t)));
         {   // part 1 of the task signal runs as a pass ahead of the row16 kernel (IRLOSC_TASK_PASS=0: in the kernel; A/B, tests); its
-            // rows buffers are allocated by the first train that needs them (ensure_trows)
+            // rows buffers are allocated by the first train that needs them (ensure_bank)
             const char* e = getenv("IRLOSC_TASK_PASS");
             c->task_pass = !(e && !strcmp(e, "0"));
             const char* ov = getenv("IRLOSC_R16_OVERLAP");
             c->r16_overlap = !(ov && !strcmp(ov, "0"));
-            const char* nb = getenv("IRLOSC_R16_BANKS");
-            c->r16_xbanks = std::max(1, std::min(nb ? atoi(nb) : 2, 1 + irlosc_ctx::MAX_XBANKS)) - 1;
         }
-        HIPCHK(nullptr, hipMemsetAsync(c->dr16_count, 0, R16_TRAIN * sizeof(int32_t), c->stream));
+        HIPCHK(nullptr, hipMemsetAsync(b0.count, 0, R16_TRAIN * sizeof(int32_t), c->stream));
     }
-    c->du = c->du_set[0];
-    c->dflags = c->dflags_set[0];
+    c->du = b0.u[0];
+    c->dflags = b0.flags[0];
+    c->count_cur = b0.count;
     HIPCHK(nullptr, hipMalloc((void**)&c->dsym, 2 * sizeof(int32_t)));
     HIPCHK(nullptr, hipMalloc((void**)&c->dstruct, sizeof(int32_t)));
     c->tree_ok.assign(c->cfg.n_slots, 0);
@@ -753,52 +738,79 @@ static void fill_params(const irlosc_ctx* c, KParams<T>& p, int B, const void* M
     }
 }
 
+// *p = a new device buffer of `bytes` (zeroed on `zero_on` when given), unless it holds one already.  -> false: out of device memory.
+template <typename P>
+static bool dev_alloc(P*& p, size_t bytes, hipStream_t zero_on = nullptr) {
+    if (p) return true;
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) == hipSuccess && (!zero_on || hipMemsetAsync(q, 0, bytes, zero_on) == hipSuccess)) {
+        p = (P*)q;
+        return true;
+    }
+    (void)hipFree(q);
+    (void)hipGetLastError();
+    return false;
+}
+
+// Bank k ready for trains of up to n steps that need `need`: task rows (8 MB per step at 65 536 instances), exchange buffers (334 entries
+// x 512 B per 64 robots: 175 MB per step), lane records (one per robot and step for the eigen pass, whole groups of 64: all of a batch may
+// be flagged) -- and, beside bank 0, the bank's own stream, event, output sets, give-up lists and counters.  Allocated on first use and
+// kept, so a context pays only for the trains it runs.  -> 0, or what could not be allocated (BANK_ALL: the bank's own buffers); the
+// caller decides what follows.
+static unsigned ensure_bank(irlosc_ctx* c, int k, int n, unsigned need) {
+    irlosc_ctx::Bank& b = c->bank[k];
+    const size_t Bm = (size_t)c->cfg.max_batch, waves = (Bm + 63) / 64;
+    if (k > 0) {
+        bool ok = (b.st || hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking) == hipSuccess) &&
+                  (b.done || hipEventCreateWithFlags(&b.done, hipEventDisableTiming) == hipSuccess) &&
+                  (c->ev_join || hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess) &&
+                  dev_alloc(b.count, R16_TRAIN * sizeof(int32_t));
+        for (int i = 0; ok && i < n; ++i)
+            ok = dev_alloc(b.list[i], Bm * sizeof(int32_t)) && dev_alloc(b.u[i], Bm * c->cfg.n * c->esz) && dev_alloc(b.flags[i], Bm * sizeof(uint32_t));
+        if (!ok) { (void)hipGetLastError(); return BANK_ALL; }
+    }
+    if (need & NEED_ROWS)
+        for (int i = 0; i < n; ++i) if (!dev_alloc(b.trows[i], Bm * 16 * sizeof(double))) return NEED_ROWS;
+    if (need & NEED_X) {
+        if (b.xentries != c->fe_xentries) free_bank(b, NEED_X);          // sized for another model's entries
+        b.xentries = c->fe_xentries;
+        for (int i = 0; i < n; ++i) if (!dev_alloc(b.xside[i], waves * c->fe_xentries * 64 * sizeof(double))) return NEED_X;
+    }
+    if (need & NEED_LANE) {
+        if (!dev_alloc(b.lane_count, R16_TRAIN * sizeof(int32_t))) return NEED_LANE;
+        for (int i = 0; i < n; ++i) if (!dev_alloc(b.lane_rec[i], waves * 64 * lane::REC_DOUBLES * sizeof(double), c->stream)) return NEED_LANE;
+    }
+    return 0;
+}
+
 // fp64-arithmetic path: one launch for a train of n steps (ps[i] complete with its own outputs), whatever the storage
 // type T of the records.  All instances run on the row16 kernel, the truncated pseudo-inverse included; the few it gives
 // up on (net of eigen-candidates full, degenerate A) are recomputed by the generic kernel (Jacobi, fp64 arithmetic) from
-// the lists it leaves behind.
-// The rows buffers of the task pass, steps 0 .. n - 1 of a train: allocated on first use (8 MB per step at 65 536 instances; a context
-// that only runs the fused path or single ticks never pays for all eight).  Out of memory: that train computes part 1 of the task signal
-// in the row16 kernel (trows = nullptr), same results.
-static bool ensure_trows(irlosc_ctx* c, int n) {
-    if (!c->task_pass) return false;
-    for (int i = 0; i < n; ++i) {
-        if (c->dtrows[i]) continue;
-        if (hipMalloc((void**)&c->dtrows[i], (size_t)c->cfg.max_batch * 16 * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->dtrows[i] = nullptr;
-            return false;
-        }
-    }
-    return true;
-}
-
-static int ensure_xbank(irlosc_ctx* c, int which, int n, bool fused);
-
+// the lists it leaves behind.  Bank 0 without task rows (out of memory): that train computes part 1 of the task signal in the
+// row16 kernel, same results.
 template <typename T>
-static int row16_train(irlosc_ctx* c, const KParams<T>* ps, int n, bool tree, hipStream_t st, const int* pos = nullptr,
-                       bool reset = true, const irlosc_ctx::Bank* bk = nullptr) {
+static int row16_train(irlosc_ctx* c, const KParams<T>* ps, int n, bool tree, hipStream_t st, int k = 0, const int* pos = nullptr,
+                       bool first = true, bool last = true) {
     // pos[i] = step of the whole train that sub-train step i is (a train that mixes tree-form and dense slots goes out as two
     // sub-trains): give-up list and counter are those of the ORIGINAL step, and only the first sub-train zeroes the counters, so
-    // that irlosc_giveup_counts reports every step of the train at its own index.
+    // that irlosc_giveup_counts reports every step of the train at its own index; the timing events bracket the whole train.
     if (n < 1 || n > R16_TRAIN) return fail(c, IRLOSC_ERR_STATE, "train of %d steps", n);
     Row16Train<T> tr;
     memset(&tr, 0, sizeof tr);
-    int32_t* cnt = bk ? bk->count : c->dr16_count;      // (bk: the second bank of an overlapped train, see irlosc_ctx::Bank)
-    if (reset) HIPCHK(c, hipMemsetAsync(cnt, 0, R16_TRAIN * sizeof(int32_t), st));
-    c->count_cur = cnt;
-    const bool rows = bk ? (c->task_pass && bk->trows[n - 1] != nullptr) : ensure_trows(c, n);
+    irlosc_ctx::Bank& bk = c->bank[k];
+    if (first) HIPCHK(c, hipMemsetAsync(bk.count, 0, R16_TRAIN * sizeof(int32_t), st));
+    c->count_cur = bk.count;
+    const bool rows = c->task_pass && ensure_bank(c, k, n, NEED_ROWS) == 0;
     for (int i = 0; i < n; ++i) {
         const int o = pos ? pos[i] : i;
         tr.p[i] = ps[i];
-        tr.x[i] = Row16Extra{c->dzeros, bk ? bk->list[o] : c->dr16_list[o], cnt + o, nullptr, nullptr, nullptr, c->span_next,
-                             rows ? (bk ? bk->trows[i] : c->dtrows[i]) : nullptr};
+        tr.x[i] = Row16Extra{c->dzeros, bk.list[o], bk.count + o, nullptr, nullptr, nullptr, c->span_next, rows ? bk.trows[i] : nullptr};
     }
-    if (c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
+    if (first && c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
     int rc = launch_row16<T>(tr, n, tree, st);
     if (rc) return fail(c, IRLOSC_ERR_HIP, "row16 kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
-    if (c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
+    if (last && c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
     return IRLOSC_OK;
 }
 
@@ -901,64 +913,66 @@ extern "C" int irlosc_step(irlosc_ctx* c, int32_t slot, int32_t B, void* u_host,
     return IRLOSC_OK;
 }
 
-// `iters` steps on the row16 path, chained R16_TRAIN per launch (step i of a train writes output set i); events (if any)
-// go around the launches from number `skip` on.  One kernel per launch, so a train whose slots do not ALL qualify for the
-// tree-structured form is issued as two sub-trains -- the qualifying steps with the tree kernel, the others with the dense
-// recursion -- instead of dropping every step to the dense recursion (one more launch, only when slots are mixed).
+// A train of n steps on bank k: step i runs slot slots[i] and writes the bank's output set i.
+typedef int (*TrainFn)(irlosc_ctx* c, const int* slots, int n, int B, int k);
+
+// `iters` steps as trains of at most R16_TRAIN steps, train t on bank t % nbanks (irlosc_ctx::Bank); banks that cannot be allocated are
+// done without, and with timing events attached every train runs on the main stream.  The other banks' streams start behind whatever the
+// main stream holds, and the main stream continues behind all of them -- on every exit, so that trains enqueued before an error stay
+// ordered before later work on it.
+static int run_trains(irlosc_ctx* c, int first_slot, int B, int iters, int nbanks, unsigned need, TrainFn train) {
+    int nb = 1;
+    while (!c->tev_begin && nb < nbanks && ensure_bank(c, nb, R16_TRAIN, need) == 0) ++nb;
+    if (nb > 1) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
+    for (int k = 1; k < nb; ++k) HIPCHK(c, hipStreamWaitEvent(c->bank[k].st, c->ev_join, 0));
+    int rc = IRLOSC_OK;
+    for (int done = 0, t = 0; done < iters && !rc; done += R16_TRAIN, ++t) {
+        const int n = std::min((int)R16_TRAIN, iters - done), k = t % nb;
+        int slots[R16_TRAIN];
+        for (int i = 0; i < n; ++i) slots[i] = (first_slot + done + i) % c->cfg.n_slots;
+        rc = train(c, slots, n, B, k);
+        if (!rc) { c->du = c->bank[k].u[n - 1]; c->dflags = c->bank[k].flags[n - 1]; c->count_cur = c->bank[k].count; }
+    }
+    for (int k = 1; k < nb; ++k) {
+        hipError_t e = hipEventRecord(c->bank[k].done, c->bank[k].st);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->bank[k].done, 0);
+        if (e != hipSuccess && !rc) rc = fail(c, IRLOSC_ERR_HIP, "joining the stream of bank %d failed: %s", k, hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// A train on dense records.  One kernel per launch, so a train whose slots do not ALL qualify for the tree-structured form is issued as
+// two sub-trains -- the qualifying steps with the tree kernel, the others with the dense recursion -- instead of dropping every step to
+// the dense recursion (one more launch, only when slots are mixed).
 template <typename T>
-static int row16_resident(irlosc_ctx* c, int first_slot, int B, int iters, const std::vector<hipEvent_t>* evs, int skip) {
-    int done = 0, launch_no = 0;
-    const hipEvent_t outer_b = c->tev_begin, outer_e = c->tev_end;      // irlosc_time_trains brackets a one-train call itself
-    // more than one train, untimed: odd trains on the second bank / stream, so that their first waves fill the tail of the train before
-    // (a call of exactly one full train already allocates the second bank: a caller's warm-up then pays for it, not its timed loop)
-    int nx = 0;
-    if (c->r16_overlap && !evs && iters >= R16_TRAIN) {
-        const int want = std::min(c->r16_xbanks, std::max(1, (iters + R16_TRAIN - 1) / R16_TRAIN - 1));
-        while (nx < want && ensure_xbank(c, nx, R16_TRAIN, false) == 0) ++nx;
+static int dense_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
+    const irlosc_ctx::Bank& bk = c->bank[k];
+    KParams<T> ps[2][R16_TRAIN];        // [1]: steps whose slot qualifies for the tree form, [0]: the others
+    int pos[2][R16_TRAIN];              // step of the train each sub-train step is
+    int cnt[2] = {0, 0};
+    for (int i = 0; i < n; ++i) {
+        const int slot = slots[i];
+        int rcf = check_slot_filled(c, slot, B);
+        if (rcf) return rcf;
+        const int kind = slot_tree(c, slot) ? 1 : 0;
+        pos[kind][cnt[kind]] = i;
+        fill_params<T>(c, ps[kind][cnt[kind]++], B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
+                       c->has_tvel[slot] ? c->dtvel[slot] : nullptr, c->has_wrench[slot] ? c->dwrench[slot] : nullptr, bk.u[i], bk.flags[i]);
     }
-    if (nx) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));
-    for (int k = 0; k < nx; ++k) HIPCHK(c, hipStreamWaitEvent(c->xb[k].st, c->ev_join, 0));
-    const irlosc_ctx::Bank* last_bank = nullptr;
-    while (done < iters) {
-        const int n = std::min((int)R16_TRAIN, iters - done);
-        const int which = launch_no % (nx + 1);
-        const irlosc_ctx::Bank* bk = which ? &c->xb[which - 1] : nullptr;
-        KParams<T> ps[2][R16_TRAIN];        // [1]: steps whose slot qualifies for the tree form, [0]: the others
-        int pos[2][R16_TRAIN];              // step of the train each sub-train step is
-        int cnt[2] = {0, 0};
-        for (int i = 0; i < n; ++i) {
-            const int slot = (first_slot + done + i) % c->cfg.n_slots;
-            int rcf = check_slot_filled(c, slot, B);
-            if (rcf) return rcf;
-            const int kind = slot_tree(c, slot) ? 1 : 0;
-            pos[kind][cnt[kind]] = i;
-            fill_params<T>(c, ps[kind][cnt[kind]++], B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
-                           c->has_tvel[slot] ? c->dtvel[slot] : nullptr, c->has_wrench[slot] ? c->dwrench[slot] : nullptr,
-                           bk ? bk->u[i] : c->du_set[i], bk ? bk->flags[i] : c->dflags_set[i]);
-        }
-        const bool timed = evs && launch_no >= skip && 2 * (launch_no - skip) + 1 < (int)evs->size();
-        hipEvent_t eb = timed ? (*evs)[2 * (launch_no - skip)] : outer_b, ee = timed ? (*evs)[2 * (launch_no - skip) + 1] : outer_e;
-        const int first = cnt[1] ? 1 : 0, last = cnt[0] ? 0 : 1;      // order: tree sub-train, then dense sub-train
-        for (int kind = 1; kind >= 0; --kind) {
-            if (!cnt[kind]) continue;
-            c->tev_begin = kind == first ? eb : nullptr;              // the event pair brackets the whole train
-            c->tev_end = kind == last ? ee : nullptr;
-            int rc = row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk ? bk->st : c->stream, pos[kind], kind == first, bk);
-            c->tev_begin = c->tev_end = nullptr;
-            if (rc) return rc;
-        }
-        last_bank = bk;
-        c->cur = n - 1;
-        done += n;
-        ++launch_no;
+    const int first = cnt[1] ? 1 : 0, last = cnt[0] ? 0 : 1;      // order: tree sub-train, then dense sub-train
+    for (int kind = 1; kind >= 0; --kind) {
+        if (!cnt[kind]) continue;
+        int rc = row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk.st, k, pos[kind], kind == first, kind == last);
+        if (rc) return rc;
     }
-    for (int k = 0; k < nx; ++k) {
-        HIPCHK(c, hipEventRecord(c->xb[k].done, c->xb[k].st));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->xb[k].done, 0));
-    }
-    c->du = last_bank ? last_bank->u[c->cur] : c->du_set[c->cur];
-    c->dflags = last_bank ? last_bank->flags[c->cur] : c->dflags_set[c->cur];
     return IRLOSC_OK;
+}
+
+// `iters` steps on the row16 path from dense records.  More than one train: odd trains on the second bank (a call of exactly one full
+// train already allocates it: a caller's warm-up then pays for it, not its timed loop).
+static int row16_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
+    return run_trains(c, first_slot, B, iters, c->r16_overlap && iters >= R16_TRAIN ? irlosc_ctx::R16_BANKS : 1, c->task_pass ? NEED_ROWS : 0,
+                      c->cfg.dtype == IRLOSC_F64 ? dense_train<double> : dense_train<float>);
 }
 
 extern "C" int irlosc_step_resident(irlosc_ctx* c, int32_t first_slot, int32_t B, int32_t iters, float* ms_total,
@@ -971,8 +985,7 @@ extern "C" int irlosc_step_resident(irlosc_ctx* c, int32_t first_slot, int32_t B
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (c->kernel == IRLOSC_KERNEL_ROW16 && B > 0) {
-        rc = c->cfg.dtype == IRLOSC_F64 ? row16_resident<double>(c, first_slot, B, iters, nullptr, 0)
-                                        : row16_resident<float>(c, first_slot, B, iters, nullptr, 0);
+        rc = row16_resident(c, first_slot, B, iters);
         if (rc) return rc;
     } else {
         for (int i = 0; i < iters; ++i) {
@@ -994,6 +1007,32 @@ extern "C" int irlosc_steps_per_launch(const irlosc_ctx* c) {
     return c->kernel == IRLOSC_KERNEL_GENERIC ? 1 : c->train;
 }
 
+static int fused_resident(irlosc_ctx* c, int first_slot, int B, int iters);
+static bool fused_ready(irlosc_ctx* c, int n);
+
+// One untimed train first (clocks, caches: nothing rides on an idle machine), then `ntrains` one-train calls back to back on the main
+// stream, train i bracketed by the event pair tev_pool[2 i], [2 i + 1] (and, with `spans`, stamped by its kernels at dspan + i).  Train j
+// of the sequence starts at slot first_slot + j * train.
+static int timed_trains(irlosc_ctx* c, int first_slot, int B, int ntrains, bool from_q, bool spans) {
+    while ((int)c->tev_pool.size() < 2 * ntrains) {
+        hipEvent_t ev;
+        HIPCHK(c, hipEventCreate(&ev));
+        c->tev_pool.push_back(ev);
+    }
+    int rc = IRLOSC_OK;
+    for (int i = -1; i < ntrains && !rc; ++i) {
+        if (i >= 0) {
+            c->tev_begin = c->tev_pool[2 * i]; c->tev_end = c->tev_pool[2 * i + 1];
+            if (spans) c->span_next = c->dspan + (size_t)R16_SPAN_WORDS * i;
+        }
+        const int s0 = (first_slot + (i + 1) * c->train) % c->cfg.n_slots;
+        rc = from_q ? fused_resident(c, s0, B, c->train) : row16_resident(c, s0, B, c->train);
+        c->tev_begin = c->tev_end = nullptr;
+        c->span_next = nullptr;
+    }
+    return rc;
+}
+
 extern "C" int irlosc_time_dominant_kernel(irlosc_ctx* c, int32_t slot, int32_t B, int32_t iters, float* ms_avg) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
@@ -1005,25 +1044,17 @@ extern "C" int irlosc_time_dominant_kernel(irlosc_ctx* c, int32_t slot, int32_t 
         rc = irlosc_step_resident(c, slot, B, iters, &tot, ms_avg);
         return rc;
     }
-    // row16 path: the same chained launches as irlosc_step_resident, with a HIP event pair around each train (task pass + row16 kernel +
-    // give-up pass) -- what a rocprofv3 kernel trace of the timed region shows, so the two averages are comparable.  The first launch is
-    // not timed.
+    // row16 path: the same trains as irlosc_step_resident, on one stream, with a HIP event pair around each (task pass + row16 kernel +
+    // give-up pass) -- what a rocprofv3 kernel trace of the timed region shows, so the two averages are comparable.
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     const int launches = std::max(1, iters / c->train);
-    while ((int)c->tev_pool.size() < 2 * launches) {
-        hipEvent_t ev;
-        HIPCHK(c, hipEventCreate(&ev));
-        c->tev_pool.push_back(ev);
-    }
-    std::vector<hipEvent_t> evs(c->tev_pool.begin(), c->tev_pool.begin() + 2 * launches);
-    rc = c->cfg.dtype == IRLOSC_F64 ? row16_resident<double>(c, slot, B, (launches + 1) * c->train, &evs, 1)
-                                    : row16_resident<float>(c, slot, B, (launches + 1) * c->train, &evs, 1);
+    rc = timed_trains(c, slot, B, launches, false, false);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = 0.0;
     for (int i = 0; i < launches; ++i) {
         float ms = 0.f;
-        HIPCHK(c, hipEventElapsedTime(&ms, evs[2 * i], evs[2 * i + 1]));
+        HIPCHK(c, hipEventElapsedTime(&ms, c->tev_pool[2 * i], c->tev_pool[2 * i + 1]));
         tot += ms;
     }
     *ms_avg = (float)(tot / launches);
@@ -1032,8 +1063,6 @@ extern "C" int irlosc_time_dominant_kernel(irlosc_ctx* c, int32_t slot, int32_t 
 
 // Roofline evidence without a tracer (include/irlosc.h): per train one HIP event pair AND the wall-clock stamps the train's
 // main kernel takes itself (first wave's start, last wave's end).
-static int fused_resident(irlosc_ctx* c, int first_slot, int B, int iters);
-static int ensure_xside(irlosc_ctx* c, int n);
 extern "C" int irlosc_time_trains(irlosc_ctx* c, int32_t first_slot, int32_t B, int32_t ntrains, int32_t from_q, double* out) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, first_slot, B);
@@ -1042,13 +1071,7 @@ extern "C" int irlosc_time_trains(irlosc_ctx* c, int32_t first_slot, int32_t B, 
     if (c->kernel != IRLOSC_KERNEL_ROW16 || B < 1) return fail(c, IRLOSC_ERR_ARG, "irlosc_time_trains needs the row16 kernel and B >= 1");
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    const int spl = from_q ? c->fused_train : c->train;
-    if (from_q && !(c->fused && ensure_xside(c, spl) == 0)) return fail(c, IRLOSC_ERR_STATE, "the fused path from joint coordinates is not available on this context");
-    while ((int)c->tev_pool.size() < 2 * ntrains) {
-        hipEvent_t ev;
-        HIPCHK(c, hipEventCreate(&ev));
-        c->tev_pool.push_back(ev);
-    }
+    if (from_q && !fused_ready(c, c->train)) return fail(c, IRLOSC_ERR_STATE, "the fused path from joint coordinates is not available on this context");
     if (c->dspan_cap < ntrains) {
         if (c->dspan) HIPCHK(c, hipFree(c->dspan));
         c->dspan = nullptr; c->dspan_cap = 0;
@@ -1063,18 +1086,7 @@ extern "C" int irlosc_time_trains(irlosc_ctx* c, int32_t first_slot, int32_t B, 
     }
     HIPCHK(c, hipMemcpyAsync(c->dspan, h.data(), h.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    // one untimed train first (clocks, caches, nothing rides on an idle machine), then the measured ones back to back
-    for (int i = -1; i < ntrains && !rc; ++i) {
-        if (i >= 0) {
-            c->tev_begin = c->tev_pool[2 * i]; c->tev_end = c->tev_pool[2 * i + 1];
-            c->span_next = c->dspan + (size_t)R16_SPAN_WORDS * i;
-        }
-        const int s0 = (first_slot + (i + 1) * spl) % c->cfg.n_slots;
-        if (from_q) rc = fused_resident(c, s0, B, spl);
-        else rc = c->cfg.dtype == IRLOSC_F64 ? row16_resident<double>(c, s0, B, spl, nullptr, 0) : row16_resident<float>(c, s0, B, spl, nullptr, 0);
-        c->tev_begin = c->tev_end = nullptr;
-        c->span_next = nullptr;
-    }
+    rc = timed_trains(c, first_slot, B, ntrains, from_q, true);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(h.data(), c->dspan, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1104,7 +1116,7 @@ extern "C" int irlosc_giveup_counts(irlosc_ctx* c, int32_t* out) {
     for (int i = 0; i < R16_TRAIN; ++i) out[i] = 0;
     if (c->kernel != IRLOSC_KERNEL_ROW16) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    HIPCHK(c, hipMemcpyAsync(out, c->count_cur ? c->count_cur : c->dr16_count, R16_TRAIN * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->count_cur, R16_TRAIN * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }
@@ -1203,28 +1215,23 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         c->fused = c->fe_lane && c->kernel == IRLOSC_KERNEL_ROW16 && !(e && !strcmp(e, "0"));
         const char* ov = getenv("IRLOSC_FQ_OVERLAP");      // "0": consecutive fused trains on one stream (A/B measurements, tests)
         c->fq_overlap = !(ov && !strcmp(ov, "0"));
-        { const char* nb = getenv("IRLOSC_FQ_BANKS"); const int v = nb ? atoi(nb) : 3; c->fq_xbanks = std::max(1, std::min(v, 1 + irlosc_ctx::MAX_XBANKS)) - 1; }
-        const char* t = getenv("IRLOSC_FUSED_TRAIN");      // steps per launch pair of the fused path (A/B measurements)
-        if (t && atoi(t) >= 1 && atoi(t) <= R16_TRAIN) c->fused_train = atoi(t);
     }
     if (c->fused) {
         FeCompactTables t;
         memset(&t, 0, sizeof t);
         frontend_lane_dual_ur5_tables(h, &t);
-        if (c->fe_xentries != t.n_entries)               // an earlier model's exchange buffers have another size
-            for (int k2 = 0; k2 < R16_TRAIN; ++k2) if (c->fe_xside[k2]) { HIPCHK(c, hipFree(c->fe_xside[k2])); c->fe_xside[k2] = nullptr; }
-        c->fe_xentries = t.n_entries;
         if (!c->dtables) HIPCHK(c, hipMalloc((void**)&c->dtables, sizeof t));
         HIPCHK(c, hipMemcpyAsync(c->dtables, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));      // t lives on this stack frame
-        // (the exchange buffers themselves are allocated by the first fused step: ensure_xside)
+        HIPCHK(c, hipStreamSynchronize(c->stream));      // t lives on this stack frame (and no train of any bank is in flight)
         // The OSC step behind the walk: lane-per-robot form when an instantiation holds this layout (IRLOSC_LANE=0: the row16 FROMQ
-        // kernel, A/B measurements and tests); its record buffers are sized for the instantiation's entries and start over with a new layout
+        // kernel, A/B measurements and tests).  Every bank's exchange buffers and lane records start over with another entry count or
+        // layout (they are allocated again by the first fused train: ensure_bank).
         const char* le = getenv("IRLOSC_LANE");
         lane::RowMap map;
         const int tier = (le && !strcmp(le, "0")) ? -1 : lane_plan(h, &map);
-        if (tier != c->lane_tier || (tier >= 0 && memcmp(&map, &c->lane_map, sizeof map)))
-            for (int k2 = 0; k2 < R16_TRAIN; ++k2) if (c->lane_rec[k2]) { HIPCHK(c, hipFree(c->lane_rec[k2])); c->lane_rec[k2] = nullptr; }
+        if (t.n_entries != c->fe_xentries || tier != c->lane_tier || (tier >= 0 && memcmp(&map, &c->lane_map, sizeof map)))
+            for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
+        c->fe_xentries = t.n_entries;
         c->lane_tier = tier;
         if (tier >= 0) c->lane_map = map;
     } else {
@@ -1242,8 +1249,17 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
             HIPCHK(c, hipMalloc((void**)&c->dqvel[s2], (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
         }
     }
+    if (c->fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
+        for (int s2 = 0; s2 < c->cfg.n_slots; ++s2) {
+            if (c->has_q[s2] <= 0) continue;
+            if (!c->dqt[s2]) HIPCHK(c, hipMalloc((void**)&c->dqt[s2], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
+            HIPCHK(c, (hipError_t)launch_q_layout(c->dqpos[s2], c->dqvel[s2], c->dqt[s2], c->has_q[s2], c->cfg.n, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return IRLOSC_OK;
 }
+
 
 extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const double* qpos, const double* qvel) {
     if (!c) return IRLOSC_ERR_ARG;
@@ -1258,8 +1274,9 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
     HIPCHK(c, hipMemcpyAsync(c->dqvel[slot], qvel, bytes, hipMemcpyHostToDevice, c->stream));
     // the fused walk reads its own layout of the same numbers ([wave][2 n][64 robots]: coalesced, hinge by hinge): one small kernel
     // behind the copies (10 us per 65 536 robots against 0.8 ms of PCIe for them)
-    // (only the fused path reads this layout; its buffer is allocated by the slot's first upload while the path is on -- and, once it
-    //  exists, refreshed by EVERY upload: a copy left stale while another model had the path switched off would be walked later)
+    // (only the fused path reads this layout; its buffer is allocated by the slot's first upload while the path is on, or by the
+    //  irlosc_set_model that turns it on -- and, once it exists, refreshed by EVERY upload: a copy left stale while another model had
+    //  the path switched off would be walked later)
     if (c->fused && !c->dqt[slot])
         HIPCHK(c, hipMalloc((void**)&c->dqt[slot], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
     if (c->dqt[slot]) HIPCHK(c, (hipError_t)launch_q_layout(c->dqpos[slot], c->dqvel[slot], c->dqt[slot], B, c->cfg.n, c->stream));
@@ -1338,36 +1355,16 @@ static int check_slot_q(irlosc_ctx* c, int slot, int B) {
     return IRLOSC_OK;
 }
 
-// Exchange buffers of the fused path: allocated by the first fused step, and only as many as the longest train so far needs
-// (a caller of irlosc_step_from_q uses one: 334 entries x 512 B per 64 robots = 175 MB at 65 536 robots; the benchmark form all R16_TRAIN: 1.4 GB) -- a context
-// that only ever runs irlosc_frontend + irlosc_step pays nothing.  Out of memory: the fused path is switched off for this
-// context and the caller continues through dense records (-> 1).
-static int ensure_xside(irlosc_ctx* c, int n) {
-    const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
-    for (int k2 = 0; k2 < n && k2 < R16_TRAIN; ++k2) {
-        if (c->fe_xside[k2]) continue;
-        if (hipMalloc((void**)&c->fe_xside[k2], waves * c->fe_xentries * 64 * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int k3 = 0; k3 < R16_TRAIN; ++k3) if (c->fe_xside[k3]) { (void)hipFree(c->fe_xside[k3]); c->fe_xside[k3] = nullptr; }
-            c->fused = 0;
-            return 1;
-        }
-    }
-    // lane form of the OSC step: one record per robot and step for the eigen pass (all of a batch may be flagged), in whole groups of
-    // 64 (transposed records; every entry of a record is written by the lane that owns it).  Out of memory here only switches the lane form off.
-    if (c->lane_tier >= 0) {
-        if (!c->dlane_count && hipMalloc((void**)&c->dlane_count, R16_TRAIN * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); c->lane_tier = -1; }
-        for (int k2 = 0; c->lane_tier >= 0 && k2 < n && k2 < R16_TRAIN; ++k2) {
-            if (c->lane_rec[k2]) continue;
-            const size_t bytes = (size_t)((c->cfg.max_batch + 63) / 64 * 64) * lane::REC_DOUBLES * sizeof(double);      // (whole groups of 64 records)
-            if (hipMalloc((void**)&c->lane_rec[k2], bytes) != hipSuccess || hipMemsetAsync(c->lane_rec[k2], 0, bytes, c->stream) != hipSuccess) {
-                (void)hipGetLastError();
-                for (int k3 = 0; k3 < R16_TRAIN; ++k3) if (c->lane_rec[k3]) { (void)hipFree(c->lane_rec[k3]); c->lane_rec[k3] = nullptr; }
-                c->lane_tier = -1;
-            }
-        }
-    }
-    return 0;
+// Bank 0 ready for a fused train of n steps, under the fused path's out-of-memory policy: without exchange buffers the path is switched
+// off for this context and the caller continues through dense records (-> false); without lane records the OSC step stays the row16
+// FROMQ kernel.  (A caller of irlosc_step_from_q needs one step's buffers, the benchmark form R16_TRAIN: 1.4 GB of exchange buffers at
+// 65 536 robots -- a context that only ever runs irlosc_frontend + irlosc_step pays nothing.)
+static bool fused_ready(irlosc_ctx* c, int n) {
+    if (!c->fused) return false;
+    const unsigned miss = ensure_bank(c, 0, n, NEED_X | (c->lane_tier >= 0 ? NEED_LANE : 0));
+    if (miss == NEED_X) { free_bank(c->bank[0], NEED_X); c->fused = 0; }
+    if (miss == NEED_LANE) { free_bank(c->bank[0], NEED_LANE); c->lane_tier = -1; }
+    return c->fused;
 }
 
 // Fused path: one train of n steps from joint coordinates (step i: slot slots[i], outputs of set i).  Three launches -- the
@@ -1377,8 +1374,13 @@ static int ensure_xside(irlosc_ctx* c, int n) {
 // eigen stage hands over get their dense records from the wave-per-robot front end (worklist form) and go through the
 // generic kernel like on the record path.  Dense M / J exist in HBM for those robots only.
 template <typename T>
-static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, const irlosc_ctx::Bank& bk) {
+static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
     if (n < 1 || n > R16_TRAIN) return fail(c, IRLOSC_ERR_STATE, "train of %d steps", n);
+    for (int i = 0; i < n; ++i) {
+        int rc = check_slot_q(c, slots[i], B);
+        if (rc) return rc;
+    }
+    const irlosc_ctx::Bank& bk = c->bank[k];
     const hipStream_t st = bk.st;
     FeLaneTrain ft;
     memset(&ft, 0, sizeof ft);
@@ -1392,10 +1394,6 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, const irlo
         const int sl = slots[i];
         ft.qpos[i] = ga.qpos[i] = c->dqpos[sl];
         ft.qvel[i] = ga.qvel[i] = c->dqvel[sl];
-        if (!c->dqt[sl]) {      // coordinates uploaded before the model made the fused path available: lay them out now
-            HIPCHK(c, hipMalloc((void**)&c->dqt[sl], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
-            HIPCHK(c, (hipError_t)launch_q_layout(c->dqpos[sl], c->dqvel[sl], c->dqt[sl], std::max(1, c->has_q[sl]), c->cfg.n, st));
-        }
         ft.qt[i] = c->dqt[sl];
         ft.side[i] = bk.xside[i];
         fill_params<T>(c, tr.p[i], B, c->dM[sl], c->dJ[sl], c->ddq[sl], c->dbias[sl], c->dee[sl], c->dtgt[sl],
@@ -1444,80 +1442,11 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, const irlo
     return IRLOSC_OK;
 }
 
-// bank 0 = the context's own buffers on its stream
-static irlosc_ctx::Bank bank0_of(irlosc_ctx* c) {
-    irlosc_ctx::Bank b;
-    b.st = c->stream;
-    for (int i = 0; i < R16_TRAIN; ++i) {
-        b.xside[i] = c->fe_xside[i]; b.lane_rec[i] = c->lane_rec[i]; b.list[i] = c->dr16_list[i];
-        b.u[i] = c->du_set[i]; b.flags[i] = c->dflags_set[i];
-    }
-    b.lane_count = c->dlane_count;
-    b.count = c->dr16_count;
-    return b;
-}
-
-// A further bank (see irlosc_ctx::Bank): same sizes as the context's own.  -> 0, or 1: not available (out of memory: fewer banks)
-static int ensure_xbank(irlosc_ctx* c, int which, int n, bool fused) {
-    irlosc_ctx::Bank& b = c->xb[which];
-    const size_t Bm = (size_t)c->cfg.max_batch, waves = (Bm + 63) / 64;
-    auto get = [](void** p, size_t bytes) { return *p || hipMalloc(p, bytes) == hipSuccess; };
-    bool ok = true;
-    if (!b.st) ok = ok && hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking) == hipSuccess;
-    if (!b.done) ok = ok && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) == hipSuccess;
-    if (!c->ev_join) ok = ok && hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess;
-    ok = ok && get((void**)&b.count, R16_TRAIN * sizeof(int32_t)) && get((void**)&b.lane_count, R16_TRAIN * sizeof(int32_t));
-    for (int i = 0; ok && i < n && i < R16_TRAIN; ++i) {
-        ok = ok && get((void**)&b.list[i], Bm * sizeof(int32_t)) && get(&b.u[i], Bm * c->cfg.n * c->esz) && get((void**)&b.flags[i], Bm * sizeof(uint32_t));
-        if (!fused) { if (ok && c->task_pass) ok = get((void**)&b.trows[i], Bm * 16 * sizeof(double)); continue; }
-        ok = ok && get((void**)&b.xside[i], waves * c->fe_xentries * 64 * sizeof(double));
-        if (ok && c->lane_tier >= 0 && !b.lane_rec[i]) {
-            const size_t bytes = (Bm + 63) / 64 * 64 * lane::REC_DOUBLES * sizeof(double);
-            ok = hipMalloc((void**)&b.lane_rec[i], bytes) == hipSuccess && hipMemsetAsync(b.lane_rec[i], 0, bytes, c->stream) == hipSuccess;
-            if (!ok) b.lane_rec[i] = nullptr;
-        }
-    }
-    if (!ok) { (void)hipGetLastError(); return 1; }
-    return 0;
-}
-
+// `iters` steps on the fused path.  Banks are allocated only when a call chains trains: one bank per train up to FQ_BANKS.
 static int fused_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
-    int done = 0, t = 0;
-    const irlosc_ctx::Bank b0 = bank0_of(c);
-    // more than one train: alternate banks / streams so that a train's first waves fill the tails of the one before (irlosc_ctx::Bank)
-    int nx = 0;                                                        // banks beside the context's own that this call rotates over
-    if (c->fq_overlap && iters >= c->fused_train && c->fused_train > 1 && !c->tev_begin) {
-        const int want = std::min(c->fq_xbanks, (iters + c->fused_train - 1) / c->fused_train - 1);
-        while (nx < want && ensure_xbank(c, nx, c->fused_train, true) == 0) ++nx;
-    }
-    if (nx) HIPCHK(c, hipEventRecord(c->ev_join, c->stream));          // the other banks' streams start behind whatever the main stream holds
-    for (int k = 0; k < nx; ++k) HIPCHK(c, hipStreamWaitEvent(c->xb[k].st, c->ev_join, 0));
-    const irlosc_ctx::Bank* last = &b0;
-    while (done < iters) {
-        const int n = std::min(c->fused_train, iters - done);
-        int slots[R16_TRAIN];
-        for (int i = 0; i < n; ++i) {
-            slots[i] = (first_slot + done + i) % c->cfg.n_slots;
-            int rc = check_slot_q(c, slots[i], B);
-            if (rc) return rc;
-        }
-        const int which = t % (nx + 1);
-        const irlosc_ctx::Bank& bk = which ? c->xb[which - 1] : b0;
-        int rc = c->cfg.dtype == IRLOSC_F64 ? fused_train<double>(c, slots, n, B, bk) : fused_train<float>(c, slots, n, B, bk);
-        if (rc) return rc;
-        last = &bk;
-        c->cur = n - 1;
-        done += n;
-        ++t;
-    }
-    for (int k = 0; k < nx; ++k) {                                     // and the main stream continues behind all of them
-        HIPCHK(c, hipEventRecord(c->xb[k].done, c->xb[k].st));
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->xb[k].done, 0));
-    }
-    c->du = last->u[c->cur];
-    c->dflags = last->flags[c->cur];
-    c->count_cur = last->count;
-    return IRLOSC_OK;
+    const int ntrains = (iters + R16_TRAIN - 1) / R16_TRAIN;
+    return run_trains(c, first_slot, B, iters, c->fq_overlap ? std::min((int)irlosc_ctx::FQ_BANKS, ntrains) : 1,
+                      NEED_X | (c->lane_tier >= 0 ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? fused_train<double> : fused_train<float>);
 }
 
 extern "C" const char* irlosc_from_q_name(const irlosc_ctx* c) {
@@ -1541,7 +1470,7 @@ extern "C" int irlosc_step_from_q(irlosc_ctx* c, int32_t slot, int32_t B, void* 
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (B > 0) {
-        if (c->fused && ensure_xside(c, 1) == 0) {
+        if (fused_ready(c, 1)) {
             rc = fused_resident(c, slot, B, 1);
         } else {
             rc = check_slot_q(c, slot, B);
@@ -1563,7 +1492,7 @@ extern "C" int irlosc_step_resident_from_q(irlosc_ctx* c, int32_t first_slot, in
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (c->fused && B > 0 && ensure_xside(c, std::min(c->fused_train, iters)) == 0) {
+    if (B > 0 && fused_ready(c, std::min((int)R16_TRAIN, iters))) {
         rc = fused_resident(c, first_slot, B, iters);
         if (rc) return rc;
     } else {

@@ -404,6 +404,31 @@ def test_row16_give_up_counters_do_not_go_stale_across_uneven_trains():
     osc.close()
 
 
+def test_a_call_whose_later_train_fails_leaves_the_next_call_exact():
+    """A call whose THIRD train meets a slot that was never filled fails with IRLOSC_ERR_STATE after two trains went out, the second on
+    the other bank's stream; those trains are still joined into the main stream, and the next valid call and its download are bit for
+    bit a single step on the last slot visited.  17 slots, the last one empty: step_resident(24) = slots 0..7, 8..15, then slot 16."""
+    nslots, B = 17, 516
+    lay = synth.make_layout("k13")
+    osc = BatchedOSC(lay, B, dtype=np.float64, n_slots=nslots)
+    assert "row16" in osc.kernel_name
+    batches = [synth.make_batch("k13", B, seed=400 + i, dtype=np.float64) for i in range(3)]
+    _, gains, _ = batches[0]
+    osc.set_gains(gains["kp"], gains["kv"], gains["ko"], gains["k"], gains["d"], gains["max_vel"], gains["null_kv"])
+    for sl in range(nslots - 1):
+        g = batches[sl % 3][2]
+        osc.upload(g["M"], g["J"], g["dq"], g["bias"], g["ee_pose"], g.get("wrench"), slot=sl)
+        osc.set_targets(g["tgt_pose"], g.get("tgt_vel"), slot=sl)
+    with pytest.raises(_lib.IrloscError, match="error -3: slot 16"):
+        osc.step_resident(24, first_slot=0, B=B)
+    osc.step_resident(12, first_slot=0)                      # 8 @ bank 0, 4 @ bank 1: step 11 runs slot 11
+    u_train, f_train = osc.download(B)
+    osc.step(slot=11)
+    u_one, f_one = osc.download(B)
+    assert np.array_equal(u_train, u_one) and np.array_equal(f_train, f_one)
+    osc.close()
+
+
 def test_time_dominant_kernel_leaves_complete_outputs():
     lay, gains, g = synth.make_batch("k13", 4096, seed=9, dtype=np.float32)
     osc = BatchedOSC(lay, 4096, dtype=np.float32)
@@ -1119,6 +1144,24 @@ def test_fused_resident_trains_equal_single_steps(iters):
         u_1, f_1 = osc.step_q(slot=(first + iters - 1) % nslots, return_flags=True)
         assert np.array_equal(u_t, u_1) and np.array_equal(f_t, f_1), rep
     osc.close()
+
+
+def test_fused_path_turned_on_after_the_coordinates_were_uploaded(monkeypatch):
+    """Coordinates uploaded while the fused path was off have no copy in the fused walk's layout yet.  The irlosc_set_model that turns
+    the path on lays them out on the main stream before it returns, so the trains of another bank's stream never read a layout still
+    being written: 19 steps over three banks, bit for bit a single fused step on the last slot visited."""
+    nslots, B, iters = 3, 700, 19
+    monkeypatch.setenv("IRLOSC_FUSED", "0")
+    lay, gains, g, model, osc, states = _from_q_setup("k13", B, np.float64, seed=43, n_slots=nslots, singular_every=6)
+    assert "through dense records" in osc.from_q_name
+    monkeypatch.delenv("IRLOSC_FUSED")
+    osc.set_model(model)
+    assert "fused" in osc.from_q_name
+    osc.step_resident_from_q(iters)
+    u_t, f_t = osc.download(B)
+    u_1, f_1 = osc.step_q(slot=(iters - 1) % nslots, return_flags=True)
+    osc.close()
+    assert np.array_equal(u_t, u_1) and np.array_equal(f_t, f_1)
 
 
 @pytest.mark.parametrize("fe", ["lane", "generic"])
