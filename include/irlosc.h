@@ -19,7 +19,10 @@
  *   the per-tick MuJoCo reads themselves: mj_fullM (robot.py:68-72),
  *   jacp / jacr (device.py:115-133), qfrc_bias (osc.py:190-191),
  *   EE xpos / xquat (device.py:97-99), from (qpos, qvel)        -> irlosc_set_model, irlosc_upload_q, then irlosc_frontend
- *                                                                  (dense records) or irlosc_step_from_q (fused: no records)
+ *                                                                  (dense records) or irlosc_step_from_q (fused: no records);
+ *                                                                  irlosc_step_from_q_device from the caller's HBM
+ *   the per-tick F/T reads rotated by the ft_frame_* site frames
+ *   (device.py:135-170) on the path from joint coordinates      -> irlosc_set_ft_sensors, irlosc_set_sensordata
  *
  * Record layouts (batch-major, row-major, element type = cfg.dtype: float or double):
  *   M[B][n][n]      joint-space inertia, symmetric positive definite (the row16 kernels read row j as column j)
@@ -297,8 +300,9 @@ IRLOSC_API int irlosc_step_device(irlosc_ctx* ctx, int32_t B, const void* dM, co
  * body frame pos + quat relative to the parent, hinge axis / anchor in the body frame, inertial frame ipos + iquat with
  * principal moments, quaternions w x y z).  Bodies must be listed parents first (MuJoCo's numbering does that);
  * joint j of the model is position j of the n-vector (n = cfg.n).  ee_body[d] = body whose frame is target device d's
- * end effector (targets order).  The F/T wrench is not a function of (qpos, qvel): it stays whatever irlosc_upload /
- * irlosc_upload_raw last put into the slot (absent: zero). */
+ * end effector (targets order).  The F/T wrench is not a function of (qpos, qvel): without a sensor feed it stays whatever
+ * irlosc_upload / irlosc_upload_raw last put into the slot (absent: zero); with one (irlosc_set_ft_sensors + irlosc_set_sensordata,
+ * below) every step from joint coordinates rotates the slot's sensor readings by the F/T site frames of its own forward kinematics. */
 #define IRLOSC_MAX_BODIES 64
 typedef struct irlosc_model {
     int32_t nb;                               /* bodies, <= IRLOSC_MAX_BODIES */
@@ -368,6 +372,54 @@ IRLOSC_API const char* irlosc_from_q_name(const irlosc_ctx* ctx);
  * stream. */
 IRLOSC_API int irlosc_step_resident_from_q(irlosc_ctx* ctx, int32_t first_slot, int32_t B, int32_t iters, float* ms_total,
                                 float* ms_step_avg);
+
+/* ---- F/T sensor feed of the path from joint coordinates (irl_control/device.py:135-170, osc.py:179-185) -----------------
+ * The reference reads the F/T sensors every tick and rotates force sensordata[f0 .. f0 + 3] and torque sensordata[t0 .. t0 + 3]
+ * of target device d into the world by the frame of the site ft_frame_<device> (site_xmat).  On the path from joint coordinates
+ * that frame comes from the step's own forward kinematics: the site's body is welded to the device's end effector, so
+ * R(site) = R(ee_quat) R_rel[d] with a constant R_rel[d] = R(ee)^T R(site), and
+ *     wrench[b][d] = (R(ee_quat) R_rel[d] force, R(ee_quat) R_rel[d] torque)      (devices without a sensor: zero)
+ * is used exactly as a record wrench is (IRLOSC_ADMITTANCE; without it the feed is accepted and changes nothing, as in the
+ * reference).  One small kernel per train (osc_ft_wrench, one lane per robot) between the walk and the OSC step -- or, on the path
+ * through dense records, between irlosc_frontend's kernel and the step; a context whose slots have no feed launches exactly what
+ * it launched before. */
+typedef struct irlosc_ft_desc {
+    int32_t n_sensor;                         /* sensordata length per robot (doubles) */
+    int32_t site_body[IRLOSC_MAX_DEV];        /* body carrying target device d's F/T site (mjModel.site_bodyid); -1 = no sensor */
+    double site_quat[IRLOSC_MAX_DEV][4];      /* site frame in that body, w x y z (mjModel.site_quat; need not be normalised) */
+    int32_t ft_force0[IRLOSC_MAX_DEV];        /* first sensordata index of the force triple (as irlosc_raw_desc) */
+    int32_t ft_torque0[IRLOSC_MAX_DEV];
+} irlosc_ft_desc;
+/* After irlosc_set_model (IRLOSC_ERR_STATE before).  Checked for every device with a sensor (IRLOSC_ERR_ARG naming the device
+ * otherwise): n_sensor >= 3, both indices in [0, n_sensor - 3], site_body a body of the model, and the site body RIGIDLY attached to
+ * the device's ee_body -- no hinge on the tree path between the two, in either direction (the shipped model: the site body
+ * robotiq_85_adapter_link_* is a welded child of ur_EE_*).  R_rel[d] is computed here, on the host, from the model's body
+ * quaternions.  Replaces an earlier description and clears every slot's sensor feed (laid out for that one); a later irlosc_set_model
+ * clears the description and every feed too. */
+IRLOSC_API int irlosc_set_ft_sensors(irlosc_ctx* ctx, const irlosc_ft_desc* desc);
+/* Host -> device copy of sensordata[B][n_sensor] (always double, like qpos) into slot `slot`'s feed: from then on the slot's sensors
+ * are the wrench source of every step from joint coordinates on it (irlosc_step_from_q, irlosc_step_resident_from_q; fused and
+ * through dense records alike), the record wrench is left alone.  The buffer (max_batch x n_sensor x 8 bytes: 9.4 MB at 65 536 x 18)
+ * is allocated by the slot's first feed.  B = 0 or sensordata = NULL clears the feed (the record wrench is the source again), and so
+ * does any irlosc_upload* / irlosc_assemble_device of the slot (they bring a wrench of their own).  A step from joint coordinates
+ * over more robots than the feed holds fails with IRLOSC_ERR_STATE.  Needs irlosc_set_ft_sensors (IRLOSC_ERR_STATE).  Synchronous,
+ * like irlosc_upload_q. */
+IRLOSC_API int irlosc_set_sensordata(irlosc_ctx* ctx, int32_t slot, int32_t B, const double* sensordata);
+/* One step from joint coordinates on caller-owned DEVICE arrays (what irlosc_step_device is to irlosc_step):
+ *   d_qpos, d_qvel[B][n]             double
+ *   d_tgt_pose[B][ndev][7]           context dtype; d_tgt_vel[B][ndev][6] or NULL (all zero), as irlosc_set_targets
+ *   d_sensordata[B][n_sensor]        double, or NULL (zero wrench); non-NULL needs irlosc_set_ft_sensors (IRLOSC_ERR_STATE)
+ *   d_u[B][n] (context dtype), d_flags[B]    outputs
+ * Same kernels as irlosc_step_from_q (the fused path when it is on, else front end + step through dense records), with every per-slot
+ * input replaced by the caller's pointers; no copies, no host synchronisation, everything enqueued on hip_stream (NULL = the context's
+ * stream).  `slot` lends its buffers as the call's scratch: the walk's layout of the coordinates, dense records of the robots the
+ * eigen stage gives up on (fused) or of all robots (dense path), and its wrench record.  AFTERWARDS THAT SLOT HOLDS NO RECORDS AND NO
+ * JOINT COORDINATES: irlosc_step, irlosc_step_from_q, irlosc_step_resident* and irlosc_download_records on it fail with
+ * IRLOSC_ERR_STATE until it is filled again; its targets and sensor feed are not touched.  Like irlosc_step_device the call uses the
+ * context's bank-0 scratch (give-up lists, counters, exchange buffer): it must not overlap with other calls on the same context. */
+IRLOSC_API int irlosc_step_from_q_device(irlosc_ctx* ctx, int32_t slot, int32_t B, const double* d_qpos, const double* d_qvel,
+                                         const void* d_tgt_pose, const void* d_tgt_vel, const double* d_sensordata,
+                                         void* d_u, uint32_t* d_flags, void* hip_stream);
 
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard

@@ -24,7 +24,7 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_comm_last_error", "irlosc_bench_allreduce", "irlosc_comm_allgather_u64", "irlosc_set_model",
            "irlosc_upload_q", "irlosc_frontend", "irlosc_step_resident_from_q", "irlosc_download_records",
            "irlosc_step_from_q", "irlosc_from_q_name", "irlosc_slot_structure", "irlosc_probe_structure", "irlosc_time_trains", "irlosc_giveup_counts",
-           "irlosc_kernel_class"]
+           "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 COMM_ID_BYTES = 128
@@ -52,6 +52,12 @@ class Model(C.Structure):
                 ("jpos", (C.c_double * 3) * MAX_N), ("armature", C.c_double * MAX_N), ("mass", C.c_double * MAX_BODIES),
                 ("ipos", (C.c_double * 3) * MAX_BODIES), ("iquat", (C.c_double * 4) * MAX_BODIES),
                 ("inertia", (C.c_double * 3) * MAX_BODIES), ("gravity", C.c_double * 3), ("ee_body", C.c_int32 * MAX_DEV)]
+
+
+class FtDesc(C.Structure):
+    """struct irlosc_ft_desc (include/irlosc.h): the F/T site of each target device (body, frame in it) and its sensordata slices."""
+    _fields_ = [("n_sensor", C.c_int32), ("site_body", C.c_int32 * MAX_DEV), ("site_quat", (C.c_double * 4) * MAX_DEV),
+                ("ft_force0", C.c_int32 * MAX_DEV), ("ft_torque0", C.c_int32 * MAX_DEV)]
 
 
 class Cfg(C.Structure):
@@ -120,6 +126,9 @@ def load():
     lib.irlosc_step_resident_from_q.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.irlosc_step_from_q.argtypes = [vp, i32, i32, vp, vp]
     lib.irlosc_from_q_name.argtypes = [vp]
+    lib.irlosc_set_ft_sensors.argtypes = [vp, C.POINTER(FtDesc)]
+    lib.irlosc_set_sensordata.argtypes = [vp, i32, i32, vp]
+    lib.irlosc_step_from_q_device.argtypes = [vp, i32, i32] + [vp] * 8
     lib.irlosc_from_q_name.restype = C.c_char_p
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int

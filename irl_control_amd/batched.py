@@ -258,11 +258,51 @@ class BatchedOSC:
         self._chk(self.lib.irlosc_step_from_q(self._h, slot, B, _lib.ptr(u), _lib.ptr(fl)))
         return (u, fl) if return_flags else u
 
-    def step_from_q(self, qpos, qvel, tgt_pose, tgt_vel=None, return_flags: bool = False):
-        """One tick from joint coordinates: upload (qpos, qvel) and the targets, one step from them, download."""
+    def step_from_q(self, qpos, qvel, tgt_pose, tgt_vel=None, return_flags: bool = False, sensordata=None):
+        """One tick from joint coordinates: upload (qpos, qvel) and the targets (and, with `sensordata` [B, n_sensor], the F/T
+        readings of this tick: set_sensordata), one step from them, download."""
         self.upload_q(qpos, qvel)
         self.set_targets(tgt_pose, tgt_vel)
+        if sensordata is not None:
+            self.set_sensordata(sensordata)
         return self.step_q(return_flags=return_flags)
+
+    # -- F/T sensor feed of the steps from joint coordinates (irlosc_set_ft_sensors / irlosc_set_sensordata) ---------------
+    def set_ft_sensors(self, sites=None, n_sensor: int = 18):
+        """Describe the F/T sensors of the target devices (after set_model; irlosc_set_ft_sensors).  Default: device d's site is
+        ft_frame_<name> of the model's `sites` table (the reference's F/T frames) and its sensordata slices those of device._FT_TABLE (as
+        raw.raw_desc); `sites` maps a device name to another site.  Devices without an entry have no sensor (zero wrench).  The site's body
+        must be welded to the device's EE body (the library checks).  n_sensor = 18: the scene's <sensor> block."""
+        model = getattr(self, "_model", None)
+        if model is None:
+            raise _lib.IrloscError("set_model must precede set_ft_sensors")
+        fd = model.ft_desc(self.layout.dev_names, sites, n_sensor)
+        self._chk(self.lib.irlosc_set_ft_sensors(self._h, C.byref(fd)))
+        self._n_sensor = int(n_sensor)
+
+    def set_sensordata(self, sensordata, slot: int = 0):
+        """F/T readings sensordata[B, n_sensor] (float64, MuJoCo's sensordata rows) of slot `slot`: the wrench source of every step from
+        joint coordinates on it until the slot gets records again (upload*) or the feed is cleared (sensordata=None)."""
+        if sensordata is None:
+            self._chk(self.lib.irlosc_set_sensordata(self._h, slot, 0, None))
+            return
+        ns = getattr(self, "_n_sensor", None)
+        if ns is None:
+            raise _lib.IrloscError("set_ft_sensors must precede set_sensordata")
+        sd = np.ascontiguousarray(sensordata, dtype=np.float64)
+        if sd.ndim != 2 or sd.shape[1] != ns:
+            raise ValueError(f"sensordata: expected shape (B, {ns}), got {sd.shape}")
+        self._chk(self.lib.irlosc_set_sensordata(self._h, slot, int(sd.shape[0]), _lib.ptr(sd)))
+
+    def step_from_q_device(self, B: int, d_qpos: int, d_qvel: int, d_tgt_pose: int, d_u: int, d_flags: int, d_tgt_vel: int = None,
+                           d_sensordata: int = None, slot: int = 0, stream: int = None):
+        """One step from joint coordinates on caller-owned DEVICE arrays (irlosc_step_from_q_device): integer device addresses
+        (e.g. tensor.data_ptr()) of qpos / qvel [B, n] float64, tgt_pose [B, ndev, 7] (and tgt_vel [B, ndev, 6]) in this context's
+        dtype, sensordata [B, n_sensor] float64 or None, outputs u [B, n] (context dtype) and flags [B] uint32.  Enqueued on `stream`
+        (a hipStream_t address; None = the context's stream), nothing copied, nothing synchronised.  `slot` lends its buffers as
+        scratch and holds no records and no joint coordinates afterwards."""
+        self._chk(self.lib.irlosc_step_from_q_device(self._h, slot, int(B), d_qpos, d_qvel, d_tgt_pose, d_tgt_vel, d_sensordata,
+                                                     d_u, d_flags, stream))
 
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""

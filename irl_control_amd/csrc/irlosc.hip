@@ -21,10 +21,12 @@
 #include "osc_row16.hpp"
 #include "osc_frontend.hpp"
 #include "osc_lane_types.hpp"
+#include "osc_ft.hpp"
 #include "launchers.hpp"
 
 using namespace irlosc;
 static_assert(FE_TRAIN == R16_TRAIN, "the walk and the OSC kernel chain the same number of steps per launch");
+static_assert(FT_TRAIN == R16_TRAIN, "the sensor-feed wrench kernel covers a whole train");
 
 static thread_local std::string g_create_error;
 
@@ -82,12 +84,14 @@ struct irlosc_ctx {
         size_t xentries = 0;               // ... sized for this many entries
         double* lane_rec[R16_TRAIN] = {};  // lane form of the fused path: eigen-pass records of each step, and their counters
         int32_t* lane_count = nullptr;
+        void* ftw[R16_TRAIN] = {};         // wrench of each step whose slot has a sensor feed (allocated by the first such step)
     };
     static constexpr int FQ_BANKS = 3;     // banks of the fused path's trains (k13 6.88 -> 7.00e8 against two; four: 7.03e8, +2.4 GB each)
     static constexpr int R16_BANKS = 2;    // banks of the dense-record trains (a third was a cache artefact of a four-slot bench)
     static constexpr int MAX_XBANKS = FQ_BANKS - 1;
     Bank bank[1 + MAX_XBANKS];
     hipEvent_t ev_join = nullptr;
+    hipEvent_t ev_dev = nullptr;           // irlosc_step_from_q_device: a caller stream starts behind the context's stream
     int fq_overlap = 1;                    // IRLOSC_FQ_OVERLAP=0: one bank, one stream (A/B measurements, tests)
     int r16_overlap = 1;                   // IRLOSC_R16_OVERLAP=0: the same switch for the trains of irlosc_step_resident on dense records
     int32_t* count_cur = nullptr;          // give-up counters of the most recent train (irlosc_giveup_counts)
@@ -98,6 +102,21 @@ struct irlosc_ctx {
     std::vector<double*> dqpos, dqvel;
     std::vector<double*> dqt;          // per slot: the same coordinates in the fused walk's layout [wave][2 n][64 robots] (irlosc_upload_q writes both)
     std::vector<int> has_q;
+    // F/T sensor feed of the steps from joint coordinates (irlosc_set_ft_sensors / irlosc_set_sensordata): the description, R_rel per
+    // device, and per slot the sensordata of the feed (allocated by the slot's first feed; the wrench computed from it is a buffer of
+    // the step's bank, Bank::ftw)
+    int ft_set = 0;
+    int32_t ft_n_sensor = 0;
+    int32_t ft_f0[IRLOSC_MAX_DEV] = {}, ft_t0[IRLOSC_MAX_DEV] = {};
+    double ft_R[IRLOSC_MAX_DEV][9] = {};
+    int32_t ft_qe[IRLOSC_MAX_DEV] = {};    // exchange entry of each EE's qw (FeCompactTables::eetab[d][3])
+    std::vector<double*> dsens;
+    std::vector<int> sens_cols;        // doubles per robot the slot's sensordata buffer holds
+    std::vector<int> has_sens;         // robots of the slot's feed (0 = no feed)
+    // host copy of what irlosc_set_ft_sensors needs of the model: tree, body frames, EE bodies
+    int hm_nb = 0;
+    int32_t hm_parent[IRLOSC_MAX_BODIES] = {}, hm_joint[IRLOSC_MAX_BODIES] = {}, hm_ee[IRLOSC_MAX_DEV] = {};
+    double hm_quat[IRLOSC_MAX_BODIES][4] = {};
     // irlosc_tick: one pinned host block and one device block per direction, grown on demand
     void* tick_hin = nullptr; void* tick_din = nullptr; size_t tick_in_bytes = 0;
     void* tick_hout = nullptr; void* tick_dout = nullptr; size_t tick_out_bytes = 0;
@@ -200,7 +219,7 @@ static void free_bank(irlosc_ctx::Bank& b, unsigned what) {
         if (what & NEED_ROWS) fr(b.trows[i]);
         if (what & NEED_X) fr(b.xside[i]);
         if (what & NEED_LANE) fr(b.lane_rec[i]);
-        if (what == BANK_ALL) { fr(b.u[i]); fr(b.flags[i]); fr(b.list[i]); }
+        if (what == BANK_ALL) { fr(b.u[i]); fr(b.flags[i]); fr(b.list[i]); fr(b.ftw[i]); }
     }
     if (what & NEED_LANE) fr(b.lane_count);
     if (what == BANK_ALL) fr(b.count);
@@ -219,9 +238,11 @@ static void free_all(irlosc_ctx* c) {
         if (bk.st && bk.st != c->stream) (void)hipStreamDestroy(bk.st);
     }
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    if (c->ev_dev) (void)hipEventDestroy(c->ev_dev);
     for (double* p : c->dqpos) if (p) (void)hipFree(p);
     for (double* p : c->dqvel) if (p) (void)hipFree(p);
     for (double* p : c->dqt) if (p) (void)hipFree(p);
+    for (double* p : c->dsens) if (p) (void)hipFree(p);
     if (c->tick_hin) (void)hipHostFree(c->tick_hin);
     if (c->tick_din) (void)hipFree(c->tick_din);
     if (c->tick_hout) (void)hipHostFree(c->tick_hout);
@@ -266,6 +287,9 @@ static int create_impl(irlosc_ctx* c) {
     c->has_tvel.assign(g.n_slots, 0);
     c->uploaded.assign(g.n_slots, 0);
     c->targeted.assign(g.n_slots, 0);
+    c->dsens.assign(g.n_slots, nullptr);
+    c->sens_cols.assign(g.n_slots, 0);
+    c->has_sens.assign(g.n_slots, 0);
     if (c->kernel == IRLOSC_KERNEL_ROW16) {
         c->train = R16_TRAIN;
         c->nsets = R16_TRAIN;               // a train completes (give-up pass included) before the next one starts
@@ -500,6 +524,7 @@ extern "C" int irlosc_upload(irlosc_ctx* c, int32_t slot, int32_t B, const void*
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
+    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!M || !J || !dq || !ee_pose) return fail(c, IRLOSC_ERR_ARG, "M, J, dq and ee_pose are required");
     if ((c->cfg.flags & IRLOSC_USE_G) && !bias) return fail(c, IRLOSC_ERR_ARG, "bias required with IRLOSC_USE_G");
@@ -627,6 +652,7 @@ extern "C" int irlosc_upload_raw_sparse(irlosc_ctx* c, int32_t slot, int32_t B, 
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
+    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!rd || !qml || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qm layout, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
@@ -653,6 +679,7 @@ extern "C" int irlosc_upload_raw(irlosc_ctx* c, int32_t slot, int32_t B, const i
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
+    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!rd || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
@@ -678,6 +705,7 @@ extern "C" int irlosc_assemble_device(irlosc_ctx* c, int32_t slot, int32_t B, co
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
+    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!rd || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
@@ -847,11 +875,12 @@ static int check_slot_filled(irlosc_ctx* c, int slot, int B) {
     return IRLOSC_OK;
 }
 
-static int launch_slot(irlosc_ctx* c, int slot, int B) {
+// feed_wr: the wrench computed from the slot's sensor feed (a step from joint coordinates), else the record wrench of the last upload
+static int launch_slot(irlosc_ctx* c, int slot, int B, const void* feed_wr = nullptr) {
     int rcf = check_slot_filled(c, slot, B);
     if (rcf) return rcf;
     return launch(c, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
-                  c->has_tvel[slot] ? c->dtvel[slot] : nullptr, c->has_wrench[slot] ? c->dwrench[slot] : nullptr,
+                  c->has_tvel[slot] ? c->dtvel[slot] : nullptr, feed_wr ? feed_wr : c->has_wrench[slot] ? c->dwrench[slot] : nullptr,
                   c->du, c->dflags, c->stream, slot_tree(c, slot));
 }
 
@@ -1199,6 +1228,15 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         for (int i = 0; i < 6; ++i) if (c->cfg.ctrlr_dof[d][i]) h.dofmask[d] |= 1u << i;
     }
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    // a new model: the F/T description (site bodies, R_rel) and every slot's sensor feed no longer apply
+    c->ft_set = 0;
+    std::fill(c->has_sens.begin(), c->has_sens.end(), 0);
+    c->hm_nb = m->nb;
+    for (int b = 0; b < m->nb; ++b) {
+        c->hm_parent[b] = m->parent[b]; c->hm_joint[b] = m->joint_of_body[b];
+        for (int i = 0; i < 4; ++i) c->hm_quat[b][i] = m->quat[b][i];
+    }
+    for (int d = 0; d < c->cfg.ndev; ++d) c->hm_ee[d] = m->ee_body[d];
     if (!c->dmodel) HIPCHK(c, hipMalloc((void**)&c->dmodel, sizeof(FeModel)));
     c->fe_smem = frontend_smem_bytes(m->nb, m->nj);
     {
@@ -1220,6 +1258,7 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         FeCompactTables t;
         memset(&t, 0, sizeof t);
         frontend_lane_dual_ur5_tables(h, &t);
+        for (int d = 0; d < c->cfg.ndev; ++d) c->ft_qe[d] = t.eetab[d][3];
         if (!c->dtables) HIPCHK(c, hipMalloc((void**)&c->dtables, sizeof t));
         HIPCHK(c, hipMemcpyAsync(c->dtables, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));      // t lives on this stack frame (and no train of any bank is in flight)
@@ -1285,11 +1324,14 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
     return IRLOSC_OK;
 }
 
-static int frontend_launch(irlosc_ctx* c, int slot, int B) {
+// qpos / qvel: the caller's device arrays instead of the slot's coordinates, on stream `cst` (irlosc_step_from_q_device)
+static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = nullptr, const double* qvel = nullptr, hipStream_t cst = nullptr) {
     if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
-    if (!c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q must precede irlosc_frontend", slot);
+    if (!qpos && !c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q must precede irlosc_frontend", slot);
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
-    if (B > c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, front end asked for %d", slot, std::max(0, c->has_q[slot]), B);
+    if (!qpos && B > c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, front end asked for %d", slot, std::max(0, c->has_q[slot]), B);
+    if (!qpos) { qpos = c->dqpos[slot]; qvel = c->dqvel[slot]; }
+    const hipStream_t st = cst ? cst : c->stream;
     if (c->fe_lane && !c->fe_side) {
         const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
         if (hipMalloc((void**)&c->fe_side, waves * frontend_lane_dual_ur5_side_doubles_per_wave() * sizeof(double)) != hipSuccess) {
@@ -1302,12 +1344,12 @@ static int frontend_launch(irlosc_ctx* c, int slot, int B) {
     int rc;
     if (c->cfg.dtype == IRLOSC_F64) {
         const FeOut<double> o{(double*)c->dM[slot], (double*)c->dJ[slot], (double*)c->ddq[slot], (double*)c->dbias[slot], (double*)c->dee[slot]};
-        rc = c->fe_lane ? launch_frontend_lane_dual_ur5<double>(c->dmodel, c->dqpos[slot], c->dqvel[slot], o, B, c->fe_side, c->stream)
-                        : launch_frontend_generic<double>(c->dmodel, c->dqpos[slot], c->dqvel[slot], o, B, c->fe_smem, c->stream);
+        rc = c->fe_lane ? launch_frontend_lane_dual_ur5<double>(c->dmodel, qpos, qvel, o, B, c->fe_side, st)
+                        : launch_frontend_generic<double>(c->dmodel, qpos, qvel, o, B, c->fe_smem, st);
     } else {
         const FeOut<float> o{(float*)c->dM[slot], (float*)c->dJ[slot], (float*)c->ddq[slot], (float*)c->dbias[slot], (float*)c->dee[slot]};
-        rc = c->fe_lane ? launch_frontend_lane_dual_ur5<float>(c->dmodel, c->dqpos[slot], c->dqvel[slot], o, B, c->fe_side, c->stream)
-                        : launch_frontend_generic<float>(c->dmodel, c->dqpos[slot], c->dqvel[slot], o, B, c->fe_smem, c->stream);
+        rc = c->fe_lane ? launch_frontend_lane_dual_ur5<float>(c->dmodel, qpos, qvel, o, B, c->fe_side, st)
+                        : launch_frontend_generic<float>(c->dmodel, qpos, qvel, o, B, c->fe_smem, st);
     }
     HIPCHK(c, (hipError_t)rc);
     // The records of this slot are now those of B robots: an earlier, larger upload must not vouch for instances the front
@@ -1355,6 +1397,38 @@ static int check_slot_q(irlosc_ctx* c, int slot, int B) {
     return IRLOSC_OK;
 }
 
+// A step from joint coordinates over B robots of a slot with a sensor feed needs B robots of sensordata in it.
+static int check_slot_feed(irlosc_ctx* c, int slot, int B) {
+    if (c->has_sens[slot] > 0 && B > c->has_sens[slot])
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: the sensor feed holds %d robots, step asked for %d", slot, c->has_sens[slot], B);
+    return IRLOSC_OK;
+}
+
+// The wrench of the sensor feed for the n steps s[0 .. n) of a train (those whose slot has a feed): one launch, blockIdx.y = step.
+static int ft_launch(irlosc_ctx* c, const FtStep* s, int n, int B, hipStream_t st) {
+    if (n < 1 || B < 1) return IRLOSC_OK;
+    FtTrain tr;
+    memset(&tr, 0, sizeof tr);
+    for (int i = 0; i < n; ++i) tr.s[i] = s[i];
+    for (int d = 0; d < c->cfg.ndev; ++d) {
+        tr.f0[d] = c->ft_f0[d]; tr.t0[d] = c->ft_t0[d]; tr.qe[d] = c->ft_qe[d];
+        for (int i = 0; i < 9; ++i) tr.R[d][i] = c->ft_R[d][i];
+    }
+    tr.B = B; tr.ndev = c->cfg.ndev; tr.n_sensor = c->ft_n_sensor; tr.n_entries = (int32_t)c->fe_xentries;
+    HIPCHK(c, (hipError_t)(c->cfg.dtype == IRLOSC_F64 ? launch_ft_wrench<double>(tr, n, st) : launch_ft_wrench<float>(tr, n, st)));
+    return IRLOSC_OK;
+}
+
+// The wrench buffer of step i of bank k's trains for a slot with a sensor feed (nullptr: out of device memory)
+static void* feed_wrench(irlosc_ctx* c, int k, int i) {
+    void*& w = c->bank[k].ftw[i];
+    if (!dev_alloc(w, (size_t)c->cfg.max_batch * c->cfg.ndev * 6 * c->esz)) {
+        fail(c, IRLOSC_ERR_HIP, "out of device memory for the wrench of the sensor feed");
+        return nullptr;
+    }
+    return w;
+}
+
 // Bank 0 ready for a fused train of n steps, under the fused path's out-of-memory policy: without exchange buffers the path is switched
 // off for this context and the caller continues through dense records (-> false); without lane records the OSC step stays the row16
 // FROMQ kernel.  (A caller of irlosc_step_from_q needs one step's buffers, the benchmark form R16_TRAIN: 1.4 GB of exchange buffers at
@@ -1367,21 +1441,37 @@ static bool fused_ready(irlosc_ctx* c, int n) {
     return c->fused;
 }
 
+// irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
+struct DevCall {
+    const double* qpos; const double* qvel;
+    const void* tgt; const void* tvel;
+    const double* sens;
+    void* u; uint32_t* flags;
+    hipStream_t st;
+};
+
 // Fused path: one train of n steps from joint coordinates (step i: slot slots[i], outputs of set i).  Three launches -- the
 // lane-per-robot walk leaves the structural non-zeros of M / J, the bias forces and the EE poses in the compact exchange
 // buffer of each step; the task pass (one lane per (robot, device)) adds the k gained task-error rows; the row16 kernel (FROMQ)
 // stages a block's lines in LDS and gathers its operands from there -- and, fourth, the give-up pass: the few robots the
 // eigen stage hands over get their dense records from the wave-per-robot front end (worklist form) and go through the
 // generic kernel like on the record path.  Dense M / J exist in HBM for those robots only.
+// With `dv` (one step on bank 0) the caller's arrays replace every per-slot input -- coordinates (the walk reads the slot's dqt, which
+// the device entry has laid them out into), targets, sensordata -- and its u / flags the output set; the slot only lends scratch.
+// A step whose slot has a sensor feed gets its wrench from the feed (osc_ft_wrench between the walk and the OSC step).
 template <typename T>
-static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
+static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, const DevCall* dv) {
     if (n < 1 || n > R16_TRAIN) return fail(c, IRLOSC_ERR_STATE, "train of %d steps", n);
-    for (int i = 0; i < n; ++i) {
+    if (dv && (n != 1 || k != 0)) return fail(c, IRLOSC_ERR_STATE, "a device-pointer step is one step on bank 0");
+    for (int i = 0; i < n && !dv; ++i) {
         int rc = check_slot_q(c, slots[i], B);
+        if (!rc) rc = check_slot_feed(c, slots[i], B);
         if (rc) return rc;
     }
     const irlosc_ctx::Bank& bk = c->bank[k];
-    const hipStream_t st = bk.st;
+    const hipStream_t st = dv ? dv->st : bk.st;
+    FtStep fts[R16_TRAIN];
+    int nft = 0;
     FeLaneTrain ft;
     memset(&ft, 0, sizeof ft);
     Row16Train<T> tr;
@@ -1392,13 +1482,19 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
     ft.B = ga.B = B;
     for (int i = 0; i < n; ++i) {
         const int sl = slots[i];
-        ft.qpos[i] = ga.qpos[i] = c->dqpos[sl];
-        ft.qvel[i] = ga.qvel[i] = c->dqvel[sl];
+        const double* qpos = dv ? dv->qpos : c->dqpos[sl];
+        const double* qvel = dv ? dv->qvel : c->dqvel[sl];
+        const double* sens = dv ? dv->sens : c->has_sens[sl] > 0 ? c->dsens[sl] : nullptr;
+        void* wr = dv ? (dv->sens ? c->dwrench[sl] : nullptr) : sens ? feed_wrench(c, k, i) : c->has_wrench[sl] ? c->dwrench[sl] : nullptr;
+        if (sens && !wr) return IRLOSC_ERR_HIP;
+        if (sens) fts[nft++] = FtStep{sens, wr, bk.xside[i], nullptr};
+        ft.qpos[i] = ga.qpos[i] = qpos;
+        ft.qvel[i] = ga.qvel[i] = qvel;
         ft.qt[i] = c->dqt[sl];
         ft.side[i] = bk.xside[i];
-        fill_params<T>(c, tr.p[i], B, c->dM[sl], c->dJ[sl], c->ddq[sl], c->dbias[sl], c->dee[sl], c->dtgt[sl],
-                       c->has_tvel[sl] ? c->dtvel[sl] : nullptr, c->has_wrench[sl] ? c->dwrench[sl] : nullptr, bk.u[i], bk.flags[i]);
-        tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], c->dqvel[sl], c->dtables, c->span_next};
+        fill_params<T>(c, tr.p[i], B, c->dM[sl], c->dJ[sl], c->ddq[sl], c->dbias[sl], c->dee[sl], dv ? dv->tgt : c->dtgt[sl],
+                       dv ? dv->tvel : c->has_tvel[sl] ? c->dtvel[sl] : nullptr, wr, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
+        tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], qvel, c->dtables, c->span_next};
         ga.out[i] = FeOut<T>{(T*)c->dM[sl], (T*)c->dJ[sl], (T*)c->ddq[sl], (T*)c->dbias[sl], (T*)c->dee[sl]};
         ga.list[i] = bk.list[i];
         ga.count[i] = bk.count + i;
@@ -1409,7 +1505,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
     lane::LaneTrain lt;
     memset(&lt, 0, sizeof lt);
     for (int i = 0; i < n && use_lane; ++i) {
-        if (c->has_tvel[slots[i]] || !bk.lane_rec[i] || !bk.lane_count) use_lane = false;
+        if ((dv ? dv->tvel != nullptr : c->has_tvel[slots[i]] != 0) || !bk.lane_rec[i] || !bk.lane_count) use_lane = false;
         lt.qt[i] = c->dqt[slots[i]];
         lt.rec[i] = bk.lane_rec[i];
         lt.rec_count[i] = bk.lane_count + i;
@@ -1421,6 +1517,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
     if (c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
     HIPCHK(c, (hipError_t)(c->fe_lane_s ? launch_frontend_lane_compact_dual_ur5_s(c->dmodel, ft, n, st)
                                         : launch_frontend_lane_compact_dual_ur5(c->dmodel, ft, n, st)));
+    int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
+    if (rcw) return rcw;
     if (use_lane) {
         if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
         static const int eig_blocks = [] { const char* e = getenv("IRLOSC_LANE_EIG_BLOCKS"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 65536 ? v : 1024; }();
@@ -1441,12 +1539,31 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
     for (int i = 0; i < n; ++i) { c->uploaded[slots[i]] = 0; c->tree_ok[slots[i]] = 0; c->fused_away[slots[i]] = 1; }
     return IRLOSC_OK;
 }
+template <typename T>
+static int fused_train_slots(irlosc_ctx* c, const int* slots, int n, int B, int k) {
+    return fused_train<T>(c, slots, n, B, k, nullptr);
+}
 
 // `iters` steps on the fused path.  Banks are allocated only when a call chains trains: one bank per train up to FQ_BANKS.
 static int fused_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
     const int ntrains = (iters + R16_TRAIN - 1) / R16_TRAIN;
     return run_trains(c, first_slot, B, iters, c->fq_overlap ? std::min((int)irlosc_ctx::FQ_BANKS, ntrains) : 1,
-                      NEED_X | (c->lane_tier >= 0 ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? fused_train<double> : fused_train<float>);
+                      NEED_X | (c->lane_tier >= 0 ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? fused_train_slots<double> : fused_train_slots<float>);
+}
+
+// A step from the slot's coordinates through dense records: front end, the wrench of the slot's sensor feed (when it has one), step.
+static int dense_from_q_step(irlosc_ctx* c, int slot, int B) {
+    int rc = check_slot_q(c, slot, B);
+    if (!rc) rc = check_slot_feed(c, slot, B);
+    if (!rc) rc = frontend_launch(c, slot, B);
+    void* wr = nullptr;
+    if (!rc && c->has_sens[slot] > 0) {
+        if (!(wr = feed_wrench(c, 0, 0))) return IRLOSC_ERR_HIP;
+        const FtStep s{c->dsens[slot], wr, nullptr, c->dee[slot]};
+        rc = ft_launch(c, &s, 1, B, c->stream);
+    }
+    if (!rc) rc = launch_slot(c, slot, B, wr);
+    return rc;
 }
 
 extern "C" const char* irlosc_from_q_name(const irlosc_ctx* c) {
@@ -1470,13 +1587,7 @@ extern "C" int irlosc_step_from_q(irlosc_ctx* c, int32_t slot, int32_t B, void* 
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (B > 0) {
-        if (fused_ready(c, 1)) {
-            rc = fused_resident(c, slot, B, 1);
-        } else {
-            rc = check_slot_q(c, slot, B);
-            if (!rc) rc = frontend_launch(c, slot, B);
-            if (!rc) rc = launch_slot(c, slot, B);
-        }
+        rc = fused_ready(c, 1) ? fused_resident(c, slot, B, 1) : dense_from_q_step(c, slot, B);
         if (rc) return rc;
     }
     if (u_host || flags_host) return irlosc_download(c, B, u_host, flags_host);
@@ -1497,11 +1608,7 @@ extern "C" int irlosc_step_resident_from_q(irlosc_ctx* c, int32_t first_slot, in
         if (rc) return rc;
     } else {
         for (int i = 0; i < iters; ++i) {
-            const int slot = (first_slot + i) % c->cfg.n_slots;
-            rc = check_slot_q(c, slot, B);
-            if (!rc) rc = frontend_launch(c, slot, B);
-            if (rc) return rc;
-            rc = launch_slot(c, slot, B);
+            rc = dense_from_q_step(c, (first_slot + i) % c->cfg.n_slots, B);
             if (rc) return rc;
         }
     }
@@ -1512,6 +1619,142 @@ extern "C" int irlosc_step_resident_from_q(irlosc_ctx* c, int32_t first_slot, in
     if (ms_total) *ms_total = ms;
     if (ms_step_avg) *ms_step_avg = ms / (float)iters;
     return IRLOSC_OK;
+}
+
+// ---- F/T sensor feed of the steps from joint coordinates ------------------------------------------------------------
+static void quat_mat(const double* q, double* R) {      // unit quaternion (w x y z) of q -> row-major rotation
+    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double w = q[0] / nq, x = q[1] / nq, y = q[2] / nq, z = q[3] / nq;
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+    R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+    R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
+}
+static void mat_mul(const double* A, const double* B, double* C, bool at = false) {     // C = A B (at: A^T B)
+    double t[9];
+    for (int r = 0; r < 3; ++r)
+        for (int cc = 0; cc < 3; ++cc) {
+            double v = 0;
+            for (int i = 0; i < 3; ++i) v += (at ? A[i * 3 + r] : A[r * 3 + i]) * B[i * 3 + cc];
+            t[r * 3 + cc] = v;
+        }
+    memcpy(C, t, sizeof t);
+}
+
+extern "C" int irlosc_set_ft_sensors(irlosc_ctx* c, const irlosc_ft_desc* fd) {
+    if (!c) return IRLOSC_ERR_ARG;
+    if (!fd) return fail(c, IRLOSC_ERR_ARG, "desc is NULL");
+    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    const int* par = c->hm_parent;
+    int32_t f0[IRLOSC_MAX_DEV], t0[IRLOSC_MAX_DEV];
+    double R[IRLOSC_MAX_DEV][9];
+    for (int d = 0; d < c->cfg.ndev; ++d) {
+        f0[d] = t0[d] = -1;
+        for (int i = 0; i < 9; ++i) R[d][i] = (i % 4 == 0) ? 1.0 : 0.0;
+        const int sb = fd->site_body[d], e = c->hm_ee[d];
+        if (sb < 0) continue;
+        if (sb >= c->hm_nb) return fail(c, IRLOSC_ERR_ARG, "device %d: site_body %d out of [0,%d)", d, sb, c->hm_nb);
+        if (fd->n_sensor < 3) return fail(c, IRLOSC_ERR_ARG, "device %d: n_sensor=%d holds no triple", d, fd->n_sensor);
+        if (fd->ft_force0[d] < 0 || fd->ft_force0[d] > fd->n_sensor - 3 || fd->ft_torque0[d] < 0 || fd->ft_torque0[d] > fd->n_sensor - 3)
+            return fail(c, IRLOSC_ERR_ARG, "device %d: sensordata indices force %d / torque %d out of [0,%d]", d, fd->ft_force0[d],
+                        fd->ft_torque0[d], fd->n_sensor - 3);
+        // the tree path between the site body and the EE body runs through their deepest common ancestor `a` (-1: the world); every
+        // body on it below `a` must be welded to its parent
+        auto above = [&](int x, int y) { for (int z = y; z >= 0; z = par[z]) if (z == x) return true; return x < 0; };   // x ancestor-or-self of y
+        int a = e;
+        while (a >= 0 && !above(a, sb)) a = par[a];
+        double P[2][9];
+        const int ends[2] = {sb, e};
+        for (int s = 0; s < 2; ++s) {
+            for (int i = 0; i < 9; ++i) P[s][i] = (i % 4 == 0) ? 1.0 : 0.0;
+            for (int x = ends[s]; x != a; x = par[x]) {      // P = R(q_x) P, from `ends[s]` up: P = R(child of a) ... R(ends[s])
+                if (c->hm_joint[x] >= 0)
+                    return fail(c, IRLOSC_ERR_ARG, "device %d: the F/T site body %d is not rigidly attached to the EE body %d (hinge %d of body %d "
+                                "lies between them)", d, sb, e, c->hm_joint[x], x);
+                double Rx[9];
+                quat_mat(c->hm_quat[x], Rx);
+                mat_mul(Rx, P[s], P[s]);
+            }
+        }
+        double Rs[9];
+        quat_mat(fd->site_quat[d], Rs);
+        mat_mul(P[0], Rs, P[0]);                   // R(a)^T R(site) = P_site R(site_quat)
+        mat_mul(P[1], P[0], R[d], true);           // R_rel = R(ee)^T R(site) = P_ee^T P_site R(site_quat)
+        f0[d] = fd->ft_force0[d]; t0[d] = fd->ft_torque0[d];
+    }
+    for (int d = 0; d < c->cfg.ndev; ++d) {
+        c->ft_f0[d] = f0[d]; c->ft_t0[d] = t0[d];
+        for (int i = 0; i < 9; ++i) c->ft_R[d][i] = R[d][i];
+    }
+    c->ft_n_sensor = fd->n_sensor;
+    c->ft_set = 1;
+    std::fill(c->has_sens.begin(), c->has_sens.end(), 0);      // feeds laid out for another description
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_set_sensordata(irlosc_ctx* c, int32_t slot, int32_t B, const double* sensordata) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    if (B == 0 || !sensordata) { c->has_sens[slot] = 0; return IRLOSC_OK; }
+    if (!c->ft_set) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_ft_sensors has not been called");
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, ns = (size_t)c->ft_n_sensor;
+    c->has_sens[slot] = 0;
+    if (c->sens_cols[slot] < (int)ns) {
+        if (c->dsens[slot]) HIPCHK(c, hipFree(c->dsens[slot]));
+        c->dsens[slot] = nullptr; c->sens_cols[slot] = 0;
+        HIPCHK(c, hipMalloc((void**)&c->dsens[slot], Bm * ns * sizeof(double)));
+        c->sens_cols[slot] = (int)ns;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->dsens[slot], sensordata, (size_t)B * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->has_sens[slot] = B;
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_step_from_q_device(irlosc_ctx* c, int32_t slot, int32_t B, const double* d_qpos, const double* d_qvel,
+                                         const void* d_tgt_pose, const void* d_tgt_vel, const double* d_sensordata,
+                                         void* d_u, uint32_t* d_flags, void* hip_stream) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    if (B == 0) return IRLOSC_OK;
+    if (!d_qpos || !d_qvel || !d_tgt_pose || !d_u || !d_flags) return fail(c, IRLOSC_ERR_ARG, "d_qpos, d_qvel, d_tgt_pose, d_u and d_flags are required");
+    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
+    if (d_sensordata && !c->ft_set) return fail(c, IRLOSC_ERR_STATE, "d_sensordata given but irlosc_set_ft_sensors has not been called");
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
+    const bool fused = fused_ready(c, 1);      // (first call: allocates bank 0's exchange buffer / lane records on the context's stream)
+    if (fused && !c->dqt[slot])
+        HIPCHK(c, hipMalloc((void**)&c->dqt[slot], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
+    if (st != c->stream) {                     // ... and whatever else the context's stream holds comes first
+        if (!c->ev_dev) HIPCHK(c, hipEventCreateWithFlags(&c->ev_dev, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_dev, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(st, c->ev_dev, 0));
+    }
+    // from here on the slot's records and coordinates are scratch of this call
+    c->uploaded[slot] = 0;
+    c->has_q[slot] = 0;
+    c->tree_ok[slot] = 0;
+    if (d_sensordata) c->has_wrench[slot] = 0;
+    const DevCall dv{d_qpos, d_qvel, d_tgt_pose, d_tgt_vel, d_sensordata, d_u, d_flags, st};
+    if (fused) {
+        HIPCHK(c, (hipError_t)launch_q_layout(d_qpos, d_qvel, c->dqt[slot], B, c->cfg.n, st));
+        const int sl = slot;
+        rc = c->cfg.dtype == IRLOSC_F64 ? fused_train<double>(c, &sl, 1, B, 0, &dv) : fused_train<float>(c, &sl, 1, B, 0, &dv);
+    } else {
+        rc = frontend_launch(c, slot, B, d_qpos, d_qvel, st);
+        if (!rc && d_sensordata) {
+            const FtStep s{d_sensordata, c->dwrench[slot], nullptr, c->dee[slot]};
+            rc = ft_launch(c, &s, 1, B, st);
+        }
+        if (!rc) rc = launch(c, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], d_tgt_pose, d_tgt_vel,
+                             d_sensordata ? c->dwrench[slot] : nullptr, d_u, d_flags, st, slot_tree(c, slot));
+    }
+    c->uploaded[slot] = 0;                     // (the front end / fused_train mark what they wrote: none of it is the slot's state)
+    c->tree_ok[slot] = 0;
+    return rc;
 }
 
 extern "C" int irlosc_device_sync(irlosc_ctx* c) {

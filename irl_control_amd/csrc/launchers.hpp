@@ -68,6 +68,11 @@ void frontend_lane_dual_ur5_tables(const FeModel& h, FeCompactTables* t);
 size_t frontend_lane_dual_ur5_side_doubles_per_wave();
 bool frontend_lane_dual_ur5_matches(const FeModel& h);
 
+// tu_ft.hip -- the wrench of the F/T sensor feed (osc_ft.hpp): one launch per train, blockIdx.y = step with a feed; T = record type
+struct FtTrain;
+template <typename T>
+int launch_ft_wrench(const FtTrain& tr, int nsteps, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;

@@ -77,6 +77,30 @@ class RigidBodyModel:
             m.ee_body[d] = self.body_id(name)
         return m
 
+    def ft_desc(self, dev_names: List[str], sites: Dict[str, str] = None, n_sensor: int = 18) -> "_lib.FtDesc":
+        """``struct irlosc_ft_desc`` for target devices `dev_names` (targets order): device d's F/T site is sites[name] (default
+        ft_frame_<name>, the reference's F/T frames) from this model's `sites` table, its sensordata slices those of device._FT_TABLE (the
+        table raw.raw_desc uses).  Devices without an entry there get site_body = -1 (no sensor)."""
+        from .device import _FT_TABLE
+        table = {s["name"]: s for s in self.table.get("sites", [])}
+        fd = _lib.FtDesc()
+        fd.n_sensor = int(n_sensor)
+        for d in range(_lib.MAX_DEV):
+            fd.site_body[d], fd.ft_force0[d], fd.ft_torque0[d] = -1, -1, -1
+            fd.site_quat[d][0] = 1.0
+        for d, name in enumerate(dev_names):
+            ent = _FT_TABLE.get(name)
+            if ent is None:
+                continue
+            site = (sites or {}).get(name, ent[0])
+            if site not in table:
+                raise KeyError(f"site {site!r} is not in the model's sites table")
+            fd.site_body[d] = int(table[site]["body"])
+            for a in range(4):
+                fd.site_quat[d][a] = float(table[site]["quat"][a])
+            fd.ft_force0[d], fd.ft_torque0[d] = ent[1].start, ent[2].start
+        return fd
+
     def random_state(self, rng: np.random.Generator, B: int, vel_scale: float = 0.5):
         """(qpos[B,nj], qvel[B,nj]): joints with a range narrower than 3 rad (the gripper) inside it, the rest in [-pi, pi]."""
         r = self.joint_ranges
