@@ -180,6 +180,20 @@ IRLOSC_API int irlosc_slot_structure(const irlosc_ctx* ctx, int32_t slot);
  * irlosc_assemble_device on a caller's stream.  Synchronous on the context's stream -- the caller synchronises its own stream
  * first.  Returns 1 / 0 like irlosc_slot_structure (and updates that verdict), or a negative irlosc_status. */
 IRLOSC_API int irlosc_probe_structure(irlosc_ctx* ctx, int32_t slot, int32_t B);
+/* Which kernels a step of B instances on `slot` runs (B <= 0: the instances the slot holds).  IRLOSC_ROUTE_LANE: the resident lane
+ * route -- float64 records of an IRLOSC_KERNEL_AUTO context in the tree-structured form, a model set whose layout has a lane tier
+ * (irlosc_from_q_name names it), no target velocities, B >= 4096.  Records that qualify are packed once, when they enter the slot
+ * (irlosc_upload / irlosc_upload_raw / irlosc_upload_raw_sparse / irlosc_frontend / irlosc_probe_structure), into a compact block of
+ * the tree's non-zeros (3.1 KB per robot, allocated by the slot's first pack); irlosc_step and irlosc_step_resident then run the
+ * lane-per-robot OSC step of the fused path on that block, the robots it gives up on the generic kernel on the dense records, which
+ * stay in the slot.  Results differ from the row16 kernel at rounding level; flags are the same.  IRLOSC_RESIDENT_LANE=0 in the
+ * environment (read at irlosc_create) turns the route off.  kernel_name / kernel_class do not change with the route. */
+#define IRLOSC_ROUTE_NONE       0      /* bad handle or slot */
+#define IRLOSC_ROUTE_GENERIC    1
+#define IRLOSC_ROUTE_ROW16      2      /* row16 kernel, dense recursion */
+#define IRLOSC_ROUTE_ROW16_TREE 3      /* row16 kernel, tree-structured form */
+#define IRLOSC_ROUTE_LANE       4      /* lane-per-robot OSC step on the slot's compact block */
+IRLOSC_API int irlosc_slot_route(const irlosc_ctx* ctx, int32_t slot, int32_t B);
 /* Host -> device copy of the targets for slot `slot`.  tgt_vel may be NULL (all zero). */
 IRLOSC_API int irlosc_set_targets(irlosc_ctx* ctx, int32_t slot, int32_t B, const void* tgt_pose,
                        const void* tgt_vel);

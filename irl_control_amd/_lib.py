@@ -24,9 +24,11 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_comm_last_error", "irlosc_bench_allreduce", "irlosc_comm_allgather_u64", "irlosc_set_model",
            "irlosc_upload_q", "irlosc_frontend", "irlosc_step_resident_from_q", "irlosc_download_records",
            "irlosc_step_from_q", "irlosc_from_q_name", "irlosc_slot_structure", "irlosc_probe_structure", "irlosc_time_trains", "irlosc_giveup_counts",
-           "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device"]
+           "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device",
+           "irlosc_slot_route"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
+ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
 COMM_ID_BYTES = 128
 
 
@@ -132,6 +134,8 @@ def load():
     lib.irlosc_from_q_name.restype = C.c_char_p
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
+    lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.irlosc_slot_route.restype = C.c_int
     lib.irlosc_probe_structure.argtypes = [vp, C.c_int32, C.c_int32]
     lib.irlosc_probe_structure.restype = C.c_int
     lib.irlosc_tick.argtypes = [vp, i32] + [vp] * 10

@@ -236,6 +236,13 @@ class BatchedOSC:
         factors M in the tree-structured form (irlosc_slot_structure, include/irlosc.h)."""
         return bool(self.lib.irlosc_slot_structure(self._h, slot))
 
+    def slot_route(self, slot: int = 0, B: Optional[int] = None) -> str:
+        """Which kernels a step of B instances (default: the slot's) on `slot` runs (irlosc_slot_route, include/irlosc.h): "lane"
+        (the lane-per-robot OSC step on the slot's compact block), "row16_tree", "row16", "generic" or "none"."""
+        rc = self.lib.irlosc_slot_route(self._h, slot, 0 if B is None else B)
+        return {_lib.ROUTE_GENERIC: "generic", _lib.ROUTE_ROW16: "row16", _lib.ROUTE_ROW16_TREE: "row16_tree",
+                _lib.ROUTE_LANE: "lane"}.get(rc, "none")
+
     def probe_structure(self, slot: int = 0, B: Optional[int] = None) -> bool:
         """Look at the records already in `slot` (irlosc_probe_structure): what assemble_device on a caller's stream cannot
         do for itself.  -> the slot's verdict, as slot_structure() reports it from then on."""

@@ -12,6 +12,7 @@
 #include <string>
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/irlosc.h"
@@ -22,6 +23,7 @@
 #include "osc_frontend.hpp"
 #include "osc_lane_types.hpp"
 #include "osc_ft.hpp"
+#include "osc_pack.hpp"
 #include "launchers.hpp"
 
 using namespace irlosc;
@@ -125,6 +127,17 @@ struct irlosc_ctx {
     // the zero pattern of the compiled Dual-UR5 tree (probe at upload) or were written by the lane front end (by construction)
     std::vector<int> tree_ok;
     int tree_enabled = 1;              // IRLOSC_TREE=0 turns the form off (A/B measurements)
+    // Resident lane route (irlosc_step / irlosc_step_resident on float64 tree-form records of an AUTO context with a lane tier): per slot, the
+    // compact block the pack pass builds from the dense records when they enter the slot ([walk wave][n_compact][64 robots], 2.7 KB per
+    // robot) and dq in the walk's coordinate layout ([walk wave][2 n][64], entry 2 j + 1 = dq_j), allocated by the slot's first pack;
+    // lane_ok[slot] = robots packed (0: no valid block -- the slot steps on the row16 kernel)
+    int auto_kernel = 0;               // created with IRLOSC_KERNEL_AUTO
+    int resident_lane = 1;             // IRLOSC_RESIDENT_LANE=0 turns the route off (A/B measurements, tests)
+    int pack_ok = 0;                   // the model's layout has a pack table (pack_plan)
+    PackTable* dpack = nullptr;
+    int32_t* dpack_bad = nullptr;      // robots whose dropped entries were not zero (the pack's check)
+    std::vector<double*> dlblk, dlqt;
+    std::vector<int> lane_ok;
     StructureMasks tree_masks;
     int32_t* dstruct = nullptr;        // result word of the structure probe
     void* dgains = nullptr;   // [nb][ndev][12] in dtype
@@ -243,6 +256,10 @@ static void free_all(irlosc_ctx* c) {
     for (double* p : c->dqvel) if (p) (void)hipFree(p);
     for (double* p : c->dqt) if (p) (void)hipFree(p);
     for (double* p : c->dsens) if (p) (void)hipFree(p);
+    for (double* p : c->dlblk) if (p) (void)hipFree(p);
+    for (double* p : c->dlqt) if (p) (void)hipFree(p);
+    if (c->dpack) (void)hipFree(c->dpack);
+    if (c->dpack_bad) (void)hipFree(c->dpack_bad);
     if (c->tick_hin) (void)hipHostFree(c->tick_hin);
     if (c->tick_din) (void)hipFree(c->tick_din);
     if (c->tick_hout) (void)hipHostFree(c->tick_hout);
@@ -322,6 +339,13 @@ static int create_impl(irlosc_ctx* c) {
     HIPCHK(nullptr, hipMalloc((void**)&c->dsym, 2 * sizeof(int32_t)));
     HIPCHK(nullptr, hipMalloc((void**)&c->dstruct, sizeof(int32_t)));
     c->tree_ok.assign(c->cfg.n_slots, 0);
+    c->lane_ok.assign(c->cfg.n_slots, 0);
+    c->dlblk.assign(c->cfg.n_slots, nullptr);
+    c->dlqt.assign(c->cfg.n_slots, nullptr);
+    {
+        const char* e = getenv("IRLOSC_RESIDENT_LANE");
+        c->resident_lane = !(e && !strcmp(e, "0"));
+    }
     row16_tree_masks(c->tree_masks.mrow, &c->tree_masks.jcols);
     {
         const char* e = getenv("IRLOSC_TREE");
@@ -368,6 +392,7 @@ extern "C" int irlosc_create(const irlosc_cfg* cfg, irlosc_ctx** out) {
     // shape has one -- on float64 records, and on float32 records too (the "mixed" path: fp32 storage, fp64 arithmetic) -- else the
     // generic kernel.
     c->kernel = IRLOSC_KERNEL_GENERIC;
+    c->auto_kernel = cfg->kernel == IRLOSC_KERNEL_AUTO;
     if (cfg->kernel == IRLOSC_KERNEL_ROW16) c->kernel = IRLOSC_KERNEL_ROW16;
     else if (cfg->kernel == IRLOSC_KERNEL_AUTO && row16_supported(c)) c->kernel = IRLOSC_KERNEL_ROW16;
     char nm[96];
@@ -487,8 +512,11 @@ static bool slot_tree(const irlosc_ctx* c, int slot) {
 
 // Zero pattern of the records in a slot (synchronous; a throughput feature: batches under 64 instances keep the dense form).
 // The pattern is that of the compiled Dual-UR5 tree, so the question only arises for its shape (n = 25).
+static int pack_slot(irlosc_ctx* c, int slot, int B, bool check);
+
 static int structure_probe(irlosc_ctx* c, int slot, int B) {
     c->tree_ok[slot] = 0;
+    c->lane_ok[slot] = 0;
     if (!c->tree_enabled || c->kernel != IRLOSC_KERNEL_ROW16 || B < 64) return IRLOSC_OK;
     int32_t bad = 0;
     HIPCHK(c, hipMemsetAsync(c->dstruct, 0, sizeof(int32_t), c->stream));
@@ -499,7 +527,7 @@ static int structure_probe(irlosc_ctx* c, int slot, int B) {
     HIPCHK(c, hipMemcpyAsync(&bad, c->dstruct, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->tree_ok[slot] = bad == 0;
-    return IRLOSC_OK;
+    return pack_slot(c, slot, B, true);      // tree-form records of a lane-route slot: their compact block
 }
 
 extern "C" int irlosc_probe_structure(irlosc_ctx* c, int32_t slot, int32_t B) {
@@ -519,12 +547,23 @@ extern "C" int irlosc_slot_structure(const irlosc_ctx* c, int32_t slot) {
     return slot_tree(c, slot) ? 1 : 0;
 }
 
+static bool slot_lane(const irlosc_ctx* c, int slot, int B);
+
+extern "C" int irlosc_slot_route(const irlosc_ctx* c, int32_t slot, int32_t B) {
+    if (!c || slot < 0 || slot >= c->cfg.n_slots) return IRLOSC_ROUTE_NONE;
+    if (c->kernel != IRLOSC_KERNEL_ROW16) return IRLOSC_ROUTE_GENERIC;
+    if (B <= 0) B = std::max(0, c->uploaded[slot]);
+    if (B > 0 && slot_lane(c, slot, B)) return IRLOSC_ROUTE_LANE;
+    return slot_tree(c, slot) ? IRLOSC_ROUTE_ROW16_TREE : IRLOSC_ROUTE_ROW16;
+}
+
 extern "C" int irlosc_upload(irlosc_ctx* c, int32_t slot, int32_t B, const void* M, const void* J, const void* dq,
                              const void* bias, const void* ee_pose, const void* wrench) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
+    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!M || !J || !dq || !ee_pose) return fail(c, IRLOSC_ERR_ARG, "M, J, dq and ee_pose are required");
     if ((c->cfg.flags & IRLOSC_USE_G) && !bias) return fail(c, IRLOSC_ERR_ARG, "bias required with IRLOSC_USE_G");
@@ -538,6 +577,7 @@ extern "C" int irlosc_upload(irlosc_ctx* c, int32_t slot, int32_t B, const void*
     if (wrench) HIPCHK(c, hipMemcpyAsync(c->dwrench[slot], wrench, b * nd * 6 * e, hipMemcpyHostToDevice, c->stream));
     c->has_wrench[slot] = wrench != nullptr;
     c->uploaded[slot] = 0;                              // nothing usable in the slot until the records are accepted
+    c->lane_ok[slot] = 0;
     if (!c->fused_away.empty()) c->fused_away[slot] = 0;      // (and if they are refused, that is why the slot is empty -- not an earlier fused step)
     if (sym_applies(c)) {
         int rcs;
@@ -653,6 +693,7 @@ extern "C" int irlosc_upload_raw_sparse(irlosc_ctx* c, int32_t slot, int32_t B, 
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
+    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!rd || !qml || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qm layout, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
@@ -680,6 +721,7 @@ extern "C" int irlosc_upload_raw(irlosc_ctx* c, int32_t slot, int32_t B, const i
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
+    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!rd || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
@@ -706,6 +748,7 @@ extern "C" int irlosc_assemble_device(irlosc_ctx* c, int32_t slot, int32_t B, co
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
+    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!rd || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
@@ -718,7 +761,8 @@ extern "C" int irlosc_assemble_device(irlosc_ctx* c, int32_t slot, int32_t B, co
                                     : assemble_launch<float>(c, slot, B, rd, dptr, st);
     if (rc) return rc;
     c->has_wrench[slot] = 1;
-    c->tree_ok[slot] = 0;          // enqueued on the caller's stream: no synchronous look at what it writes
+    c->tree_ok[slot] = 0;          // enqueued on the caller's stream: no synchronous look at what it writes (irlosc_probe_structure: and
+                                   // the compact block of the lane route)
     c->uploaded[slot] = B;
     if (!c->fused_away.empty()) c->fused_away[slot] = 0;
     return IRLOSC_OK;
@@ -811,6 +855,97 @@ static unsigned ensure_bank(irlosc_ctx* c, int k, int n, unsigned need) {
     return 0;
 }
 
+// Resident lane route: records of at least this many robots qualify (a smaller batch keeps the row16 kernel: irlosc_tick at B = 1 pays
+// for no pack)
+static constexpr int LANE_MIN_B = 4096;
+
+// Records of B robots in the slot may take the lane route: AUTO context, float64 records, the tree verdict, a model whose layout has a
+// lane tier and a pack table, IRLOSC_RESIDENT_LANE not 0
+static bool lane_eligible(const irlosc_ctx* c, int slot, int B) {
+    return c->resident_lane && c->auto_kernel && c->cfg.dtype == IRLOSC_F64 && c->kernel == IRLOSC_KERNEL_ROW16 && c->lane_tier >= 0 &&
+           c->pack_ok && slot_tree(c, slot) && B >= LANE_MIN_B;
+}
+
+// A step of B robots on the slot takes the lane route (target velocities: the row16 kernel, as on the fused path)
+static bool slot_lane(const irlosc_ctx* c, int slot, int B) {
+    return c->lane_ok[slot] >= B && !c->has_tvel[slot] && lane_eligible(c, slot, B);
+}
+
+// The compact block of the slot's records of B robots, on the context's stream behind whatever wrote them.  `check`: the pack counts the
+// robots whose dropped entries are not zero and the block is only valid without one (synchronous; the record-form front end writes the
+// tree's zeros by construction and needs no check).  Out of device memory: no block, the slot keeps the row16 route.
+static int pack_slot(irlosc_ctx* c, int slot, int B, bool check) {
+    c->lane_ok[slot] = 0;
+    if (!lane_eligible(c, slot, B)) return IRLOSC_OK;
+    const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
+    if (!dev_alloc(c->dlblk[slot], waves * pack_entries() * 64 * sizeof(double)) ||
+        !dev_alloc(c->dlqt[slot], waves * 2 * c->cfg.n * 64 * sizeof(double)))
+        return IRLOSC_OK;
+    PackArgs a;
+    memset(&a, 0, sizeof a);
+    a.table = c->dpack;
+    a.src[PACK_M] = (const double*)c->dM[slot]; a.src[PACK_J] = (const double*)c->dJ[slot]; a.src[PACK_DQ] = (const double*)c->ddq[slot];
+    a.src[PACK_BIAS] = (const double*)c->dbias[slot]; a.src[PACK_EE] = (const double*)c->dee[slot];
+    a.blk = c->dlblk[slot]; a.dqb = c->dlqt[slot];
+    a.bad = check ? c->dpack_bad : nullptr;
+    a.B = B;
+    if (check) HIPCHK(c, hipMemsetAsync(c->dpack_bad, 0, sizeof(int32_t), c->stream));
+    HIPCHK(c, (hipError_t)launch_pack(a, c->stream));
+    if (check) {
+        int32_t bad = 0;
+        HIPCHK(c, hipMemcpyAsync(&bad, c->dpack_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bad) return IRLOSC_OK;
+    }
+    c->lane_ok[slot] = B;
+    return IRLOSC_OK;
+}
+
+// the eigen pass of the lane form: grid cap, and the flagged robots of a step from which it runs one lane per robot (below: four records
+// per wave, row16 form); the choice is made on the device, per step, from the count the lane kernel leaves (A/B measurements)
+static int lane_eig_blocks() {
+    static const int v = [] { const char* e = getenv("IRLOSC_LANE_EIG_BLOCKS"); const int x = e ? atoi(e) : 0; return x >= 64 && x <= 65536 ? x : 1024; }();
+    return v;
+}
+static int lane_eig_min() {
+    static const int v = [] { const char* e = getenv("IRLOSC_LANE_EIG_MIN"); return e ? atoi(e) : 3000; }();
+    return v;
+}
+
+// Resident lane route: a (sub-)train of n steps on bank k whose slots sl[i] hold a valid compact block -- the lane-per-robot OSC step
+// and its eigen pass read the block, the give-up pass (generic kernel) the slot's dense records, which stay valid.  ps[i]: the step's
+// parameters with its outputs; pos[i]: the step of the whole train it is (give-up list and counter of that step, as in row16_train).
+static int lane_train(irlosc_ctx* c, const KParams<double>* ps, const int* sl, int n, int k, const int* pos, bool first, bool last) {
+    if (n < 1 || n > R16_TRAIN) return fail(c, IRLOSC_ERR_STATE, "train of %d steps", n);
+    irlosc_ctx::Bank& bk = c->bank[k];
+    const hipStream_t st = bk.st;
+    if (first) HIPCHK(c, hipMemsetAsync(bk.count, 0, R16_TRAIN * sizeof(int32_t), st));
+    c->count_cur = bk.count;
+    Row16Train<double> tr;
+    memset(&tr, 0, sizeof tr);
+    lane::LaneTrain lt;
+    memset(&lt, 0, sizeof lt);
+    for (int i = 0; i < n; ++i) {
+        const int o = pos[i];
+        tr.p[i] = ps[i];
+        tr.x[i] = Row16Extra{c->dzeros, bk.list[o], bk.count + o, c->dlblk[sl[i]], nullptr, c->dtables, c->span_next, nullptr};
+        lt.qt[i] = c->dlqt[sl[i]];
+        lt.rec[i] = bk.lane_rec[i];
+        lt.rec_count[i] = bk.lane_count + i;
+    }
+    lt.map = c->lane_map;
+    HIPCHK(c, hipMemsetAsync(bk.lane_count, 0, R16_TRAIN * sizeof(int32_t), st));
+    if (first && c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
+    // (A/B builds whose lane kernel takes the task rows from a pass: it writes them into the slot's block -- the same values for every
+    //  step of the slot, whichever bank runs it)
+    if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<double>(tr, n, st, 1));
+    HIPCHK(c, (hipError_t)launch_lane_osc<double>(tr, lt, n, c->lane_tier, lane_eig_blocks(), lane_eig_min(), st));
+    if (c->span_next) HIPCHK(c, (hipError_t)launch_span_end(c->span_next, st));      // (irlosc_time_trains: the step ends with its eigen pass)
+    HIPCHK(c, (hipError_t)launch_row16_worklist<double>(tr, n, nullptr, st));
+    if (last && c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
+    return IRLOSC_OK;
+}
+
 // fp64-arithmetic path: one launch for a train of n steps (ps[i] complete with its own outputs), whatever the storage
 // type T of the records.  All instances run on the row16 kernel, the truncated pseudo-inverse included; the few it gives
 // up on (net of eigen-candidates full, degenerate A) are recomputed by the generic kernel (Jacobi, fp64 arithmetic) from
@@ -879,6 +1014,16 @@ static int check_slot_filled(irlosc_ctx* c, int slot, int B) {
 static int launch_slot(irlosc_ctx* c, int slot, int B, const void* feed_wr = nullptr) {
     int rcf = check_slot_filled(c, slot, B);
     if (rcf) return rcf;
+    if (B > 0 && c->gains_nb > 0 && !feed_wr && slot_lane(c, slot, B)) {      // the resident lane route, as irlosc_step_resident takes it
+        if (ensure_bank(c, 0, 1, NEED_LANE) == 0) {
+            KParams<double> p;
+            fill_params<double>(c, p, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot], nullptr,
+                                c->has_wrench[slot] ? c->dwrench[slot] : nullptr, c->du, c->dflags);
+            const int pos = 0;
+            return lane_train(c, &p, &slot, 1, 0, &pos, true, true);
+        }
+        free_bank(c->bank[0], NEED_LANE);
+    }
     return launch(c, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
                   c->has_tvel[slot] ? c->dtvel[slot] : nullptr, feed_wr ? feed_wr : c->has_wrench[slot] ? c->dwrench[slot] : nullptr,
                   c->du, c->dflags, c->stream, slot_tree(c, slot));
@@ -973,25 +1118,38 @@ static int run_trains(irlosc_ctx* c, int first_slot, int B, int iters, int nbank
 // A train on dense records.  One kernel per launch, so a train whose slots do not ALL qualify for the tree-structured form is issued as
 // two sub-trains -- the qualifying steps with the tree kernel, the others with the dense recursion -- instead of dropping every step to
 // the dense recursion (one more launch, only when slots are mixed).
+// Slots of the resident lane route (slot_lane) go out as a third sub-train, ahead of the other two (lane_train).
 template <typename T>
 static int dense_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
-    const irlosc_ctx::Bank& bk = c->bank[k];
-    KParams<T> ps[2][R16_TRAIN];        // [1]: steps whose slot qualifies for the tree form, [0]: the others
-    int pos[2][R16_TRAIN];              // step of the train each sub-train step is
-    int cnt[2] = {0, 0};
+    irlosc_ctx::Bank& bk = c->bank[k];
+    KParams<T> ps[3][R16_TRAIN];        // [2]: steps whose slot takes the lane route, [1]: the tree form, [0]: the others
+    int pos[3][R16_TRAIN];              // step of the train each sub-train step is
+    int sl[3][R16_TRAIN];               // its slot
+    int cnt[3] = {0, 0, 0};
+    bool lane_ok = false;               // some slot takes the route: the bank's lane records (out of memory: the row16 kernel)
+    if constexpr (std::is_same<T, double>::value)
+        for (int i = 0; i < n; ++i) lane_ok = lane_ok || slot_lane(c, slots[i], B);
+    if (lane_ok && ensure_bank(c, k, n, NEED_LANE)) { free_bank(bk, NEED_LANE); lane_ok = false; }
     for (int i = 0; i < n; ++i) {
         const int slot = slots[i];
         int rcf = check_slot_filled(c, slot, B);
         if (rcf) return rcf;
-        const int kind = slot_tree(c, slot) ? 1 : 0;
+        const int kind = lane_ok && slot_lane(c, slot, B) ? 2 : slot_tree(c, slot) ? 1 : 0;
         pos[kind][cnt[kind]] = i;
+        sl[kind][cnt[kind]] = slot;
         fill_params<T>(c, ps[kind][cnt[kind]++], B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
                        c->has_tvel[slot] ? c->dtvel[slot] : nullptr, c->has_wrench[slot] ? c->dwrench[slot] : nullptr, bk.u[i], bk.flags[i]);
     }
-    const int first = cnt[1] ? 1 : 0, last = cnt[0] ? 0 : 1;      // order: tree sub-train, then dense sub-train
-    for (int kind = 1; kind >= 0; --kind) {
+    int first = -1, last = -1;      // order: lane sub-train, tree sub-train, dense sub-train
+    for (int kind = 2; kind >= 0; --kind) if (cnt[kind]) { if (first < 0) first = kind; last = kind; }
+    for (int kind = 2; kind >= 0; --kind) {
         if (!cnt[kind]) continue;
-        int rc = row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk.st, k, pos[kind], kind == first, kind == last);
+        int rc;
+        if constexpr (std::is_same<T, double>::value)
+            rc = kind == 2 ? lane_train(c, ps[kind], sl[kind], cnt[kind], k, pos[kind], kind == first, kind == last)
+                           : row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk.st, k, pos[kind], kind == first, kind == last);
+        else
+            rc = row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk.st, k, pos[kind], kind == first, kind == last);
         if (rc) return rc;
     }
     return IRLOSC_OK;
@@ -1000,8 +1158,10 @@ static int dense_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
 // `iters` steps on the row16 path from dense records.  More than one train: odd trains on the second bank (a call of exactly one full
 // train already allocates it: a caller's warm-up then pays for it, not its timed loop).
 static int row16_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
-    return run_trains(c, first_slot, B, iters, c->r16_overlap && iters >= R16_TRAIN ? irlosc_ctx::R16_BANKS : 1, c->task_pass ? NEED_ROWS : 0,
-                      c->cfg.dtype == IRLOSC_F64 ? dense_train<double> : dense_train<float>);
+    bool lane = false;
+    for (int i = 0; i < std::min(iters, c->cfg.n_slots) && !lane; ++i) lane = slot_lane(c, (first_slot + i) % c->cfg.n_slots, B);
+    return run_trains(c, first_slot, B, iters, c->r16_overlap && iters >= R16_TRAIN ? irlosc_ctx::R16_BANKS : 1,
+                      (c->task_pass ? NEED_ROWS : 0) | (lane ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? dense_train<double> : dense_train<float>);
 }
 
 extern "C" int irlosc_step_resident(irlosc_ctx* c, int32_t first_slot, int32_t B, int32_t iters, float* ms_total,
@@ -1276,6 +1436,19 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
     } else {
         c->lane_tier = -1;
     }
+    // The resident lane route: the pack table of this layout (every slot's compact block is built again by its next upload / front end)
+    std::fill(c->lane_ok.begin(), c->lane_ok.end(), 0);
+    c->pack_ok = 0;
+    if (c->lane_tier >= 0) {
+        PackTable pt;
+        if (pack_plan(h, &pt)) {
+            if (!c->dpack) HIPCHK(c, hipMalloc((void**)&c->dpack, sizeof pt));
+            if (!c->dpack_bad) HIPCHK(c, hipMalloc((void**)&c->dpack_bad, sizeof(int32_t)));
+            HIPCHK(c, hipMemcpyAsync(c->dpack, &pt, sizeof pt, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));      // pt lives on this stack frame
+            c->pack_ok = 1;
+        }
+    }
     HIPCHK(c, hipMemcpyAsync(c->dmodel, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->dqpos.empty()) {
@@ -1328,6 +1501,7 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
 static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = nullptr, const double* qvel = nullptr, hipStream_t cst = nullptr) {
     if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
     if (!qpos && !c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q must precede irlosc_frontend", slot);
+    c->lane_ok[slot] = 0;
     if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
     if (!qpos && B > c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, front end asked for %d", slot, std::max(0, c->has_q[slot]), B);
     if (!qpos) { qpos = c->dqpos[slot]; qvel = c->dqvel[slot]; }
@@ -1357,7 +1531,8 @@ static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = 
     c->uploaded[slot] = B;
     if (!c->fused_away.empty()) c->fused_away[slot] = 0;
     c->tree_ok[slot] = c->fe_lane;     // the lane kernel walks the compiled tree: its records carry the tree's zeros by construction
-    return IRLOSC_OK;
+    // (and so need no check for the compact block of the lane route; a caller's stream gets no pack: the slot steps on the row16 kernel)
+    return cst ? IRLOSC_OK : pack_slot(c, slot, B, false);
 }
 
 extern "C" int irlosc_frontend(irlosc_ctx* c, int32_t slot, int32_t B) {
@@ -1521,11 +1696,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     if (rcw) return rcw;
     if (use_lane) {
         if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
-        static const int eig_blocks = [] { const char* e = getenv("IRLOSC_LANE_EIG_BLOCKS"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 65536 ? v : 1024; }();
-        // flagged robots of a step from which the eigen pass runs one lane per robot (below: four records per wave, row16 form); the
-        // choice is made on the device, per step, from the count the lane kernel leaves (IRLOSC_LANE_EIG_MIN: A/B measurements)
-        static const int lane_min = [] { const char* e = getenv("IRLOSC_LANE_EIG_MIN"); return e ? atoi(e) : 3000; }();
-        HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->lane_tier, eig_blocks, lane_min, st));
+        HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->lane_tier, lane_eig_blocks(), lane_eig_min(), st));
     } else {
         HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st));
     }
@@ -1536,7 +1707,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     // slots held before no longer belongs to one state.  They hold no records from here on -- irlosc_step / irlosc_step_resident
     // / irlosc_download_records on them fail with IRLOSC_ERR_STATE until irlosc_frontend / irlosc_upload* fills them again.
     if (c->fused_away.empty()) c->fused_away.assign(c->cfg.n_slots, 0);
-    for (int i = 0; i < n; ++i) { c->uploaded[slots[i]] = 0; c->tree_ok[slots[i]] = 0; c->fused_away[slots[i]] = 1; }
+    for (int i = 0; i < n; ++i) { c->uploaded[slots[i]] = 0; c->tree_ok[slots[i]] = 0; c->lane_ok[slots[i]] = 0; c->fused_away[slots[i]] = 1; }
     return IRLOSC_OK;
 }
 template <typename T>

@@ -73,6 +73,14 @@ struct FtTrain;
 template <typename T>
 int launch_ft_wrench(const FtTrain& tr, int nsteps, hipStream_t st);
 
+// tu_pack.hip -- dense records of a slot -> the compact block of the lane-per-robot OSC step (osc_pack.hpp)
+struct PackTable;
+struct PackArgs;
+bool pack_plan(const FeModel& h, PackTable* t);         // -> false: the layout has no pack (then the slots keep the row16 route)
+int pack_entries();                                     // entries per robot of the compact block (FeTopo<TopoDualUr5>::n_compact)
+int launch_pack(const PackArgs& a, hipStream_t st);
+int launch_span_end(unsigned long long* span, hipStream_t st);      // atomicMax(span + 1, wall clock) behind what the stream holds
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;
