@@ -32,17 +32,84 @@ static_assert(FT_TRAIN == R16_TRAIN, "the sensor-feed wrench kernel covers a who
 
 static thread_local std::string g_create_error;
 
+// One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
+// (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
+// the fused path is on (ensure_qt), sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
+// empty batch.
+// The state of the records and of what follows them is written by the transitions below and by nothing else.  INVARIANT: `tree` and
+// `packed` -- and so the route irlosc_slot_route reports -- are non-zero only while `records` > 0: every transition that lowers
+// `records` clears both, and only accepted() / block_packed() raise them.  (targets / has_tvel, coords and feed / sens_cols count
+// independent inputs, each written by its one entry point: irlosc_set_targets, irlosc_upload_q, irlosc_set_sensordata.)
+struct Slot {
+    // dense records
+    void *M = nullptr, *J = nullptr, *dq = nullptr, *bias = nullptr, *ee = nullptr, *wrench = nullptr;
+    int records = 0;           // instances they hold
+    int has_wrench = 0;
+    int tree = 0;              // 1: verified to carry the zero pattern of the compiled Dual-UR5 tree (probe), or written by the lane front end
+    int fused_away = 0;        // 1: invalidated by a fused step from joint coordinates (error text only)
+    // their compact block for the resident lane route ([walk wave][n_compact][64 robots], 2.7 KB per robot) and dq in the walk's
+    // coordinate layout ([walk wave][2 n][64], entry 2 j + 1 = dq_j)
+    double *blk = nullptr, *blk_dq = nullptr;
+    int packed = 0;            // robots packed (0: no valid block -- the slot steps on the row16 kernel)
+    // targets
+    void *tgt = nullptr, *tvel = nullptr;
+    int targets = 0, has_tvel = 0;
+    // joint coordinates; qt: the same in the fused walk's layout [wave][2 n][64 robots] (irlosc_upload_q writes both)
+    double *qpos = nullptr, *qvel = nullptr, *qt = nullptr;
+    int coords = 0;
+    // F/T sensor feed of the steps from joint coordinates: the sensordata (the wrench computed from it is a buffer of the step's
+    // bank, Bank::ftw)
+    double* sens = nullptr;
+    int sens_cols = 0;         // doubles per robot the buffer holds
+    int feed = 0;              // robots of the feed (0 = no feed)
+
+    // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
+    void end_feed() { feed = 0; }
+    // The compact block no longer follows the records (and, with `feed_too`, the feed ends): an upload (own wrench) or the front end (none)
+    // has named the slot -- before it looks at its other arguments: dropping the block early only costs a re-pack and is never wrong --
+    // or the model changed, for which blocks and feeds were laid out.
+    void drop_block(bool feed_too) { packed = 0; if (feed_too) end_feed(); }
+    // Records are about to be written (arguments validated, no device write yet): nothing usable in the slot until they are accepted,
+    // and if they are refused or a copy fails, that is why the slot is empty -- not an earlier fused step.
+    void writing() { records = 0; tree = 0; packed = 0; fused_away = 0; }
+    // Records of B robots are in the slot: with or without a wrench, and `tree` the verdict on them (1: probed or by construction, 0: not,
+    // or unknown).  Also a new verdict on records already there (irlosc_probe_structure).  Their block is packed after this.
+    void accepted(int B, bool wrench_, int tree_) { records = B; has_wrench = wrench_; tree = tree_; packed = 0; }
+    // An empty batch (B == 0) was uploaded.
+    void emptied() { records = -1; tree = 0; packed = 0; }
+    // A fused step's give-up pass wrote records of some robots over them: no records, and the error text says why.
+    void voided() { records = 0; tree = 0; packed = 0; fused_away = 1; }
+    // Records and coordinates (`wrench_too`: and the wrench buffer) are scratch of a device-pointer step: none of it is the slot's state.
+    void lent(bool wrench_too) { records = 0; tree = 0; packed = 0; coords = 0; if (wrench_too) has_wrench = 0; }
+    // pack_slot built the block of B robots from records it found eligible (lane_eligible: the tree verdict, so records > 0).
+    void block_packed(int B) { packed = B; }
+};
+
+// The device arrays a step reads, in the context's dtype (tvel / wrench: nullptr = none; bias: nullptr without IRLOSC_USE_G)
+struct StepInputs {
+    const void *M, *J, *dq, *bias, *ee, *tgt, *tvel, *wrench;
+};
+
+// The one way from a slot to a step's inputs: target velocities only if the slot has them; the wrench `feed_wrench` computed from a
+// sensor feed when given, else the records' own if they carry one.
+static StepInputs slot_inputs(const Slot& s, const void* feed_wrench = nullptr) {
+    return StepInputs{s.M, s.J, s.dq, s.bias, s.ee, s.tgt, s.has_tvel ? s.tvel : nullptr,
+                      feed_wrench ? feed_wrench : s.has_wrench ? s.wrench : nullptr};
+}
+
+// ... and to the record arrays a front end writes
+template <typename T>
+static FeOut<T> slot_out(const Slot& s) {
+    return FeOut<T>{(T*)s.M, (T*)s.J, (T*)s.dq, (T*)s.bias, (T*)s.ee};
+}
+
 struct irlosc_ctx {
     irlosc_cfg cfg{};
     int k = 0;
     size_t esz = 4;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // resident inputs, one set per slot
-    std::vector<void*> dM, dJ, ddq, dbias, dee, dwrench, dtgt, dtvel;
-    std::vector<int> has_wrench, has_tvel;
-    std::vector<int> uploaded, targeted;    // instances of the slot that hold state / targets (0 = nothing yet, -1 = an empty batch)
-    std::vector<int> fused_away;            // 1: the slot's dense records were invalidated by a fused step from joint coordinates (error text only)
+    std::vector<Slot> slot;            // resident inputs, one set per slot
     int nsets = 1;                     // output sets of bank 0: step i of a row16 train writes set i; the generic path only ever uses set 0
     int train = 1;                     // steps per launch in irlosc_step_resident
     hipEvent_t tev_begin = nullptr, tev_end = nullptr;   // timing events handed to the next train launch (or null)
@@ -101,20 +168,13 @@ struct irlosc_ctx {
     // FROMQ kernel stays) and its row map
     int lane_tier = -1;
     lane::RowMap lane_map{};
-    std::vector<double*> dqpos, dqvel;
-    std::vector<double*> dqt;          // per slot: the same coordinates in the fused walk's layout [wave][2 n][64 robots] (irlosc_upload_q writes both)
-    std::vector<int> has_q;
-    // F/T sensor feed of the steps from joint coordinates (irlosc_set_ft_sensors / irlosc_set_sensordata): the description, R_rel per
-    // device, and per slot the sensordata of the feed (allocated by the slot's first feed; the wrench computed from it is a buffer of
-    // the step's bank, Bank::ftw)
+    // F/T sensor feed of the steps from joint coordinates (irlosc_set_ft_sensors / irlosc_set_sensordata): the description and R_rel
+    // per device (the sensordata: Slot::sens)
     int ft_set = 0;
     int32_t ft_n_sensor = 0;
     int32_t ft_f0[IRLOSC_MAX_DEV] = {}, ft_t0[IRLOSC_MAX_DEV] = {};
     double ft_R[IRLOSC_MAX_DEV][9] = {};
     int32_t ft_qe[IRLOSC_MAX_DEV] = {};    // exchange entry of each EE's qw (FeCompactTables::eetab[d][3])
-    std::vector<double*> dsens;
-    std::vector<int> sens_cols;        // doubles per robot the slot's sensordata buffer holds
-    std::vector<int> has_sens;         // robots of the slot's feed (0 = no feed)
     // host copy of what irlosc_set_ft_sensors needs of the model: tree, body frames, EE bodies
     int hm_nb = 0;
     int32_t hm_parent[IRLOSC_MAX_BODIES] = {}, hm_joint[IRLOSC_MAX_BODIES] = {}, hm_ee[IRLOSC_MAX_DEV] = {};
@@ -123,21 +183,15 @@ struct irlosc_ctx {
     void* tick_hin = nullptr; void* tick_din = nullptr; size_t tick_in_bytes = 0;
     void* tick_hout = nullptr; void* tick_dout = nullptr; size_t tick_out_bytes = 0;
     int32_t* dsym = nullptr;  // symmetry probe of the throughput paths: {count, first instance}
-    // Tree-structured factorisation on dense records (row16 kernel): per slot, 1 when the records in it were verified to carry
-    // the zero pattern of the compiled Dual-UR5 tree (probe at upload) or were written by the lane front end (by construction)
-    std::vector<int> tree_ok;
+    // Tree-structured factorisation on dense records (row16 kernel), for slots whose records carry the tree's zeros (Slot::tree)
     int tree_enabled = 1;              // IRLOSC_TREE=0 turns the form off (A/B measurements)
-    // Resident lane route (irlosc_step / irlosc_step_resident on float64 tree-form records of an AUTO context with a lane tier): per slot, the
-    // compact block the pack pass builds from the dense records when they enter the slot ([walk wave][n_compact][64 robots], 2.7 KB per
-    // robot) and dq in the walk's coordinate layout ([walk wave][2 n][64], entry 2 j + 1 = dq_j), allocated by the slot's first pack;
-    // lane_ok[slot] = robots packed (0: no valid block -- the slot steps on the row16 kernel)
+    // Resident lane route (irlosc_step / irlosc_step_resident on float64 tree-form records of an AUTO context with a lane tier): the pack
+    // pass builds the slot's compact block from the dense records when they enter the slot (Slot::blk, Slot::packed)
     int auto_kernel = 0;               // created with IRLOSC_KERNEL_AUTO
     int resident_lane = 1;             // IRLOSC_RESIDENT_LANE=0 turns the route off (A/B measurements, tests)
     int pack_ok = 0;                   // the model's layout has a pack table (pack_plan)
     PackTable* dpack = nullptr;
     int32_t* dpack_bad = nullptr;      // robots whose dropped entries were not zero (the pack's check)
-    std::vector<double*> dlblk, dlqt;
-    std::vector<int> lane_ok;
     StructureMasks tree_masks;
     int32_t* dstruct = nullptr;        // result word of the structure probe
     void* dgains = nullptr;   // [nb][ndev][12] in dtype
@@ -238,9 +292,16 @@ static void free_bank(irlosc_ctx::Bank& b, unsigned what) {
     if (what == BANK_ALL) fr(b.count);
 }
 
+// Frees every buffer of the slot.
+static void free_slot(Slot& s) {
+    for (void* p : {s.M, s.J, s.dq, s.bias, s.ee, s.wrench, s.tgt, s.tvel, (void*)s.blk, (void*)s.blk_dq, (void*)s.qpos, (void*)s.qvel,
+                    (void*)s.qt, (void*)s.sens})
+        if (p) (void)hipFree(p);
+    s = Slot{};
+}
+
 static void free_all(irlosc_ctx* c) {
-    auto fr = [](std::vector<void*>& v) { for (void* p : v) if (p) (void)hipFree(p); v.clear(); };
-    fr(c->dM); fr(c->dJ); fr(c->ddq); fr(c->dbias); fr(c->dee); fr(c->dwrench); fr(c->dtgt); fr(c->dtvel);
+    for (Slot& s : c->slot) free_slot(s);
     if (c->draw) (void)hipFree(c->draw);
     if (c->dmodel) (void)hipFree(c->dmodel);
     if (c->fe_side) (void)hipFree(c->fe_side);
@@ -252,12 +313,6 @@ static void free_all(irlosc_ctx* c) {
     }
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_dev) (void)hipEventDestroy(c->ev_dev);
-    for (double* p : c->dqpos) if (p) (void)hipFree(p);
-    for (double* p : c->dqvel) if (p) (void)hipFree(p);
-    for (double* p : c->dqt) if (p) (void)hipFree(p);
-    for (double* p : c->dsens) if (p) (void)hipFree(p);
-    for (double* p : c->dlblk) if (p) (void)hipFree(p);
-    for (double* p : c->dlqt) if (p) (void)hipFree(p);
     if (c->dpack) (void)hipFree(c->dpack);
     if (c->dpack_bad) (void)hipFree(c->dpack_bad);
     if (c->tick_hin) (void)hipHostFree(c->tick_hin);
@@ -277,6 +332,14 @@ static void free_all(irlosc_ctx* c) {
     if (c->stream) (void)hipStreamDestroy(c->stream);
 }
 
+// The A/B switches of the environment, each read when its comment says (irlosc_create or irlosc_set_model): NAME holds `value` /
+// NAME=0 (the feature is off)
+static bool env_is(const char* name, const char* value) {
+    const char* e = getenv(name);
+    return e && !strcmp(e, value);
+}
+static bool env_off(const char* name) { return env_is(name, "0"); }
+
 static int create_impl(irlosc_ctx* c) {
     const irlosc_cfg& g = c->cfg;
     HIPCHK(nullptr, hipSetDevice(g.hip_device));
@@ -284,29 +347,12 @@ static int create_impl(irlosc_ctx* c) {
     HIPCHK(nullptr, hipEventCreate(&c->ev0));
     HIPCHK(nullptr, hipEventCreate(&c->ev1));
     const size_t B = (size_t)g.max_batch, n = (size_t)g.n, k = (size_t)c->k, nd = (size_t)g.ndev, e = c->esz;
-    auto alloc_slots = [&](std::vector<void*>& v, size_t bytes) -> hipError_t {
-        v.assign(g.n_slots, nullptr);
-        for (int s = 0; s < g.n_slots; ++s) {
-            hipError_t r = hipMalloc(&v[s], bytes);
-            if (r != hipSuccess) return r;
-        }
-        return hipSuccess;
-    };
-    HIPCHK(nullptr, alloc_slots(c->dM, B * n * n * e));
-    HIPCHK(nullptr, alloc_slots(c->dJ, B * k * n * e));
-    HIPCHK(nullptr, alloc_slots(c->ddq, B * n * e));
-    HIPCHK(nullptr, alloc_slots(c->dbias, B * n * e));
-    HIPCHK(nullptr, alloc_slots(c->dee, B * nd * 7 * e));
-    HIPCHK(nullptr, alloc_slots(c->dwrench, B * nd * 6 * e));
-    HIPCHK(nullptr, alloc_slots(c->dtgt, B * nd * 7 * e));
-    HIPCHK(nullptr, alloc_slots(c->dtvel, B * nd * 6 * e));
-    c->has_wrench.assign(g.n_slots, 0);
-    c->has_tvel.assign(g.n_slots, 0);
-    c->uploaded.assign(g.n_slots, 0);
-    c->targeted.assign(g.n_slots, 0);
-    c->dsens.assign(g.n_slots, nullptr);
-    c->sens_cols.assign(g.n_slots, 0);
-    c->has_sens.assign(g.n_slots, 0);
+    c->slot.assign(g.n_slots, Slot{});
+    const struct { void* Slot::*buf; size_t bytes; } resident[] = {
+        {&Slot::M, B * n * n * e}, {&Slot::J, B * k * n * e}, {&Slot::dq, B * n * e}, {&Slot::bias, B * n * e},
+        {&Slot::ee, B * nd * 7 * e}, {&Slot::wrench, B * nd * 6 * e}, {&Slot::tgt, B * nd * 7 * e}, {&Slot::tvel, B * nd * 6 * e}};
+    for (const auto& r : resident)
+        for (Slot& s : c->slot) HIPCHK(nullptr, hipMalloc(&(s.*r.buf), r.bytes));
     if (c->kernel == IRLOSC_KERNEL_ROW16) {
         c->train = R16_TRAIN;
         c->nsets = R16_TRAIN;               // a train completes (give-up pass included) before the next one starts
@@ -324,13 +370,10 @@ static int create_impl(irlosc_ctx* c) {
         HIPCHK(nullptr, hipMemsetAsync(c->dzeros, 0, ZB, c->stream));
         for (int k2 = 0; k2 < R16_TRAIN; ++k2) HIPCHK(nullptr, hipMalloc((void**)&b0.list[k2], B * sizeof(int32_t)));
         HIPCHK(nullptr, hipMalloc((void**)&b0.count, R16_TRAIN * sizeof(int32_t)));
-        {   // part 1 of the task signal runs as a pass ahead of the row16 kernel (IRLOSC_TASK_PASS=0: in the kernel; A/B, tests); its
-            // rows buffers are allocated by the first train that needs them (ensure_bank)
-            const char* e = getenv("IRLOSC_TASK_PASS");
-            c->task_pass = !(e && !strcmp(e, "0"));
-            const char* ov = getenv("IRLOSC_R16_OVERLAP");
-            c->r16_overlap = !(ov && !strcmp(ov, "0"));
-        }
+        // part 1 of the task signal runs as a pass ahead of the row16 kernel (IRLOSC_TASK_PASS=0: in the kernel; A/B, tests); its
+        // rows buffers are allocated by the first train that needs them (ensure_bank)
+        c->task_pass = !env_off("IRLOSC_TASK_PASS");
+        c->r16_overlap = !env_off("IRLOSC_R16_OVERLAP");
         HIPCHK(nullptr, hipMemsetAsync(b0.count, 0, R16_TRAIN * sizeof(int32_t), c->stream));
     }
     c->du = b0.u[0];
@@ -338,19 +381,9 @@ static int create_impl(irlosc_ctx* c) {
     c->count_cur = b0.count;
     HIPCHK(nullptr, hipMalloc((void**)&c->dsym, 2 * sizeof(int32_t)));
     HIPCHK(nullptr, hipMalloc((void**)&c->dstruct, sizeof(int32_t)));
-    c->tree_ok.assign(c->cfg.n_slots, 0);
-    c->lane_ok.assign(c->cfg.n_slots, 0);
-    c->dlblk.assign(c->cfg.n_slots, nullptr);
-    c->dlqt.assign(c->cfg.n_slots, nullptr);
-    {
-        const char* e = getenv("IRLOSC_RESIDENT_LANE");
-        c->resident_lane = !(e && !strcmp(e, "0"));
-    }
+    c->resident_lane = !env_off("IRLOSC_RESIDENT_LANE");
     row16_tree_masks(c->tree_masks.mrow, &c->tree_masks.jcols);
-    {
-        const char* e = getenv("IRLOSC_TREE");
-        c->tree_enabled = !(e && !strcmp(e, "0"));
-    }
+    c->tree_enabled = !env_off("IRLOSC_TREE");
     HIPCHK(nullptr, hipMalloc(&c->dgains, B * nd * IRLOSC_GAIN_WORDS * e));
     HIPCHK(nullptr, hipMalloc(&c->dnullkv, B * e));
     if (c->kernel != IRLOSC_KERNEL_GENERIC && getenv("IRLOSC_PHASE_TIMING"))     // debug aid: cycles per kernel phase
@@ -507,37 +540,63 @@ static int symmetry_verdict(irlosc_ctx* c, const int32_t res[2]) {
 
 // the tree-structured form of the row16 kernel applies to the records of this slot
 static bool slot_tree(const irlosc_ctx* c, int slot) {
-    return c->tree_enabled && c->kernel == IRLOSC_KERNEL_ROW16 && c->tree_ok[slot] != 0;
+    return c->tree_enabled && c->kernel == IRLOSC_KERNEL_ROW16 && c->slot[slot].tree != 0;
 }
 
 // Zero pattern of the records in a slot (synchronous; a throughput feature: batches under 64 instances keep the dense form).
 // The pattern is that of the compiled Dual-UR5 tree, so the question only arises for its shape (n = 25).
 static int pack_slot(irlosc_ctx* c, int slot, int B, bool check);
 
-static int structure_probe(irlosc_ctx* c, int slot, int B) {
-    c->tree_ok[slot] = 0;
-    c->lane_ok[slot] = 0;
+// -> *tree: the verdict on the first B records in the slot (0 where the question does not arise, and on failure)
+static int structure_probe(irlosc_ctx* c, const Slot& s, int B, int* tree) {
+    *tree = 0;
     if (!c->tree_enabled || c->kernel != IRLOSC_KERNEL_ROW16 || B < 64) return IRLOSC_OK;
     int32_t bad = 0;
     HIPCHK(c, hipMemsetAsync(c->dstruct, 0, sizeof(int32_t), c->stream));
     const int rc = c->cfg.dtype == IRLOSC_F64
-        ? launch_structure_probe<double>((const double*)c->dM[slot], (const double*)c->dJ[slot], c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream)
-        : launch_structure_probe<float>((const float*)c->dM[slot], (const float*)c->dJ[slot], c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream);
+        ? launch_structure_probe<double>((const double*)s.M, (const double*)s.J, c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream)
+        : launch_structure_probe<float>((const float*)s.M, (const float*)s.J, c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream);
     HIPCHK(c, (hipError_t)rc);
     HIPCHK(c, hipMemcpyAsync(&bad, c->dstruct, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->tree_ok[slot] = bad == 0;
-    return pack_slot(c, slot, B, true);      // tree-form records of a lane-route slot: their compact block
+    *tree = bad == 0;
+    return IRLOSC_OK;
+}
+
+// Shared head of the four upload entry points, right after check_slot.  -> true: an empty batch, the call is done.
+static bool upload_head(Slot& s, int B) {
+    s.drop_block(true);      // records bring a wrench of their own: the slot's sensor feed ends here (and the compact block follows the
+                             // records: rebuilt from the new ones)
+    if (B == 0) s.emptied();
+    return B == 0;
+}
+
+// Shared tail of the four upload entry points, the records of B robots written and (from the host) found symmetric: the slot holds them.
+// `probe`: they were written on the context's stream and it has drained, so their zero pattern is looked at (synchronous) and
+// tree-form records of a lane-route slot get their compact block; else the verdict is unknown (irlosc_probe_structure: and the block).
+static int upload_tail(irlosc_ctx* c, int slot, int B, bool has_wrench, bool probe) {
+    Slot& s = c->slot[slot];
+    int tree = 0;
+    if (probe) {
+        const int rc = structure_probe(c, s, B, &tree);
+        if (rc) return rc;
+    }
+    s.accepted(B, has_wrench, tree);
+    return probe ? pack_slot(c, slot, B, true) : IRLOSC_OK;
 }
 
 extern "C" int irlosc_probe_structure(irlosc_ctx* c, int32_t slot, int32_t B) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    if (B > std::max(0, c->uploaded[slot]))
-        return fail(c, IRLOSC_ERR_STATE, "slot %d holds records of %d instances, probe asked for %d", slot, std::max(0, c->uploaded[slot]), B);
+    Slot& s = c->slot[slot];
+    if (B > std::max(0, s.records))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds records of %d instances, probe asked for %d", slot, std::max(0, s.records), B);
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    rc = structure_probe(c, slot, B);
+    int tree = 0;
+    rc = structure_probe(c, s, B, &tree);
+    s.accepted(s.records, s.has_wrench, tree);      // the same records under a new verdict (none, if the probe failed)
+    if (!rc) rc = pack_slot(c, slot, B, true);
     if (rc) return rc;
     return slot_tree(c, slot) ? 1 : 0;
 }
@@ -552,7 +611,7 @@ static bool slot_lane(const irlosc_ctx* c, int slot, int B);
 extern "C" int irlosc_slot_route(const irlosc_ctx* c, int32_t slot, int32_t B) {
     if (!c || slot < 0 || slot >= c->cfg.n_slots) return IRLOSC_ROUTE_NONE;
     if (c->kernel != IRLOSC_KERNEL_ROW16) return IRLOSC_ROUTE_GENERIC;
-    if (B <= 0) B = std::max(0, c->uploaded[slot]);
+    if (B <= 0) B = std::max(0, c->slot[slot].records);
     if (B > 0 && slot_lane(c, slot, B)) return IRLOSC_ROUTE_LANE;
     return slot_tree(c, slot) ? IRLOSC_ROUTE_ROW16_TREE : IRLOSC_ROUTE_ROW16;
 }
@@ -562,30 +621,26 @@ extern "C" int irlosc_upload(irlosc_ctx* c, int32_t slot, int32_t B, const void*
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
-    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
-    if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
+    Slot& s = c->slot[slot];
+    if (upload_head(s, B)) return IRLOSC_OK;
     if (!M || !J || !dq || !ee_pose) return fail(c, IRLOSC_ERR_ARG, "M, J, dq and ee_pose are required");
     if ((c->cfg.flags & IRLOSC_USE_G) && !bias) return fail(c, IRLOSC_ERR_ARG, "bias required with IRLOSC_USE_G");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, n = (size_t)c->cfg.n, k = (size_t)c->k, nd = (size_t)c->cfg.ndev, e = c->esz;
-    HIPCHK(c, hipMemcpyAsync(c->dM[slot], M, b * n * n * e, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dJ[slot], J, b * k * n * e, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->ddq[slot], dq, b * n * e, hipMemcpyHostToDevice, c->stream));
-    if (bias) HIPCHK(c, hipMemcpyAsync(c->dbias[slot], bias, b * n * e, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dee[slot], ee_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
-    if (wrench) HIPCHK(c, hipMemcpyAsync(c->dwrench[slot], wrench, b * nd * 6 * e, hipMemcpyHostToDevice, c->stream));
-    c->has_wrench[slot] = wrench != nullptr;
-    c->uploaded[slot] = 0;                              // nothing usable in the slot until the records are accepted
-    c->lane_ok[slot] = 0;
-    if (!c->fused_away.empty()) c->fused_away[slot] = 0;      // (and if they are refused, that is why the slot is empty -- not an earlier fused step)
+    s.writing();
+    HIPCHK(c, hipMemcpyAsync(s.M, M, b * n * n * e, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.J, J, b * k * n * e, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.dq, dq, b * n * e, hipMemcpyHostToDevice, c->stream));
+    if (bias) HIPCHK(c, hipMemcpyAsync(s.bias, bias, b * n * e, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.ee, ee_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
+    if (wrench) HIPCHK(c, hipMemcpyAsync(s.wrench, wrench, b * nd * 6 * e, hipMemcpyHostToDevice, c->stream));
     if (sym_applies(c)) {
         int rcs;
         if (B <= SYM_HOST_MAX_B) {
             rcs = symmetry_host(c, M, B);
         } else {
             int32_t res[2] = {0, 0};
-            rcs = symmetry_probe(c, c->dM[slot], B, c->dsym, c->stream);
+            rcs = symmetry_probe(c, s.M, B, c->dsym, c->stream);
             if (rcs) return rcs;
             HIPCHK(c, hipMemcpyAsync(res, c->dsym, sizeof res, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -594,16 +649,12 @@ extern "C" int irlosc_upload(irlosc_ctx* c, int32_t slot, int32_t B, const void*
         if (rcs) return rcs;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    int rcp = structure_probe(c, slot, B);
-    if (rcp) return rcp;
-    c->uploaded[slot] = B;
-    if (!c->fused_away.empty()) c->fused_away[slot] = 0;
-    return IRLOSC_OK;
+    return upload_tail(c, slot, B, wrench != nullptr, true);
 }
 
 // Enqueue the assembly kernel: dptr = device pointers {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata}.
 template <typename T>
-static int assemble_launch(irlosc_ctx* c, int slot, int B, const irlosc_raw_desc* rd, const void* const* dptr, hipStream_t st,
+static int assemble_launch(irlosc_ctx* c, const Slot& s, int B, const irlosc_raw_desc* rd, const void* const* dptr, hipStream_t st,
                            const irlosc_qm_layout* qml = nullptr) {
     RawDesc d;
     memset(&d, 0, sizeof d);
@@ -624,8 +675,8 @@ static int assemble_launch(irlosc_ctx* c, int slot, int B, const irlosc_raw_desc
     r.qM = (const T*)dptr[0]; r.qvel = (const T*)dptr[1]; r.qfrc_bias = (const T*)dptr[2];
     r.jacp = (const T*)dptr[3]; r.jacr = (const T*)dptr[4]; r.ee_xpos = (const T*)dptr[5]; r.ee_xquat = (const T*)dptr[6];
     r.site_xmat = ft ? (const T*)dptr[7] : nullptr; r.sensordata = ft ? (const T*)dptr[8] : nullptr;
-    r.M = (T*)c->dM[slot]; r.J = (T*)c->dJ[slot]; r.dq = (T*)c->ddq[slot]; r.bias = (T*)c->dbias[slot];
-    r.ee = (T*)c->dee[slot]; r.wrench = (T*)c->dwrench[slot];
+    const FeOut<T> o = slot_out<T>(s);
+    r.M = o.M; r.J = o.J; r.dq = o.dq; r.bias = o.bias; r.ee = o.ee; r.wrench = (T*)s.wrench;
     HIPCHK(c, (hipError_t)launch_assemble<T>(d, r, B, st));
     return IRLOSC_OK;
 }
@@ -645,15 +696,12 @@ static int check_raw_desc(irlosc_ctx* c, const irlosc_raw_desc* rd) {
 }
 
 template <typename T>
-static int upload_raw_t(irlosc_ctx* c, int slot, int B, const irlosc_raw_desc* rd, const void* qM, const void* qvel,
-                        const void* qfrc_bias, const void* jacp, const void* jacr, const void* ee_xpos,
-                        const void* ee_xquat, const void* site_xmat, const void* sensordata, const irlosc_qm_layout* qml = nullptr) {
+static int upload_raw_t(irlosc_ctx* c, const Slot& s, int B, const irlosc_raw_desc* rd, const void* const* src, const irlosc_qm_layout* qml) {
     const size_t b = (size_t)B, nv = (size_t)rd->nv, nd = (size_t)c->cfg.ndev, ns = (size_t)rd->n_sensor, e = sizeof(T);
-    const bool ft = site_xmat && sensordata && ns > 0;
+    const bool ft = src[7] && src[8] && ns > 0;
     // staging layout: qM (dense nv x nv, or MuJoCo's nM-entry form) | qvel | qfrc_bias | jacp | jacr | ee_xpos | ee_xquat | site_xmat | sensordata
     const size_t sz[9] = {qml ? b * (size_t)qml->nM * e : b * nv * nv * e, b * nv * e, b * nv * e, b * nd * 3 * nv * e, b * nd * 3 * nv * e,
                           b * nd * 3 * e, b * nd * 4 * e, ft ? b * nd * 9 * e : 0, ft ? b * ns * e : 0};
-    const void* src[9] = {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata};
     size_t off[9], total = 0;
     for (int i = 0; i < 9; ++i) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
     if (total > c->draw_bytes) {
@@ -667,7 +715,7 @@ static int upload_raw_t(irlosc_ctx* c, int slot, int B, const irlosc_raw_desc* r
         if (sz[i]) HIPCHK(c, hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, c->stream));
     const void* dptr[9];
     for (int i = 0; i < 9; ++i) dptr[i] = sz[i] ? (const void*)(base + off[i]) : nullptr;
-    int rc = assemble_launch<T>(c, slot, B, rd, dptr, c->stream, qml);
+    int rc = assemble_launch<T>(c, s, B, rd, dptr, c->stream, qml);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
@@ -686,31 +734,34 @@ static int check_qm_layout(irlosc_ctx* c, const irlosc_raw_desc* rd, const irlos
     return IRLOSC_OK;
 }
 
+// What the three raw entry points share behind their own argument checks: the description checked, then the records of B robots
+// assembled into the slot from src = {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata} -- host arrays through
+// the staging block on the context's stream (st == nullptr; synchronous, and probed: the expansion of `qml` mirrors every entry, the
+// dense form is the caller's), or device arrays on `st` (enqueued: no synchronous look at what it writes).
+static int raw_records(irlosc_ctx* c, int slot, int B, const irlosc_raw_desc* rd, const irlosc_qm_layout* qml, const void* const* src, hipStream_t st) {
+    int rc = check_raw_desc(c, rd);
+    if (!rc && qml) rc = check_qm_layout(c, rd, qml);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Slot& s = c->slot[slot];
+    s.writing();
+    if (c->cfg.dtype == IRLOSC_F64) rc = st ? assemble_launch<double>(c, s, B, rd, src, st) : upload_raw_t<double>(c, s, B, rd, src, qml);
+    else rc = st ? assemble_launch<float>(c, s, B, rd, src, st) : upload_raw_t<float>(c, s, B, rd, src, qml);
+    if (rc) return rc;
+    return upload_tail(c, slot, B, true, st == nullptr);
+}
+
 extern "C" int irlosc_upload_raw_sparse(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_raw_desc* rd, const irlosc_qm_layout* qml,
                                         const void* qM, const void* qvel, const void* qfrc_bias, const void* jacp, const void* jacr,
                                         const void* ee_xpos, const void* ee_xquat, const void* site_xmat, const void* sensordata) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
-    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
-    if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
+    if (upload_head(c->slot[slot], B)) return IRLOSC_OK;
     if (!rd || !qml || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qm layout, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
-    rc = check_raw_desc(c, rd);
-    if (!rc) rc = check_qm_layout(c, rd, qml);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    rc = c->cfg.dtype == IRLOSC_F64
-             ? upload_raw_t<double>(c, slot, B, rd, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata, qml)
-             : upload_raw_t<float>(c, slot, B, rd, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata, qml);
-    if (rc) return rc;
-    c->has_wrench[slot] = 1;
-    rc = structure_probe(c, slot, B);      // (symmetric by construction: the expansion mirrors every entry)
-    if (rc) return rc;
-    c->uploaded[slot] = B;
-    if (!c->fused_away.empty()) c->fused_away[slot] = 0;
-    return IRLOSC_OK;
+    const void* src[9] = {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata};
+    return raw_records(c, slot, B, rd, qml, src, nullptr);
 }
 
 extern "C" int irlosc_upload_raw(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_raw_desc* rd, const void* qM,
@@ -720,24 +771,11 @@ extern "C" int irlosc_upload_raw(irlosc_ctx* c, int32_t slot, int32_t B, const i
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
-    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
-    if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
+    if (upload_head(c->slot[slot], B)) return IRLOSC_OK;
     if (!rd || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
-    rc = check_raw_desc(c, rd);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    rc = c->cfg.dtype == IRLOSC_F64
-             ? upload_raw_t<double>(c, slot, B, rd, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata)
-             : upload_raw_t<float>(c, slot, B, rd, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata);
-    if (rc) return rc;
-    c->has_wrench[slot] = 1;
-    rc = structure_probe(c, slot, B);
-    if (rc) return rc;
-    c->uploaded[slot] = B;
-    if (!c->fused_away.empty()) c->fused_away[slot] = 0;
-    return IRLOSC_OK;
+    const void* src[9] = {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata};
+    return raw_records(c, slot, B, rd, nullptr, src, nullptr);
 }
 
 extern "C" int irlosc_assemble_device(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_raw_desc* rd, const void* qM,
@@ -747,50 +785,35 @@ extern "C" int irlosc_assemble_device(irlosc_ctx* c, int32_t slot, int32_t B, co
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    c->has_sens[slot] = 0;                 // records bring a wrench of their own: the slot's sensor feed ends here
-    c->lane_ok[slot] = 0;                  // (the compact block follows the records: rebuilt by the probe of the new ones)
-    if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
+    if (upload_head(c->slot[slot], B)) return IRLOSC_OK;
     if (!rd || !qM || !qvel || !qfrc_bias || !jacp || !jacr || !ee_xpos || !ee_xquat)
         return fail(c, IRLOSC_ERR_ARG, "desc, qM, qvel, qfrc_bias, jacp, jacr, ee_xpos and ee_xquat are required");
-    rc = check_raw_desc(c, rd);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    const void* dptr[9] = {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata};
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    rc = c->cfg.dtype == IRLOSC_F64 ? assemble_launch<double>(c, slot, B, rd, dptr, st)
-                                    : assemble_launch<float>(c, slot, B, rd, dptr, st);
-    if (rc) return rc;
-    c->has_wrench[slot] = 1;
-    c->tree_ok[slot] = 0;          // enqueued on the caller's stream: no synchronous look at what it writes (irlosc_probe_structure: and
-                                   // the compact block of the lane route)
-    c->uploaded[slot] = B;
-    if (!c->fused_away.empty()) c->fused_away[slot] = 0;
-    return IRLOSC_OK;
+    const void* src[9] = {qM, qvel, qfrc_bias, jacp, jacr, ee_xpos, ee_xquat, site_xmat, sensordata};
+    return raw_records(c, slot, B, rd, nullptr, src, hip_stream ? (hipStream_t)hip_stream : c->stream);
 }
 
 extern "C" int irlosc_set_targets(irlosc_ctx* c, int32_t slot, int32_t B, const void* tgt_pose, const void* tgt_vel) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    if (B == 0) { c->targeted[slot] = -1; return IRLOSC_OK; }
+    Slot& s = c->slot[slot];
+    if (B == 0) { s.targets = -1; return IRLOSC_OK; }
     if (!tgt_pose) return fail(c, IRLOSC_ERR_ARG, "tgt_pose is NULL");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, nd = (size_t)c->cfg.ndev, e = c->esz;
-    HIPCHK(c, hipMemcpyAsync(c->dtgt[slot], tgt_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
-    if (tgt_vel) HIPCHK(c, hipMemcpyAsync(c->dtvel[slot], tgt_vel, b * nd * 6 * e, hipMemcpyHostToDevice, c->stream));
-    c->has_tvel[slot] = tgt_vel != nullptr;
+    HIPCHK(c, hipMemcpyAsync(s.tgt, tgt_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
+    if (tgt_vel) HIPCHK(c, hipMemcpyAsync(s.tvel, tgt_vel, b * nd * 6 * e, hipMemcpyHostToDevice, c->stream));
+    s.has_tvel = tgt_vel != nullptr;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->targeted[slot] = B;
+    s.targets = B;
     return IRLOSC_OK;
 }
 
 template <typename T>
-static void fill_params(const irlosc_ctx* c, KParams<T>& p, int B, const void* M, const void* J, const void* dq,
-                        const void* bias, const void* ee, const void* tgt, const void* tvel, const void* wrench,
-                        void* u, uint32_t* flags) {
+static void fill_params(const irlosc_ctx* c, KParams<T>& p, int B, const StepInputs& in, void* u, uint32_t* flags) {
     memset(&p, 0, sizeof p);
-    p.M = (const T*)M; p.J = (const T*)J; p.dq = (const T*)dq; p.bias = (const T*)bias;
-    p.ee = (const T*)ee; p.tgt = (const T*)tgt; p.tvel = (const T*)tvel; p.wrench = (const T*)wrench;
+    p.M = (const T*)in.M; p.J = (const T*)in.J; p.dq = (const T*)in.dq; p.bias = (const T*)in.bias;
+    p.ee = (const T*)in.ee; p.tgt = (const T*)in.tgt; p.tvel = (const T*)in.tvel; p.wrench = (const T*)in.wrench;
     p.u = (T*)u; p.flags = flags;
     p.gains = (const T*)c->dgains; p.null_kv = (const T*)c->dnullkv;
     p.index = nullptr;
@@ -855,6 +878,12 @@ static unsigned ensure_bank(irlosc_ctx* c, int k, int n, unsigned need) {
     return 0;
 }
 
+// Bytes of a coordinate buffer in the fused walk's layout [walk wave][2 n][64 robots] (Slot::qt, Slot::blk_dq)
+static size_t qt_bytes(const irlosc_ctx* c) { return (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double); }
+
+// The slot's qt, allocated by its first use while the fused path is on.
+static hipError_t ensure_qt(const irlosc_ctx* c, Slot& s) { return s.qt ? hipSuccess : hipMalloc((void**)&s.qt, qt_bytes(c)); }
+
 // Resident lane route: records of at least this many robots qualify (a smaller batch keeps the row16 kernel: irlosc_tick at B = 1 pays
 // for no pack)
 static constexpr int LANE_MIN_B = 4096;
@@ -868,25 +897,24 @@ static bool lane_eligible(const irlosc_ctx* c, int slot, int B) {
 
 // A step of B robots on the slot takes the lane route (target velocities: the row16 kernel, as on the fused path)
 static bool slot_lane(const irlosc_ctx* c, int slot, int B) {
-    return c->lane_ok[slot] >= B && !c->has_tvel[slot] && lane_eligible(c, slot, B);
+    return c->slot[slot].packed >= B && !c->slot[slot].has_tvel && lane_eligible(c, slot, B);
 }
 
 // The compact block of the slot's records of B robots, on the context's stream behind whatever wrote them.  `check`: the pack counts the
 // robots whose dropped entries are not zero and the block is only valid without one (synchronous; the record-form front end writes the
 // tree's zeros by construction and needs no check).  Out of device memory: no block, the slot keeps the row16 route.
+// Called behind accepted(), which has dropped the block of the records before.
 static int pack_slot(irlosc_ctx* c, int slot, int B, bool check) {
-    c->lane_ok[slot] = 0;
+    Slot& s = c->slot[slot];
     if (!lane_eligible(c, slot, B)) return IRLOSC_OK;
     const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
-    if (!dev_alloc(c->dlblk[slot], waves * pack_entries() * 64 * sizeof(double)) ||
-        !dev_alloc(c->dlqt[slot], waves * 2 * c->cfg.n * 64 * sizeof(double)))
-        return IRLOSC_OK;
+    if (!dev_alloc(s.blk, waves * pack_entries() * 64 * sizeof(double)) || !dev_alloc(s.blk_dq, qt_bytes(c))) return IRLOSC_OK;
     PackArgs a;
     memset(&a, 0, sizeof a);
     a.table = c->dpack;
-    a.src[PACK_M] = (const double*)c->dM[slot]; a.src[PACK_J] = (const double*)c->dJ[slot]; a.src[PACK_DQ] = (const double*)c->ddq[slot];
-    a.src[PACK_BIAS] = (const double*)c->dbias[slot]; a.src[PACK_EE] = (const double*)c->dee[slot];
-    a.blk = c->dlblk[slot]; a.dqb = c->dlqt[slot];
+    const FeOut<double> rec = slot_out<double>(s);
+    a.src[PACK_M] = rec.M; a.src[PACK_J] = rec.J; a.src[PACK_DQ] = rec.dq; a.src[PACK_BIAS] = rec.bias; a.src[PACK_EE] = rec.ee;
+    a.blk = s.blk; a.dqb = s.blk_dq;
     a.bad = check ? c->dpack_bad : nullptr;
     a.B = B;
     if (check) HIPCHK(c, hipMemsetAsync(c->dpack_bad, 0, sizeof(int32_t), c->stream));
@@ -897,7 +925,7 @@ static int pack_slot(irlosc_ctx* c, int slot, int B, bool check) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (bad) return IRLOSC_OK;
     }
-    c->lane_ok[slot] = B;
+    s.block_packed(B);
     return IRLOSC_OK;
 }
 
@@ -928,8 +956,8 @@ static int lane_train(irlosc_ctx* c, const KParams<double>* ps, const int* sl, i
     for (int i = 0; i < n; ++i) {
         const int o = pos[i];
         tr.p[i] = ps[i];
-        tr.x[i] = Row16Extra{c->dzeros, bk.list[o], bk.count + o, c->dlblk[sl[i]], nullptr, c->dtables, c->span_next, nullptr};
-        lt.qt[i] = c->dlqt[sl[i]];
+        tr.x[i] = Row16Extra{c->dzeros, bk.list[o], bk.count + o, c->slot[sl[i]].blk, nullptr, c->dtables, c->span_next, nullptr};
+        lt.qt[i] = c->slot[sl[i]].blk_dq;
         lt.rec[i] = bk.lane_rec[i];
         lt.rec_count[i] = bk.lane_count + i;
     }
@@ -978,35 +1006,32 @@ static int row16_train(irlosc_ctx* c, const KParams<T>* ps, int n, bool tree, hi
 }
 
 template <typename T>
-static int launch_t(irlosc_ctx* c, int B, const void* M, const void* J, const void* dq, const void* bias,
-                    const void* ee, const void* tgt, const void* tvel, const void* wrench, void* u,
-                    uint32_t* flags, hipStream_t st, bool tree) {
+static int launch_t(irlosc_ctx* c, int B, const StepInputs& in, void* u, uint32_t* flags, hipStream_t st, bool tree) {
     KParams<T> p;
-    fill_params<T>(c, p, B, M, J, dq, bias, ee, tgt, tvel, wrench, u, flags);
+    fill_params<T>(c, p, B, in, u, flags);
     if (c->kernel == IRLOSC_KERNEL_ROW16) return row16_train<T>(c, &p, 1, tree, st);
     HIPCHK(c, (hipError_t)launch_generic<T>(p, B, st));
     return IRLOSC_OK;
 }
 
-static int launch(irlosc_ctx* c, int B, const void* M, const void* J, const void* dq, const void* bias,
-                  const void* ee, const void* tgt, const void* tvel, const void* wrench, void* u,
-                  uint32_t* flags, hipStream_t st, bool tree = false) {
+static int launch(irlosc_ctx* c, int B, const StepInputs& in, void* u, uint32_t* flags, hipStream_t st, bool tree = false) {
     if (B == 0) return IRLOSC_OK;
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
-    if (c->cfg.dtype == IRLOSC_F64) return launch_t<double>(c, B, M, J, dq, bias, ee, tgt, tvel, wrench, u, flags, st, tree);
-    return launch_t<float>(c, B, M, J, dq, bias, ee, tgt, tvel, wrench, u, flags, st, tree);
+    if (c->cfg.dtype == IRLOSC_F64) return launch_t<double>(c, B, in, u, flags, st, tree);
+    return launch_t<float>(c, B, in, u, flags, st, tree);
 }
 
 // A step over B instances needs B instances of state AND of targets in the slot (stale or uninitialised HBM otherwise).
 static int check_slot_filled(irlosc_ctx* c, int slot, int B) {
-    if (!c->uploaded[slot] && !c->fused_away.empty() && c->fused_away[slot])
+    const Slot& s = c->slot[slot];
+    if (!s.records && s.fused_away)
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds no dense records: the preceding fused irlosc_step_from_q / irlosc_step_resident_from_q "
                     "invalidated them (it never writes M / J); run irlosc_frontend or an upload first", slot);
-    if (!c->uploaded[slot] || !c->targeted[slot])
+    if (!s.records || !s.targets)
         return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload and irlosc_set_targets must precede a step", slot);
-    if (B > std::max(0, c->uploaded[slot]) || B > std::max(0, c->targeted[slot]))
+    if (B > std::max(0, s.records) || B > std::max(0, s.targets))
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds state for %d and targets for %d instances, step asked for %d", slot,
-                    std::max(0, c->uploaded[slot]), std::max(0, c->targeted[slot]), B);
+                    std::max(0, s.records), std::max(0, s.targets), B);
     return IRLOSC_OK;
 }
 
@@ -1017,16 +1042,13 @@ static int launch_slot(irlosc_ctx* c, int slot, int B, const void* feed_wr = nul
     if (B > 0 && c->gains_nb > 0 && !feed_wr && slot_lane(c, slot, B)) {      // the resident lane route, as irlosc_step_resident takes it
         if (ensure_bank(c, 0, 1, NEED_LANE) == 0) {
             KParams<double> p;
-            fill_params<double>(c, p, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot], nullptr,
-                                c->has_wrench[slot] ? c->dwrench[slot] : nullptr, c->du, c->dflags);
+            fill_params<double>(c, p, B, slot_inputs(c->slot[slot]), c->du, c->dflags);
             const int pos = 0;
             return lane_train(c, &p, &slot, 1, 0, &pos, true, true);
         }
         free_bank(c->bank[0], NEED_LANE);
     }
-    return launch(c, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
-                  c->has_tvel[slot] ? c->dtvel[slot] : nullptr, feed_wr ? feed_wr : c->has_wrench[slot] ? c->dwrench[slot] : nullptr,
-                  c->du, c->dflags, c->stream, slot_tree(c, slot));
+    return launch(c, B, slot_inputs(c->slot[slot], feed_wr), c->du, c->dflags, c->stream, slot_tree(c, slot));
 }
 
 extern "C" int irlosc_download(irlosc_ctx* c, int32_t B, void* u_host, uint32_t* flags_host) {
@@ -1137,8 +1159,7 @@ static int dense_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
         const int kind = lane_ok && slot_lane(c, slot, B) ? 2 : slot_tree(c, slot) ? 1 : 0;
         pos[kind][cnt[kind]] = i;
         sl[kind][cnt[kind]] = slot;
-        fill_params<T>(c, ps[kind][cnt[kind]++], B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], c->dtgt[slot],
-                       c->has_tvel[slot] ? c->dtvel[slot] : nullptr, c->has_wrench[slot] ? c->dwrench[slot] : nullptr, bk.u[i], bk.flags[i]);
+        fill_params<T>(c, ps[kind][cnt[kind]++], B, slot_inputs(c->slot[slot]), bk.u[i], bk.flags[i]);
     }
     int first = -1, last = -1;      // order: lane sub-train, tree sub-train, dense sub-train
     for (int kind = 2; kind >= 0; --kind) if (cnt[kind]) { if (first < 0) first = kind; last = kind; }
@@ -1164,8 +1185,10 @@ static int row16_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
                       (c->task_pass ? NEED_ROWS : 0) | (lane ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? dense_train<double> : dense_train<float>);
 }
 
-extern "C" int irlosc_step_resident(irlosc_ctx* c, int32_t first_slot, int32_t B, int32_t iters, float* ms_total,
-                                    float* ms_kernel_avg) {
+// The shared frame of irlosc_step_resident and irlosc_step_resident_from_q: the argument checks, `steps()` (the `iters` steps, enqueued)
+// between the context's event pair, and the time of the whole and per step.
+template <typename Steps>
+static int timed_resident(irlosc_ctx* c, int first_slot, int B, int iters, float* ms_total, float* ms_avg, Steps steps) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, first_slot, B);
     if (rc) return rc;
@@ -1173,22 +1196,25 @@ extern "C" int irlosc_step_resident(irlosc_ctx* c, int32_t first_slot, int32_t B
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (c->kernel == IRLOSC_KERNEL_ROW16 && B > 0) {
-        rc = row16_resident(c, first_slot, B, iters);
-        if (rc) return rc;
-    } else {
-        for (int i = 0; i < iters; ++i) {
-            rc = launch_slot(c, (first_slot + i) % c->cfg.n_slots, B);
-            if (rc) return rc;
-        }
-    }
+    rc = steps();
+    if (rc) return rc;
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev1));
     float ms = 0.f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     if (ms_total) *ms_total = ms;
-    if (ms_kernel_avg) *ms_kernel_avg = ms / (float)iters;
+    if (ms_avg) *ms_avg = ms / (float)iters;
     return IRLOSC_OK;
+}
+
+extern "C" int irlosc_step_resident(irlosc_ctx* c, int32_t first_slot, int32_t B, int32_t iters, float* ms_total,
+                                    float* ms_kernel_avg) {
+    return timed_resident(c, first_slot, B, iters, ms_total, ms_kernel_avg, [&] {
+        if (c->kernel == IRLOSC_KERNEL_ROW16 && B > 0) return row16_resident(c, first_slot, B, iters);
+        int rc = IRLOSC_OK;
+        for (int i = 0; i < iters && !rc; ++i) rc = launch_slot(c, (first_slot + i) % c->cfg.n_slots, B);
+        return rc;
+    });
 }
 
 extern "C" int irlosc_steps_per_launch(const irlosc_ctx* c) {
@@ -1389,8 +1415,9 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
     }
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     // a new model: the F/T description (site bodies, R_rel) and every slot's sensor feed no longer apply
+    // (and the pack table: every slot's compact block is built again by its next upload / front end)
     c->ft_set = 0;
-    std::fill(c->has_sens.begin(), c->has_sens.end(), 0);
+    for (Slot& s : c->slot) s.drop_block(true);
     c->hm_nb = m->nb;
     for (int b = 0; b < m->nb; ++b) {
         c->hm_parent[b] = m->parent[b]; c->hm_joint[b] = m->joint_of_body[b];
@@ -1399,21 +1426,16 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
     for (int d = 0; d < c->cfg.ndev; ++d) c->hm_ee[d] = m->ee_body[d];
     if (!c->dmodel) HIPCHK(c, hipMalloc((void**)&c->dmodel, sizeof(FeModel)));
     c->fe_smem = frontend_smem_bytes(m->nb, m->nj);
-    {
-        const char* e = getenv("IRLOSC_FRONTEND");           // "generic": force the wave-per-instance kernel (A/B measurements)
-        c->fe_lane = frontend_lane_dual_ur5_matches(h) && !(e && !strcmp(e, "generic"));
-        const char* w = getenv("IRLOSC_WALK");               // "general": the shape-only walk on the fused path (A/B measurements, tests)
-        c->fe_lane_s = c->fe_lane && frontend_lane_dual_ur5_s_matches(h) && !(w && !strcmp(w, "general"));
-    }
+    // IRLOSC_FRONTEND=generic: force the wave-per-instance kernel (A/B measurements); IRLOSC_WALK=general: the shape-only walk on the
+    // fused path (A/B measurements, tests)
+    c->fe_lane = frontend_lane_dual_ur5_matches(h) && !env_is("IRLOSC_FRONTEND", "generic");
+    c->fe_lane_s = c->fe_lane && frontend_lane_dual_ur5_s_matches(h) && !env_is("IRLOSC_WALK", "general");
     // (the lane kernel's side buffer -- 139 MB at 65 536 robots -- is allocated by the first irlosc_frontend: a context that only
     // ever takes the fused path never needs it)
-    {   // The fused path needs the compiled tree shape (lane kernel) and the fp64 row16 kernel; IRLOSC_FUSED=0 forces the
-        // two-kernel path through dense records (A/B measurements).
-        const char* e = getenv("IRLOSC_FUSED");
-        c->fused = c->fe_lane && c->kernel == IRLOSC_KERNEL_ROW16 && !(e && !strcmp(e, "0"));
-        const char* ov = getenv("IRLOSC_FQ_OVERLAP");      // "0": consecutive fused trains on one stream (A/B measurements, tests)
-        c->fq_overlap = !(ov && !strcmp(ov, "0"));
-    }
+    // The fused path needs the compiled tree shape (lane kernel) and the fp64 row16 kernel; IRLOSC_FUSED=0 forces the
+    // two-kernel path through dense records (A/B measurements).
+    c->fused = c->fe_lane && c->kernel == IRLOSC_KERNEL_ROW16 && !env_off("IRLOSC_FUSED");
+    c->fq_overlap = !env_off("IRLOSC_FQ_OVERLAP");      // "0": consecutive fused trains on one stream (A/B measurements, tests)
     if (c->fused) {
         FeCompactTables t;
         memset(&t, 0, sizeof t);
@@ -1425,9 +1447,8 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         // The OSC step behind the walk: lane-per-robot form when an instantiation holds this layout (IRLOSC_LANE=0: the row16 FROMQ
         // kernel, A/B measurements and tests).  Every bank's exchange buffers and lane records start over with another entry count or
         // layout (they are allocated again by the first fused train: ensure_bank).
-        const char* le = getenv("IRLOSC_LANE");
         lane::RowMap map;
-        const int tier = (le && !strcmp(le, "0")) ? -1 : lane_plan(h, &map);
+        const int tier = env_off("IRLOSC_LANE") ? -1 : lane_plan(h, &map);
         if (t.n_entries != c->fe_xentries || tier != c->lane_tier || (tier >= 0 && memcmp(&map, &c->lane_map, sizeof map)))
             for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
         c->fe_xentries = t.n_entries;
@@ -1436,8 +1457,7 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
     } else {
         c->lane_tier = -1;
     }
-    // The resident lane route: the pack table of this layout (every slot's compact block is built again by its next upload / front end)
-    std::fill(c->lane_ok.begin(), c->lane_ok.end(), 0);
+    // The resident lane route: the pack table of this layout
     c->pack_ok = 0;
     if (c->lane_tier >= 0) {
         PackTable pt;
@@ -1451,21 +1471,15 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
     }
     HIPCHK(c, hipMemcpyAsync(c->dmodel, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->dqpos.empty()) {
-        c->dqpos.assign(c->cfg.n_slots, nullptr);
-        c->dqvel.assign(c->cfg.n_slots, nullptr);
-        c->dqt.assign(c->cfg.n_slots, nullptr);
-        c->has_q.assign(c->cfg.n_slots, 0);
-        for (int s2 = 0; s2 < c->cfg.n_slots; ++s2) {
-            HIPCHK(c, hipMalloc((void**)&c->dqpos[s2], (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
-            HIPCHK(c, hipMalloc((void**)&c->dqvel[s2], (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
-        }
+    for (Slot& s : c->slot) {      // the first model of the context: the slots' coordinate buffers
+        if (!s.qpos) HIPCHK(c, hipMalloc((void**)&s.qpos, (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
+        if (!s.qvel) HIPCHK(c, hipMalloc((void**)&s.qvel, (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
     }
     if (c->fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
-        for (int s2 = 0; s2 < c->cfg.n_slots; ++s2) {
-            if (c->has_q[s2] <= 0) continue;
-            if (!c->dqt[s2]) HIPCHK(c, hipMalloc((void**)&c->dqt[s2], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
-            HIPCHK(c, (hipError_t)launch_q_layout(c->dqpos[s2], c->dqvel[s2], c->dqt[s2], c->has_q[s2], c->cfg.n, c->stream));
+        for (Slot& s : c->slot) {
+            if (s.coords <= 0) continue;
+            HIPCHK(c, ensure_qt(c, s));
+            HIPCHK(c, (hipError_t)launch_q_layout(s.qpos, s.qvel, s.qt, s.coords, c->cfg.n, c->stream));
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -1478,33 +1492,34 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
-    if (B == 0) { c->has_q[slot] = -1; return IRLOSC_OK; }
+    Slot& s = c->slot[slot];
+    if (B == 0) { s.coords = -1; return IRLOSC_OK; }
     if (!qpos || !qvel) return fail(c, IRLOSC_ERR_ARG, "qpos and qvel are required");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t bytes = (size_t)B * c->cfg.n * sizeof(double);
-    HIPCHK(c, hipMemcpyAsync(c->dqpos[slot], qpos, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dqvel[slot], qvel, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.qpos, qpos, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.qvel, qvel, bytes, hipMemcpyHostToDevice, c->stream));
     // the fused walk reads its own layout of the same numbers ([wave][2 n][64 robots]: coalesced, hinge by hinge): one small kernel
     // behind the copies (10 us per 65 536 robots against 0.8 ms of PCIe for them)
     // (only the fused path reads this layout; its buffer is allocated by the slot's first upload while the path is on, or by the
     //  irlosc_set_model that turns it on -- and, once it exists, refreshed by EVERY upload: a copy left stale while another model had
     //  the path switched off would be walked later)
-    if (c->fused && !c->dqt[slot])
-        HIPCHK(c, hipMalloc((void**)&c->dqt[slot], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
-    if (c->dqt[slot]) HIPCHK(c, (hipError_t)launch_q_layout(c->dqpos[slot], c->dqvel[slot], c->dqt[slot], B, c->cfg.n, c->stream));
+    if (c->fused) HIPCHK(c, ensure_qt(c, s));
+    if (s.qt) HIPCHK(c, (hipError_t)launch_q_layout(s.qpos, s.qvel, s.qt, B, c->cfg.n, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->has_q[slot] = B;
+    s.coords = B;
     return IRLOSC_OK;
 }
 
 // qpos / qvel: the caller's device arrays instead of the slot's coordinates, on stream `cst` (irlosc_step_from_q_device)
 static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = nullptr, const double* qvel = nullptr, hipStream_t cst = nullptr) {
     if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
-    if (!qpos && !c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q must precede irlosc_frontend", slot);
-    c->lane_ok[slot] = 0;
-    if (B == 0) { c->uploaded[slot] = -1; return IRLOSC_OK; }
-    if (!qpos && B > c->has_q[slot]) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, front end asked for %d", slot, std::max(0, c->has_q[slot]), B);
-    if (!qpos) { qpos = c->dqpos[slot]; qvel = c->dqvel[slot]; }
+    Slot& s = c->slot[slot];
+    if (!qpos && !s.coords) return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q must precede irlosc_frontend", slot);
+    s.drop_block(false);
+    if (B == 0) { s.emptied(); return IRLOSC_OK; }
+    if (!qpos && B > s.coords) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, front end asked for %d", slot, std::max(0, s.coords), B);
+    if (!qpos) { qpos = s.qpos; qvel = s.qvel; }
     const hipStream_t st = cst ? cst : c->stream;
     if (c->fe_lane && !c->fe_side) {
         const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
@@ -1515,22 +1530,21 @@ static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = 
             c->fused = 0;
         }
     }
+    s.writing();
     int rc;
     if (c->cfg.dtype == IRLOSC_F64) {
-        const FeOut<double> o{(double*)c->dM[slot], (double*)c->dJ[slot], (double*)c->ddq[slot], (double*)c->dbias[slot], (double*)c->dee[slot]};
+        const FeOut<double> o = slot_out<double>(s);
         rc = c->fe_lane ? launch_frontend_lane_dual_ur5<double>(c->dmodel, qpos, qvel, o, B, c->fe_side, st)
                         : launch_frontend_generic<double>(c->dmodel, qpos, qvel, o, B, c->fe_smem, st);
     } else {
-        const FeOut<float> o{(float*)c->dM[slot], (float*)c->dJ[slot], (float*)c->ddq[slot], (float*)c->dbias[slot], (float*)c->dee[slot]};
+        const FeOut<float> o = slot_out<float>(s);
         rc = c->fe_lane ? launch_frontend_lane_dual_ur5<float>(c->dmodel, qpos, qvel, o, B, c->fe_side, st)
                         : launch_frontend_generic<float>(c->dmodel, qpos, qvel, o, B, c->fe_smem, st);
     }
     HIPCHK(c, (hipError_t)rc);
     // The records of this slot are now those of B robots: an earlier, larger upload must not vouch for instances the front
     // end did not write (the wrench of the slot stays what the last irlosc_upload / irlosc_upload_raw put there).
-    c->uploaded[slot] = B;
-    if (!c->fused_away.empty()) c->fused_away[slot] = 0;
-    c->tree_ok[slot] = c->fe_lane;     // the lane kernel walks the compiled tree: its records carry the tree's zeros by construction
+    s.accepted(B, s.has_wrench, c->fe_lane);     // the lane kernel walks the compiled tree: its records carry the tree's zeros by construction
     // (and so need no check for the compact block of the lane route; a caller's stream gets no pack: the slot steps on the row16 kernel)
     return cst ? IRLOSC_OK : pack_slot(c, slot, B, false);
 }
@@ -1548,15 +1562,16 @@ extern "C" int irlosc_download_records(irlosc_ctx* c, int32_t slot, int32_t B, v
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    if (B > std::max(0, c->uploaded[slot])) return fail(c, IRLOSC_ERR_STATE, "slot %d holds state for %d instances", slot, std::max(0, c->uploaded[slot]));
+    const Slot& s = c->slot[slot];
+    if (B > std::max(0, s.records)) return fail(c, IRLOSC_ERR_STATE, "slot %d holds state for %d instances", slot, std::max(0, s.records));
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, n = (size_t)c->cfg.n, k = (size_t)c->k, nd = (size_t)c->cfg.ndev, e = c->esz;
-    if (M) HIPCHK(c, hipMemcpyAsync(M, c->dM[slot], b * n * n * e, hipMemcpyDeviceToHost, c->stream));
-    if (J) HIPCHK(c, hipMemcpyAsync(J, c->dJ[slot], b * k * n * e, hipMemcpyDeviceToHost, c->stream));
-    if (dq) HIPCHK(c, hipMemcpyAsync(dq, c->ddq[slot], b * n * e, hipMemcpyDeviceToHost, c->stream));
-    if (bias) HIPCHK(c, hipMemcpyAsync(bias, c->dbias[slot], b * n * e, hipMemcpyDeviceToHost, c->stream));
-    if (ee_pose) HIPCHK(c, hipMemcpyAsync(ee_pose, c->dee[slot], b * nd * 7 * e, hipMemcpyDeviceToHost, c->stream));
+    if (M) HIPCHK(c, hipMemcpyAsync(M, s.M, b * n * n * e, hipMemcpyDeviceToHost, c->stream));
+    if (J) HIPCHK(c, hipMemcpyAsync(J, s.J, b * k * n * e, hipMemcpyDeviceToHost, c->stream));
+    if (dq) HIPCHK(c, hipMemcpyAsync(dq, s.dq, b * n * e, hipMemcpyDeviceToHost, c->stream));
+    if (bias) HIPCHK(c, hipMemcpyAsync(bias, s.bias, b * n * e, hipMemcpyDeviceToHost, c->stream));
+    if (ee_pose) HIPCHK(c, hipMemcpyAsync(ee_pose, s.ee, b * nd * 7 * e, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }
@@ -1564,18 +1579,19 @@ extern "C" int irlosc_download_records(irlosc_ctx* c, int32_t slot, int32_t B, v
 // A step from joint coordinates over B robots needs B robots of (qpos, qvel) AND of targets in the slot.
 static int check_slot_q(irlosc_ctx* c, int slot, int B) {
     if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
-    if (!c->has_q[slot] || !c->targeted[slot])
+    const Slot& s = c->slot[slot];
+    if (!s.coords || !s.targets)
         return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q and irlosc_set_targets must precede a step from joint coordinates", slot);
-    if (B > std::max(0, c->has_q[slot]) || B > std::max(0, c->targeted[slot]))
+    if (B > std::max(0, s.coords) || B > std::max(0, s.targets))
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d and targets for %d instances, step asked for %d", slot,
-                    std::max(0, c->has_q[slot]), std::max(0, c->targeted[slot]), B);
+                    std::max(0, s.coords), std::max(0, s.targets), B);
     return IRLOSC_OK;
 }
 
 // A step from joint coordinates over B robots of a slot with a sensor feed needs B robots of sensordata in it.
 static int check_slot_feed(irlosc_ctx* c, int slot, int B) {
-    if (c->has_sens[slot] > 0 && B > c->has_sens[slot])
-        return fail(c, IRLOSC_ERR_STATE, "slot %d: the sensor feed holds %d robots, step asked for %d", slot, c->has_sens[slot], B);
+    const int feed = c->slot[slot].feed;
+    if (feed > 0 && B > feed) return fail(c, IRLOSC_ERR_STATE, "slot %d: the sensor feed holds %d robots, step asked for %d", slot, feed, B);
     return IRLOSC_OK;
 }
 
@@ -1656,21 +1672,22 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     HIPCHK(c, hipMemsetAsync(bk.count, 0, R16_TRAIN * sizeof(int32_t), st));
     ft.B = ga.B = B;
     for (int i = 0; i < n; ++i) {
-        const int sl = slots[i];
-        const double* qpos = dv ? dv->qpos : c->dqpos[sl];
-        const double* qvel = dv ? dv->qvel : c->dqvel[sl];
-        const double* sens = dv ? dv->sens : c->has_sens[sl] > 0 ? c->dsens[sl] : nullptr;
-        void* wr = dv ? (dv->sens ? c->dwrench[sl] : nullptr) : sens ? feed_wrench(c, k, i) : c->has_wrench[sl] ? c->dwrench[sl] : nullptr;
+        const Slot& s = c->slot[slots[i]];
+        const double* qpos = dv ? dv->qpos : s.qpos;
+        const double* qvel = dv ? dv->qvel : s.qvel;
+        const double* sens = dv ? dv->sens : s.feed > 0 ? s.sens : nullptr;
+        void* wr = !sens ? nullptr : dv ? s.wrench : feed_wrench(c, k, i);      // the feed's wrench (a device call: in the scratch slot)
         if (sens && !wr) return IRLOSC_ERR_HIP;
         if (sens) fts[nft++] = FtStep{sens, wr, bk.xside[i], nullptr};
         ft.qpos[i] = ga.qpos[i] = qpos;
         ft.qvel[i] = ga.qvel[i] = qvel;
-        ft.qt[i] = c->dqt[sl];
+        ft.qt[i] = s.qt;
         ft.side[i] = bk.xside[i];
-        fill_params<T>(c, tr.p[i], B, c->dM[sl], c->dJ[sl], c->ddq[sl], c->dbias[sl], c->dee[sl], dv ? dv->tgt : c->dtgt[sl],
-                       dv ? dv->tvel : c->has_tvel[sl] ? c->dtvel[sl] : nullptr, wr, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
+        StepInputs in = slot_inputs(s, wr);
+        if (dv) { in.tgt = dv->tgt; in.tvel = dv->tvel; in.wrench = wr; }
+        fill_params<T>(c, tr.p[i], B, in, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
         tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], qvel, c->dtables, c->span_next};
-        ga.out[i] = FeOut<T>{(T*)c->dM[sl], (T*)c->dJ[sl], (T*)c->ddq[sl], (T*)c->dbias[sl], (T*)c->dee[sl]};
+        ga.out[i] = slot_out<T>(s);
         ga.list[i] = bk.list[i];
         ga.count[i] = bk.count + i;
     }
@@ -1680,8 +1697,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     lane::LaneTrain lt;
     memset(&lt, 0, sizeof lt);
     for (int i = 0; i < n && use_lane; ++i) {
-        if ((dv ? dv->tvel != nullptr : c->has_tvel[slots[i]] != 0) || !bk.lane_rec[i] || !bk.lane_count) use_lane = false;
-        lt.qt[i] = c->dqt[slots[i]];
+        if ((dv ? dv->tvel != nullptr : c->slot[slots[i]].has_tvel != 0) || !bk.lane_rec[i] || !bk.lane_count) use_lane = false;
+        lt.qt[i] = c->slot[slots[i]].qt;
         lt.rec[i] = bk.lane_rec[i];
         lt.rec_count[i] = bk.lane_count + i;
     }
@@ -1706,8 +1723,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     // The give-up pass wrote dense records of the robots on its lists into the slots (and nothing for the others): what the
     // slots held before no longer belongs to one state.  They hold no records from here on -- irlosc_step / irlosc_step_resident
     // / irlosc_download_records on them fail with IRLOSC_ERR_STATE until irlosc_frontend / irlosc_upload* fills them again.
-    if (c->fused_away.empty()) c->fused_away.assign(c->cfg.n_slots, 0);
-    for (int i = 0; i < n; ++i) { c->uploaded[slots[i]] = 0; c->tree_ok[slots[i]] = 0; c->lane_ok[slots[i]] = 0; c->fused_away[slots[i]] = 1; }
+    for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
     return IRLOSC_OK;
 }
 template <typename T>
@@ -1728,9 +1744,9 @@ static int dense_from_q_step(irlosc_ctx* c, int slot, int B) {
     if (!rc) rc = check_slot_feed(c, slot, B);
     if (!rc) rc = frontend_launch(c, slot, B);
     void* wr = nullptr;
-    if (!rc && c->has_sens[slot] > 0) {
+    if (!rc && c->slot[slot].feed > 0) {
         if (!(wr = feed_wrench(c, 0, 0))) return IRLOSC_ERR_HIP;
-        const FtStep s{c->dsens[slot], wr, nullptr, c->dee[slot]};
+        const FtStep s{c->slot[slot].sens, wr, nullptr, c->slot[slot].ee};
         rc = ft_launch(c, &s, 1, B, c->stream);
     }
     if (!rc) rc = launch_slot(c, slot, B, wr);
@@ -1767,29 +1783,12 @@ extern "C" int irlosc_step_from_q(irlosc_ctx* c, int32_t slot, int32_t B, void* 
 
 extern "C" int irlosc_step_resident_from_q(irlosc_ctx* c, int32_t first_slot, int32_t B, int32_t iters, float* ms_total,
                                            float* ms_step_avg) {
-    if (!c) return IRLOSC_ERR_ARG;
-    int rc = check_slot(c, first_slot, B);
-    if (rc) return rc;
-    if (iters < 1) return fail(c, IRLOSC_ERR_ARG, "iters must be >= 1");
-    if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
-    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (B > 0 && fused_ready(c, std::min((int)R16_TRAIN, iters))) {
-        rc = fused_resident(c, first_slot, B, iters);
-        if (rc) return rc;
-    } else {
-        for (int i = 0; i < iters; ++i) {
-            rc = dense_from_q_step(c, (first_slot + i) % c->cfg.n_slots, B);
-            if (rc) return rc;
-        }
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    float ms = 0.f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (ms_total) *ms_total = ms;
-    if (ms_step_avg) *ms_step_avg = ms / (float)iters;
-    return IRLOSC_OK;
+    return timed_resident(c, first_slot, B, iters, ms_total, ms_step_avg, [&] {
+        if (B > 0 && fused_ready(c, std::min((int)R16_TRAIN, iters))) return fused_resident(c, first_slot, B, iters);
+        int rc = IRLOSC_OK;
+        for (int i = 0; i < iters && !rc; ++i) rc = dense_from_q_step(c, (first_slot + i) % c->cfg.n_slots, B);
+        return rc;
+    });
 }
 
 // ---- F/T sensor feed of the steps from joint coordinates ------------------------------------------------------------
@@ -1858,7 +1857,7 @@ extern "C" int irlosc_set_ft_sensors(irlosc_ctx* c, const irlosc_ft_desc* fd) {
     }
     c->ft_n_sensor = fd->n_sensor;
     c->ft_set = 1;
-    std::fill(c->has_sens.begin(), c->has_sens.end(), 0);      // feeds laid out for another description
+    for (Slot& s : c->slot) s.end_feed();      // feeds laid out for another description
     return IRLOSC_OK;
 }
 
@@ -1866,20 +1865,21 @@ extern "C" int irlosc_set_sensordata(irlosc_ctx* c, int32_t slot, int32_t B, con
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    if (B == 0 || !sensordata) { c->has_sens[slot] = 0; return IRLOSC_OK; }
+    Slot& s = c->slot[slot];
+    if (B == 0 || !sensordata) { s.end_feed(); return IRLOSC_OK; }
     if (!c->ft_set) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_ft_sensors has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t Bm = (size_t)c->cfg.max_batch, ns = (size_t)c->ft_n_sensor;
-    c->has_sens[slot] = 0;
-    if (c->sens_cols[slot] < (int)ns) {
-        if (c->dsens[slot]) HIPCHK(c, hipFree(c->dsens[slot]));
-        c->dsens[slot] = nullptr; c->sens_cols[slot] = 0;
-        HIPCHK(c, hipMalloc((void**)&c->dsens[slot], Bm * ns * sizeof(double)));
-        c->sens_cols[slot] = (int)ns;
+    s.end_feed();      // (none until the new one is in the buffer)
+    if (s.sens_cols < (int)ns) {
+        if (s.sens) HIPCHK(c, hipFree(s.sens));
+        s.sens = nullptr; s.sens_cols = 0;
+        HIPCHK(c, hipMalloc((void**)&s.sens, Bm * ns * sizeof(double)));
+        s.sens_cols = (int)ns;
     }
-    HIPCHK(c, hipMemcpyAsync(c->dsens[slot], sensordata, (size_t)B * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s.sens, sensordata, (size_t)B * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->has_sens[slot] = B;
+    s.feed = B;
     return IRLOSC_OK;
 }
 
@@ -1897,34 +1897,30 @@ extern "C" int irlosc_step_from_q_device(irlosc_ctx* c, int32_t slot, int32_t B,
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const bool fused = fused_ready(c, 1);      // (first call: allocates bank 0's exchange buffer / lane records on the context's stream)
-    if (fused && !c->dqt[slot])
-        HIPCHK(c, hipMalloc((void**)&c->dqt[slot], (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double)));
+    Slot& s = c->slot[slot];
+    if (fused) HIPCHK(c, ensure_qt(c, s));
     if (st != c->stream) {                     // ... and whatever else the context's stream holds comes first
         if (!c->ev_dev) HIPCHK(c, hipEventCreateWithFlags(&c->ev_dev, hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_dev, c->stream));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_dev, 0));
     }
-    // from here on the slot's records and coordinates are scratch of this call
-    c->uploaded[slot] = 0;
-    c->has_q[slot] = 0;
-    c->tree_ok[slot] = 0;
-    if (d_sensordata) c->has_wrench[slot] = 0;
+    s.lent(d_sensordata != nullptr);      // from here on the slot's records and coordinates are scratch of this call
     const DevCall dv{d_qpos, d_qvel, d_tgt_pose, d_tgt_vel, d_sensordata, d_u, d_flags, st};
     if (fused) {
-        HIPCHK(c, (hipError_t)launch_q_layout(d_qpos, d_qvel, c->dqt[slot], B, c->cfg.n, st));
+        HIPCHK(c, (hipError_t)launch_q_layout(d_qpos, d_qvel, s.qt, B, c->cfg.n, st));
         const int sl = slot;
         rc = c->cfg.dtype == IRLOSC_F64 ? fused_train<double>(c, &sl, 1, B, 0, &dv) : fused_train<float>(c, &sl, 1, B, 0, &dv);
     } else {
         rc = frontend_launch(c, slot, B, d_qpos, d_qvel, st);
         if (!rc && d_sensordata) {
-            const FtStep s{d_sensordata, c->dwrench[slot], nullptr, c->dee[slot]};
-            rc = ft_launch(c, &s, 1, B, st);
+            const FtStep fs{d_sensordata, s.wrench, nullptr, s.ee};
+            rc = ft_launch(c, &fs, 1, B, st);
         }
-        if (!rc) rc = launch(c, B, c->dM[slot], c->dJ[slot], c->ddq[slot], c->dbias[slot], c->dee[slot], d_tgt_pose, d_tgt_vel,
-                             d_sensordata ? c->dwrench[slot] : nullptr, d_u, d_flags, st, slot_tree(c, slot));
+        StepInputs in = slot_inputs(s);
+        in.tgt = d_tgt_pose; in.tvel = d_tgt_vel; in.wrench = d_sensordata ? s.wrench : nullptr;
+        if (!rc) rc = launch(c, B, in, d_u, d_flags, st, slot_tree(c, slot));
     }
-    c->uploaded[slot] = 0;                     // (the front end / fused_train mark what they wrote: none of it is the slot's state)
-    c->tree_ok[slot] = 0;
+    s.lent(d_sensordata != nullptr);      // (the front end / fused_train mark what they wrote: none of it is the slot's state)
     return rc;
 }
 
@@ -1986,8 +1982,8 @@ extern "C" int irlosc_tick(irlosc_ctx* c, int32_t B, const void* M, const void* 
         int rcs = symmetry_probe(c, din + off[0], B, (int32_t*)(dout + sym_off), c->stream);
         if (rcs) return rcs;
     }
-    int rc = launch(c, B, din + off[0], din + off[1], din + off[2], sz[3] ? din + off[3] : nullptr, din + off[4], din + off[5],
-                    sz[7] ? din + off[7] : nullptr, sz[6] ? din + off[6] : nullptr, dout, dfl, c->stream);
+    int rc = launch(c, B, StepInputs{din + off[0], din + off[1], din + off[2], sz[3] ? din + off[3] : nullptr, din + off[4], din + off[5],
+                                     sz[7] ? din + off[7] : nullptr, sz[6] ? din + off[6] : nullptr}, dout, dfl, c->stream);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->tick_hout, dout, out_total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2161,5 +2157,5 @@ extern "C" int irlosc_step_device(irlosc_ctx* c, int32_t B, const void* dM, cons
     if ((c->cfg.flags & IRLOSC_USE_G) && !dbias) return fail(c, IRLOSC_ERR_ARG, "dbias required with IRLOSC_USE_G");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    return launch(c, B, dM, dJ, ddq, dbias, dee_pose, dtgt_pose, dtgt_vel, dwrench, du, dflags, st);
+    return launch(c, B, StepInputs{dM, dJ, ddq, dbias, dee_pose, dtgt_pose, dtgt_vel, dwrench}, du, dflags, st);
 }

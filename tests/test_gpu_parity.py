@@ -1323,7 +1323,8 @@ def test_step_refuses_more_instances_than_the_slot_holds():
 def test_library_refuses_an_asymmetric_M_on_the_throughput_paths(dtype, kernel):
     """The throughput kernels read row j of M as column j; the reference uses M as given (osc.py:49,151).  Records that
     come from the host are probed ON THE DEVICE (irlosc_upload, irlosc_tick): an asymmetric M is IRLOSC_ERR_ARG naming the
-    instance, the slot then holds nothing, and the generic kernel still takes such an M as it is."""
+    instance, the slot then holds nothing -- no records, and neither the tree verdict nor the route of the records the refused
+    ones overwrote -- and the generic kernel still takes such an M as it is."""
     B = 300
     lay, gains, g = synth.make_batch("k13", B, seed=4, dtype=dtype)
     osc = BatchedOSC(lay, B, dtype=dtype, kernel=kernel)
@@ -1350,6 +1351,23 @@ def test_library_refuses_an_asymmetric_M_on_the_throughput_paths(dtype, kernel):
     u6 = osc.tick(g["M"][sl], g["J"][sl], g["dq"][sl], g["bias"][sl], g["ee_pose"][sl], g["tgt_pose"][sl])
     assert np.array_equal(u6, u[sl])
     assert np.all(np.isfinite(u6))
+    # tree-form records (the front end's: synthetic ones do not carry the tree's zeros) accepted with their verdict, then refused ones
+    # written over them: the verdict and the route went with the records
+    assert not osc.slot_structure(0)
+    fe = _from_q_setup("k13", B, dtype, seed=4)[4]
+    fe.frontend()
+    rec = fe.download_records(0)
+    fe.close()
+    osc.upload(rec["M"], rec["J"], rec["dq"], rec["bias"], rec["ee_pose"])
+    assert osc.slot_structure(0) and osc.slot_route(0) == "row16_tree"
+    Mtree = rec["M"].copy()
+    Mtree[123, 20, 2] += 0.5
+    with pytest.raises(_lib.IrloscError, match="M of instance 123 is not symmetric"):
+        osc.upload(Mtree, rec["J"], rec["dq"], rec["bias"], rec["ee_pose"])
+    assert not osc.slot_structure(0)
+    assert osc.slot_route(0) not in ("row16_tree", "lane")
+    with pytest.raises(_lib.IrloscError, match="must precede a step"):
+        osc.step()
     osc.close()
     gen = BatchedOSC(lay, B, dtype=dtype, kernel=_lib.KERNEL_GENERIC)
     gen.set_gains(gains["kp"], gains["kv"], gains["ko"], gains["k"], gains["d"], gains["max_vel"], gains["null_kv"])
@@ -1692,6 +1710,14 @@ def test_a_fused_step_leaves_no_records_in_the_slot():
     assert np.array_equal(osc.step_q(), u_fused)             # (qpos, qvel) and the targets are still there
     osc.frontend()
     assert osc.slot_structure(0) and np.array_equal(osc.step(), u_rec)
+    empty = lambda: osc.lib.irlosc_upload(osc._h, 0, 0, None, None, None, None, None, None)
+    assert empty() == 0                                      # an empty batch over records with the verdict: it goes with them
+    assert not osc.slot_structure(0) and osc.slot_route(0) == "row16"
+    osc.frontend()
+    assert osc.slot_structure(0)
+    osc.step_q()
+    assert empty() == 0                                      # ... and over the slot a fused step left
+    assert not osc.slot_structure(0) and osc.slot_route(0) == "row16"
     osc.close()
 
 
