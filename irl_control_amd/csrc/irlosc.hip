@@ -103,6 +103,56 @@ static FeOut<T> slot_out(const Slot& s) {
     return FeOut<T>{(T*)s.M, (T*)s.J, (T*)s.dq, (T*)s.bias, (T*)s.ee};
 }
 
+// What a model means for the context, planned ON THE HOST by irlosc_set_model (derive_model, then plan_routes: neither touches the
+// context's state or the device).  The defaults are the state before the first model: no walk, no fused path, no lane tier, no pack table.
+struct ModelPlan {
+    FeModel h{};                      // the validated model with its derived tables (the device copy: Model::dmodel)
+    size_t fe_smem = 0;               // LDS of the wave-per-robot front end
+    int fe_lane = 0;                  // 1: the model has the compiled Dual-UR5 shape -> lane-per-instance front end
+    int fe_lane_s = 0;                // 1: ... and the structural constants of its MJCF -> the fused walk with them compiled in (TopoDualUr5S)
+    // fused path (irlosc_step_from_q / irlosc_step_resident_from_q on the row16 kernel): entry tables of the compact exchange buffer
+    // (one buffer per step of a train: Bank::xside)
+    int fused = 0;
+    int fq_overlap = 1;               // IRLOSC_FQ_OVERLAP=0: one bank, one stream (A/B measurements, tests)
+    FeCompactTables tables{};
+    size_t fe_xentries = 0;
+    int32_t ft_qe[IRLOSC_MAX_DEV] = {};    // exchange entry of each EE's qw (FeCompactTables::eetab[d][3]): the F/T sensor feed reads it
+    // the OSC step of the fused path in lane-per-robot form (osc_lane.hpp): the instantiation that holds the layout (-1: none: the row16
+    // FROMQ kernel stays) and its row map
+    int lane_tier = -1;
+    lane::RowMap lane_map{};
+    // resident lane route: the pack table of the layout (pack_plan; pack_ok = 0: none)
+    int pack_ok = 0;
+    PackTable pack{};
+
+    void plan_routes(const irlosc_ctx* c);
+};
+
+// The model of a context: the plan in force with its device copies.  Written by the methods below and by nothing else: commit() is the
+// one way a plan becomes the context's, the give_up_*() are the routes a context loses when their buffers cannot be allocated.  While
+// `in_force` is 0 the plan is the default one and the entry points from joint coordinates answer IRLOSC_ERR_STATE -- before the first
+// irlosc_set_model, and after one that failed on the device (never half of a model).
+struct Model : ModelPlan {
+    int in_force = 0;
+    FeModel* dmodel = nullptr;
+    FeCompactTables* dtables = nullptr;
+    PackTable* dpack = nullptr;
+    int32_t* dpack_bad = nullptr;     // robots whose dropped entries were not zero (the pack's check)
+    double* fe_side = nullptr;        // side buffer of the lane front end: [wave][entry][64], allocated by the first irlosc_frontend
+
+    int commit(irlosc_ctx* c, const ModelPlan& p);
+    // Bank 0 has no exchange buffers: no fused path on this context, the steps from joint coordinates go through dense records.
+    void give_up_fused(irlosc_ctx* c);
+    // Bank 0 has no lane records: the OSC step of the fused path stays the row16 FROMQ kernel (and no slot takes the resident lane route).
+    void give_up_lane(irlosc_ctx* c);
+    // No side buffer: the wave-per-robot front end, which needs none, writes the records -- and with the lane walk goes the fused path.
+    void give_up_lane_walk() { fe_lane = 0; fused = 0; }
+    void free_device() {
+        for (void* p : {(void*)dmodel, (void*)dtables, (void*)dpack, (void*)dpack_bad, (void*)fe_side}) if (p) (void)hipFree(p);
+        dmodel = nullptr; dtables = nullptr; dpack = nullptr; dpack_bad = nullptr; fe_side = nullptr;
+    }
+};
+
 struct irlosc_ctx {
     irlosc_cfg cfg{};
     int k = 0;
@@ -122,18 +172,8 @@ struct irlosc_ctx {
     void* draw = nullptr;     // staging for irlosc_upload_raw (raw simulator arrays), grown on demand
     size_t draw_bytes = 0;
     void* dzeros = nullptr;            // fp64 row16 path: zero page for the padding lanes
-    // rigid-body front end (irlosc_set_model): device copy of the tables, resident joint coordinates per slot
-    FeModel* dmodel = nullptr;
-    size_t fe_smem = 0;
-    int fe_lane = 0;                  // 1: the model has the compiled Dual-UR5 shape -> lane-per-instance front end
-    int fe_lane_s = 0;                // 1: ... and the structural constants of its MJCF -> the fused walk with them compiled in (TopoDualUr5S)
-    double* fe_side = nullptr;        // side buffer of the lane kernel: [wave][entry][64]
-    // fused path (irlosc_step_from_q / irlosc_step_resident_from_q on the row16 kernel): entry tables of the compact exchange
-    // buffer and one buffer per step of a train
-    FeCompactTables* dtables = nullptr;
-    size_t fe_xentries = 0;
+    Model model;                       // rigid-body front end and everything else irlosc_set_model decides
     int task_pass = 1;                     // IRLOSC_TASK_PASS=0: part 1 of the task signal in the row16 kernel (A/B, tests)
-    int fused = 0;
     // Consecutive trains of irlosc_step_resident_from_q / irlosc_step_resident rotate over BANKS of buffers, each on a stream of its own:
     // the walk and the lane kernel run one wave per SIMD, eight waves deep per train, so every kernel boundary leaves SIMDs idle for up to
     // a wave's lifetime (~50 us) -- measured as a fixed ~126 us per train of 990 us (trains of 8 / 4 / 2 steps: 124 / 140 / 163 us per
@@ -161,24 +201,14 @@ struct irlosc_ctx {
     Bank bank[1 + MAX_XBANKS];
     hipEvent_t ev_join = nullptr;
     hipEvent_t ev_dev = nullptr;           // irlosc_step_from_q_device: a caller stream starts behind the context's stream
-    int fq_overlap = 1;                    // IRLOSC_FQ_OVERLAP=0: one bank, one stream (A/B measurements, tests)
-    int r16_overlap = 1;                   // IRLOSC_R16_OVERLAP=0: the same switch for the trains of irlosc_step_resident on dense records
+    int r16_overlap = 1;                   // IRLOSC_R16_OVERLAP=0: one bank, one stream for the trains of irlosc_step_resident on dense records
     int32_t* count_cur = nullptr;          // give-up counters of the most recent train (irlosc_giveup_counts)
-    // the OSC step of the fused path in lane-per-robot form (osc_lane.hpp): the instantiation that holds the layout (-1: none: the row16
-    // FROMQ kernel stays) and its row map
-    int lane_tier = -1;
-    lane::RowMap lane_map{};
     // F/T sensor feed of the steps from joint coordinates (irlosc_set_ft_sensors / irlosc_set_sensordata): the description and R_rel
-    // per device (the sensordata: Slot::sens)
+    // per device (the sensordata: Slot::sens; the exchange entries it reads: ModelPlan::ft_qe)
     int ft_set = 0;
     int32_t ft_n_sensor = 0;
     int32_t ft_f0[IRLOSC_MAX_DEV] = {}, ft_t0[IRLOSC_MAX_DEV] = {};
     double ft_R[IRLOSC_MAX_DEV][9] = {};
-    int32_t ft_qe[IRLOSC_MAX_DEV] = {};    // exchange entry of each EE's qw (FeCompactTables::eetab[d][3])
-    // host copy of what irlosc_set_ft_sensors needs of the model: tree, body frames, EE bodies
-    int hm_nb = 0;
-    int32_t hm_parent[IRLOSC_MAX_BODIES] = {}, hm_joint[IRLOSC_MAX_BODIES] = {}, hm_ee[IRLOSC_MAX_DEV] = {};
-    double hm_quat[IRLOSC_MAX_BODIES][4] = {};
     // irlosc_tick: one pinned host block and one device block per direction, grown on demand
     void* tick_hin = nullptr; void* tick_din = nullptr; size_t tick_in_bytes = 0;
     void* tick_hout = nullptr; void* tick_dout = nullptr; size_t tick_out_bytes = 0;
@@ -189,9 +219,6 @@ struct irlosc_ctx {
     // pass builds the slot's compact block from the dense records when they enter the slot (Slot::blk, Slot::packed)
     int auto_kernel = 0;               // created with IRLOSC_KERNEL_AUTO
     int resident_lane = 1;             // IRLOSC_RESIDENT_LANE=0 turns the route off (A/B measurements, tests)
-    int pack_ok = 0;                   // the model's layout has a pack table (pack_plan)
-    PackTable* dpack = nullptr;
-    int32_t* dpack_bad = nullptr;      // robots whose dropped entries were not zero (the pack's check)
     StructureMasks tree_masks;
     int32_t* dstruct = nullptr;        // result word of the structure probe
     void* dgains = nullptr;   // [nb][ndev][12] in dtype
@@ -238,9 +265,9 @@ extern "C" const char* irlosc_last_error(const irlosc_ctx* ctx) {
 }
 
 extern "C" const char* irlosc_frontend_name(const irlosc_ctx* ctx) {
-    if (!ctx || !ctx->dmodel) return "";
+    if (!ctx || !ctx->model.in_force) return "";
     const bool f64 = ctx->cfg.dtype == IRLOSC_F64;
-    if (ctx->fe_lane) return f64 ? "osc_frontend_lane_dual_ur5_f64out" : "osc_frontend_lane_dual_ur5_f32out";
+    if (ctx->model.fe_lane) return f64 ? "osc_frontend_lane_dual_ur5_f64out" : "osc_frontend_lane_dual_ur5_f32out";
     return f64 ? "osc_frontend_generic_f64out" : "osc_frontend_generic_f32out";
 }
 
@@ -303,9 +330,7 @@ static void free_slot(Slot& s) {
 static void free_all(irlosc_ctx* c) {
     for (Slot& s : c->slot) free_slot(s);
     if (c->draw) (void)hipFree(c->draw);
-    if (c->dmodel) (void)hipFree(c->dmodel);
-    if (c->fe_side) (void)hipFree(c->fe_side);
-    if (c->dtables) (void)hipFree(c->dtables);
+    c->model.free_device();
     for (irlosc_ctx::Bank& bk : c->bank) {
         free_bank(bk, BANK_ALL);
         if (bk.done) (void)hipEventDestroy(bk.done);
@@ -313,8 +338,6 @@ static void free_all(irlosc_ctx* c) {
     }
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->ev_dev) (void)hipEventDestroy(c->ev_dev);
-    if (c->dpack) (void)hipFree(c->dpack);
-    if (c->dpack_bad) (void)hipFree(c->dpack_bad);
     if (c->tick_hin) (void)hipHostFree(c->tick_hin);
     if (c->tick_din) (void)hipFree(c->tick_din);
     if (c->tick_hout) (void)hipHostFree(c->tick_hout);
@@ -606,14 +629,11 @@ extern "C" int irlosc_slot_structure(const irlosc_ctx* c, int32_t slot) {
     return slot_tree(c, slot) ? 1 : 0;
 }
 
-static bool slot_lane(const irlosc_ctx* c, int slot, int B);
+static int record_route(const irlosc_ctx* c, int slot, int B);
 
 extern "C" int irlosc_slot_route(const irlosc_ctx* c, int32_t slot, int32_t B) {
     if (!c || slot < 0 || slot >= c->cfg.n_slots) return IRLOSC_ROUTE_NONE;
-    if (c->kernel != IRLOSC_KERNEL_ROW16) return IRLOSC_ROUTE_GENERIC;
-    if (B <= 0) B = std::max(0, c->slot[slot].records);
-    if (B > 0 && slot_lane(c, slot, B)) return IRLOSC_ROUTE_LANE;
-    return slot_tree(c, slot) ? IRLOSC_ROUTE_ROW16_TREE : IRLOSC_ROUTE_ROW16;
+    return record_route(c, slot, B > 0 ? B : std::max(0, c->slot[slot].records));
 }
 
 extern "C" int irlosc_upload(irlosc_ctx* c, int32_t slot, int32_t B, const void* M, const void* J, const void* dq,
@@ -867,9 +887,9 @@ static unsigned ensure_bank(irlosc_ctx* c, int k, int n, unsigned need) {
     if (need & NEED_ROWS)
         for (int i = 0; i < n; ++i) if (!dev_alloc(b.trows[i], Bm * 16 * sizeof(double))) return NEED_ROWS;
     if (need & NEED_X) {
-        if (b.xentries != c->fe_xentries) free_bank(b, NEED_X);          // sized for another model's entries
-        b.xentries = c->fe_xentries;
-        for (int i = 0; i < n; ++i) if (!dev_alloc(b.xside[i], waves * c->fe_xentries * 64 * sizeof(double))) return NEED_X;
+        if (b.xentries != c->model.fe_xentries) free_bank(b, NEED_X);          // sized for another model's entries
+        b.xentries = c->model.fe_xentries;
+        for (int i = 0; i < n; ++i) if (!dev_alloc(b.xside[i], waves * b.xentries * 64 * sizeof(double))) return NEED_X;
     }
     if (need & NEED_LANE) {
         if (!dev_alloc(b.lane_count, R16_TRAIN * sizeof(int32_t))) return NEED_LANE;
@@ -891,14 +911,43 @@ static constexpr int LANE_MIN_B = 4096;
 // Records of B robots in the slot may take the lane route: AUTO context, float64 records, the tree verdict, a model whose layout has a
 // lane tier and a pack table, IRLOSC_RESIDENT_LANE not 0
 static bool lane_eligible(const irlosc_ctx* c, int slot, int B) {
-    return c->resident_lane && c->auto_kernel && c->cfg.dtype == IRLOSC_F64 && c->kernel == IRLOSC_KERNEL_ROW16 && c->lane_tier >= 0 &&
-           c->pack_ok && slot_tree(c, slot) && B >= LANE_MIN_B;
+    return c->resident_lane && c->auto_kernel && c->cfg.dtype == IRLOSC_F64 && c->kernel == IRLOSC_KERNEL_ROW16 && c->model.lane_tier >= 0 &&
+           c->model.pack_ok && slot_tree(c, slot) && B >= LANE_MIN_B;
 }
 
-// A step of B robots on the slot takes the lane route (target velocities: the row16 kernel, as on the fused path)
-static bool slot_lane(const irlosc_ctx* c, int slot, int B) {
-    return c->slot[slot].packed >= B && !c->slot[slot].has_tvel && lane_eligible(c, slot, B);
+// THE route of a step of B robots on the slot's records (IRLOSC_ROUTE_*): what irlosc_slot_route reports is what launch_slot and
+// dense_train launch.  The lane route needs a block that follows the records and no target velocities (those: the row16 kernel, as on
+// the fused path).
+static int record_route(const irlosc_ctx* c, int slot, int B) {
+    if (c->kernel != IRLOSC_KERNEL_ROW16) return IRLOSC_ROUTE_GENERIC;
+    const Slot& s = c->slot[slot];
+    if (B > 0 && s.packed >= B && !s.has_tvel && lane_eligible(c, slot, B)) return IRLOSC_ROUTE_LANE;
+    return slot_tree(c, slot) ? IRLOSC_ROUTE_ROW16_TREE : IRLOSC_ROUTE_ROW16;
 }
+// ... and the route that is left when the lane route's bank records cannot be allocated, or a sensor feed brings the wrench
+static int row16_route(int route) { return route == IRLOSC_ROUTE_LANE ? IRLOSC_ROUTE_ROW16_TREE : route; }
+
+// The form of a step from joint coordinates (`tvel`: with target velocities): through dense records (front end, then record_route),
+// or fused -- the walk into the compact exchange buffer, then the row16 FROMQ kernel or the lane-per-robot OSC step (not with target
+// velocities: branch B of osc.py:173-177 reads dx between the two halves of the task signal).
+enum FromQ { FROMQ_DENSE, FROMQ_ROW16, FROMQ_LANE };
+static FromQ from_q_form(const irlosc_ctx* c, bool tvel) {
+    return !c->model.fused ? FROMQ_DENSE : c->model.lane_tier >= 0 && !tvel ? FROMQ_LANE : FROMQ_ROW16;
+}
+// What a fused train needs of its bank
+static unsigned fused_need(const irlosc_ctx* c) { return NEED_X | (from_q_form(c, false) == FROMQ_LANE ? NEED_LANE : 0); }
+// The walk of the fused path: its launcher and the name irlosc_from_q_name reports
+struct Walk {
+    int (*launch)(const FeModel* dmodel, const FeLaneTrain& tr, int nsteps, hipStream_t st);
+    const char* name;
+};
+static Walk fused_walk(const irlosc_ctx* c) {
+    return c->model.fe_lane_s ? Walk{launch_frontend_lane_compact_dual_ur5_s, "osc_frontend_lane_compact_dual_ur5_s"}
+                              : Walk{launch_frontend_lane_compact_dual_ur5, "osc_frontend_lane_compact_dual_ur5"};
+}
+
+void Model::give_up_fused(irlosc_ctx* c) { free_bank(c->bank[0], NEED_X); fused = 0; }
+void Model::give_up_lane(irlosc_ctx* c) { free_bank(c->bank[0], NEED_LANE); lane_tier = -1; }
 
 // The compact block of the slot's records of B robots, on the context's stream behind whatever wrote them.  `check`: the pack counts the
 // robots whose dropped entries are not zero and the block is only valid without one (synchronous; the record-form front end writes the
@@ -911,17 +960,17 @@ static int pack_slot(irlosc_ctx* c, int slot, int B, bool check) {
     if (!dev_alloc(s.blk, waves * pack_entries() * 64 * sizeof(double)) || !dev_alloc(s.blk_dq, qt_bytes(c))) return IRLOSC_OK;
     PackArgs a;
     memset(&a, 0, sizeof a);
-    a.table = c->dpack;
+    a.table = c->model.dpack;
     const FeOut<double> rec = slot_out<double>(s);
     a.src[PACK_M] = rec.M; a.src[PACK_J] = rec.J; a.src[PACK_DQ] = rec.dq; a.src[PACK_BIAS] = rec.bias; a.src[PACK_EE] = rec.ee;
     a.blk = s.blk; a.dqb = s.blk_dq;
-    a.bad = check ? c->dpack_bad : nullptr;
+    a.bad = check ? c->model.dpack_bad : nullptr;
     a.B = B;
-    if (check) HIPCHK(c, hipMemsetAsync(c->dpack_bad, 0, sizeof(int32_t), c->stream));
+    if (check) HIPCHK(c, hipMemsetAsync(a.bad, 0, sizeof(int32_t), c->stream));
     HIPCHK(c, (hipError_t)launch_pack(a, c->stream));
     if (check) {
         int32_t bad = 0;
-        HIPCHK(c, hipMemcpyAsync(&bad, c->dpack_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&bad, a.bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (bad) return IRLOSC_OK;
     }
@@ -956,18 +1005,18 @@ static int lane_train(irlosc_ctx* c, const KParams<double>* ps, const int* sl, i
     for (int i = 0; i < n; ++i) {
         const int o = pos[i];
         tr.p[i] = ps[i];
-        tr.x[i] = Row16Extra{c->dzeros, bk.list[o], bk.count + o, c->slot[sl[i]].blk, nullptr, c->dtables, c->span_next, nullptr};
+        tr.x[i] = Row16Extra{c->dzeros, bk.list[o], bk.count + o, c->slot[sl[i]].blk, nullptr, c->model.dtables, c->span_next, nullptr};
         lt.qt[i] = c->slot[sl[i]].blk_dq;
         lt.rec[i] = bk.lane_rec[i];
         lt.rec_count[i] = bk.lane_count + i;
     }
-    lt.map = c->lane_map;
+    lt.map = c->model.lane_map;
     HIPCHK(c, hipMemsetAsync(bk.lane_count, 0, R16_TRAIN * sizeof(int32_t), st));
     if (first && c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
     // (A/B builds whose lane kernel takes the task rows from a pass: it writes them into the slot's block -- the same values for every
     //  step of the slot, whichever bank runs it)
     if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<double>(tr, n, st, 1));
-    HIPCHK(c, (hipError_t)launch_lane_osc<double>(tr, lt, n, c->lane_tier, lane_eig_blocks(), lane_eig_min(), st));
+    HIPCHK(c, (hipError_t)launch_lane_osc<double>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
     if (c->span_next) HIPCHK(c, (hipError_t)launch_span_end(c->span_next, st));      // (irlosc_time_trains: the step ends with its eigen pass)
     HIPCHK(c, (hipError_t)launch_row16_worklist<double>(tr, n, nullptr, st));
     if (last && c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
@@ -1039,7 +1088,8 @@ static int check_slot_filled(irlosc_ctx* c, int slot, int B) {
 static int launch_slot(irlosc_ctx* c, int slot, int B, const void* feed_wr = nullptr) {
     int rcf = check_slot_filled(c, slot, B);
     if (rcf) return rcf;
-    if (B > 0 && c->gains_nb > 0 && !feed_wr && slot_lane(c, slot, B)) {      // the resident lane route, as irlosc_step_resident takes it
+    const int route = record_route(c, slot, B);
+    if (route == IRLOSC_ROUTE_LANE && c->gains_nb > 0 && !feed_wr) {      // the resident lane route, as irlosc_step_resident takes it
         if (ensure_bank(c, 0, 1, NEED_LANE) == 0) {
             KParams<double> p;
             fill_params<double>(c, p, B, slot_inputs(c->slot[slot]), c->du, c->dflags);
@@ -1048,7 +1098,7 @@ static int launch_slot(irlosc_ctx* c, int slot, int B, const void* feed_wr = nul
         }
         free_bank(c->bank[0], NEED_LANE);
     }
-    return launch(c, B, slot_inputs(c->slot[slot], feed_wr), c->du, c->dflags, c->stream, slot_tree(c, slot));
+    return launch(c, B, slot_inputs(c->slot[slot], feed_wr), c->du, c->dflags, c->stream, row16_route(route) == IRLOSC_ROUTE_ROW16_TREE);
 }
 
 extern "C" int irlosc_download(irlosc_ctx* c, int32_t B, void* u_host, uint32_t* flags_host) {
@@ -1140,37 +1190,37 @@ static int run_trains(irlosc_ctx* c, int first_slot, int B, int iters, int nbank
 // A train on dense records.  One kernel per launch, so a train whose slots do not ALL qualify for the tree-structured form is issued as
 // two sub-trains -- the qualifying steps with the tree kernel, the others with the dense recursion -- instead of dropping every step to
 // the dense recursion (one more launch, only when slots are mixed).
-// Slots of the resident lane route (slot_lane) go out as a third sub-train, ahead of the other two (lane_train).
+// Slots of the resident lane route go out as a third sub-train, ahead of the other two (lane_train).
 template <typename T>
 static int dense_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
     irlosc_ctx::Bank& bk = c->bank[k];
-    KParams<T> ps[3][R16_TRAIN];        // [2]: steps whose slot takes the lane route, [1]: the tree form, [0]: the others
-    int pos[3][R16_TRAIN];              // step of the train each sub-train step is
-    int sl[3][R16_TRAIN];               // its slot
-    int cnt[3] = {0, 0, 0};
+    constexpr int R0 = IRLOSC_ROUTE_ROW16, NR = IRLOSC_ROUTE_LANE - R0 + 1;      // sub-trains by record_route: dense, tree form, lane
+    KParams<T> ps[NR][R16_TRAIN];
+    int pos[NR][R16_TRAIN];             // step of the train each sub-train step is
+    int sl[NR][R16_TRAIN];              // its slot
+    int cnt[NR] = {};
     bool lane_ok = false;               // some slot takes the route: the bank's lane records (out of memory: the row16 kernel)
-    if constexpr (std::is_same<T, double>::value)
-        for (int i = 0; i < n; ++i) lane_ok = lane_ok || slot_lane(c, slots[i], B);
+    for (int i = 0; i < n; ++i) lane_ok = lane_ok || record_route(c, slots[i], B) == IRLOSC_ROUTE_LANE;
     if (lane_ok && ensure_bank(c, k, n, NEED_LANE)) { free_bank(bk, NEED_LANE); lane_ok = false; }
     for (int i = 0; i < n; ++i) {
         const int slot = slots[i];
         int rcf = check_slot_filled(c, slot, B);
         if (rcf) return rcf;
-        const int kind = lane_ok && slot_lane(c, slot, B) ? 2 : slot_tree(c, slot) ? 1 : 0;
-        pos[kind][cnt[kind]] = i;
-        sl[kind][cnt[kind]] = slot;
-        fill_params<T>(c, ps[kind][cnt[kind]++], B, slot_inputs(c->slot[slot]), bk.u[i], bk.flags[i]);
+        const int route = record_route(c, slot, B), r = (lane_ok ? route : row16_route(route)) - R0;
+        pos[r][cnt[r]] = i;
+        sl[r][cnt[r]] = slot;
+        fill_params<T>(c, ps[r][cnt[r]++], B, slot_inputs(c->slot[slot]), bk.u[i], bk.flags[i]);
     }
     int first = -1, last = -1;      // order: lane sub-train, tree sub-train, dense sub-train
-    for (int kind = 2; kind >= 0; --kind) if (cnt[kind]) { if (first < 0) first = kind; last = kind; }
-    for (int kind = 2; kind >= 0; --kind) {
-        if (!cnt[kind]) continue;
+    for (int r = NR - 1; r >= 0; --r) if (cnt[r]) { if (first < 0) first = r; last = r; }
+    for (int r = NR - 1; r >= 0; --r) {
+        if (!cnt[r]) continue;
         int rc;
-        if constexpr (std::is_same<T, double>::value)
-            rc = kind == 2 ? lane_train(c, ps[kind], sl[kind], cnt[kind], k, pos[kind], kind == first, kind == last)
-                           : row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk.st, k, pos[kind], kind == first, kind == last);
+        if constexpr (std::is_same<T, double>::value)      // (the lane route: float64 records only, lane_eligible)
+            rc = r + R0 == IRLOSC_ROUTE_LANE ? lane_train(c, ps[r], sl[r], cnt[r], k, pos[r], r == first, r == last)
+                                             : row16_train<T>(c, ps[r], cnt[r], r + R0 == IRLOSC_ROUTE_ROW16_TREE, bk.st, k, pos[r], r == first, r == last);
         else
-            rc = row16_train<T>(c, ps[kind], cnt[kind], kind == 1, bk.st, k, pos[kind], kind == first, kind == last);
+            rc = row16_train<T>(c, ps[r], cnt[r], r + R0 == IRLOSC_ROUTE_ROW16_TREE, bk.st, k, pos[r], r == first, r == last);
         if (rc) return rc;
     }
     return IRLOSC_OK;
@@ -1180,7 +1230,7 @@ static int dense_train(irlosc_ctx* c, const int* slots, int n, int B, int k) {
 // train already allocates it: a caller's warm-up then pays for it, not its timed loop).
 static int row16_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
     bool lane = false;
-    for (int i = 0; i < std::min(iters, c->cfg.n_slots) && !lane; ++i) lane = slot_lane(c, (first_slot + i) % c->cfg.n_slots, B);
+    for (int i = 0; i < std::min(iters, c->cfg.n_slots) && !lane; ++i) lane = record_route(c, (first_slot + i) % c->cfg.n_slots, B) == IRLOSC_ROUTE_LANE;
     return run_trains(c, first_slot, B, iters, c->r16_overlap && iters >= R16_TRAIN ? irlosc_ctx::R16_BANKS : 1,
                       (c->task_pass ? NEED_ROWS : 0) | (lane ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? dense_train<double> : dense_train<float>);
 }
@@ -1344,12 +1394,22 @@ extern "C" int irlosc_sync(irlosc_ctx* c) {
 }
 
 // ---- rigid-body front end ------------------------------------------------------------------------------------------
-extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
-    if (!c) return IRLOSC_ERR_ARG;
+// q (w x y z) -> row-major rotation; `normalise`: of q / |q| (a caller's quaternion), else q is taken as given (the model's own, as the
+// kernels take them)
+static void quat_mat(const double* q, double* R, bool normalise) {
+    const double nq = normalise ? std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) : 1.0;      // (x / 1.0 is x, bit for bit)
+    const double w = q[0] / nq, x = q[1] / nq, y = q[2] / nq, z = q[3] / nq;
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+    R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+    R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
+}
+
+// Validate and derive: the caller's model checked against the cfg and turned into the walk's tables.  A pure function of `m`, c->cfg and
+// c->k (of the context it writes the error text only); every IRLOSC_ERR_ARG of irlosc_set_model is returned here.
+static int derive_model(irlosc_ctx* c, const irlosc_model* m, FeModel& h) {
     if (!m) return fail(c, IRLOSC_ERR_ARG, "model is NULL");
     if (m->nb < 1 || m->nb > IRLOSC_MAX_BODIES) return fail(c, IRLOSC_ERR_ARG, "nb=%d out of [1,%d]", m->nb, IRLOSC_MAX_BODIES);
     if (m->nj != c->cfg.n) return fail(c, IRLOSC_ERR_ARG, "model has %d hinges but cfg.n = %d", m->nj, c->cfg.n);
-    FeModel h;
     memset(&h, 0, sizeof h);
     h.nb = m->nb; h.nj = m->nj; h.ndev = c->cfg.ndev; h.k = c->k;
     std::vector<int> seen(m->nj, 0);
@@ -1375,27 +1435,19 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         for (int b = 0; b < m->nb; ++b) if ((h.anc_mask[b] >> j) & 1u) h.sub_mask[j] |= 1ull << b;
     }
     for (int i = 0; i < 3; ++i) h.gravity[i] = m->gravity[i];
-    {   // derived tables of the lane-per-instance kernel
-        auto q2m_host = [](const double* q, double* R) {
-            const double w = q[0], x = q[1], y = q[2], z = q[3];
-            R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-            R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-            R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
-        };
-        for (int b = 0; b < m->nb; ++b) {
-            double R[9];
-            const int jb = h.joint_of_body[b];
-            if (jb >= 0) {
-                q2m_host(h.quat[b], R);
-                for (int r = 0; r < 3; ++r) h.jpos_par[jb][r] = R[r * 3] * h.jpos[jb][0] + R[r * 3 + 1] * h.jpos[jb][1] + R[r * 3 + 2] * h.jpos[jb][2];
-            }
-            for (int j = 0; j < m->nj; ++j) if ((h.anc_mask[b] >> j) & 1u) h.cmass[j] += h.mass[b];
-            q2m_host(h.iquat[b], R);
-            int e = 0;
-            for (int r = 0; r < 3; ++r)
-                for (int cc = r; cc < 3; ++cc)
-                    h.icb[b][e++] = R[r * 3] * h.inertia[b][0] * R[cc * 3] + R[r * 3 + 1] * h.inertia[b][1] * R[cc * 3 + 1] + R[r * 3 + 2] * h.inertia[b][2] * R[cc * 3 + 2];
+    for (int b = 0; b < m->nb; ++b) {      // derived tables of the lane-per-instance kernel
+        double R[9];
+        const int jb = h.joint_of_body[b];
+        if (jb >= 0) {
+            quat_mat(h.quat[b], R, false);
+            for (int r = 0; r < 3; ++r) h.jpos_par[jb][r] = R[r * 3] * h.jpos[jb][0] + R[r * 3 + 1] * h.jpos[jb][1] + R[r * 3 + 2] * h.jpos[jb][2];
         }
+        for (int j = 0; j < m->nj; ++j) if ((h.anc_mask[b] >> j) & 1u) h.cmass[j] += h.mass[b];
+        quat_mat(h.iquat[b], R, false);
+        int e = 0;
+        for (int r = 0; r < 3; ++r)
+            for (int cc = r; cc < 3; ++cc)
+                h.icb[b][e++] = R[r * 3] * h.inertia[b][0] * R[cc * 3] + R[r * 3 + 1] * h.inertia[b][1] * R[cc * 3 + 1] + R[r * 3 + 2] * h.inertia[b][2] * R[cc * 3 + 2];
     }
     for (int b = 0; b < m->nb; ++b) {      // the per-body records of the walk (FeModel::rec)
         double* w = h.rec[b];
@@ -1413,69 +1465,63 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         h.row0[d] = row; row += c->cfg.dev_rows[d];
         for (int i = 0; i < 6; ++i) if (c->cfg.ctrlr_dof[d][i]) h.dofmask[d] |= 1u << i;
     }
-    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    // a new model: the F/T description (site bodies, R_rel) and every slot's sensor feed no longer apply
-    // (and the pack table: every slot's compact block is built again by its next upload / front end)
-    c->ft_set = 0;
-    for (Slot& s : c->slot) s.drop_block(true);
-    c->hm_nb = m->nb;
-    for (int b = 0; b < m->nb; ++b) {
-        c->hm_parent[b] = m->parent[b]; c->hm_joint[b] = m->joint_of_body[b];
-        for (int i = 0; i < 4; ++i) c->hm_quat[b][i] = m->quat[b][i];
-    }
-    for (int d = 0; d < c->cfg.ndev; ++d) c->hm_ee[d] = m->ee_body[d];
-    if (!c->dmodel) HIPCHK(c, hipMalloc((void**)&c->dmodel, sizeof(FeModel)));
-    c->fe_smem = frontend_smem_bytes(m->nb, m->nj);
+    return IRLOSC_OK;
+}
+
+// Plan the routes of the derived model `h` on this context: which front end, whether the fused path, which OSC step behind its walk,
+// whether the resident lane route -- with the tables each needs.  Host arithmetic and the A/B switches of the environment only.
+void ModelPlan::plan_routes(const irlosc_ctx* c) {
+    fe_smem = frontend_smem_bytes(h.nb, h.nj);
     // IRLOSC_FRONTEND=generic: force the wave-per-instance kernel (A/B measurements); IRLOSC_WALK=general: the shape-only walk on the
     // fused path (A/B measurements, tests)
-    c->fe_lane = frontend_lane_dual_ur5_matches(h) && !env_is("IRLOSC_FRONTEND", "generic");
-    c->fe_lane_s = c->fe_lane && frontend_lane_dual_ur5_s_matches(h) && !env_is("IRLOSC_WALK", "general");
-    // (the lane kernel's side buffer -- 139 MB at 65 536 robots -- is allocated by the first irlosc_frontend: a context that only
-    // ever takes the fused path never needs it)
+    fe_lane = frontend_lane_dual_ur5_matches(h) && !env_is("IRLOSC_FRONTEND", "generic");
+    fe_lane_s = fe_lane && frontend_lane_dual_ur5_s_matches(h) && !env_is("IRLOSC_WALK", "general");
     // The fused path needs the compiled tree shape (lane kernel) and the fp64 row16 kernel; IRLOSC_FUSED=0 forces the
     // two-kernel path through dense records (A/B measurements).
-    c->fused = c->fe_lane && c->kernel == IRLOSC_KERNEL_ROW16 && !env_off("IRLOSC_FUSED");
-    c->fq_overlap = !env_off("IRLOSC_FQ_OVERLAP");      // "0": consecutive fused trains on one stream (A/B measurements, tests)
-    if (c->fused) {
-        FeCompactTables t;
-        memset(&t, 0, sizeof t);
-        frontend_lane_dual_ur5_tables(h, &t);
-        for (int d = 0; d < c->cfg.ndev; ++d) c->ft_qe[d] = t.eetab[d][3];
-        if (!c->dtables) HIPCHK(c, hipMalloc((void**)&c->dtables, sizeof t));
-        HIPCHK(c, hipMemcpyAsync(c->dtables, &t, sizeof t, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));      // t lives on this stack frame (and no train of any bank is in flight)
-        // The OSC step behind the walk: lane-per-robot form when an instantiation holds this layout (IRLOSC_LANE=0: the row16 FROMQ
-        // kernel, A/B measurements and tests).  Every bank's exchange buffers and lane records start over with another entry count or
-        // layout (they are allocated again by the first fused train: ensure_bank).
-        lane::RowMap map;
-        const int tier = env_off("IRLOSC_LANE") ? -1 : lane_plan(h, &map);
-        if (t.n_entries != c->fe_xentries || tier != c->lane_tier || (tier >= 0 && memcmp(&map, &c->lane_map, sizeof map)))
-            for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-        c->fe_xentries = t.n_entries;
-        c->lane_tier = tier;
-        if (tier >= 0) c->lane_map = map;
-    } else {
-        c->lane_tier = -1;
-    }
-    // The resident lane route: the pack table of this layout
-    c->pack_ok = 0;
-    if (c->lane_tier >= 0) {
-        PackTable pt;
-        if (pack_plan(h, &pt)) {
-            if (!c->dpack) HIPCHK(c, hipMalloc((void**)&c->dpack, sizeof pt));
-            if (!c->dpack_bad) HIPCHK(c, hipMalloc((void**)&c->dpack_bad, sizeof(int32_t)));
-            HIPCHK(c, hipMemcpyAsync(c->dpack, &pt, sizeof pt, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));      // pt lives on this stack frame
-            c->pack_ok = 1;
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync(c->dmodel, &h, sizeof h, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    fused = fe_lane && c->kernel == IRLOSC_KERNEL_ROW16 && !env_off("IRLOSC_FUSED");
+    fq_overlap = !env_off("IRLOSC_FQ_OVERLAP");      // "0": consecutive fused trains on one stream (A/B measurements, tests)
+    if (!fused) return;
+    frontend_lane_dual_ur5_tables(h, &tables);
+    fe_xentries = tables.n_entries;
+    for (int d = 0; d < c->cfg.ndev; ++d) ft_qe[d] = tables.eetab[d][3];
+    // The OSC step behind the walk: lane-per-robot form when an instantiation holds this layout (IRLOSC_LANE=0: the row16 FROMQ
+    // kernel, A/B measurements and tests) -- and then the resident lane route, when the layout has a pack table
+    lane_tier = env_off("IRLOSC_LANE") ? -1 : lane_plan(h, &lane_map);
+    pack_ok = lane_tier >= 0 && pack_plan(h, &pack);
+}
+
+// The plan becomes the context's model.  No model is in force from the first line to the last: a HIP failure in between leaves the
+// context as it was before its first irlosc_set_model (the entry points from joint coordinates answer IRLOSC_ERR_STATE, no slot takes
+// the lane route), not between two models.  `p` outlives the call: one synchronisation behind all uploads -- with which no train of
+// any bank is in flight either, so the banks can be freed.
+int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
+    // Every bank's exchange buffers and lane records start over with another entry count or layout (they are allocated again by the
+    // first fused train: ensure_bank)
+    const bool resize = p.fused && (p.fe_xentries != fe_xentries || p.lane_tier != lane_tier ||
+                                    (p.lane_tier >= 0 && memcmp(&p.lane_map, &lane_map, sizeof lane_map)));
+    in_force = 0;
+    static_cast<ModelPlan&>(*this) = ModelPlan{};
+    if (!dmodel) HIPCHK(c, hipMalloc((void**)&dmodel, sizeof(FeModel)));
+    if (p.fused && !dtables) HIPCHK(c, hipMalloc((void**)&dtables, sizeof(FeCompactTables)));
+    if (p.pack_ok && !dpack) HIPCHK(c, hipMalloc((void**)&dpack, sizeof(PackTable)));
+    if (p.pack_ok && !dpack_bad) HIPCHK(c, hipMalloc((void**)&dpack_bad, sizeof(int32_t)));
+    // (the lane front end's side buffer -- 139 MB at 65 536 robots -- is allocated by the first irlosc_frontend: a context that only
+    // ever takes the fused path never needs it)
     for (Slot& s : c->slot) {      // the first model of the context: the slots' coordinate buffers
         if (!s.qpos) HIPCHK(c, hipMalloc((void**)&s.qpos, (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
         if (!s.qvel) HIPCHK(c, hipMalloc((void**)&s.qvel, (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
     }
-    if (c->fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
+    HIPCHK(c, hipMemcpyAsync(dmodel, &p.h, sizeof p.h, hipMemcpyHostToDevice, c->stream));
+    if (p.fused) HIPCHK(c, hipMemcpyAsync(dtables, &p.tables, sizeof p.tables, hipMemcpyHostToDevice, c->stream));
+    if (p.pack_ok) HIPCHK(c, hipMemcpyAsync(dpack, &p.pack, sizeof p.pack, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    static_cast<ModelPlan&>(*this) = p;
+    // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
+    // sensor feed, the F/T description (site bodies, R_rel)
+    if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
+    for (Slot& s : c->slot) s.drop_block(true);
+    c->ft_set = 0;
+    if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
         for (Slot& s : c->slot) {
             if (s.coords <= 0) continue;
             HIPCHK(c, ensure_qt(c, s));
@@ -1483,15 +1529,25 @@ extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    in_force = 1;
     return IRLOSC_OK;
 }
 
+extern "C" int irlosc_set_model(irlosc_ctx* c, const irlosc_model* m) {
+    if (!c) return IRLOSC_ERR_ARG;
+    ModelPlan p;
+    const int rc = derive_model(c, m, p.h);      // refused: the model in force stays, whole
+    if (rc) return rc;
+    p.plan_routes(c);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    return c->model.commit(c, p);
+}
 
 extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const double* qpos, const double* qvel) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
-    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
     Slot& s = c->slot[slot];
     if (B == 0) { s.coords = -1; return IRLOSC_OK; }
     if (!qpos || !qvel) return fail(c, IRLOSC_ERR_ARG, "qpos and qvel are required");
@@ -1504,7 +1560,7 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
     // (only the fused path reads this layout; its buffer is allocated by the slot's first upload while the path is on, or by the
     //  irlosc_set_model that turns it on -- and, once it exists, refreshed by EVERY upload: a copy left stale while another model had
     //  the path switched off would be walked later)
-    if (c->fused) HIPCHK(c, ensure_qt(c, s));
+    if (c->model.fused) HIPCHK(c, ensure_qt(c, s));
     if (s.qt) HIPCHK(c, (hipError_t)launch_q_layout(s.qpos, s.qvel, s.qt, B, c->cfg.n, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.coords = B;
@@ -1513,7 +1569,7 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
 
 // qpos / qvel: the caller's device arrays instead of the slot's coordinates, on stream `cst` (irlosc_step_from_q_device)
 static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = nullptr, const double* qvel = nullptr, hipStream_t cst = nullptr) {
-    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
     Slot& s = c->slot[slot];
     if (!qpos && !s.coords) return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q must precede irlosc_frontend", slot);
     s.drop_block(false);
@@ -1521,30 +1577,24 @@ static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = 
     if (!qpos && B > s.coords) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, front end asked for %d", slot, std::max(0, s.coords), B);
     if (!qpos) { qpos = s.qpos; qvel = s.qvel; }
     const hipStream_t st = cst ? cst : c->stream;
-    if (c->fe_lane && !c->fe_side) {
-        const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
-        if (hipMalloc((void**)&c->fe_side, waves * frontend_lane_dual_ur5_side_doubles_per_wave() * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->fe_side = nullptr;
-            c->fe_lane = 0;              // out of memory: the wave-per-robot kernel needs no side buffer
-            c->fused = 0;
-        }
-    }
+    Model& m = c->model;
+    if (m.fe_lane && !dev_alloc(m.fe_side, (((size_t)c->cfg.max_batch + 63) / 64) * frontend_lane_dual_ur5_side_doubles_per_wave() * sizeof(double)))
+        m.give_up_lane_walk();
     s.writing();
     int rc;
     if (c->cfg.dtype == IRLOSC_F64) {
         const FeOut<double> o = slot_out<double>(s);
-        rc = c->fe_lane ? launch_frontend_lane_dual_ur5<double>(c->dmodel, qpos, qvel, o, B, c->fe_side, st)
-                        : launch_frontend_generic<double>(c->dmodel, qpos, qvel, o, B, c->fe_smem, st);
+        rc = m.fe_lane ? launch_frontend_lane_dual_ur5<double>(m.dmodel, qpos, qvel, o, B, m.fe_side, st)
+                       : launch_frontend_generic<double>(m.dmodel, qpos, qvel, o, B, m.fe_smem, st);
     } else {
         const FeOut<float> o = slot_out<float>(s);
-        rc = c->fe_lane ? launch_frontend_lane_dual_ur5<float>(c->dmodel, qpos, qvel, o, B, c->fe_side, st)
-                        : launch_frontend_generic<float>(c->dmodel, qpos, qvel, o, B, c->fe_smem, st);
+        rc = m.fe_lane ? launch_frontend_lane_dual_ur5<float>(m.dmodel, qpos, qvel, o, B, m.fe_side, st)
+                       : launch_frontend_generic<float>(m.dmodel, qpos, qvel, o, B, m.fe_smem, st);
     }
     HIPCHK(c, (hipError_t)rc);
     // The records of this slot are now those of B robots: an earlier, larger upload must not vouch for instances the front
     // end did not write (the wrench of the slot stays what the last irlosc_upload / irlosc_upload_raw put there).
-    s.accepted(B, s.has_wrench, c->fe_lane);     // the lane kernel walks the compiled tree: its records carry the tree's zeros by construction
+    s.accepted(B, s.has_wrench, m.fe_lane);     // the lane kernel walks the compiled tree: its records carry the tree's zeros by construction
     // (and so need no check for the compact block of the lane route; a caller's stream gets no pack: the slot steps on the row16 kernel)
     return cst ? IRLOSC_OK : pack_slot(c, slot, B, false);
 }
@@ -1578,7 +1628,7 @@ extern "C" int irlosc_download_records(irlosc_ctx* c, int32_t slot, int32_t B, v
 
 // A step from joint coordinates over B robots needs B robots of (qpos, qvel) AND of targets in the slot.
 static int check_slot_q(irlosc_ctx* c, int slot, int B) {
-    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
     const Slot& s = c->slot[slot];
     if (!s.coords || !s.targets)
         return fail(c, IRLOSC_ERR_STATE, "slot %d: irlosc_upload_q and irlosc_set_targets must precede a step from joint coordinates", slot);
@@ -1602,10 +1652,10 @@ static int ft_launch(irlosc_ctx* c, const FtStep* s, int n, int B, hipStream_t s
     memset(&tr, 0, sizeof tr);
     for (int i = 0; i < n; ++i) tr.s[i] = s[i];
     for (int d = 0; d < c->cfg.ndev; ++d) {
-        tr.f0[d] = c->ft_f0[d]; tr.t0[d] = c->ft_t0[d]; tr.qe[d] = c->ft_qe[d];
+        tr.f0[d] = c->ft_f0[d]; tr.t0[d] = c->ft_t0[d]; tr.qe[d] = c->model.ft_qe[d];
         for (int i = 0; i < 9; ++i) tr.R[d][i] = c->ft_R[d][i];
     }
-    tr.B = B; tr.ndev = c->cfg.ndev; tr.n_sensor = c->ft_n_sensor; tr.n_entries = (int32_t)c->fe_xentries;
+    tr.B = B; tr.ndev = c->cfg.ndev; tr.n_sensor = c->ft_n_sensor; tr.n_entries = (int32_t)c->model.fe_xentries;
     HIPCHK(c, (hipError_t)(c->cfg.dtype == IRLOSC_F64 ? launch_ft_wrench<double>(tr, n, st) : launch_ft_wrench<float>(tr, n, st)));
     return IRLOSC_OK;
 }
@@ -1625,11 +1675,11 @@ static void* feed_wrench(irlosc_ctx* c, int k, int i) {
 // FROMQ kernel.  (A caller of irlosc_step_from_q needs one step's buffers, the benchmark form R16_TRAIN: 1.4 GB of exchange buffers at
 // 65 536 robots -- a context that only ever runs irlosc_frontend + irlosc_step pays nothing.)
 static bool fused_ready(irlosc_ctx* c, int n) {
-    if (!c->fused) return false;
-    const unsigned miss = ensure_bank(c, 0, n, NEED_X | (c->lane_tier >= 0 ? NEED_LANE : 0));
-    if (miss == NEED_X) { free_bank(c->bank[0], NEED_X); c->fused = 0; }
-    if (miss == NEED_LANE) { free_bank(c->bank[0], NEED_LANE); c->lane_tier = -1; }
-    return c->fused;
+    if (from_q_form(c, false) == FROMQ_DENSE) return false;
+    const unsigned miss = ensure_bank(c, 0, n, fused_need(c));
+    if (miss == NEED_X) c->model.give_up_fused(c);
+    if (miss == NEED_LANE) c->model.give_up_lane(c);
+    return from_q_form(c, false) != FROMQ_DENSE;
 }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
@@ -1686,38 +1736,37 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
         StepInputs in = slot_inputs(s, wr);
         if (dv) { in.tgt = dv->tgt; in.tvel = dv->tvel; in.wrench = wr; }
         fill_params<T>(c, tr.p[i], B, in, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
-        tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], qvel, c->dtables, c->span_next};
+        tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], qvel, c->model.dtables, c->span_next};
         ga.out[i] = slot_out<T>(s);
         ga.list[i] = bk.list[i];
         ga.count[i] = bk.count + i;
     }
-    // lane form of the OSC step: not with target velocities (branch B of osc.py:173-177 reads dx between the two halves of the task
-    // signal: the row16 FROMQ kernel keeps those trains)
-    bool use_lane = c->lane_tier >= 0;
+    // lane form of the OSC step: when every step of the train takes it (from_q_form) and the bank has its records
+    bool use_lane = true;
     lane::LaneTrain lt;
     memset(&lt, 0, sizeof lt);
     for (int i = 0; i < n && use_lane; ++i) {
-        if ((dv ? dv->tvel != nullptr : c->slot[slots[i]].has_tvel != 0) || !bk.lane_rec[i] || !bk.lane_count) use_lane = false;
+        const bool tvel = dv ? dv->tvel != nullptr : c->slot[slots[i]].has_tvel != 0;
+        if (from_q_form(c, tvel) != FROMQ_LANE || !bk.lane_rec[i] || !bk.lane_count) use_lane = false;
         lt.qt[i] = c->slot[slots[i]].qt;
         lt.rec[i] = bk.lane_rec[i];
         lt.rec_count[i] = bk.lane_count + i;
     }
     if (use_lane) {
-        lt.map = c->lane_map;
+        lt.map = c->model.lane_map;
         HIPCHK(c, hipMemsetAsync(bk.lane_count, 0, R16_TRAIN * sizeof(int32_t), st));
     }
     if (c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
-    HIPCHK(c, (hipError_t)(c->fe_lane_s ? launch_frontend_lane_compact_dual_ur5_s(c->dmodel, ft, n, st)
-                                        : launch_frontend_lane_compact_dual_ur5(c->dmodel, ft, n, st)));
+    HIPCHK(c, (hipError_t)fused_walk(c).launch(c->model.dmodel, ft, n, st));
     int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
     if (rcw) return rcw;
     if (use_lane) {
         if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
-        HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->lane_tier, lane_eig_blocks(), lane_eig_min(), st));
+        HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
     } else {
         HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st));
     }
-    HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->dmodel, ga, n, c->fe_smem, st));
+    HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
     if (c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
     // The give-up pass wrote dense records of the robots on its lists into the slots (and nothing for the others): what the
@@ -1734,8 +1783,7 @@ static int fused_train_slots(irlosc_ctx* c, const int* slots, int n, int B, int 
 // `iters` steps on the fused path.  Banks are allocated only when a call chains trains: one bank per train up to FQ_BANKS.
 static int fused_resident(irlosc_ctx* c, int first_slot, int B, int iters) {
     const int ntrains = (iters + R16_TRAIN - 1) / R16_TRAIN;
-    return run_trains(c, first_slot, B, iters, c->fq_overlap ? std::min((int)irlosc_ctx::FQ_BANKS, ntrains) : 1,
-                      NEED_X | (c->lane_tier >= 0 ? NEED_LANE : 0), c->cfg.dtype == IRLOSC_F64 ? fused_train_slots<double> : fused_train_slots<float>);
+    return run_trains(c, first_slot, B, iters, c->model.fq_overlap ? std::min((int)irlosc_ctx::FQ_BANKS, ntrains) : 1, fused_need(c), c->cfg.dtype == IRLOSC_F64 ? fused_train_slots<double> : fused_train_slots<float>);
 }
 
 // A step from the slot's coordinates through dense records: front end, the wrench of the slot's sensor feed (when it has one), step.
@@ -1755,14 +1803,15 @@ static int dense_from_q_step(irlosc_ctx* c, int slot, int B) {
 
 extern "C" const char* irlosc_from_q_name(const irlosc_ctx* c) {
     static thread_local std::string nm;
-    if (!c || !c->dmodel) return "";
-    if (c->fused && c->lane_tier >= 0) {
+    if (!c || !c->model.in_force) return "";
+    const FromQ form = from_q_form(c, false);
+    if (form == FROMQ_LANE) {
         char sh[64];
-        snprintf(sh, sizeof sh, "osc_lane_%s_rows_%d_%d_%d + eigen pass", c->cfg.dtype == IRLOSC_F64 ? "f64" : "f32in_f64", lane::TIER_ROWS[c->lane_tier][0],
-                 lane::TIER_ROWS[c->lane_tier][1], lane::TIER_ROWS[c->lane_tier][2]);
-        nm = std::string(c->fe_lane_s ? "osc_frontend_lane_compact_dual_ur5_s + " : "osc_frontend_lane_compact_dual_ur5 + ") + sh +
+        const int* rows = lane::TIER_ROWS[c->model.lane_tier];
+        snprintf(sh, sizeof sh, "osc_lane_%s_rows_%d_%d_%d + eigen pass", c->cfg.dtype == IRLOSC_F64 ? "f64" : "f32in_f64", rows[0], rows[1], rows[2]);
+        nm = std::string(fused_walk(c).name) + " + " + sh +
              " (fused: compact exchange buffer, no dense M / J; OSC step one lane per robot; target velocities: " + c->kernel_name + "_fromq)";
-    } else if (c->fused) nm = std::string(c->fe_lane_s ? "osc_frontend_lane_compact_dual_ur5_s + " : "osc_frontend_lane_compact_dual_ur5 + ") + c->kernel_name + "_fromq (fused: compact exchange buffer, no dense M / J)";
+    } else if (form == FROMQ_ROW16) nm = std::string(fused_walk(c).name) + " + " + c->kernel_name + "_fromq (fused: compact exchange buffer, no dense M / J)";
     else nm = std::string(irlosc_frontend_name(c)) + " + " + c->kernel_name + " (through dense records)";
     return nm.c_str();
 }
@@ -1792,13 +1841,6 @@ extern "C" int irlosc_step_resident_from_q(irlosc_ctx* c, int32_t first_slot, in
 }
 
 // ---- F/T sensor feed of the steps from joint coordinates ------------------------------------------------------------
-static void quat_mat(const double* q, double* R) {      // unit quaternion (w x y z) of q -> row-major rotation
-    const double nq = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double w = q[0] / nq, x = q[1] / nq, y = q[2] / nq, z = q[3] / nq;
-    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
-    R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-    R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
-}
 static void mat_mul(const double* A, const double* B, double* C, bool at = false) {     // C = A B (at: A^T B)
     double t[9];
     for (int r = 0; r < 3; ++r)
@@ -1813,16 +1855,17 @@ static void mat_mul(const double* A, const double* B, double* C, bool at = false
 extern "C" int irlosc_set_ft_sensors(irlosc_ctx* c, const irlosc_ft_desc* fd) {
     if (!c) return IRLOSC_ERR_ARG;
     if (!fd) return fail(c, IRLOSC_ERR_ARG, "desc is NULL");
-    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
-    const int* par = c->hm_parent;
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    const FeModel& h = c->model.h;
+    const int32_t* par = h.parent;
     int32_t f0[IRLOSC_MAX_DEV], t0[IRLOSC_MAX_DEV];
     double R[IRLOSC_MAX_DEV][9];
     for (int d = 0; d < c->cfg.ndev; ++d) {
         f0[d] = t0[d] = -1;
         for (int i = 0; i < 9; ++i) R[d][i] = (i % 4 == 0) ? 1.0 : 0.0;
-        const int sb = fd->site_body[d], e = c->hm_ee[d];
+        const int sb = fd->site_body[d], e = h.ee_body[d];
         if (sb < 0) continue;
-        if (sb >= c->hm_nb) return fail(c, IRLOSC_ERR_ARG, "device %d: site_body %d out of [0,%d)", d, sb, c->hm_nb);
+        if (sb >= h.nb) return fail(c, IRLOSC_ERR_ARG, "device %d: site_body %d out of [0,%d)", d, sb, h.nb);
         if (fd->n_sensor < 3) return fail(c, IRLOSC_ERR_ARG, "device %d: n_sensor=%d holds no triple", d, fd->n_sensor);
         if (fd->ft_force0[d] < 0 || fd->ft_force0[d] > fd->n_sensor - 3 || fd->ft_torque0[d] < 0 || fd->ft_torque0[d] > fd->n_sensor - 3)
             return fail(c, IRLOSC_ERR_ARG, "device %d: sensordata indices force %d / torque %d out of [0,%d]", d, fd->ft_force0[d],
@@ -1837,16 +1880,16 @@ extern "C" int irlosc_set_ft_sensors(irlosc_ctx* c, const irlosc_ft_desc* fd) {
         for (int s = 0; s < 2; ++s) {
             for (int i = 0; i < 9; ++i) P[s][i] = (i % 4 == 0) ? 1.0 : 0.0;
             for (int x = ends[s]; x != a; x = par[x]) {      // P = R(q_x) P, from `ends[s]` up: P = R(child of a) ... R(ends[s])
-                if (c->hm_joint[x] >= 0)
+                if (h.joint_of_body[x] >= 0)
                     return fail(c, IRLOSC_ERR_ARG, "device %d: the F/T site body %d is not rigidly attached to the EE body %d (hinge %d of body %d "
-                                "lies between them)", d, sb, e, c->hm_joint[x], x);
+                                "lies between them)", d, sb, e, h.joint_of_body[x], x);
                 double Rx[9];
-                quat_mat(c->hm_quat[x], Rx);
+                quat_mat(h.quat[x], Rx, true);
                 mat_mul(Rx, P[s], P[s]);
             }
         }
         double Rs[9];
-        quat_mat(fd->site_quat[d], Rs);
+        quat_mat(fd->site_quat[d], Rs, true);
         mat_mul(P[0], Rs, P[0]);                   // R(a)^T R(site) = P_site R(site_quat)
         mat_mul(P[1], P[0], R[d], true);           // R_rel = R(ee)^T R(site) = P_ee^T P_site R(site_quat)
         f0[d] = fd->ft_force0[d]; t0[d] = fd->ft_torque0[d];
@@ -1891,7 +1934,7 @@ extern "C" int irlosc_step_from_q_device(irlosc_ctx* c, int32_t slot, int32_t B,
     if (rc) return rc;
     if (B == 0) return IRLOSC_OK;
     if (!d_qpos || !d_qvel || !d_tgt_pose || !d_u || !d_flags) return fail(c, IRLOSC_ERR_ARG, "d_qpos, d_qvel, d_tgt_pose, d_u and d_flags are required");
-    if (!c->dmodel) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     if (d_sensordata && !c->ft_set) return fail(c, IRLOSC_ERR_STATE, "d_sensordata given but irlosc_set_ft_sensors has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
@@ -1918,7 +1961,7 @@ extern "C" int irlosc_step_from_q_device(irlosc_ctx* c, int32_t slot, int32_t B,
         }
         StepInputs in = slot_inputs(s);
         in.tgt = d_tgt_pose; in.tvel = d_tgt_vel; in.wrench = d_sensordata ? s.wrench : nullptr;
-        if (!rc) rc = launch(c, B, in, d_u, d_flags, st, slot_tree(c, slot));
+        if (!rc) rc = launch(c, B, in, d_u, d_flags, st, row16_route(record_route(c, slot, B)) == IRLOSC_ROUTE_ROW16_TREE);
     }
     s.lent(d_sensordata != nullptr);      // (the front end / fused_train mark what they wrote: none of it is the slot's state)
     return rc;

@@ -11,7 +11,7 @@ namespace irlosc {
 template <typename T>
 int launch_generic(const KParams<T>& p, int blocks, hipStream_t st);
 
-// tu_row16_f64.hip / tu_row16_f32.hip -- fp64-arithmetic row16 path (osc_row16.hpp); TIN = record type
+// tu_row16_f64.hip / tu_row16_f32.hip (body: tu_row16_impl.hpp) -- fp64-arithmetic row16 path (osc_row16.hpp); TIN = record type
 template <typename TIN> struct Row16Train;
 template <typename TIN>
 int launch_row16(const Row16Train<TIN>& tr, int nsteps, bool tree, hipStream_t st);      // tree: tree-structured factorisation

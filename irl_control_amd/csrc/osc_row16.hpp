@@ -1422,11 +1422,20 @@ __global__ __launch_bounds__(64 * IRLOSC_MAX_DEV) void osc_task_rows_dense_kerne
         if ((size_t)blockIdx.x * (64 * 16) + i < last) out[i] = (i & 15) < k ? rows[i >> 4][i & 15] : 0.0;
 }
 
-// Shapes with an instantiation of their own (tuned: register budget, prefetch depth) ...
+// Shapes (k, ndev) with an instantiation of their own (tuned: register budget, prefetch depth): THE list -- the host's kernel class
+// (row16_kernel_exact) and every dispatch of the launchers (tu_row16_impl.hpp) are derived from it, so a shape is added in this line ...
+template <int K, int NDEV> struct R16Shape { static constexpr int k = K, ndev = NDEV; };
+template <class... S> struct R16Shapes {};
+using R16ExactShapes = R16Shapes<R16Shape<13, 3>, R16Shape<12, 2>, R16Shape<7, 3>, R16Shape<6, 2>>;
+// f(R16Shape<k, ndev>{}) for the listed shape that equals (k, ndev).  -> false: it is not on the list
+template <class F, class... S>
+inline bool row16_exact_shape(R16Shapes<S...>, int k, int ndev, F&& f) {
+    return ((k == S::k && ndev == S::ndev ? (f(S{}), true) : false) || ...);
+}
 inline bool row16_kernel_exact(int n, int k, int ndev) {
     const char* e = getenv("IRLOSC_FORCE_PAD");      // A/B aid, read by irlosc_create only: the padded variant on a shape that has an instantiation
     if (e && e[0] == '1') return false;
-    return n == 25 && ((k == 13 && ndev == 3) || (k == 12 && ndev == 2) || (k == 7 && ndev == 3) || (k == 6 && ndev == 2));
+    return n == 25 && row16_exact_shape(R16ExactShapes{}, k, ndev, [](auto) {});
 }
 // ... and the KMAX-padded variants that take every other n = 25 layout: the smallest tier that holds k
 constexpr int R16_PAD_TIERS[] = {4, 7, 10, 13, 16};

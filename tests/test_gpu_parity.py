@@ -1298,6 +1298,47 @@ def test_frontend_needs_a_model_and_coordinates():
     osc.close()
 
 
+def test_a_refused_model_leaves_the_model_in_force_whole():
+    """An irlosc_set_model refused with IRLOSC_ERR_ARG -- here ee_body out of range, found after the whole model was validated and
+    its tables derived -- changes nothing: the steps from joint coordinates keep their form and name, a slot's records keep their
+    route (the resident lane route: its compact block and the pack table stay), the F/T description and the slot's sensor feed stay,
+    and a step computes the same bits."""
+    import ctypes as C
+    from irl_control_amd.rigid_body import DUAL_UR5_EE, RigidBodyModel
+    B = 4096
+    lay, gains, g = synth.make_batch("k12_admit", B, seed=71)
+    model = RigidBodyModel.load("dual_ur5")
+    osc = BatchedOSC(lay, B, dtype=np.float64, n_slots=2)
+    osc.set_gains(gains["kp"], gains["kv"], gains["ko"], gains["k"], gains["d"], gains["max_vel"], gains["null_kv"])
+    osc.set_model(model)
+    osc.set_ft_sensors()
+    rng = np.random.default_rng(72)
+    qpos, qvel = model.random_state(rng, B)
+    for sl in range(2):                  # the same robots in both slots; slot 0 with a sensor feed, slot 1 with records
+        osc.upload_q(qpos, qvel, slot=sl)
+        osc.set_targets(g["tgt_pose"], slot=sl)
+    osc.set_sensordata(rng.normal(0.0, 5.0, size=(B, 18)), slot=0)
+    osc.frontend(slot=1)
+
+    def observed():
+        u, fl = osc.step_q(slot=0, return_flags=True)
+        return osc.from_q_name, osc.slot_route(1), u, fl
+
+    name0, route0, u0, fl0 = observed()
+    assert "fused" in name0 and route0 == "lane"
+    u_plain = osc.step_q(slot=1)
+    osc.frontend(slot=1)                 # (the fused step took slot 1's records: here they are again)
+    assert not np.array_equal(u_plain, u0)      # slot 0's feed is felt: losing it would show
+    st = model.to_struct([DUAL_UR5_EE[d] for d in lay.dev_names])
+    st.ee_body[lay.ndev - 1] = model.nb
+    assert osc.lib.irlosc_set_model(osc._h, C.byref(st)) == -1      # IRLOSC_ERR_ARG
+    assert b"ee_body" in osc.lib.irlosc_last_error(osc._h)
+    name1, route1, u1, fl1 = observed()
+    osc.close()
+    assert name1 == name0 and route1 == route0
+    assert np.array_equal(u1, u0) and np.array_equal(fl1, fl0)
+
+
 def test_step_refuses_more_instances_than_the_slot_holds():
     """state, targets and step sizes are tied together: stepping over more instances than were uploaded (or
     targeted) is IRLOSC_ERR_STATE instead of a silent pass over stale HBM; an asymmetric M is refused on request."""
