@@ -435,6 +435,42 @@ IRLOSC_API int irlosc_step_from_q_device(irlosc_ctx* ctx, int32_t slot, int32_t 
                                          const void* d_tgt_pose, const void* d_tgt_vel, const double* d_sensordata,
                                          void* d_u, uint32_t* d_flags, void* hip_stream);
 
+/* ---- closed loops on the GPU: a contact-free plant behind the fused step (csrc/osc_plant.hpp) ---------------------------
+ * What examples/closed_loop_headless.py does on the host per tick, as one more kernel behind a fused step from joint coordinates:
+ *     rhs_j = (ctrl_mask bit j ? u_j : 0) - bias_j - damping qvel_j;   qacc = M^-1 rhs;   qvel += dt qacc;   qpos += dt qvel
+ * from the M, bias the step's own walk left in its exchange buffer and the u the step computed, written back into the slot's
+ * coordinates (row-major and walk layout alike).  NOT a simulator: no contacts, no joint limits, no equality constraints.  float64
+ * arithmetic whatever the context's dtype (u is read in the context's dtype). */
+typedef struct irlosc_plant {
+    double dt;               /* > 0, finite */
+    double damping;          /* >= 0, finite: joint damping, the same for every joint */
+    uint32_t ctrl_mask;      /* bit j: joint j is torque-driven by u_j (bits >= n must be clear) */
+    uint32_t reserved;       /* 0 */
+} irlosc_plant;
+/* After irlosc_set_model (IRLOSC_ERR_STATE before).  A plant that fails the checks above is refused (IRLOSC_ERR_ARG) and the one in
+ * force stays.  A later irlosc_set_model clears the plant.  Setting a plant launches nothing and changes no other entry point. */
+IRLOSC_API int irlosc_set_plant(irlosc_ctx* ctx, const irlosc_plant* plant);
+/* `ticks` (>= 1) dependent ticks on slot `slot`'s B robots, enqueued back to back on the context's stream, one host synchronisation
+ * at the end.  A tick is one fused train of one step on bank 0 -- walk, the sensor feed's wrench if the slot has a feed (its readings
+ * stay what irlosc_set_sensordata put there), OSC step, eigen pass, give-up pass -- and behind it the plant kernel.  Targets (target
+ * velocities included) are the slot's, gains the context's.  The slot keeps B robots of coordinates, targets and feed; as after
+ * every fused step it holds no dense records afterwards.
+ *   trace_every > 0 and ee_trace_host != NULL: ee_trace_host[i][B][ndev][7] (double) = the EE poses at the START of tick
+ *       i * trace_every, ceil(ticks / trace_every) samples.  The device buffer behind it is bounded (256 MiB, at least one sample):
+ *       a longer trace crosses PCIe in chunks, each copy ordered on the stream behind the ticks that filled it.
+ *   u_host[B][n] (context dtype, or NULL): the torques of the LAST tick;  flags_any_host[B] (or NULL): the OR of every tick's flags.
+ * A robot whose u or qacc is not finite, or whose M has a pivot that is not positive, is FROZEN for that tick (coordinates
+ * unchanged) with IRLOSC_FLAG_NONFINITE resp. IRLOSC_FLAG_M_NOT_PD in flags_any; other robots are unaffected.
+ * The plant reads the exchange buffer, so the rollout exists where the fused path does: IRLOSC_ERR_STATE with the reason in
+ * irlosc_last_error otherwise (no model / plant / gains, a model or context without the fused path, IRLOSC_FUSED=0, exchange buffers
+ * that could not be allocated, a slot without coordinates or targets for B robots).  There is no second form. */
+IRLOSC_API int irlosc_rollout_from_q(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t ticks, int32_t trace_every,
+                                     double* ee_trace_host, void* u_host, uint32_t* flags_any_host);
+/* The slot's joint coordinates as they sit in HBM (uploaded, or advanced by irlosc_rollout_from_q): qpos, qvel [B][n] double, either
+ * may be NULL.  IRLOSC_ERR_STATE on a slot that holds coordinates of fewer than B robots (none after irlosc_step_from_q_device lent
+ * it).  Synchronous. */
+IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, double* qpos, double* qvel);
+
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard
  * and NOTHING is exchanged per tick.  RCCL (over xGMI) is used once per benchmark: sum of the steps done, max of the

@@ -25,7 +25,7 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_upload_q", "irlosc_frontend", "irlosc_step_resident_from_q", "irlosc_download_records",
            "irlosc_step_from_q", "irlosc_from_q_name", "irlosc_slot_structure", "irlosc_probe_structure", "irlosc_time_trains", "irlosc_giveup_counts",
            "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device",
-           "irlosc_slot_route"]
+           "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -60,6 +60,11 @@ class FtDesc(C.Structure):
     """struct irlosc_ft_desc (include/irlosc.h): the F/T site of each target device (body, frame in it) and its sensordata slices."""
     _fields_ = [("n_sensor", C.c_int32), ("site_body", C.c_int32 * MAX_DEV), ("site_quat", (C.c_double * 4) * MAX_DEV),
                 ("ft_force0", C.c_int32 * MAX_DEV), ("ft_torque0", C.c_int32 * MAX_DEV)]
+
+
+class Plant(C.Structure):
+    """struct irlosc_plant (include/irlosc.h): the contact-free plant of irlosc_rollout_from_q."""
+    _fields_ = [("dt", C.c_double), ("damping", C.c_double), ("ctrl_mask", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Cfg(C.Structure):
@@ -132,6 +137,9 @@ def load():
     lib.irlosc_set_sensordata.argtypes = [vp, i32, i32, vp]
     lib.irlosc_step_from_q_device.argtypes = [vp, i32, i32] + [vp] * 8
     lib.irlosc_from_q_name.restype = C.c_char_p
+    lib.irlosc_set_plant.argtypes = [vp, C.POINTER(Plant)]
+    lib.irlosc_rollout_from_q.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
+    lib.irlosc_download_q.argtypes = [vp, i32, i32, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

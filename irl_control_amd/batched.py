@@ -311,6 +311,43 @@ class BatchedOSC:
         self._chk(self.lib.irlosc_step_from_q_device(self._h, slot, int(B), d_qpos, d_qvel, d_tgt_pose, d_tgt_vel, d_sensordata,
                                                      d_u, d_flags, stream))
 
+    # -- closed loops on the GPU: a contact-free plant behind the fused step (irlosc_set_plant / irlosc_rollout_from_q) ------------
+    def set_plant(self, dt: float, damping: float = 0.0, actuated=None):
+        """The plant of `rollout` (after set_model): qacc = M^-1 (u - bias - damping qvel), semi-implicit Euler with step `dt`.
+        `actuated`: indices of the joints driven by u (default: all n, as examples/closed_loop_headless.py; the others see u = 0).
+        No contacts, no joint limits, no equality constraints.  set_model clears it."""
+        n = self.layout.n
+        idx = list(range(n)) if actuated is None else [int(j) for j in actuated]
+        if any(j < 0 or j >= n for j in idx):
+            raise ValueError(f"actuated: joint indices must lie in [0, {n})")
+        mask = 0
+        for j in idx:
+            mask |= 1 << j
+        pl = _lib.Plant(float(dt), float(damping), mask, 0)
+        self._chk(self.lib.irlosc_set_plant(self._h, C.byref(pl)))
+
+    def rollout(self, ticks: int, trace_every: int = 0, slot: int = 0):
+        """`ticks` closed-loop ticks on the slot's resident robots without the host in between (irlosc_rollout_from_q): per tick
+        the fused step from the slot's coordinates towards its targets, then the plant kernel advances the coordinates.
+        -> dict(qpos, qvel: the coordinates afterwards; u: the last tick's torques; flags_any: OR of all ticks' flags;
+        ee_trace[ceil(ticks / trace_every), B, ndev, 7]: EE poses at the start of every trace_every-th tick, or None)."""
+        L, B = self.layout, self._B[slot]
+        ticks, trace_every = int(ticks), int(trace_every)
+        u = np.empty((B, L.n), dtype=self.dtype)
+        fl = np.empty(B, dtype=np.uint32)
+        tr = np.empty((-(-ticks // trace_every), B, L.ndev, 7), dtype=np.float64) if trace_every > 0 and ticks > 0 else None
+        self._chk(self.lib.irlosc_rollout_from_q(self._h, slot, B, ticks, trace_every, _lib.ptr(tr), _lib.ptr(u), _lib.ptr(fl)))
+        qpos, qvel = self.download_q(slot)
+        return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=tr)
+
+    def download_q(self, slot: int = 0):
+        """-> (qpos, qvel) [B, n] float64 of the slot as they sit in HBM: uploaded, or advanced by `rollout` (irlosc_download_q)."""
+        B = self._B[slot]
+        qpos = np.empty((B, self.layout.n), dtype=np.float64)
+        qvel = np.empty((B, self.layout.n), dtype=np.float64)
+        self._chk(self.lib.irlosc_download_q(self._h, slot, B, _lib.ptr(qpos), _lib.ptr(qvel)))
+        return qpos, qvel
+
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""
         B = self._B[first_slot] if B is None else B

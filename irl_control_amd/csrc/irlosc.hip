@@ -24,6 +24,7 @@
 #include "osc_lane_types.hpp"
 #include "osc_ft.hpp"
 #include "osc_pack.hpp"
+#include "osc_plant.hpp"
 #include "launchers.hpp"
 
 using namespace irlosc;
@@ -81,6 +82,9 @@ struct Slot {
     void voided() { records = 0; tree = 0; packed = 0; fused_away = 1; }
     // Records and coordinates (`wrench_too`: and the wrench buffer) are scratch of a device-pointer step: none of it is the slot's state.
     void lent(bool wrench_too) { records = 0; tree = 0; packed = 0; coords = 0; if (wrench_too) has_wrench = 0; }
+    // The plant kernel of a rollout advanced the coordinates of B robots on the device: row-major and walk layout alike, so they stay the
+    // slot's coordinates (targets and feed are not touched; the records went with the fused step of the tick: voided()).
+    void advanced(int B) { coords = B; }
     // pack_slot built the block of B robots from records it found eligible (lane_eligible: the tree verdict, so records > 0).
     void block_packed(int B) { packed = B; }
 };
@@ -166,6 +170,7 @@ struct irlosc_ctx {
     unsigned long long* dspan = nullptr;   // irlosc_time_trains: [ntrains][2] wall-clock stamps written by the kernels
     int dspan_cap = 0;
     unsigned long long* span_next = nullptr;   // the pair the next train launch stamps (or null)
+    const struct PlantCall* plant_next = nullptr;   // irlosc_rollout_from_q: the plant call the next fused train ends with (or null)
     std::vector<hipEvent_t> tev_pool;
     void* du = nullptr;                // output set written by the most recent step
     uint32_t* dflags = nullptr;
@@ -212,6 +217,11 @@ struct irlosc_ctx {
     // irlosc_tick: one pinned host block and one device block per direction, grown on demand
     void* tick_hin = nullptr; void* tick_din = nullptr; size_t tick_in_bytes = 0;
     void* tick_hout = nullptr; void* tick_dout = nullptr; size_t tick_out_bytes = 0;
+    // irlosc_rollout_from_q: the plant in force (irlosc_set_plant), the OR of the ticks' flags, the bounded device buffer of the EE trace
+    int plant_set = 0;
+    irlosc_plant plant{};
+    uint32_t* dflags_any = nullptr;
+    double* dtrace = nullptr;
     int32_t* dsym = nullptr;  // symmetry probe of the throughput paths: {count, first instance}
     // Tree-structured factorisation on dense records (row16 kernel), for slots whose records carry the tree's zeros (Slot::tree)
     int tree_enabled = 1;              // IRLOSC_TREE=0 turns the form off (A/B measurements)
@@ -344,6 +354,8 @@ static void free_all(irlosc_ctx* c) {
     if (c->tick_dout) (void)hipFree(c->tick_dout);
     if (c->dzeros) (void)hipFree(c->dzeros);
     if (c->dsym) (void)hipFree(c->dsym);
+    if (c->dflags_any) (void)hipFree(c->dflags_any);
+    if (c->dtrace) (void)hipFree(c->dtrace);
     if (c->dspan) (void)hipFree(c->dspan);
     if (c->dstruct) (void)hipFree(c->dstruct);
     if (c->dgains) (void)hipFree(c->dgains);
@@ -1521,6 +1533,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
     for (Slot& s : c->slot) s.drop_block(true);
     c->ft_set = 0;
+    c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
         for (Slot& s : c->slot) {
             if (s.coords <= 0) continue;
@@ -1682,6 +1695,12 @@ static bool fused_ready(irlosc_ctx* c, int n) {
     return from_q_form(c, false) != FROMQ_DENSE;
 }
 
+// irlosc_rollout_from_q: the plant kernel behind the step (one step on bank 0), handed to the next train like the timing events
+// (irlosc_ctx::plant_next); trace: the device sample of this tick's EE poses, or nullptr
+struct PlantCall {
+    double* trace;
+};
+
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
 struct DevCall {
     const double* qpos; const double* qvel;
@@ -1700,10 +1719,13 @@ struct DevCall {
 // With `dv` (one step on bank 0) the caller's arrays replace every per-slot input -- coordinates (the walk reads the slot's dqt, which
 // the device entry has laid them out into), targets, sensordata -- and its u / flags the output set; the slot only lends scratch.
 // A step whose slot has a sensor feed gets its wrench from the feed (osc_ft_wrench between the walk and the OSC step).
+// With `pl` (one step on bank 0 of the slot's own inputs: a tick of irlosc_rollout_from_q) the plant kernel follows the give-up pass --
+// the robots the generic kernel finishes have their u by then -- and advances the slot's coordinates.
 template <typename T>
-static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, const DevCall* dv) {
+static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, const DevCall* dv, const PlantCall* pl = nullptr) {
     if (n < 1 || n > R16_TRAIN) return fail(c, IRLOSC_ERR_STATE, "train of %d steps", n);
     if (dv && (n != 1 || k != 0)) return fail(c, IRLOSC_ERR_STATE, "a device-pointer step is one step on bank 0");
+    if (pl && (n != 1 || k != 0 || dv)) return fail(c, IRLOSC_ERR_STATE, "a tick of a rollout is one step on bank 0 from the slot's coordinates");
     for (int i = 0; i < n && !dv; ++i) {
         int rc = check_slot_q(c, slots[i], B);
         if (!rc) rc = check_slot_feed(c, slots[i], B);
@@ -1768,16 +1790,29 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     }
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
+    if (pl) {
+        const Slot& s = c->slot[slots[0]];
+        PlantArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.xside = bk.xside[0]; pa.u = bk.u[0]; pa.flags = bk.flags[0];
+        pa.qt = s.qt; pa.qpos = s.qpos; pa.qvel = s.qvel;
+        pa.trace = pl->trace; pa.flags_any = c->dflags_any;
+        pa.dt = c->plant.dt; pa.damping = c->plant.damping; pa.ctrl_mask = c->plant.ctrl_mask;
+        pa.B = B; pa.ndev = c->cfg.ndev;
+        for (int d = 0; d < c->cfg.ndev; ++d) pa.ee0[d] = c->model.tables.eetab[d][0];
+        HIPCHK(c, (hipError_t)launch_plant<T>(pa, st));
+    }
     if (c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
     // The give-up pass wrote dense records of the robots on its lists into the slots (and nothing for the others): what the
     // slots held before no longer belongs to one state.  They hold no records from here on -- irlosc_step / irlosc_step_resident
     // / irlosc_download_records on them fail with IRLOSC_ERR_STATE until irlosc_frontend / irlosc_upload* fills them again.
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
+    if (pl) c->slot[slots[0]].advanced(B);
     return IRLOSC_OK;
 }
 template <typename T>
 static int fused_train_slots(irlosc_ctx* c, const int* slots, int n, int B, int k) {
-    return fused_train<T>(c, slots, n, B, k, nullptr);
+    return fused_train<T>(c, slots, n, B, k, nullptr, c->plant_next);
 }
 
 // `iters` steps on the fused path.  Banks are allocated only when a call chains trains: one bank per train up to FQ_BANKS.
@@ -1964,6 +1999,103 @@ extern "C" int irlosc_step_from_q_device(irlosc_ctx* c, int32_t slot, int32_t B,
         if (!rc) rc = launch(c, B, in, d_u, d_flags, st, row16_route(record_route(c, slot, B)) == IRLOSC_ROUTE_ROW16_TREE);
     }
     s.lent(d_sensordata != nullptr);      // (the front end / fused_train mark what they wrote: none of it is the slot's state)
+    return rc;
+}
+
+// ---- closed loops on the GPU: the plant behind the fused step (osc_plant.hpp) ---------------------------------------------
+extern "C" int irlosc_set_plant(irlosc_ctx* c, const irlosc_plant* p) {
+    if (!c) return IRLOSC_ERR_ARG;
+    if (!p) return fail(c, IRLOSC_ERR_ARG, "plant is NULL");
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (!(std::isfinite(p->dt) && p->dt > 0.0)) return fail(c, IRLOSC_ERR_ARG, "plant: dt=%g must be finite and > 0", p->dt);
+    if (!(std::isfinite(p->damping) && p->damping >= 0.0)) return fail(c, IRLOSC_ERR_ARG, "plant: damping=%g must be finite and >= 0", p->damping);
+    if (p->reserved != 0) return fail(c, IRLOSC_ERR_ARG, "plant: reserved must be 0");
+    if (c->cfg.n < 32 && (p->ctrl_mask >> c->cfg.n)) return fail(c, IRLOSC_ERR_ARG, "plant: ctrl_mask has bits >= n=%d", c->cfg.n);
+    c->plant = *p;
+    c->plant_set = 1;
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_q(irlosc_ctx* c, int32_t slot, int32_t B, double* qpos, double* qvel) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Slot& s = c->slot[slot];
+    if (B > std::max(0, s.coords)) return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances", slot, std::max(0, s.coords));
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t bytes = (size_t)B * c->cfg.n * sizeof(double);
+    if (qpos) HIPCHK(c, hipMemcpyAsync(qpos, s.qpos, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (qvel) HIPCHK(c, hipMemcpyAsync(qvel, s.qvel, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return IRLOSC_OK;
+}
+
+// The ticks of a rollout, enqueued; the caller synchronises (also after an error: earlier ticks are in flight).
+static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, double* trace_host) {
+    const size_t sample = (size_t)B * c->cfg.ndev * 7;      // doubles
+    const int nsamples = every > 0 && trace_host ? (ticks + every - 1) / every : 0;
+    // the trace's device buffer: whole samples up to TRACE_BYTES, at least one; a chunk goes to the host when it is full
+    constexpr size_t TRACE_BYTES = (size_t)256 << 20;
+    const size_t max_sample = (size_t)c->cfg.max_batch * c->cfg.ndev * 7 * sizeof(double);
+    const int cap = (int)std::max<size_t>(1, TRACE_BYTES / max_sample);
+    if (nsamples && !dev_alloc(c->dtrace, (size_t)cap * max_sample))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the EE trace (%zu bytes)", (size_t)cap * max_sample);
+    HIPCHK(c, hipMemsetAsync(c->dflags_any, 0, (size_t)B * sizeof(uint32_t), c->stream));
+    int filled = 0, sent = 0;      // samples written / copied to the host
+    for (int t = 0; t < ticks; ++t) {
+        const bool traced = nsamples && t % every == 0;
+        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr};
+        c->plant_next = &pl;
+        const int rc = fused_resident(c, slot, B, 1);
+        c->plant_next = nullptr;
+        if (rc) return rc;
+        if (traced && (++filled % cap == 0 || filled == nsamples)) {
+            HIPCHK(c, hipMemcpyAsync(trace_host + (size_t)sent * sample, c->dtrace, (size_t)(filled - sent) * sample * sizeof(double),
+                                     hipMemcpyDeviceToHost, c->stream));
+            sent = filled;
+        }
+    }
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, int32_t trace_every, double* ee_trace_host,
+                                     void* u_host, uint32_t* flags_any_host) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    if (ticks < 1) return fail(c, IRLOSC_ERR_ARG, "ticks=%d must be >= 1", ticks);
+    if (trace_every < 0) return fail(c, IRLOSC_ERR_ARG, "trace_every=%d must be >= 0", trace_every);
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (!c->plant_set) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_plant has not been called (since the last irlosc_set_model)");
+    if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
+    if (!c->model.fused)
+        return fail(c, IRLOSC_ERR_STATE, "no rollout on this context: the plant reads the exchange buffer of the fused path, which is off (%s); "
+                    "steps from joint coordinates run %s", env_off("IRLOSC_FUSED") ? "IRLOSC_FUSED=0" :
+                    c->kernel != IRLOSC_KERNEL_ROW16 ? "the context runs the generic kernel" : c->model.fe_lane ? "its buffers could not be allocated"
+                    : "the model has not the compiled Dual-UR5 tree, or IRLOSC_FRONTEND=generic", irlosc_from_q_name(c));
+    if (c->cfg.n != plant_joints()) return fail(c, IRLOSC_ERR_STATE, "no rollout on this context: the plant kernel holds %d joints, n=%d", plant_joints(), c->cfg.n);
+    rc = check_slot_q(c, slot, B);
+    if (!rc) rc = check_slot_feed(c, slot, B);
+    if (rc) return rc;
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    if (!fused_ready(c, 1))
+        return fail(c, IRLOSC_ERR_STATE, "no rollout on this context: the exchange buffers of the fused path could not be allocated (the path "
+                    "is switched off; steps from joint coordinates run through dense records)");
+    HIPCHK(c, ensure_qt(c, c->slot[slot]));
+    if (!dev_alloc(c->dflags_any, (size_t)c->cfg.max_batch * sizeof(uint32_t))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for flags_any");
+    rc = rollout_ticks(c, slot, B, ticks, trace_every, ee_trace_host);
+    if (!rc && u_host) {
+        const hipError_t e = hipMemcpyAsync(u_host, c->du, (size_t)B * c->cfg.n * c->esz, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, IRLOSC_ERR_HIP, "copy of u failed: %s", hipGetErrorString(e));
+    }
+    if (!rc && flags_any_host) {
+        const hipError_t e = hipMemcpyAsync(flags_any_host, c->dflags_any, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = fail(c, IRLOSC_ERR_HIP, "copy of flags_any failed: %s", hipGetErrorString(e));
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    if (es != hipSuccess && !rc) rc = fail(c, IRLOSC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
     return rc;
 }
 

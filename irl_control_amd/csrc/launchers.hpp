@@ -81,6 +81,13 @@ int pack_entries();                                     // entries per robot of 
 int launch_pack(const PackArgs& a, hipStream_t st);
 int launch_span_end(unsigned long long* span, hipStream_t st);      // atomicMax(span + 1, wall clock) behind what the stream holds
 
+// tu_plant.hip -- the plant kernel behind a tick of irlosc_rollout_from_q (osc_plant.hpp): one lane per robot on the compiled Dual-UR5
+// tree; T = record type (of u)
+struct PlantArgs;
+template <typename T>
+int launch_plant(const PlantArgs& a, hipStream_t st);
+int plant_joints();                                     // hinges of the tree the kernel is compiled for
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;
