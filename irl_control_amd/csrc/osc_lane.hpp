@@ -63,19 +63,13 @@ struct LT {
     static constexpr int ee_rank(int j) { int n = 0; for (int i = 0; i < j; ++i) n += hinge_ee(i) ? 1 : 0; return n; }      // position among the EE hinges
     static constexpr int n_ee() { return ee_rank(NJ); }
     static constexpr int jentry0(int r, int j) { return TI::ee_index(row_body(r)) + 7 + 6 * TI::anc_rank(j, row_body(r)); }
-    static constexpr int subtree_last(int j) { int l = j; for (int c = j; c < NJ; ++c) if (TI::above(j, c)) l = c; return l; }
-    static constexpr bool has_below(int j) { return subtree_last(j) > j; }
     // the deepest hinge (largest index = first in the descending recursion) that moves row r's body, resp. both bodies
     static constexpr int deepest(int r) { int d = -1; for (int j = 0; j < NJ; ++j) if (row_moved(r, j)) d = j; return d; }
     static constexpr int deepest2(int r, int s) { int d = -1; for (int j = 0; j < NJ; ++j) if (row_moved(r, j) && row_moved(s, j)) d = j; return d; }
     // is there an EE hinge strictly below j that moves row r's body?  (then DJ[r][j] has been written when hinge j is reached)
     static constexpr bool dj_written(int r, int j) { for (int c = j + 1; c < NJ; ++c) if (TI::above(j, c) && row_moved(r, c)) return true; return false; }
-    static constexpr int m_entry(int i, int j) { return i == j ? TI::diag_index(j) : TI::pair_index(i, j); }      // i at or above j
     static constexpr int tri(int r, int s) { return r * (r + 1) / 2 + s; }                                         // s <= r
 };
-
-using r16::static_for;
-using r16::static_for_down;
 
 // Anchor a value where it is computed.  The recursion below is pure arithmetic between loads; the instruction selector orders pure
 // nodes by their USES, and every use sits behind the recursion (the k x k stage) -- left alone, all 330 loads and the M dq sums come
@@ -98,8 +92,6 @@ __device__ __forceinline__ void st_su(gptr ubase, const uint32_t voff, const dou
     *reinterpret_cast<gptr>(reinterpret_cast<__attribute__((address_space(1))) char*>(ubase) + voff) = v;
 }
 __device__ __forceinline__ void st_su(double* ubase, const uint32_t voff, const double v) { st_su((gptr)ubase, voff, v); }
-using r16::rsq_refined;
-using r16::rcp_refined;
 
 // Records of the flagged robots, transposed: [group of 64 records][entry][64] doubles -- what a lane writes and what a lane of the eigen
 // pass reads sits next to its neighbours' (slots of a wave's flagged lanes are consecutive: coalesced both ways).  Entries: the lower
@@ -126,6 +118,73 @@ struct Rec {
     static constexpr int E = OM + 2;
     static_assert(E <= REC_DOUBLES, "the host allocates REC_DOUBLES per robot");
 };
+
+// ---- the k x k stage's per-lane building blocks, shared by the lane kernel and the lane-form eigen pass ---------------------------------
+// In-place L~ D L~^T of the packed lower triangle F: L~ below the diagonal, the pivots not kept (invd = 1 / d).  The pivot of a row in nr
+// (padding, or an exact zero row) or a non-positive one is taken as 1; pd = no real pivot was non-positive.  One schedule barrier per
+// column: left to itself the scheduler interleaves the whole stage and everything long-lived spills.
+// SHIFTED = false, the lane kernel's: A itself (no `+ sigma`: IEEE does not fold a `+ 0.0`, a dependent add per pivot), dtrue[] gets the
+// pivots as they came out and det the product of the ones used; the tests branch-free (& and |: see that kernel's note on branches).
+// SHIFTED = true, the eigen pass's: A + sigma I, nothing kept; the tests short-circuit (with the bitwise form its k = 13 instantiation
+// spills 27 more registers).
+template <class L, bool SHIFTED>
+__device__ __forceinline__ void ldl_inplace(double (&F)[L::K * (L::K + 1) / 2], const bool (&nr)[L::K], double (&invd)[L::K], bool& pd,
+                                            const double sigma, double* dtrue, double* det) {
+    constexpr int K = L::K;
+    pd = true;
+    static_for<0, K>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        double d = F[L::tri(j, j)];
+        bool bad;
+        if constexpr (SHIFTED) {
+            d += sigma;
+            bad = !nr[j] && !(d > 0.0);
+            pd = pd && !bad;
+            d = (bad || nr[j]) ? 1.0 : d;
+        } else {
+            dtrue[j] = d;
+            bad = !nr[j] & !(d > 0.0);
+            pd = pd & !bad;
+            d = (bad | nr[j]) ? 1.0 : d;
+            *det *= d;
+        }
+        const double iv = rcp_refined(d);
+        invd[j] = iv;
+        double f[K];
+        static_for<j + 1, K>([&](auto ic) { constexpr int i = decltype(ic)::value; f[i] = F[L::tri(i, j)] * iv; });
+        static_for<j + 1, K>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            static_for<j + 1, i + 1>([&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                F[L::tri(i, c)] = fma(-f[i], F[L::tri(c, j)], F[L::tri(i, c)]);
+            });
+        });
+        static_for<j + 1, K>([&](auto ic) { constexpr int i = decltype(ic)::value; F[L::tri(i, j)] = f[i]; });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
+// trace(A^-1) over the real rows = sum over the columns m of W = L~^-1 of sum_c W[c][m]^2 / d_c; two columns of W per schedule barrier
+template <class L>
+__device__ __forceinline__ double trace_inv(const double (&F)[L::K * (L::K + 1) / 2], const bool (&nr)[L::K], const double (&invd)[L::K]) {
+    constexpr int K = L::K;
+    double trA = 0.0;
+    static_for<0, K>([&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        double xw[K];
+        xw[m] = 1.0;
+        double acc = nr[m] ? 0.0 : invd[m];
+        static_for<m + 1, K>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            double s = -F[L::tri(c, m)];
+            static_for<m + 1, c>([&](auto qc) { constexpr int q2 = decltype(qc)::value; s = fma(-F[L::tri(c, q2)], xw[q2], s); });
+            xw[c] = s;
+            acc = fma(s * s, nr[c] ? 0.0 : invd[c], acc);
+        });
+        trA += acc;
+        if constexpr (m % 2 == 1) __builtin_amdgcn_sched_barrier(0);
+    });
+    return trA;
+}
 
 template <class TOPO, class SH, typename TIN>
 __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> tr, const LaneTrain lt) {
@@ -222,9 +281,9 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
         static_for<0, j + 1>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (TI::above(i, j)) {
-                constexpr int e = L::m_entry(i, j);
+                constexpr int e = TI::m_entry(i, j);
                 Mv[e] = col[(size_t)e * 64];
-                if constexpr (L::subtree_last(i) == j) dq[i] = gq[(2 * i + 1) * 64];      // row j is the first that multiplies with dq_i
+                if constexpr (TI::subtree_last(i) == j) dq[i] = gq[(2 * i + 1) * 64];      // row j is the first that multiplies with dq_i
             }
         });
         {   // (the entry of zeros when the bias forces are off: a selected address, no branch)
@@ -253,8 +312,8 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
         // Part 1 of the task signal -- calc_error, velocity limit, gains, stiffness (osc.py:101-118,70-99,160-168) [+ the wrench,
         // osc.py:184-185] -- computed HERE, device by device, while the first rows of M are on their way: this wave has nothing else to do
         // until they arrive (one wave per SIMD), so the ~450 instructions per device are free, and the task pass (58 us per train, 230 MB
-        // of traffic) is not launched at all.  Same formulas in the same order as osc_task_rows_fromq_kernel (task_rot, atan2,
-        // apply_gains6_fast).  The rows go to their CANONICAL positions in LDS (padding rows: zero).
+        // of traffic) is not launched at all.  The rows themselves are r16::gained_error6, as in that pass; they go to their CANONICAL
+        // positions in LDS (padding rows: zero).
 #pragma unroll
         for (int r = 0; r < K; ++r) s_w[r * 64 + lane] = 0.0;
 #pragma unroll 1
@@ -274,17 +333,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
 #pragma unroll
             for (int i = 0; i < 6; ++i) wr6[i] = (double)wp[wsel * i];
             double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            if (dm.calc & 1u) { e[0] = ee[0] - tg[0]; e[1] = ee[1] - tg[1]; e[2] = ee[2] - tg[2]; }
-            if (dm.calc & 2u) {
-                const r16::TaskRot R = r16::task_rot(ee, tg);
-#pragma unroll
-                for (int a2 = 0; a2 < 3; ++a2) {
-                    double ay, ax;
-                    R.angle_args(a2, ay, ax);
-                    e[3 + a2] = atan2(ay, ax);
-                }
-            }
-            r16::apply_gains6_fast(g, e);
+            r16::gained_error6(dm.calc, ee, tg, g, e);
             int cnt = 0;
 #pragma unroll
             for (int i = 0; i < 6; ++i)
@@ -312,18 +361,18 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
         constexpr int j = decltype(jc)::value;
         if constexpr (j - PFD >= 0) fetch(std::integral_constant<int, (j - PFD >= 0 ? j - PFD : 0)>{});
         __builtin_amdgcn_sched_barrier(0);
-        constexpr int ed = L::m_entry(j, j);
-        constexpr bool below = L::has_below(j);
+        constexpr int ed = TI::m_entry(j, j);
+        constexpr bool below = TI::has_below(j);
         double d = Mv[ed];
         double mj = d * dq[j];
         if constexpr (below) { mj += macc[j]; d -= Dl[ed]; }
         static_for<0, j>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (TI::above(i, j)) {
-                constexpr int e = L::m_entry(i, j);
+                constexpr int e = TI::m_entry(i, j);
                 const double m = Mv[e];
                 mj = fma(m, dq[i], mj);
-                if constexpr (L::subtree_last(i) == j) macc[i] = m * dq[j];
+                if constexpr (TI::subtree_last(i) == j) macc[i] = m * dq[j];
                 else macc[i] = fma(m, dq[j], macc[i]);
                 pin(macc[i]);
                 lrow[i] = below ? m - Dl[e] : m;
@@ -349,9 +398,9 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
                 static_for<0, a + 1>([&](auto bc2) {
                     constexpr int b2 = decltype(bc2)::value;
                     if constexpr (TI::above(b2, j)) {
-                        constexpr int e = L::m_entry(b2, a);
+                        constexpr int e = TI::m_entry(b2, a);
                         // the first hinge (in this order) under both: the last index of the deeper one's subtree
-                        if constexpr (L::subtree_last(a) == j) Dl[e] = lrow[a] * lrow[b2];
+                        if constexpr (TI::subtree_last(a) == j) Dl[e] = lrow[a] * lrow[b2];
                         else Dl[e] = fma(lrow[a], lrow[b2], Dl[e]);
                         pin(Dl[e]);
                     }
@@ -442,47 +491,10 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     // a pivot replaced by 1 is a change of that diagonal entry of A and of nothing else.
     double (&Lf)[K * (K + 1) / 2] = Al;
     double invd[K], dtrue[K];
-    bool pd = true;
+    bool pd;
     double det = 1.0;
-    static_for<0, K>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        double d = Lf[L::tri(j, j)];
-        dtrue[j] = d;
-        const bool bad = !nr[j] & !(d > 0.0);
-        pd = pd & !bad;
-        d = (bad | nr[j]) ? 1.0 : d;
-        det *= d;
-        const double iv = rcp_refined(d);
-        invd[j] = iv;
-        double f[K];
-        static_for<j + 1, K>([&](auto ic) { constexpr int i = decltype(ic)::value; f[i] = Lf[L::tri(i, j)] * iv; });
-        static_for<j + 1, K>([&](auto ic) {
-            constexpr int i = decltype(ic)::value;
-            static_for<j + 1, i + 1>([&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-                Lf[L::tri(i, c)] = fma(-f[i], Lf[L::tri(c, j)], Lf[L::tri(i, c)]);
-            });
-        });
-        static_for<j + 1, K>([&](auto ic) { constexpr int i = decltype(ic)::value; Lf[L::tri(i, j)] = f[i]; });
-        __builtin_amdgcn_sched_barrier(0);      // (column by column: left to itself the scheduler interleaves the whole stage and everything long-lived spills)
-    });
-    // trace(A^-1) = sum over the columns m of W = L~^-1 of sum_c W[c][m]^2 / d_c (real rows only)
-    double trA = 0.0;
-    static_for<0, K>([&](auto mc) {
-        constexpr int m = decltype(mc)::value;
-        double xw[K];
-        xw[m] = 1.0;
-        double acc = nr[m] ? 0.0 : invd[m];
-        static_for<m + 1, K>([&](auto cc) {
-            constexpr int c = decltype(cc)::value;
-            double s = -Lf[L::tri(c, m)];
-            static_for<m + 1, c>([&](auto qc) { constexpr int q2 = decltype(qc)::value; s = fma(-Lf[L::tri(c, q2)], xw[q2], s); });
-            xw[c] = s;
-            acc = fma(s * s, nr[c] ? 0.0 : invd[c], acc);
-        });
-        trA += acc;
-        if constexpr (m % 2 == 1) __builtin_amdgcn_sched_barrier(0);      // two columns of W at a time
-    });
+    ldl_inplace<L, false>(Lf, nr, invd, pd, 0.0, dtrue, &det);
+    const double trA = trace_inv<L>(Lf, nr, invd);
     const bool small_det = !pd | !(fabs(det) >= 1e-4) | anyzero;
     const double cond_bound = sqrt(nA2) * trA;
     const bool plain = pd & t_finite(cond_bound) & (!small_det | (cond_bound < 0.99e5));
@@ -492,6 +504,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     double t[K], w[K];
 #pragma unroll
     for (int r = 0; r < K; ++r) w[r] = s_w[r * 64 + lane];
+    // (not the eigen pass's solve(): this back substitution sums i ascending, that one descending -- the last bit differs; both stay)
     static_for<0, K>([&](auto cc) {
         constexpr int c = decltype(cc)::value;
         double s = w[c];
@@ -659,30 +672,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
                 static_for<0, 8>([&](auto ec) { constexpr int e = e0 + decltype(ec)::value; if constexpr (e < NA) dst[e] = ld_su(bp + (e - e0) * 64, vo); });
             });
         };
-        // in place: L~ below the diagonal, pivots not kept (invd); a pivot of a padded / zero row, or a non-positive one, is taken as 1
-        auto factor = [&](double (&F)[NA], const double sigma, bool& pd) {
-            pd = true;
-            static_for<0, K>([&](auto jc) {
-                constexpr int j = decltype(jc)::value;
-                double d = F[L::tri(j, j)] + sigma;
-                const bool npd = !nr[j] && !(d > 0.0);
-                pd = pd && !npd;
-                d = (npd || nr[j]) ? 1.0 : d;
-                const double iv = rcp_refined(d);
-                invd[j] = iv;
-                double f[K];
-                static_for<j + 1, K>([&](auto ic) { constexpr int i = decltype(ic)::value; f[i] = F[L::tri(i, j)] * iv; });
-                static_for<j + 1, K>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    static_for<j + 1, i + 1>([&](auto cc) {
-                        constexpr int c = decltype(cc)::value;
-                        F[L::tri(i, c)] = fma(-f[i], F[L::tri(c, j)], F[L::tri(i, c)]);
-                    });
-                });
-                static_for<j + 1, K>([&](auto ic) { constexpr int i = decltype(ic)::value; F[L::tri(i, j)] = f[i]; });
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        };
+        auto factor = [&](double (&F)[NA], const double sigma, bool& pd) { ldl_inplace<L, true>(F, nr, invd, pd, sigma, nullptr, nullptr); };
         auto solve = [&](double (&z)[K]) {      // z <- (L~ D L~^T)^-1 z: the FMA chains of r16::solve16, per lane
             static_for<0, K - 1>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
@@ -711,22 +701,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
         }
         bool pdA;
         factor(Lf, 0.0, pdA);
-        double trA = 0.0;      // trace(A^-1) over the real rows: columns of L~^-1
-        static_for<0, K>([&](auto mc) {
-            constexpr int m = decltype(mc)::value;
-            double xw[K];
-            xw[m] = 1.0;
-            double acc = nr[m] ? 0.0 : invd[m];
-            static_for<m + 1, K>([&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-                double s2 = -Lf[L::tri(c, m)];
-                static_for<m + 1, c>([&](auto qc) { constexpr int q2 = decltype(qc)::value; s2 = fma(-Lf[L::tri(c, q2)], xw[q2], s2); });
-                xw[c] = s2;
-                acc = fma(s2 * s2, nr[c] ? 0.0 : invd[c], acc);
-            });
-            trA += acc;
-            if constexpr (m % 2 == 1) __builtin_amdgcn_sched_barrier(0);
-        });
+        const double trA = trace_inv<L>(Lf, nr, invd);
         // ---- r16::eigen16, per lane ------------------------------------------------------------------------------------------------
         const double hi = sqrt(nA2);
         double sigma = 0.0;
@@ -854,7 +829,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
                         turned = turned || rot;
                         double theta = (hqq - hpp) * rcp_refined(rot ? 2.0 * hpq : 1.0);
                         theta = fmin(fmax(theta, -1e100), 1e100);
-                        const double tq = (theta >= 0.0 ? 1.0 : -1.0) * rcp_refined(fabs(theta) + r16::sqrt_fast(theta * theta + 1.0));
+                        const double tq = (theta >= 0.0 ? 1.0 : -1.0) * rcp_refined(fabs(theta) + sqrt_fast(theta * theta + 1.0));
                         const double cs = rot ? rsq_refined(tq * tq + 1.0) : 1.0;
                         const double sn = rot ? tq * cs : 0.0;
                         h[p2][p2] = rot ? hpp - tq * hpq : hpp;

@@ -8,7 +8,7 @@
 // ([walk wave][entry][64 robots]: every operand one coalesced 512-byte load, compile-time entry indices of FeTopo<TOPO>), the OSC step
 // (or the give-up pass behind it) left u[B][n] row-major in the record type: a wave's 64 x NJ tile is transposed through LDS.
 //
-//   M = L^T L from the leaves up (hinges NJ-1 .. 0, no fill-in: the recursion of osc_lane.hpp, restated): row j of M is read when
+//   M = L^T L from the leaves up (hinges NJ-1 .. 0, no fill-in: the recursion of osc_lane.hpp without M dq, Y and the pins): row j of M is read when
 //       hinge j is eliminated, L[j][i] = (m_ji - Delta[j][i]) / L[j][j], Delta[a][b] += L[j][a] L[j][b] for the hinges a, b above j;
 //   L^T y = rhs rides along (rhs_i -= L[j][i] y_j), rhs_j = (ctrl_mask bit j ? u_j : 0) - bias_j - damping qvel_j;
 //   L qacc = y from the root down needs the rows of L again in ASCENDING order.  155 off-diagonal entries + 25 pivots are 360
@@ -41,24 +41,6 @@ struct PlantArgs {
     uint32_t ctrl_mask;
     int32_t B, ndev;
     int32_t ee0[IRLOSC_MAX_DEV];      // exchange entry of each device's EE pose (x y z qw qx qy qz follow each other)
-};
-
-template <int B_, int E_, typename F>      // E_-1 down to B_
-__device__ __forceinline__ void plant_for_down(F&& f) {
-    if constexpr (B_ < E_) {
-        f(std::integral_constant<int, E_ - 1>{});
-        plant_for_down<B_, E_ - 1>(f);
-    }
-}
-
-template <class TOPO>
-struct PlantTopo {
-    // the last hinge of hinge j's subtree (hinges numbered depth first): the first one under j the descending recursion meets
-    static constexpr int subtree_last(int j) {
-        int l = j;
-        for (int c = j; c < TOPO::NJ; ++c) if (FeTopo<TOPO>::above(j, c)) l = c;
-        return l;
-    }
 };
 
 template <class TOPO, typename TIN>
@@ -111,33 +93,31 @@ __global__ __launch_bounds__(64, 2) void osc_plant_lane_kernel(const PlantArgs a
     const double* src = col;
     auto fetch = [&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        fe_static_for<0, j + 1>([&](auto ic) {
+        static_for<0, j + 1>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (TI::above(i, j)) {
-                constexpr int e = i == j ? TI::diag_index(j) : TI::pair_index(i, j);
+                constexpr int e = TI::m_entry(i, j);
                 Mv[e] = src[(size_t)e * 64];
             }
         });
     };
-    plant_for_down<NJ - PFD < 0 ? 0 : NJ - PFD, NJ>([&](auto jc) { fetch(jc); });
+    static_for_down<NJ - PFD < 0 ? 0 : NJ - PFD, NJ>([&](auto jc) { fetch(jc); });
     bool npd = false;
-    plant_for_down<0, NJ>([&](auto jc) {
+    static_for_down<0, NJ>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         if constexpr (j - PFD >= 0) fetch(std::integral_constant<int, (j - PFD >= 0 ? j - PFD : 0)>{});
         __builtin_amdgcn_sched_barrier(0);
         constexpr int ed = TI::diag_index(j);
-        constexpr bool below = PlantTopo<TOPO>::subtree_last(j) > j;
+        constexpr bool below = TI::has_below(j);
         double d = Mv[ed];
         if constexpr (below) d -= Dl[ed];
         npd = npd | !(d > 0.0);                                // also catches NaN
         d = fmax(d, 1e-300);
-        const double q0 = __builtin_amdgcn_rsq(d);             // 2^-24 seed, one cubic correction -> fp64 (r16::rsq_refined)
-        const double e0 = fma(-(d * q0), q0, 1.0);
-        const double rs = fma(q0 * e0, fma(0.375, e0, 0.5), q0);
+        const double rs = rsq_refined(d);
         const double yj = rhs[j] * rs;
         rhs[j] = yj;                                           // y_j from here on
         col[(size_t)ed * 64] = rs;                             // 1 / L[j][j] in place of M[j][j]
-        fe_static_for<0, j>([&](auto ic) {
+        static_for<0, j>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (TI::above(i, j)) {
                 constexpr int e = TI::pair_index(i, j);
@@ -148,14 +128,14 @@ __global__ __launch_bounds__(64, 2) void osc_plant_lane_kernel(const PlantArgs a
                 rhs[i] = fma(-l, yj, rhs[i]);                  // L^T y = rhs: what hinge j takes out of its ancestors' rows
             }
         });
-        fe_static_for<0, j>([&](auto ac) {
+        static_for<0, j>([&](auto ac) {
             constexpr int ai = decltype(ac)::value;
             if constexpr (TI::above(ai, j)) {
-                constexpr int alast = PlantTopo<TOPO>::subtree_last(ai);
-                fe_static_for<0, ai + 1>([&](auto bc) {
+                constexpr int alast = TI::subtree_last(ai);
+                static_for<0, ai + 1>([&](auto bc) {
                     constexpr int bi = decltype(bc)::value;
                     if constexpr (TI::above(bi, j)) {
-                        constexpr int e = bi == ai ? TI::diag_index(ai) : TI::pair_index(bi, ai);
+                        constexpr int e = TI::m_entry(bi, ai);
                         // the first hinge (in this order) under both: the last index of the deeper one's subtree
                         if constexpr (alast == j) Dl[e] = lrow[ai] * lrow[bi];
                         else Dl[e] = fma(lrow[ai], lrow[bi], Dl[e]);
@@ -169,14 +149,14 @@ __global__ __launch_bounds__(64, 2) void osc_plant_lane_kernel(const PlantArgs a
     // ---- L qacc = y, hinges 0 .. NJ - 1: row j of L comes back from the block (this lane's own stores) --------------------------------
     // (the address laundered: a compiler that sees the stores above forwards all 180 values to these loads -- in registers)
     asm volatile("" : "+v"(src) : : "memory");
-    fe_static_for<0, (PFD < NJ ? PFD : NJ)>([&](auto jc) { fetch(jc); });
+    static_for<0, (PFD < NJ ? PFD : NJ)>([&](auto jc) { fetch(jc); });
     bool bad_a = false;
-    fe_static_for<0, NJ>([&](auto jc) {
+    static_for<0, NJ>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         if constexpr (j + PFD < NJ) fetch(std::integral_constant<int, (j + PFD < NJ ? j + PFD : 0)>{});
         __builtin_amdgcn_sched_barrier(0);
         double x = rhs[j];
-        fe_static_for<0, j>([&](auto ic) {
+        static_for<0, j>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (TI::above(i, j)) {
                 constexpr int e = TI::pair_index(i, j);

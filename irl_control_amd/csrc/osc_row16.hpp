@@ -74,21 +74,6 @@
 namespace irlosc {
 namespace r16 {
 
-template <int B_, int E_, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B_ < E_) {
-        f(std::integral_constant<int, B_>{});
-        static_for<B_ + 1, E_>(f);
-    }
-}
-template <int B_, int E_, typename F>      // E_-1 down to B_
-__device__ __forceinline__ void static_for_down(F&& f) {
-    if constexpr (B_ < E_) {
-        f(std::integral_constant<int, E_ - 1>{});
-        static_for_down<B_, E_ - 1>(f);
-    }
-}
-
 // acc += bcast(src, lane LANE of the row) * mul
 template <int LANE>
 __device__ __forceinline__ void fmac_bc(double& acc, const double src, const double mul) {
@@ -139,20 +124,6 @@ __device__ __forceinline__ double quad_bcast(double v, int g) {
         default: return dpp_mov64<0xFF>(v);
     }
 }
-
-// 1/sqrt(d) and 1/d to fp64 accuracy from the 2^-24 hardware seeds (one cubic / quadratic correction; measured
-// max relative error 2.6e-16 and 0 against 1/sqrt and 1/ of the host, tools/probe/dpp64.hip)
-__device__ __forceinline__ double rsq_refined(double d) {
-    const double q = __builtin_amdgcn_rsq(d);
-    const double e = fma(-(d * q), q, 1.0);
-    return fma(q * e, fma(0.375, e, 0.5), q);
-}
-__device__ __forceinline__ double rcp_refined(double d) {
-    const double r = __builtin_amdgcn_rcp(d);
-    const double e = fma(-d, r, 1.0);
-    return fma(r * e, 1.0 + e, r);
-}
-__device__ __forceinline__ double sqrt_fast(double x) { return x > 0.0 ? x * rsq_refined(x) : 0.0; }
 
 // ---- k x k building blocks: lane c of a row holds column c (= row c) of a symmetric K x K matrix in K registers -----
 
@@ -494,41 +465,32 @@ __device__ __forceinline__ TaskRot task_rot(const double (&ee)[7], const double 
     return R;
 }
 
-// Compile-time shape queries for the tree-structured factorisation (hinge numbering = MuJoCo's depth-first order)
-template <class TOPO>
-constexpr int tree_subtree_size(int j) {
-    int n = 0;
-    for (int c = 0; c < TOPO::NJ; ++c) n += FeTopo<TOPO>::above(j, c) ? 1 : 0;
-    return n;
-}
-template <class TOPO>
-constexpr bool tree_subtree_contiguous(int j) {
-    const int sz = tree_subtree_size<TOPO>(j);
-    for (int c = 0; c < TOPO::NJ; ++c)
-        if (FeTopo<TOPO>::above(j, c) != (c >= j && c < j + sz)) return false;
-    return true;
+// Part 1 of the task signal of ONE device, one (robot, device) pair per lane: calc_error, velocity limit, gains, stiffness
+// (osc.py:101-118,70-99,160-168) on the refined seeds.  THE statement of it for the per-lane forms -- the task passes of the fused and
+// the dense-record path and the lane kernel -- whose results are held to bit-identity.  Loading ee / tg / g and scattering e by the
+// device's dofmask is the caller's, and so is e = 0 on entry (the part that is not computed stays zero).  The row16 kernel's in-kernel
+// form spreads the same formulas over lanes (one Euler angle each).
+__device__ __forceinline__ void gained_error6(const uint32_t calc, const double (&ee)[7], const double (&tg)[7], const double* __restrict__ g,
+                                              double (&e)[6]) {
+    if (calc & 1u) { e[0] = ee[0] - tg[0]; e[1] = ee[1] - tg[1]; e[2] = ee[2] - tg[2]; }
+    if (calc & 2u) {
+        const TaskRot R = task_rot(ee, tg);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            double ay, ax;
+            R.angle_args(a, ay, ax);
+            e[3 + a] = atan2(ay, ax);
+        }
+    }
+    apply_gains6_fast(g, e);
 }
 
-// hinge j moves a body that may be named as an end effector: every other column of J is structurally zero, and with the
-// factorisation running from the leaves up (row j of Y = L^-T J^T only sees rows of its own subtree) so is that row of Y
-template <class TOPO>
-constexpr bool tree_moves_ee(int j) {
-    for (int b = 0; b < TOPO::NB; ++b)
-        if (TOPO::ee_cand[b] != 0 && FeTopo<TOPO>::moves(j, b)) return true;
-    return false;
-}
+// Compile-time plans of the tree-structured factorisation (shape queries: FeTopo<TOPO>, osc_frontend_lane.hpp)
 template <class TOPO>
 constexpr int tree_ee_run(int c0, int cend) {          // length of the run of columns from c0 that are all EE hinges / all not
     int n = 1;
-    while (c0 + n < cend && tree_moves_ee<TOPO>(c0 + n) == tree_moves_ee<TOPO>(c0)) ++n;
+    while (c0 + n < cend && FeTopo<TOPO>::moves_ee(c0 + n) == FeTopo<TOPO>::moves_ee(c0)) ++n;
     return n;
-}
-// row j of M has no structural non-zero in columns 16 .. NJ - 1 (its slot-1 half): nothing to load, nothing to multiply
-template <class TOPO>
-constexpr bool tree_slot1_zero(int j) {
-    for (int c = 16; c < TOPO::NJ; ++c)
-        if (FeTopo<TOPO>::above(j, c) || FeTopo<TOPO>::above(c, j)) return false;
-    return true;
 }
 // Prefetch plan of the tree form on dense records: rows are requested in processing order (NJ - 1 .. 0) so that at most
 // BUDGET doubles per lane are in flight -- a row with an empty slot-1 half costs one register pair instead of two, so twice
@@ -546,11 +508,11 @@ constexpr TreeFetch<TOPO, BUDGET> tree_fetch() {
     TreeFetch<TOPO, BUDGET> f{};
     int next = 0, inflight = 0;
     for (int e = 0; e <= NJ; ++e) {
-        if (e > 0) inflight -= tree_slot1_zero<TOPO>(NJ - e) ? 1 : 2;      // step e - 1 has taken row NJ - 1 - (e - 1)
+        if (e > 0) inflight -= FeTopo<TOPO>::slot1_zero(NJ - e) ? 1 : 2;      // step e - 1 has taken row NJ - 1 - (e - 1)
         f.first[e] = next;
         int n = 0;
-        while (next < NJ && inflight + (tree_slot1_zero<TOPO>(NJ - 1 - next) ? 1 : 2) <= BUDGET) {
-            inflight += tree_slot1_zero<TOPO>(NJ - 1 - next) ? 1 : 2;
+        while (next < NJ && inflight + (FeTopo<TOPO>::slot1_zero(NJ - 1 - next) ? 1 : 2) <= BUDGET) {
+            inflight += FeTopo<TOPO>::slot1_zero(NJ - 1 - next) ? 1 : 2;
             ++next;
             ++n;
         }
@@ -570,7 +532,7 @@ inline void tree_structure_masks(uint32_t mrow[32], uint32_t* jcols) {
         if (j >= TOPO::NJ) continue;
         for (int c = 0; c < TOPO::NJ; ++c)
             if (FeTopo<TOPO>::above(j, c) || FeTopo<TOPO>::above(c, j)) mrow[j] |= 1u << c;
-        if (tree_moves_ee<TOPO>(j)) *jcols |= 1u << j;
+        if (FeTopo<TOPO>::moves_ee(j)) *jcols |= 1u << j;
     }
 }
 
@@ -646,12 +608,12 @@ struct Row16Train {
 template <class TOPO>
 constexpr bool tree_row_slot1_zero(int j) {
     if constexpr (std::is_void_v<TOPO>) return false;
-    else return r16::tree_slot1_zero<TOPO>(j);
+    else return FeTopo<TOPO>::slot1_zero(j);
 }
 template <class TOPO>
 constexpr bool tree_row_of_y(int i) {
     if constexpr (std::is_void_v<TOPO>) return true;
-    else return r16::tree_moves_ee<TOPO>(i);
+    else return FeTopo<TOPO>::moves_ee(i);
 }
 // Column terms c = C0 .. C0 + NC - 1 (the subtree of hinge J below it) of the tree-structured recursion: the rows of the
 // factor in R0 / R1, of Y in T; runs of columns under an end effector carry the Y chain, the others (T[c] = 0) do not.
@@ -661,13 +623,13 @@ __device__ __forceinline__ void tree_chains(double& m0, double& m1, double& tj, 
     if constexpr (NC > 0) {
         constexpr int gj = J & 15;
         constexpr int RUN = r16::tree_ee_run<TOPO>(C0, C0 + NC);
-        constexpr bool y = r16::tree_moves_ee<TOPO>(J) && r16::tree_moves_ee<TOPO>(C0);
+        constexpr bool y = FeTopo<TOPO>::moves_ee(J) && FeTopo<TOPO>::moves_ee(C0);
         if constexpr (J >= 16) {                                  // row J is a slot-1 row: the broadcasts come from R1
             if constexpr (y) r16::fmac3_chain<gj, C0, RUN>(m1, m0, tj, R1, R0, T);
             else r16::fmac2_chain<gj, C0, RUN>(m1, m0, R1, R0);
         } else {                                                  // slot-1 rows are done
             if constexpr (y) r16::fmac2_chain<gj, C0, RUN>(m0, tj, R0, T);
-            else r16::static_for<C0, C0 + RUN>([&](auto cc) { r16::fmac_bc_n<gj>(m0, R0[decltype(cc)::value], R0[decltype(cc)::value]); });
+            else static_for<C0, C0 + RUN>([&](auto cc) { r16::fmac_bc_n<gj>(m0, R0[decltype(cc)::value], R0[decltype(cc)::value]); });
         }
         tree_chains<TOPO, J, C0 + RUN, NC - RUN>(m0, m1, tj, R0, R1, T);
     }
@@ -832,7 +794,7 @@ void osc_row16_kernel(const Row16Train<TIN> tr) {
             static_for<0, kTreeFetch<TOPO, IRLOSC_R16_TREE_BUDGET>.count[0]>([&](auto pc) {
                 constexpr int j = N - 1 - decltype(pc)::value;
                 pm0[j] = m0p[j * N];
-                if constexpr (!tree_slot1_zero<TOPO>(j)) pm1[j] = m1p[j * N];
+                if constexpr (!FeTopo<TOPO>::slot1_zero(j)) pm1[j] = m1p[j * N];
             });
         } else {
             static_for<0, PF>([&](auto jc) { constexpr int j = decltype(jc)::value; pm0[j] = m0p[j * N]; pm1[j] = m1p[j * N]; });
@@ -960,17 +922,17 @@ void osc_row16_kernel(const Row16Train<TIN> tr) {
         static_for_down<0, N>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int sj = j >> 4, gj = j & 15;
-            constexpr int SZ = tree_subtree_size<TOPO>(j);          // hinges j .. j + SZ - 1 are the subtree of j
-            static_assert(tree_subtree_contiguous<TOPO>(j), "depth-first numbering: a subtree is a run of indices");
-            constexpr bool EEJ = tree_moves_ee<TOPO>(j);            // otherwise column j of J and row j of Y are zero
-            constexpr bool S1Z = tree_slot1_zero<TOPO>(j);          // no slot-1 half: m1 = 0, nothing loaded for it
+            constexpr int SZ = FeTopo<TOPO>::subtree_size(j);          // hinges j .. j + SZ - 1 are the subtree of j
+            static_assert(FeTopo<TOPO>::subtree_contiguous(j), "depth-first numbering: a subtree is a run of indices");
+            constexpr bool EEJ = FeTopo<TOPO>::moves_ee(j);            // otherwise column j of J and row j of Y are zero
+            constexpr bool S1Z = FeTopo<TOPO>::slot1_zero(j);          // no slot-1 half: m1 = 0, nothing loaded for it
             if constexpr (FROMQ) {
                 if constexpr (j - PFQ >= 0) {
                     pm0[j - PFQ] = tile_at(mo0);
-                    if constexpr (!tree_slot1_zero<TOPO>(j - PFQ)) pm1[j - PFQ] = tile_at(mo1);
+                    if constexpr (!FeTopo<TOPO>::slot1_zero(j - PFQ)) pm1[j - PFQ] = tile_at(mo1);
                     if constexpr (j - PFQ - 1 >= 0) {
                         mo0 = Tm[(j - PFQ - 1) * 32 + l];
-                        if constexpr (!tree_slot1_zero<TOPO>(j - PFQ - 1)) mo1 = Tm[(j - PFQ - 1) * 32 + 16 + l];
+                        if constexpr (!FeTopo<TOPO>::slot1_zero(j - PFQ - 1)) mo1 = Tm[(j - PFQ - 1) * 32 + 16 + l];
                     }
                 }
             }
@@ -981,11 +943,11 @@ void osc_row16_kernel(const Row16Train<TIN> tr) {
                 static_for<0, kTreeFetch<TOPO, IRLOSC_R16_TREE_BUDGET>.count[e]>([&](auto pc) {
                     constexpr int jn = N - 1 - (kTreeFetch<TOPO, IRLOSC_R16_TREE_BUDGET>.first[e] + decltype(pc)::value);
                     pm0[jn] = m0p[jn * N];
-                    if constexpr (!tree_slot1_zero<TOPO>(jn)) pm1[jn] = m1p[jn * N];
+                    if constexpr (!FeTopo<TOPO>::slot1_zero(jn)) pm1[jn] = m1p[jn * N];
                 });
             }
             double tj = EEJ ? tnext : 0.0;
-            if constexpr (j > 0) { if constexpr (tree_moves_ee<TOPO>(j - 1)) tnext = jcol(j - 1); }
+            if constexpr (j > 0) { if constexpr (FeTopo<TOPO>::moves_ee(j - 1)) tnext = jcol(j - 1); }
             const double dqs = sj ? dq1 : dq0;
             __builtin_amdgcn_sched_barrier(0);
             fmac_bc_nop<gj>(mdq0, dqs, m0);
@@ -1286,8 +1248,8 @@ __global__ __launch_bounds__(64) void osc_generic_worklist_kernel(const Row16Tra
 // FROMQ: part 1 of the task-space signal (calc_error, velocity limit, gains, stiffness: osc.py:101-118,70-99,160-168) as a PASS OF ITS
 // OWN between the walk and the OSC kernel -- ONE LANE PER ROBOT, block x = walk wave x (its 64 robots), blockIdx.y = step.  Reads
 // the end-effector poses the walk parked (coalesced: [entry][64 robots]), the targets and gains, and leaves the k gained error rows
-// as k more entries of the exchange block (FeTopo::task_index), which the OSC kernel's tile picks up like everything else.  Same
-// formulas as the in-kernel form of the dense-record path (task_rot, apply_gains6_fast).  ~450 instructions per wave of 64
+// as k more entries of the exchange block (FeTopo::task_index), which the OSC kernel's tile picks up like everything else.  The
+// rows themselves: r16::gained_error6.  ~450 instructions per wave of 64
 // (robot, device) pairs against ~400 per wave of FOUR robots in the OSC kernel.
 // PAD: one instantiation for every layout (NDEV = IRLOSC_MAX_DEV; the block has 64 x p.ndev threads).
 template <int K, int NDEV, typename TIN, class TOPO, bool PAD = false>
@@ -1334,17 +1296,7 @@ __global__ __launch_bounds__(64 * NDEV) void osc_task_rows_fromq_kernel(const Ro
 #pragma unroll
     for (int i = 0; i < 7; ++i) tg[i] = tgs[lane * TW + d * 7 + i];
     double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (dm.calc & 1u) { e[0] = ee[0] - tg[0]; e[1] = ee[1] - tg[1]; e[2] = ee[2] - tg[2]; }
-    if (dm.calc & 2u) {
-        const TaskRot R = task_rot(ee, tg);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            double ay, ax;
-            R.angle_args(a, ay, ax);
-            e[3 + a] = atan2(ay, ax);
-        }
-    }
-    apply_gains6_fast(g, e);
+    gained_error6(dm.calc, ee, tg, g, e);
     int cnt = 0;
 #pragma unroll
     for (int i = 0; i < 6; ++i)
@@ -1355,7 +1307,7 @@ __global__ __launch_bounds__(64 * NDEV) void osc_task_rows_fromq_kernel(const Ro
 // 70-99,160-168) as a pass ahead of the row16 kernel -- ONE LANE PER (INSTANCE, DEVICE): block x = instances 64 x .. 64 x + 63, wave d =
 // target device d (the block has 64 x ndev threads), blockIdx.y = step.  Reads pose, target and gains of its pair, leaves the k gained
 // error rows of the block's instances in Row16Extra::trows ([B][16] doubles; rows >= k: zeros), transposed through LDS so that the
-// 8 KB go out as whole lines.  Same formulas, in the same order, as the in-kernel form (task_rot, atan2, apply_gains6_fast): the
+// 8 KB go out as whole lines.  The rows themselves: r16::gained_error6, the in-kernel form's formulas in the same order -- the
 // row16 kernel's results do not depend on which of the two ran.
 template <typename TIN>
 __global__ __launch_bounds__(64 * IRLOSC_MAX_DEV) void osc_task_rows_dense_kernel(const Row16Train<TIN> tr) {
@@ -1398,17 +1350,7 @@ __global__ __launch_bounds__(64 * IRLOSC_MAX_DEV) void osc_task_rows_dense_kerne
 #pragma unroll
     for (int i = 0; i < 7; ++i) { ee[i] = (double)s_ee[(lane * nd + d) * 7 + i]; tg[i] = (double)s_tg[(lane * nd + d) * 7 + i]; }
     double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (dm.calc & 1u) { e[0] = ee[0] - tg[0]; e[1] = ee[1] - tg[1]; e[2] = ee[2] - tg[2]; }
-    if (dm.calc & 2u) {
-        const TaskRot R = task_rot(ee, tg);
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            double ay, ax;
-            R.angle_args(a, ay, ax);
-            e[3 + a] = atan2(ay, ax);
-        }
-    }
-    apply_gains6_fast(g, e);
+    gained_error6(dm.calc, ee, tg, g, e);
     __syncthreads();                               // every wave has its poses and targets in registers: the rows take their place
     int cnt = 0;
 #pragma unroll
