@@ -471,6 +471,41 @@ IRLOSC_API int irlosc_rollout_from_q(irlosc_ctx* ctx, int32_t slot, int32_t B, i
  * it).  Synchronous. */
 IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, double* qpos, double* qvel);
 
+/* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
+ * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
+ * the give-up pass and the plant.  Robot b, device d with W_d > 0 waypoints and index idx in [0, W_d] (idx == W_d: path finished,
+ * loop[d] == 0 only; a finished device is skipped):
+ *     e = EE xyz of this tick's walk (double);   t = (double) tgt[b][d][0..2] as stored          -- what the OSC step of this tick saw
+ *     d2 = (e0-t0)^2 + (e1-t1)^2 + (e2-t2)^2;    reached = d2 < threshold[d]^2                   -- a NaN anywhere: not reached
+ *     if reached:  arrivals += 1;  last_tick = tick;  idx = idx + 1 < W_d ? idx + 1 : (loop[d] ? 0 : W_d)
+ *                  tgt[b][d][0..2] = waypoint min(idx, W_d - 1), in the context's dtype          -- the quaternion words stay
+ * The reference's order: the index moves after `generate` and is judged on the state `generate` used.  `tick` counts the slot's
+ * rollout ticks since irlosc_set_waypoints and continues across calls of irlosc_rollout_from_q.  A robot is judged on its EE position
+ * alone: one the plant freezes keeps its place in the path unless a NaN reaches that position. */
+#define IRLOSC_MAX_WAYPOINTS 64
+typedef struct irlosc_waypoints {
+    int32_t count[IRLOSC_MAX_DEV];      /* W_d in [0, IRLOSC_MAX_WAYPOINTS]; 0 = device d keeps the slot's target (devices >= ndev: 0) */
+    double threshold[IRLOSC_MAX_DEV];   /* metres; finite and > 0 where count > 0 */
+    uint8_t loop[IRLOSC_MAX_DEV];       /* 1: wrap to waypoint 0 (gain_test); 0: finish on the last one */
+    int32_t nb;                         /* 1 = one table for the fleet, B = a table per robot */
+} irlosc_waypoints;
+/* Gives slot `slot`'s B robots their paths: xyz[nb][ndev][Wmax][3] double, Wmax = max count (entries [w >= count[d]] are not read).
+ * After irlosc_set_model and irlosc_set_targets for at least B robots on the slot (IRLOSC_ERR_STATE otherwise).  Every argument is
+ * checked before anything is touched (IRLOSC_ERR_ARG: a count outside [0, 64], a threshold or listed waypoint that is not finite
+ * resp. not > 0, loop not 0 / 1, nb not 1 or B, B < 1; the paths in force stay, whole -- as they do when the call answers
+ * IRLOSC_ERR_STATE).  On success: idx = 0, arrivals = 0,
+ * last_tick = -1 for every listed pair, tick base 0, and waypoint 0 is written into the xyz of the slot's targets of every listed
+ * device.  desc == NULL or all counts 0 clears the slot's paths (its targets stay as they are).  irlosc_set_targets on the slot and
+ * irlosc_set_model clear them too: targets are written by one entry point at a time; uploads of coordinates, records and sensor
+ * feeds leave them alone.  Only irlosc_rollout_from_q runs the paths (on at most the B robots given here: IRLOSC_ERR_STATE beyond);
+ * every other step ignores them and leaves their state as it is.  Buffers are allocated by the first use; IRLOSC_ERR_HIP when that
+ * fails, and the slot is left without paths.  Synchronous. */
+IRLOSC_API int irlosc_set_waypoints(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_waypoints* desc, const double* xyz);
+/* index, arrivals, last_tick: each [B][ndev], any may be NULL.  Devices without a list report index -1, arrivals 0, last_tick -1.
+ * IRLOSC_ERR_STATE on a slot without paths, or with paths for fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_waypoint_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* index, uint32_t* arrivals,
+                                              int32_t* last_tick);
+
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard
  * and NOTHING is exchanged per tick.  RCCL (over xGMI) is used once per benchmark: sum of the steps done, max of the

@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IRLOSC_LIB", os.path.join(_HERE, "libirlosc.so"))   # override: A/B builds only
 
 MAX_DEV, MAX_N, MAX_K, GAIN_WORDS, MAX_BODIES = 4, 32, 16, 12, 64
+MAX_WAYPOINTS = 64
 F32, F64 = 0, 1
 USE_G, ADMITTANCE, NULLSPACE = 1, 2, 4
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_ROW16 = 0, 1, 3      # (2: the fp32-arithmetic kernel removed in ABI version 3)
@@ -25,7 +26,8 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_upload_q", "irlosc_frontend", "irlosc_step_resident_from_q", "irlosc_download_records",
            "irlosc_step_from_q", "irlosc_from_q_name", "irlosc_slot_structure", "irlosc_probe_structure", "irlosc_time_trains", "irlosc_giveup_counts",
            "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device",
-           "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q"]
+           "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q",
+           "irlosc_set_waypoints", "irlosc_download_waypoint_state"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -65,6 +67,11 @@ class FtDesc(C.Structure):
 class Plant(C.Structure):
     """struct irlosc_plant (include/irlosc.h): the contact-free plant of irlosc_rollout_from_q."""
     _fields_ = [("dt", C.c_double), ("damping", C.c_double), ("ctrl_mask", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Waypoints(C.Structure):
+    """struct irlosc_waypoints (include/irlosc.h): the waypoint paths of irlosc_set_waypoints."""
+    _fields_ = [("count", C.c_int32 * MAX_DEV), ("threshold", C.c_double * MAX_DEV), ("loop", C.c_uint8 * MAX_DEV), ("nb", C.c_int32)]
 
 
 class Cfg(C.Structure):
@@ -140,6 +147,8 @@ def load():
     lib.irlosc_set_plant.argtypes = [vp, C.POINTER(Plant)]
     lib.irlosc_rollout_from_q.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.irlosc_download_q.argtypes = [vp, i32, i32, vp, vp]
+    lib.irlosc_set_waypoints.argtypes = [vp, i32, i32, C.POINTER(Waypoints), vp]
+    lib.irlosc_download_waypoint_state.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

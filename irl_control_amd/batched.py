@@ -348,6 +348,49 @@ class BatchedOSC:
         self._chk(self.lib.irlosc_download_q(self._h, slot, B, _lib.ptr(qpos), _lib.ptr(qvel)))
         return qpos, qvel
 
+    # -- waypoint paths of the rollout (irlosc_set_waypoints / irlosc_download_waypoint_state) -------------------------------------
+    def set_waypoints(self, xyz, threshold, loop=True, slot: int = 0):
+        """Paths for the slot's robots, cycled on the GPU by `rollout` as examples/headless_loops.py::gain_test_loop cycles them on the
+        host: a device whose EE comes within `threshold` (metres) of its target moves on to its next waypoint, wraps at the end
+        (`loop`) or finishes on the last one.  `xyz`: per device (layout order) a [W, 3] array (one path for the fleet), a [B, W, 3]
+        array (a path per robot) or None (the device keeps the slot's target); W <= 64.  `threshold`, `loop`: one value or one per
+        device.  After set_model and set_targets; writes waypoint 0 into the slot's targets and resets the state.  xyz=None (or all
+        None) clears the paths, as set_targets and set_model do."""
+        L, B = self.layout, self._B[slot]
+        paths = [None] * L.ndev if xyz is None else [None if p is None else np.asarray(p, dtype=np.float64) for p in xyz]
+        if len(paths) != L.ndev:
+            raise ValueError(f"xyz: expected one entry per device ({L.ndev}), got {len(paths)}")
+        if all(p is None for p in paths):
+            self._chk(self.lib.irlosc_set_waypoints(self._h, slot, B, None, None))
+            return
+        for d, p in enumerate(paths):
+            if p is not None and not (p.ndim in (2, 3) and p.shape[-1] == 3 and p.shape[-2] >= 1 and (p.ndim == 2 or p.shape[0] == B)):
+                raise ValueError(f"xyz[{d}]: expected shape (W, 3) or ({B}, W, 3) with W >= 1, got {p.shape}")
+        nb = B if any(p is not None and p.ndim == 3 for p in paths) else 1
+        wmax = max(p.shape[-2] for p in paths if p is not None)
+        thr = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (L.ndev,))
+        lp = np.broadcast_to(np.asarray(loop, dtype=bool), (L.ndev,))
+        desc = _lib.Waypoints()
+        desc.nb = nb
+        tab = np.zeros((nb, L.ndev, wmax, 3), dtype=np.float64)
+        for d, p in enumerate(paths):
+            if p is None:
+                continue
+            desc.count[d], desc.threshold[d], desc.loop[d] = p.shape[-2], float(thr[d]), int(lp[d])
+            tab[:, d, :p.shape[-2]] = p
+        self._chk(self.lib.irlosc_set_waypoints(self._h, slot, B, C.byref(desc), _lib.ptr(tab)))
+
+    def waypoint_state(self, slot: int = 0):
+        """-> dict(index, arrivals, last_tick), each [B, ndev]: where every (robot, device) pair stands in its path (index == W: finished),
+        how often it arrived and at which rollout tick since set_waypoints it last did (-1: never).  Devices without a path report
+        (-1, 0, -1).  (irlosc_download_waypoint_state)"""
+        L, B = self.layout, self._B[slot]
+        idx = np.empty((B, L.ndev), dtype=np.int32)
+        arr = np.empty((B, L.ndev), dtype=np.uint32)
+        last = np.empty((B, L.ndev), dtype=np.int32)
+        self._chk(self.lib.irlosc_download_waypoint_state(self._h, slot, B, _lib.ptr(idx), _lib.ptr(arr), _lib.ptr(last)))
+        return dict(index=idx, arrivals=arr, last_tick=last)
+
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""
         B = self._B[first_slot] if B is None else B

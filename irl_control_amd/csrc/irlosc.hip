@@ -25,6 +25,7 @@
 #include "osc_ft.hpp"
 #include "osc_pack.hpp"
 #include "osc_plant.hpp"
+#include "osc_waypoint.hpp"
 #include "launchers.hpp"
 
 using namespace irlosc;
@@ -63,6 +64,15 @@ struct Slot {
     double* sens = nullptr;
     int sens_cols = 0;         // doubles per robot the buffer holds
     int feed = 0;              // robots of the feed (0 = no feed)
+    // waypoint paths of the rollout (irlosc_set_waypoints): per-robot state [ndev][waypoints] each, the table ([walk wave][dev][w][3][64]
+    // per robot, [dev][w][3] shared), allocated by the first use; the description in force and the widest list
+    int32_t* wp_index = nullptr; uint32_t* wp_arrivals = nullptr; int32_t* wp_last = nullptr;
+    double* wp_table = nullptr;
+    size_t wp_table_bytes = 0;
+    irlosc_waypoints wp{};
+    int wp_max = 0;
+    int waypoints = 0;         // robots with paths (0 = none: a rollout tick launches no cycler)
+    int wp_tick = 0;           // rollout ticks since irlosc_set_waypoints
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -85,6 +95,13 @@ struct Slot {
     // The plant kernel of a rollout advanced the coordinates of B robots on the device: row-major and walk layout alike, so they stay the
     // slot's coordinates (targets and feed are not touched; the records went with the fused step of the tick: voided()).
     void advanced(int B) { coords = B; }
+    // Paths of B robots are in the slot, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
+    void pathed(int B, const irlosc_waypoints& d, int wmax) { waypoints = B; wp = d; wp_max = wmax; wp_tick = 0; }
+    // The paths end: cleared by the caller, the targets were written by irlosc_set_targets, the model changed, or their buffers failed.
+    void unpathed() { waypoints = 0; wp_tick = 0; }
+    // The cycler ran behind a tick of a rollout.  (Marked once the whole tick is enqueued: if a launch behind the cycler fails, the
+    // device state is one tick ahead of wp_tick -- on a context whose stream has already failed, where the rollout's result is void anyway.)
+    void ticked() { ++wp_tick; }
     // pack_slot built the block of B robots from records it found eligible (lane_eligible: the tree verdict, so records > 0).
     void block_packed(int B) { packed = B; }
 };
@@ -332,7 +349,7 @@ static void free_bank(irlosc_ctx::Bank& b, unsigned what) {
 // Frees every buffer of the slot.
 static void free_slot(Slot& s) {
     for (void* p : {s.M, s.J, s.dq, s.bias, s.ee, s.wrench, s.tgt, s.tvel, (void*)s.blk, (void*)s.blk_dq, (void*)s.qpos, (void*)s.qvel,
-                    (void*)s.qt, (void*)s.sens})
+                    (void*)s.qt, (void*)s.sens, (void*)s.wp_index, (void*)s.wp_arrivals, (void*)s.wp_last, (void*)s.wp_table})
         if (p) (void)hipFree(p);
     s = Slot{};
 }
@@ -829,8 +846,9 @@ extern "C" int irlosc_set_targets(irlosc_ctx* c, int32_t slot, int32_t B, const 
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (B == 0) { s.targets = -1; return IRLOSC_OK; }
+    if (B == 0) { s.targets = -1; s.unpathed(); return IRLOSC_OK; }
     if (!tgt_pose) return fail(c, IRLOSC_ERR_ARG, "tgt_pose is NULL");
+    s.unpathed();      // the targets are the caller's from here on: one entry point writes them at a time
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, nd = (size_t)c->cfg.ndev, e = c->esz;
     HIPCHK(c, hipMemcpyAsync(s.tgt, tgt_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
@@ -1531,7 +1549,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) s.drop_block(true);
+    for (Slot& s : c->slot) { s.drop_block(true); s.unpathed(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1697,9 +1715,28 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 
 // irlosc_rollout_from_q: the plant kernel behind the step (one step on bank 0), handed to the next train like the timing events
 // (irlosc_ctx::plant_next); trace: the device sample of this tick's EE poses, or nullptr
+// wp_tick: >= 0: the slot has waypoint paths and its cycler runs between the give-up pass and the plant, as this tick; -1: none
 struct PlantCall {
     double* trace;
+    int wp_tick;
 };
+
+// The arguments of the slot's waypoint cycler over B robots (init: the launch of irlosc_set_waypoints; else a tick on exchange block xside)
+static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, int wmax, int stride, const double* xside, int tick) {
+    WaypointArgs a;
+    memset(&a, 0, sizeof a);
+    a.xside = xside; a.tgt = s.tgt;
+    a.index = s.wp_index; a.arrivals = s.wp_arrivals; a.last_tick = s.wp_last; a.table = s.wp_table;
+    for (int d = 0; d < c->cfg.ndev; ++d) {
+        a.thr2[d] = w.threshold[d] * w.threshold[d];
+        a.count[d] = w.count[d];
+        a.loop[d] = w.loop[d];
+        a.ee0[d] = xside ? c->model.tables.eetab[d][0] : 0;
+    }
+    a.B = B; a.ndev = c->cfg.ndev; a.stride = stride; a.wmax = wmax; a.per_robot = w.nb > 1;
+    a.n_entries = (int32_t)c->model.fe_xentries; a.tick = tick; a.init = xside ? 0 : 1;
+    return a;
+}
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
 struct DevCall {
@@ -1790,6 +1827,10 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     }
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
+    if (pl && pl->wp_tick >= 0) {      // the targets move where an arm arrived: behind every OSC kernel of the tick, in front of the plant
+        const Slot& s = c->slot[slots[0]];
+        HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s, B, s.wp, s.wp_max, s.waypoints, bk.xside[0], pl->wp_tick), st));
+    }
     if (pl) {
         const Slot& s = c->slot[slots[0]];
         PlantArgs pa;
@@ -1808,6 +1849,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     // / irlosc_download_records on them fail with IRLOSC_ERR_STATE until irlosc_frontend / irlosc_upload* fills them again.
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
     if (pl) c->slot[slots[0]].advanced(B);
+    if (pl && pl->wp_tick >= 0) c->slot[slots[0]].ticked();
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2045,7 +2087,8 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     int filled = 0, sent = 0;      // samples written / copied to the host
     for (int t = 0; t < ticks; ++t) {
         const bool traced = nsamples && t % every == 0;
-        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr};
+        const Slot& s = c->slot[slot];
+        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr, s.waypoints > 0 ? s.wp_tick : -1};
         c->plant_next = &pl;
         const int rc = fused_resident(c, slot, B, 1);
         c->plant_next = nullptr;
@@ -2078,6 +2121,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     rc = check_slot_q(c, slot, B);
     if (!rc) rc = check_slot_feed(c, slot, B);
     if (rc) return rc;
+    if (c->slot[slot].waypoints > 0 && B > c->slot[slot].waypoints)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its waypoint paths cover %d robots, rollout asked for %d", slot, c->slot[slot].waypoints, B);
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (!fused_ready(c, 1))
@@ -2097,6 +2142,89 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (es != hipSuccess && !rc) rc = fail(c, IRLOSC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
     return rc;
+}
+
+// ---- waypoint paths of the rollout (osc_waypoint.hpp) -----------------------------------------------------------------------
+extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_waypoints* w, const double* xyz) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    Slot& s = c->slot[slot];
+    const int nd = c->cfg.ndev;
+    int wmax = 0;
+    for (int d = 0; w && d < IRLOSC_MAX_DEV; ++d) {
+        if (w->count[d] < 0 || w->count[d] > IRLOSC_MAX_WAYPOINTS || (d >= nd && w->count[d] != 0))
+            return fail(c, IRLOSC_ERR_ARG, "waypoints: count[%d]=%d out of [0,%d]", d, w->count[d], d < nd ? IRLOSC_MAX_WAYPOINTS : 0);
+        wmax = std::max(wmax, (int)w->count[d]);
+    }
+    if (!w || wmax == 0) { s.unpathed(); return IRLOSC_OK; }
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "waypoints: B=%d must be >= 1", B);
+    if (w->nb != 1 && w->nb != B) return fail(c, IRLOSC_ERR_ARG, "waypoints: nb=%d must be 1 or B=%d", w->nb, B);
+    if (!xyz) return fail(c, IRLOSC_ERR_ARG, "waypoints: xyz is NULL");
+    for (int d = 0; d < nd; ++d) {
+        if (!w->count[d]) continue;
+        if (!(std::isfinite(w->threshold[d]) && w->threshold[d] > 0.0))
+            return fail(c, IRLOSC_ERR_ARG, "waypoints: threshold[%d]=%g must be finite and > 0", d, w->threshold[d]);
+        if (w->loop[d] > 1) return fail(c, IRLOSC_ERR_ARG, "waypoints: loop[%d]=%d must be 0 or 1", d, (int)w->loop[d]);
+        for (int b = 0; b < w->nb; ++b)
+            for (int i = 0; i < w->count[d] * 3; ++i)
+                if (!std::isfinite(xyz[(((size_t)b * nd + d) * wmax) * 3 + i]))
+                    return fail(c, IRLOSC_ERR_ARG, "waypoints: waypoint %d of device %d, robot %d is not finite", i / 3, d, b);
+    }
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, waypoints given for %d: irlosc_set_targets first", slot,
+                    std::max(0, s.targets), B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    s.unpathed();      // (none until the new ones are in their buffers)
+    // the table in the kernel's layout: per robot [walk wave][dev][w][3][64] (idle lanes and unlisted entries zero), shared as given
+    const bool per_robot = w->nb > 1;
+    const size_t waves = ((size_t)B + 63) / 64;
+    std::vector<double> tab(per_robot ? waves * nd * wmax * 3 * 64 : (size_t)nd * wmax * 3, 0.0);
+    for (int b = 0; b < w->nb; ++b)
+        for (int d = 0; d < nd; ++d)
+            for (int i = 0; i < w->count[d] * 3; ++i) {
+                const size_t e = ((size_t)d * wmax) * 3 + i;
+                tab[per_robot ? ((size_t)(b / 64) * nd * wmax * 3 + e) * 64 + b % 64 : e] = xyz[(size_t)b * nd * wmax * 3 + e];
+            }
+    const size_t bytes = tab.size() * sizeof(double), state = (size_t)nd * c->cfg.max_batch * sizeof(int32_t);
+    if (s.wp_table && s.wp_table_bytes < bytes) { (void)hipFree(s.wp_table); s.wp_table = nullptr; s.wp_table_bytes = 0; }
+    if (!s.wp_table && dev_alloc(s.wp_table, bytes)) s.wp_table_bytes = bytes;
+    if (!s.wp_table || !dev_alloc(s.wp_index, state) || !dev_alloc(s.wp_arrivals, state) || !dev_alloc(s.wp_last, state))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the waypoint paths of slot %d (%zu bytes)", slot, bytes + 3 * state);
+    HIPCHK(c, hipMemcpyAsync(s.wp_table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    const WaypointArgs a = waypoint_args(c, s, B, *w, wmax, B, nullptr, 0);
+    rc = c->cfg.dtype == IRLOSC_F64 ? launch_waypoints<double>(a, c->stream) : launch_waypoints<float>(a, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when the launch failed: `tab` is the copy's source)
+    HIPCHK(c, (hipError_t)rc);
+    HIPCHK(c, es);
+    s.pathed(B, *w, wmax);
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_waypoint_state(irlosc_ctx* c, int32_t slot, int32_t B, int32_t* index, uint32_t* arrivals, int32_t* last_tick) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Slot& s = c->slot[slot];
+    if (s.waypoints <= 0) return fail(c, IRLOSC_ERR_STATE, "slot %d has no waypoint paths (irlosc_set_waypoints)", slot);
+    if (B > s.waypoints) return fail(c, IRLOSC_ERR_STATE, "slot %d: its waypoint paths cover %d robots, asked for %d", slot, s.waypoints, B);
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    // SoA [ndev][waypoints] on the device -> [B][ndev] for the caller
+    const int nd = c->cfg.ndev;
+    const size_t n = (size_t)nd * s.waypoints;
+    std::vector<int32_t> h(n);
+    const void* src[3] = {s.wp_index, s.wp_arrivals, s.wp_last};
+    int32_t* dst[3] = {index, (int32_t*)arrivals, last_tick};
+    for (int i = 0; i < 3; ++i) {
+        if (!dst[i]) continue;
+        HIPCHK(c, hipMemcpyAsync(h.data(), src[i], n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int b = 0; b < B; ++b)
+            for (int d = 0; d < nd; ++d) dst[i][(size_t)b * nd + d] = h[(size_t)d * s.waypoints + b];
+    }
+    return IRLOSC_OK;
 }
 
 extern "C" int irlosc_device_sync(irlosc_ctx* c) {

@@ -88,6 +88,12 @@ template <typename T>
 int launch_plant(const PlantArgs& a, hipStream_t st);
 int plant_joints();                                     // hinges of the tree the kernel is compiled for
 
+// tu_waypoint.hip -- the waypoint cycler between the give-up pass and the plant of a rollout tick whose slot has paths
+// (osc_waypoint.hpp); T = record type (of the targets)
+struct WaypointArgs;
+template <typename T>
+int launch_waypoints(const WaypointArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;
