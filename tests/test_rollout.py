@@ -51,16 +51,18 @@ def make_ctx(cfg, B, dtype=np.float64, feed=False, seed=0, **kw):
 _ORACLE = {}
 
 
-def _mb_chunk(span):
+def _mb_chunk(span, cfg="k13", ee=False):
+    """(cfg: the layout whose device order the EE poses follow; M and bias do not depend on it.  ee: return the EE poses as well)"""
     lo, hi = span
     om = rb.Model()
-    lay = synth.make_layout("k13").as_oracle_dict()
+    lay = synth.make_layout(cfg).as_oracle_dict()
     q, qd = _ORACLE["q"], _ORACLE["qd"]
     M, bias = np.zeros((hi - lo, 25, 25)), np.zeros((hi - lo, 25))
+    pose = np.zeros((hi - lo, len(lay["dev_names"]), 7))
     for b in range(lo, hi):
         r = rb.records(om, lay, DUAL_UR5_EE, q[b], qd[b])
-        M[b - lo], bias[b - lo] = r["M"], r["bias"]
-    return lo, M, bias
+        M[b - lo], bias[b - lo], pose[b - lo] = r["M"], r["bias"], r["ee_pose"]
+    return (lo, M, bias, pose) if ee else (lo, M, bias)
 
 
 def oracle_M_bias(q, qd):
