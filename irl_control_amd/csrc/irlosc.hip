@@ -27,6 +27,7 @@
 #include "osc_plant.hpp"
 #include "osc_waypoint.hpp"
 #include "launchers.hpp"
+#include "dev_mem.hpp"
 
 using namespace irlosc;
 static_assert(FE_TRAIN == R16_TRAIN, "the walk and the OSC kernel chain the same number of steps per launch");
@@ -36,39 +37,37 @@ static thread_local std::string g_create_error;
 
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
 // (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
-// the fused path is on (ensure_qt), sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
+// the fused path is on, sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
 // empty batch.
 // The state of the records and of what follows them is written by the transitions below and by nothing else.  INVARIANT: `tree` and
 // `packed` -- and so the route irlosc_slot_route reports -- are non-zero only while `records` > 0: every transition that lowers
-// `records` clears both, and only accepted() / block_packed() raise them.  (targets / has_tvel, coords and feed / sens_cols count
+// `records` clears both, and only accepted() / block_packed() raise them.  (targets / has_tvel, coords and feed count
 // independent inputs, each written by its one entry point: irlosc_set_targets, irlosc_upload_q, irlosc_set_sensordata.)
 struct Slot {
     // dense records
-    void *M = nullptr, *J = nullptr, *dq = nullptr, *bias = nullptr, *ee = nullptr, *wrench = nullptr;
+    DevBuf<void> M, J, dq, bias, ee, wrench;
     int records = 0;           // instances they hold
     int has_wrench = 0;
     int tree = 0;              // 1: verified to carry the zero pattern of the compiled Dual-UR5 tree (probe), or written by the lane front end
     int fused_away = 0;        // 1: invalidated by a fused step from joint coordinates (error text only)
     // their compact block for the resident lane route ([walk wave][n_compact][64 robots], 2.7 KB per robot) and dq in the walk's
     // coordinate layout ([walk wave][2 n][64], entry 2 j + 1 = dq_j)
-    double *blk = nullptr, *blk_dq = nullptr;
+    DevBuf<double> blk, blk_dq;
     int packed = 0;            // robots packed (0: no valid block -- the slot steps on the row16 kernel)
     // targets
-    void *tgt = nullptr, *tvel = nullptr;
+    DevBuf<void> tgt, tvel;
     int targets = 0, has_tvel = 0;
     // joint coordinates; qt: the same in the fused walk's layout [wave][2 n][64 robots] (irlosc_upload_q writes both)
-    double *qpos = nullptr, *qvel = nullptr, *qt = nullptr;
+    DevBuf<double> qpos, qvel, qt;
     int coords = 0;
     // F/T sensor feed of the steps from joint coordinates: the sensordata (the wrench computed from it is a buffer of the step's
     // bank, Bank::ftw)
-    double* sens = nullptr;
-    int sens_cols = 0;         // doubles per robot the buffer holds
+    DevBuf<double> sens;       // (grown to max_batch x the description's n_sensor doubles)
     int feed = 0;              // robots of the feed (0 = no feed)
     // waypoint paths of the rollout (irlosc_set_waypoints): per-robot state [ndev][waypoints] each, the table ([walk wave][dev][w][3][64]
     // per robot, [dev][w][3] shared), allocated by the first use; the description in force and the widest list
-    int32_t* wp_index = nullptr; uint32_t* wp_arrivals = nullptr; int32_t* wp_last = nullptr;
-    double* wp_table = nullptr;
-    size_t wp_table_bytes = 0;
+    DevBuf<int32_t> wp_index; DevBuf<uint32_t> wp_arrivals; DevBuf<int32_t> wp_last;
+    DevBuf<double> wp_table;
     irlosc_waypoints wp{};
     int wp_max = 0;
     int waypoints = 0;         // robots with paths (0 = none: a rollout tick launches no cycler)
@@ -121,7 +120,7 @@ static StepInputs slot_inputs(const Slot& s, const void* feed_wrench = nullptr) 
 // ... and to the record arrays a front end writes
 template <typename T>
 static FeOut<T> slot_out(const Slot& s) {
-    return FeOut<T>{(T*)s.M, (T*)s.J, (T*)s.dq, (T*)s.bias, (T*)s.ee};
+    return FeOut<T>{(T*)s.M.get(), (T*)s.J.get(), (T*)s.dq.get(), (T*)s.bias.get(), (T*)s.ee.get()};
 }
 
 // What a model means for the context, planned ON THE HOST by irlosc_set_model (derive_model, then plan_routes: neither touches the
@@ -155,11 +154,11 @@ struct ModelPlan {
 // irlosc_set_model, and after one that failed on the device (never half of a model).
 struct Model : ModelPlan {
     int in_force = 0;
-    FeModel* dmodel = nullptr;
-    FeCompactTables* dtables = nullptr;
-    PackTable* dpack = nullptr;
-    int32_t* dpack_bad = nullptr;     // robots whose dropped entries were not zero (the pack's check)
-    double* fe_side = nullptr;        // side buffer of the lane front end: [wave][entry][64], allocated by the first irlosc_frontend
+    DevBuf<FeModel> dmodel;
+    DevBuf<FeCompactTables> dtables;
+    DevBuf<PackTable> dpack;
+    DevBuf<int32_t> dpack_bad;        // robots whose dropped entries were not zero (the pack's check)
+    DevBuf<double> fe_side;           // side buffer of the lane front end: [wave][entry][64], allocated by the first irlosc_frontend
 
     int commit(irlosc_ctx* c, const ModelPlan& p);
     // Bank 0 has no exchange buffers: no fused path on this context, the steps from joint coordinates go through dense records.
@@ -168,32 +167,26 @@ struct Model : ModelPlan {
     void give_up_lane(irlosc_ctx* c);
     // No side buffer: the wave-per-robot front end, which needs none, writes the records -- and with the lane walk goes the fused path.
     void give_up_lane_walk() { fe_lane = 0; fused = 0; }
-    void free_device() {
-        for (void* p : {(void*)dmodel, (void*)dtables, (void*)dpack, (void*)dpack_bad, (void*)fe_side}) if (p) (void)hipFree(p);
-        dmodel = nullptr; dtables = nullptr; dpack = nullptr; dpack_bad = nullptr; fe_side = nullptr;
-    }
 };
 
 struct irlosc_ctx {
     irlosc_cfg cfg{};
     int k = 0;
     size_t esz = 4;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stream stream;                     // (declared ahead of everything enqueued on it: destroyed last)
+    Event ev0, ev1;
     std::vector<Slot> slot;            // resident inputs, one set per slot
     int nsets = 1;                     // output sets of bank 0: step i of a row16 train writes set i; the generic path only ever uses set 0
     int train = 1;                     // steps per launch in irlosc_step_resident
     hipEvent_t tev_begin = nullptr, tev_end = nullptr;   // timing events handed to the next train launch (or null)
-    unsigned long long* dspan = nullptr;   // irlosc_time_trains: [ntrains][2] wall-clock stamps written by the kernels
-    int dspan_cap = 0;
+    DevBuf<unsigned long long> dspan;      // irlosc_time_trains: [ntrains][2] wall-clock stamps written by the kernels, grown on demand
     unsigned long long* span_next = nullptr;   // the pair the next train launch stamps (or null)
     const struct PlantCall* plant_next = nullptr;   // irlosc_rollout_from_q: the plant call the next fused train ends with (or null)
-    std::vector<hipEvent_t> tev_pool;
+    std::vector<Event> tev_pool;
     void* du = nullptr;                // output set written by the most recent step
     uint32_t* dflags = nullptr;
-    void* draw = nullptr;     // staging for irlosc_upload_raw (raw simulator arrays), grown on demand
-    size_t draw_bytes = 0;
-    void* dzeros = nullptr;            // fp64 row16 path: zero page for the padding lanes
+    DevBuf<unsigned char> draw;        // staging for irlosc_upload_raw (raw simulator arrays), grown on demand
+    DevBuf<void> dzeros;               // fp64 row16 path: zero page for the padding lanes
     Model model;                       // rigid-body front end and everything else irlosc_set_model decides
     int task_pass = 1;                     // IRLOSC_TASK_PASS=0: part 1 of the task signal in the row16 kernel (A/B, tests)
     // Consecutive trains of irlosc_step_resident_from_q / irlosc_step_resident rotate over BANKS of buffers, each on a stream of its own:
@@ -204,25 +197,26 @@ struct irlosc_ctx {
     // (create_impl) and serve single steps too.  The other banks, and every bank's per-step buffers of the task pass, the fused path's
     // exchange buffers and the lane form's records, are allocated by the first call that needs them (ensure_bank).
     struct Bank {
-        hipStream_t st = nullptr;
-        hipEvent_t done = nullptr;
-        void* u[R16_TRAIN] = {};           // output sets
-        uint32_t* flags[R16_TRAIN] = {};
-        int32_t* list[R16_TRAIN] = {};     // give-up list of each step of a train
-        int32_t* count = nullptr;          // [R16_TRAIN] give-up counters, zeroed in front of every train
-        double* trows[R16_TRAIN] = {};     // dense-record trains: task rows of each step (osc_task_rows_dense_kernel)
-        double* xside[R16_TRAIN] = {};     // fused path: compact exchange buffer of each step ...
-        size_t xentries = 0;               // ... sized for this many entries
-        double* lane_rec[R16_TRAIN] = {};  // lane form of the fused path: eigen-pass records of each step, and their counters
-        int32_t* lane_count = nullptr;
-        void* ftw[R16_TRAIN] = {};         // wrench of each step whose slot has a sensor feed (allocated by the first such step)
+        hipStream_t st = nullptr;          // bank 0: the context's stream; the others: own_st
+        Stream own_st;
+        Event done;
+        DevBuf<void> u[R16_TRAIN];             // output sets
+        DevBuf<uint32_t> flags[R16_TRAIN];
+        DevBuf<int32_t> list[R16_TRAIN];       // give-up list of each step of a train
+        DevBuf<int32_t> count;                 // [R16_TRAIN] give-up counters, zeroed in front of every train
+        DevBuf<double> trows[R16_TRAIN];       // dense-record trains: task rows of each step (osc_task_rows_dense_kernel)
+        DevBuf<double> xside[R16_TRAIN];       // fused path: compact exchange buffer of each step ...
+        size_t xentries = 0;                   // ... sized for this many entries
+        DevBuf<double> lane_rec[R16_TRAIN];    // lane form of the fused path: eigen-pass records of each step, and their counters
+        DevBuf<int32_t> lane_count;
+        DevBuf<void> ftw[R16_TRAIN];           // wrench of each step whose slot has a sensor feed (allocated by the first such step)
     };
     static constexpr int FQ_BANKS = 3;     // banks of the fused path's trains (k13 6.88 -> 7.00e8 against two; four: 7.03e8, +2.4 GB each)
     static constexpr int R16_BANKS = 2;    // banks of the dense-record trains (a third was a cache artefact of a four-slot bench)
     static constexpr int MAX_XBANKS = FQ_BANKS - 1;
     Bank bank[1 + MAX_XBANKS];
-    hipEvent_t ev_join = nullptr;
-    hipEvent_t ev_dev = nullptr;           // irlosc_step_from_q_device: a caller stream starts behind the context's stream
+    Event ev_join;
+    Event ev_dev;                          // irlosc_step_from_q_device: a caller stream starts behind the context's stream
     int r16_overlap = 1;                   // IRLOSC_R16_OVERLAP=0: one bank, one stream for the trains of irlosc_step_resident on dense records
     int32_t* count_cur = nullptr;          // give-up counters of the most recent train (irlosc_giveup_counts)
     // F/T sensor feed of the steps from joint coordinates (irlosc_set_ft_sensors / irlosc_set_sensordata): the description and R_rel
@@ -232,14 +226,14 @@ struct irlosc_ctx {
     int32_t ft_f0[IRLOSC_MAX_DEV] = {}, ft_t0[IRLOSC_MAX_DEV] = {};
     double ft_R[IRLOSC_MAX_DEV][9] = {};
     // irlosc_tick: one pinned host block and one device block per direction, grown on demand
-    void* tick_hin = nullptr; void* tick_din = nullptr; size_t tick_in_bytes = 0;
-    void* tick_hout = nullptr; void* tick_dout = nullptr; size_t tick_out_bytes = 0;
+    PinnedBuf tick_hin, tick_hout;
+    DevBuf<unsigned char> tick_din, tick_dout;
     // irlosc_rollout_from_q: the plant in force (irlosc_set_plant), the OR of the ticks' flags, the bounded device buffer of the EE trace
     int plant_set = 0;
     irlosc_plant plant{};
-    uint32_t* dflags_any = nullptr;
-    double* dtrace = nullptr;
-    int32_t* dsym = nullptr;  // symmetry probe of the throughput paths: {count, first instance}
+    DevBuf<uint32_t> dflags_any;
+    DevBuf<double> dtrace;
+    DevBuf<int32_t> dsym;     // symmetry probe of the throughput paths: {count, first instance}
     // Tree-structured factorisation on dense records (row16 kernel), for slots whose records carry the tree's zeros (Slot::tree)
     int tree_enabled = 1;              // IRLOSC_TREE=0 turns the form off (A/B measurements)
     // Resident lane route (irlosc_step / irlosc_step_resident on float64 tree-form records of an AUTO context with a lane tier): the pack
@@ -247,11 +241,11 @@ struct irlosc_ctx {
     int auto_kernel = 0;               // created with IRLOSC_KERNEL_AUTO
     int resident_lane = 1;             // IRLOSC_RESIDENT_LANE=0 turns the route off (A/B measurements, tests)
     StructureMasks tree_masks;
-    int32_t* dstruct = nullptr;        // result word of the structure probe
-    void* dgains = nullptr;   // [nb][ndev][12] in dtype
-    void* dnullkv = nullptr;  // [nb]
+    DevBuf<int32_t> dstruct;           // result word of the structure probe
+    DevBuf<void> dgains;      // [nb][ndev][12] in dtype
+    DevBuf<void> dnullkv;     // [nb]
     int gains_nb = 0;
-    unsigned long long* ddbg = nullptr;  // IRLOSC_PHASE_TIMING=1: 8 cycle stamps + 2 wall-clock stamps per stage-1 wave
+    DevBuf<unsigned long long> ddbg;     // IRLOSC_PHASE_TIMING=1: 8 cycle stamps + 2 wall-clock stamps per stage-1 wave
     int kernel = IRLOSC_KERNEL_GENERIC;
     int kernel_class = IRLOSC_CLASS_GENERIC;
     std::string kernel_name;
@@ -333,55 +327,14 @@ static int validate(const irlosc_cfg* c, int* k_out) {
 // What a train needs of its bank beside the output sets, give-up lists and counters (irlosc_ctx::Bank, ensure_bank)
 enum : unsigned { NEED_ROWS = 1, NEED_X = 2, NEED_LANE = 4, BANK_ALL = ~0u };
 
-// Frees the buffers of `b` that `what` names (BANK_ALL: every buffer of the bank; its stream and event stay).
+// Frees the buffers of `b` that `what` names: the one place that says which buffers a NEED_* class is.
 static void free_bank(irlosc_ctx::Bank& b, unsigned what) {
-    auto fr = [](auto*& p) { if (p) (void)hipFree(p); p = nullptr; };
     for (int i = 0; i < R16_TRAIN; ++i) {
-        if (what & NEED_ROWS) fr(b.trows[i]);
-        if (what & NEED_X) fr(b.xside[i]);
-        if (what & NEED_LANE) fr(b.lane_rec[i]);
-        if (what == BANK_ALL) { fr(b.u[i]); fr(b.flags[i]); fr(b.list[i]); fr(b.ftw[i]); }
+        if (what & NEED_ROWS) b.trows[i].reset();
+        if (what & NEED_X) b.xside[i].reset();
+        if (what & NEED_LANE) b.lane_rec[i].reset();
     }
-    if (what & NEED_LANE) fr(b.lane_count);
-    if (what == BANK_ALL) fr(b.count);
-}
-
-// Frees every buffer of the slot.
-static void free_slot(Slot& s) {
-    for (void* p : {s.M, s.J, s.dq, s.bias, s.ee, s.wrench, s.tgt, s.tvel, (void*)s.blk, (void*)s.blk_dq, (void*)s.qpos, (void*)s.qvel,
-                    (void*)s.qt, (void*)s.sens, (void*)s.wp_index, (void*)s.wp_arrivals, (void*)s.wp_last, (void*)s.wp_table})
-        if (p) (void)hipFree(p);
-    s = Slot{};
-}
-
-static void free_all(irlosc_ctx* c) {
-    for (Slot& s : c->slot) free_slot(s);
-    if (c->draw) (void)hipFree(c->draw);
-    c->model.free_device();
-    for (irlosc_ctx::Bank& bk : c->bank) {
-        free_bank(bk, BANK_ALL);
-        if (bk.done) (void)hipEventDestroy(bk.done);
-        if (bk.st && bk.st != c->stream) (void)hipStreamDestroy(bk.st);
-    }
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->ev_dev) (void)hipEventDestroy(c->ev_dev);
-    if (c->tick_hin) (void)hipHostFree(c->tick_hin);
-    if (c->tick_din) (void)hipFree(c->tick_din);
-    if (c->tick_hout) (void)hipHostFree(c->tick_hout);
-    if (c->tick_dout) (void)hipFree(c->tick_dout);
-    if (c->dzeros) (void)hipFree(c->dzeros);
-    if (c->dsym) (void)hipFree(c->dsym);
-    if (c->dflags_any) (void)hipFree(c->dflags_any);
-    if (c->dtrace) (void)hipFree(c->dtrace);
-    if (c->dspan) (void)hipFree(c->dspan);
-    if (c->dstruct) (void)hipFree(c->dstruct);
-    if (c->dgains) (void)hipFree(c->dgains);
-    if (c->dnullkv) (void)hipFree(c->dnullkv);
-    if (c->ddbg) (void)hipFree(c->ddbg);
-    for (hipEvent_t ev : c->tev_pool) (void)hipEventDestroy(ev);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (what & NEED_LANE) b.lane_count.reset();
 }
 
 // The A/B switches of the environment, each read when its comment says (irlosc_create or irlosc_set_model): NAME holds `value` /
@@ -395,16 +348,16 @@ static bool env_off(const char* name) { return env_is(name, "0"); }
 static int create_impl(irlosc_ctx* c) {
     const irlosc_cfg& g = c->cfg;
     HIPCHK(nullptr, hipSetDevice(g.hip_device));
-    HIPCHK(nullptr, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(nullptr, hipEventCreate(&c->ev0));
-    HIPCHK(nullptr, hipEventCreate(&c->ev1));
+    HIPCHK(nullptr, c->stream.ensure());
+    HIPCHK(nullptr, c->ev0.ensure());
+    HIPCHK(nullptr, c->ev1.ensure());
     const size_t B = (size_t)g.max_batch, n = (size_t)g.n, k = (size_t)c->k, nd = (size_t)g.ndev, e = c->esz;
-    c->slot.assign(g.n_slots, Slot{});
-    const struct { void* Slot::*buf; size_t bytes; } resident[] = {
+    c->slot.resize(g.n_slots);
+    const struct { DevBuf<void> Slot::*buf; size_t bytes; } resident[] = {
         {&Slot::M, B * n * n * e}, {&Slot::J, B * k * n * e}, {&Slot::dq, B * n * e}, {&Slot::bias, B * n * e},
         {&Slot::ee, B * nd * 7 * e}, {&Slot::wrench, B * nd * 6 * e}, {&Slot::tgt, B * nd * 7 * e}, {&Slot::tvel, B * nd * 6 * e}};
     for (const auto& r : resident)
-        for (Slot& s : c->slot) HIPCHK(nullptr, hipMalloc(&(s.*r.buf), r.bytes));
+        for (Slot& s : c->slot) HIPCHK(nullptr, (s.*r.buf).ensure(r.bytes));
     if (c->kernel == IRLOSC_KERNEL_ROW16) {
         c->train = R16_TRAIN;
         c->nsets = R16_TRAIN;               // a train completes (give-up pass included) before the next one starts
@@ -412,34 +365,30 @@ static int create_impl(irlosc_ctx* c) {
     irlosc_ctx::Bank& b0 = c->bank[0];
     b0.st = c->stream;
     for (int k2 = 0; k2 < c->nsets; ++k2) {
-        HIPCHK(nullptr, hipMalloc(&b0.u[k2], B * n * e));
-        HIPCHK(nullptr, hipMalloc((void**)&b0.flags[k2], B * sizeof(uint32_t)));
-        HIPCHK(nullptr, hipMemsetAsync(b0.flags[k2], 0, B * sizeof(uint32_t), c->stream));
+        HIPCHK(nullptr, b0.u[k2].ensure(B * n * e));
+        HIPCHK(nullptr, b0.flags[k2].ensure(B * sizeof(uint32_t), c->stream));
     }
     if (c->kernel == IRLOSC_KERNEL_ROW16) {
-        constexpr size_t ZB = 64 * 1024;
-        HIPCHK(nullptr, hipMalloc(&c->dzeros, ZB));
-        HIPCHK(nullptr, hipMemsetAsync(c->dzeros, 0, ZB, c->stream));
-        for (int k2 = 0; k2 < R16_TRAIN; ++k2) HIPCHK(nullptr, hipMalloc((void**)&b0.list[k2], B * sizeof(int32_t)));
-        HIPCHK(nullptr, hipMalloc((void**)&b0.count, R16_TRAIN * sizeof(int32_t)));
+        HIPCHK(nullptr, c->dzeros.ensure(64 * 1024, c->stream));
+        for (int k2 = 0; k2 < R16_TRAIN; ++k2) HIPCHK(nullptr, b0.list[k2].ensure(B * sizeof(int32_t)));
+        HIPCHK(nullptr, b0.count.ensure(R16_TRAIN * sizeof(int32_t), c->stream));
         // part 1 of the task signal runs as a pass ahead of the row16 kernel (IRLOSC_TASK_PASS=0: in the kernel; A/B, tests); its
         // rows buffers are allocated by the first train that needs them (ensure_bank)
         c->task_pass = !env_off("IRLOSC_TASK_PASS");
         c->r16_overlap = !env_off("IRLOSC_R16_OVERLAP");
-        HIPCHK(nullptr, hipMemsetAsync(b0.count, 0, R16_TRAIN * sizeof(int32_t), c->stream));
     }
     c->du = b0.u[0];
     c->dflags = b0.flags[0];
     c->count_cur = b0.count;
-    HIPCHK(nullptr, hipMalloc((void**)&c->dsym, 2 * sizeof(int32_t)));
-    HIPCHK(nullptr, hipMalloc((void**)&c->dstruct, sizeof(int32_t)));
+    HIPCHK(nullptr, c->dsym.ensure(2 * sizeof(int32_t)));
+    HIPCHK(nullptr, c->dstruct.ensure(sizeof(int32_t)));
     c->resident_lane = !env_off("IRLOSC_RESIDENT_LANE");
     row16_tree_masks(c->tree_masks.mrow, &c->tree_masks.jcols);
     c->tree_enabled = !env_off("IRLOSC_TREE");
-    HIPCHK(nullptr, hipMalloc(&c->dgains, B * nd * IRLOSC_GAIN_WORDS * e));
-    HIPCHK(nullptr, hipMalloc(&c->dnullkv, B * e));
+    HIPCHK(nullptr, c->dgains.ensure(B * nd * IRLOSC_GAIN_WORDS * e));
+    HIPCHK(nullptr, c->dnullkv.ensure(B * e));
     if (c->kernel != IRLOSC_KERNEL_GENERIC && getenv("IRLOSC_PHASE_TIMING"))     // debug aid: cycles per kernel phase
-        HIPCHK(nullptr, hipMalloc((void**)&c->ddbg, (B / 4 + 1) * 10 * sizeof(unsigned long long)));
+        HIPCHK(nullptr, c->ddbg.ensure((B / 4 + 1) * 10 * sizeof(unsigned long long)));
     HIPCHK(nullptr, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }
@@ -494,8 +443,7 @@ extern "C" int irlosc_create(const irlosc_cfg* cfg, irlosc_ctx** out) {
     }
     rc = create_impl(c);
     if (rc) {
-        free_all(c);
-        delete c;
+        delete c;      // (its owners release what was allocated: the device is current, set by create_impl's first line)
         return rc;
     }
     *out = c;
@@ -506,7 +454,6 @@ extern "C" void irlosc_destroy(irlosc_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.hip_device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    free_all(c);
     delete c;
 }
 
@@ -606,8 +553,8 @@ static int structure_probe(irlosc_ctx* c, const Slot& s, int B, int* tree) {
     int32_t bad = 0;
     HIPCHK(c, hipMemsetAsync(c->dstruct, 0, sizeof(int32_t), c->stream));
     const int rc = c->cfg.dtype == IRLOSC_F64
-        ? launch_structure_probe<double>((const double*)s.M, (const double*)s.J, c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream)
-        : launch_structure_probe<float>((const float*)s.M, (const float*)s.J, c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream);
+        ? launch_structure_probe<double>((const double*)s.M.get(), (const double*)s.J.get(), c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream)
+        : launch_structure_probe<float>((const float*)s.M.get(), (const float*)s.J.get(), c->cfg.n, c->k, B, c->tree_masks, c->dstruct, c->stream);
     HIPCHK(c, (hipError_t)rc);
     HIPCHK(c, hipMemcpyAsync(&bad, c->dstruct, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -725,7 +672,7 @@ static int assemble_launch(irlosc_ctx* c, const Slot& s, int B, const irlosc_raw
     r.jacp = (const T*)dptr[3]; r.jacr = (const T*)dptr[4]; r.ee_xpos = (const T*)dptr[5]; r.ee_xquat = (const T*)dptr[6];
     r.site_xmat = ft ? (const T*)dptr[7] : nullptr; r.sensordata = ft ? (const T*)dptr[8] : nullptr;
     const FeOut<T> o = slot_out<T>(s);
-    r.M = o.M; r.J = o.J; r.dq = o.dq; r.bias = o.bias; r.ee = o.ee; r.wrench = (T*)s.wrench;
+    r.M = o.M; r.J = o.J; r.dq = o.dq; r.bias = o.bias; r.ee = o.ee; r.wrench = (T*)s.wrench.get();
     HIPCHK(c, (hipError_t)launch_assemble<T>(d, r, B, st));
     return IRLOSC_OK;
 }
@@ -753,13 +700,8 @@ static int upload_raw_t(irlosc_ctx* c, const Slot& s, int B, const irlosc_raw_de
                           b * nd * 3 * e, b * nd * 4 * e, ft ? b * nd * 9 * e : 0, ft ? b * ns * e : 0};
     size_t off[9], total = 0;
     for (int i = 0; i < 9; ++i) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
-    if (total > c->draw_bytes) {
-        if (c->draw) HIPCHK(c, hipFree(c->draw));
-        c->draw = nullptr; c->draw_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->draw, total));
-        c->draw_bytes = total;
-    }
-    unsigned char* base = (unsigned char*)c->draw;
+    HIPCHK(c, c->draw.reserve(total));
+    unsigned char* base = c->draw;
     for (int i = 0; i < 9; ++i)
         if (sz[i]) HIPCHK(c, hipMemcpyAsync(base + off[i], src[i], sz[i], hipMemcpyHostToDevice, c->stream));
     const void* dptr[9];
@@ -865,7 +807,7 @@ static void fill_params(const irlosc_ctx* c, KParams<T>& p, int B, const StepInp
     p.M = (const T*)in.M; p.J = (const T*)in.J; p.dq = (const T*)in.dq; p.bias = (const T*)in.bias;
     p.ee = (const T*)in.ee; p.tgt = (const T*)in.tgt; p.tvel = (const T*)in.tvel; p.wrench = (const T*)in.wrench;
     p.u = (T*)u; p.flags = flags;
-    p.gains = (const T*)c->dgains; p.null_kv = (const T*)c->dnullkv;
+    p.gains = (const T*)c->dgains.get(); p.null_kv = (const T*)c->dnullkv.get();
     p.index = nullptr;
     p.dbg = c->ddbg;
     p.gains_per_instance = c->gains_nb > 1;
@@ -883,19 +825,8 @@ static void fill_params(const irlosc_ctx* c, KParams<T>& p, int B, const StepInp
     }
 }
 
-// *p = a new device buffer of `bytes` (zeroed on `zero_on` when given), unless it holds one already.  -> false: out of device memory.
-template <typename P>
-static bool dev_alloc(P*& p, size_t bytes, hipStream_t zero_on = nullptr) {
-    if (p) return true;
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) == hipSuccess && (!zero_on || hipMemsetAsync(q, 0, bytes, zero_on) == hipSuccess)) {
-        p = (P*)q;
-        return true;
-    }
-    (void)hipFree(q);
-    (void)hipGetLastError();
-    return false;
-}
+// An owner's ensure() / reserve() gave what was asked for (else: out of device memory, and the caller decides what follows)
+static bool got(hipError_t e) { return e == hipSuccess; }
 
 // Bank k ready for trains of up to n steps that need `need`: task rows (8 MB per step at 65 536 instances), exchange buffers (334 entries
 // x 512 B per 64 robots: 175 MB per step), lane records (one per robot and step for the eigen pass, whole groups of 64: all of a batch may
@@ -906,33 +837,29 @@ static unsigned ensure_bank(irlosc_ctx* c, int k, int n, unsigned need) {
     irlosc_ctx::Bank& b = c->bank[k];
     const size_t Bm = (size_t)c->cfg.max_batch, waves = (Bm + 63) / 64;
     if (k > 0) {
-        bool ok = (b.st || hipStreamCreateWithFlags(&b.st, hipStreamNonBlocking) == hipSuccess) &&
-                  (b.done || hipEventCreateWithFlags(&b.done, hipEventDisableTiming) == hipSuccess) &&
-                  (c->ev_join || hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) == hipSuccess) &&
-                  dev_alloc(b.count, R16_TRAIN * sizeof(int32_t));
+        bool ok = got(b.own_st.ensure()) && got(b.done.ensure(hipEventDisableTiming)) && got(c->ev_join.ensure(hipEventDisableTiming)) &&
+                  got(b.count.ensure(R16_TRAIN * sizeof(int32_t)));
+        b.st = b.own_st;
         for (int i = 0; ok && i < n; ++i)
-            ok = dev_alloc(b.list[i], Bm * sizeof(int32_t)) && dev_alloc(b.u[i], Bm * c->cfg.n * c->esz) && dev_alloc(b.flags[i], Bm * sizeof(uint32_t));
+            ok = got(b.list[i].ensure(Bm * sizeof(int32_t))) && got(b.u[i].ensure(Bm * c->cfg.n * c->esz)) && got(b.flags[i].ensure(Bm * sizeof(uint32_t)));
         if (!ok) { (void)hipGetLastError(); return BANK_ALL; }
     }
     if (need & NEED_ROWS)
-        for (int i = 0; i < n; ++i) if (!dev_alloc(b.trows[i], Bm * 16 * sizeof(double))) return NEED_ROWS;
+        for (int i = 0; i < n; ++i) if (!got(b.trows[i].ensure(Bm * 16 * sizeof(double)))) return NEED_ROWS;
     if (need & NEED_X) {
         if (b.xentries != c->model.fe_xentries) free_bank(b, NEED_X);          // sized for another model's entries
         b.xentries = c->model.fe_xentries;
-        for (int i = 0; i < n; ++i) if (!dev_alloc(b.xside[i], waves * b.xentries * 64 * sizeof(double))) return NEED_X;
+        for (int i = 0; i < n; ++i) if (!got(b.xside[i].ensure(waves * b.xentries * 64 * sizeof(double)))) return NEED_X;
     }
     if (need & NEED_LANE) {
-        if (!dev_alloc(b.lane_count, R16_TRAIN * sizeof(int32_t))) return NEED_LANE;
-        for (int i = 0; i < n; ++i) if (!dev_alloc(b.lane_rec[i], waves * 64 * lane::REC_DOUBLES * sizeof(double), c->stream)) return NEED_LANE;
+        if (!got(b.lane_count.ensure(R16_TRAIN * sizeof(int32_t)))) return NEED_LANE;
+        for (int i = 0; i < n; ++i) if (!got(b.lane_rec[i].ensure(waves * 64 * lane::REC_DOUBLES * sizeof(double), c->stream))) return NEED_LANE;
     }
     return 0;
 }
 
 // Bytes of a coordinate buffer in the fused walk's layout [walk wave][2 n][64 robots] (Slot::qt, Slot::blk_dq)
 static size_t qt_bytes(const irlosc_ctx* c) { return (((size_t)c->cfg.max_batch + 63) / 64) * 2 * c->cfg.n * 64 * sizeof(double); }
-
-// The slot's qt, allocated by its first use while the fused path is on.
-static hipError_t ensure_qt(const irlosc_ctx* c, Slot& s) { return s.qt ? hipSuccess : hipMalloc((void**)&s.qt, qt_bytes(c)); }
 
 // Resident lane route: records of at least this many robots qualify (a smaller batch keeps the row16 kernel: irlosc_tick at B = 1 pays
 // for no pack)
@@ -987,7 +914,7 @@ static int pack_slot(irlosc_ctx* c, int slot, int B, bool check) {
     Slot& s = c->slot[slot];
     if (!lane_eligible(c, slot, B)) return IRLOSC_OK;
     const size_t waves = ((size_t)c->cfg.max_batch + 63) / 64;
-    if (!dev_alloc(s.blk, waves * pack_entries() * 64 * sizeof(double)) || !dev_alloc(s.blk_dq, qt_bytes(c))) return IRLOSC_OK;
+    if (!got(s.blk.ensure(waves * pack_entries() * 64 * sizeof(double))) || !got(s.blk_dq.ensure(qt_bytes(c)))) return IRLOSC_OK;
     PackArgs a;
     memset(&a, 0, sizeof a);
     a.table = c->model.dpack;
@@ -1310,9 +1237,9 @@ static bool fused_ready(irlosc_ctx* c, int n);
 // of the sequence starts at slot first_slot + j * train.
 static int timed_trains(irlosc_ctx* c, int first_slot, int B, int ntrains, bool from_q, bool spans) {
     while ((int)c->tev_pool.size() < 2 * ntrains) {
-        hipEvent_t ev;
-        HIPCHK(c, hipEventCreate(&ev));
-        c->tev_pool.push_back(ev);
+        Event ev;
+        HIPCHK(c, ev.ensure());
+        c->tev_pool.push_back(std::move(ev));
     }
     int rc = IRLOSC_OK;
     for (int i = -1; i < ntrains && !rc; ++i) {
@@ -1367,12 +1294,7 @@ extern "C" int irlosc_time_trains(irlosc_ctx* c, int32_t first_slot, int32_t B, 
     if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (from_q && !fused_ready(c, c->train)) return fail(c, IRLOSC_ERR_STATE, "the fused path from joint coordinates is not available on this context");
-    if (c->dspan_cap < ntrains) {
-        if (c->dspan) HIPCHK(c, hipFree(c->dspan));
-        c->dspan = nullptr; c->dspan_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->dspan, (size_t)ntrains * R16_SPAN_WORDS * sizeof(unsigned long long)));
-        c->dspan_cap = ntrains;
-    }
+    HIPCHK(c, c->dspan.reserve((size_t)ntrains * R16_SPAN_WORDS * sizeof(unsigned long long)));
     std::vector<unsigned long long> h((size_t)ntrains * R16_SPAN_WORDS);
     for (int i = 0; i < ntrains; ++i) {
         unsigned long long* t = h.data() + (size_t)i * R16_SPAN_WORDS;
@@ -1531,15 +1453,15 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
                                     (p.lane_tier >= 0 && memcmp(&p.lane_map, &lane_map, sizeof lane_map)));
     in_force = 0;
     static_cast<ModelPlan&>(*this) = ModelPlan{};
-    if (!dmodel) HIPCHK(c, hipMalloc((void**)&dmodel, sizeof(FeModel)));
-    if (p.fused && !dtables) HIPCHK(c, hipMalloc((void**)&dtables, sizeof(FeCompactTables)));
-    if (p.pack_ok && !dpack) HIPCHK(c, hipMalloc((void**)&dpack, sizeof(PackTable)));
-    if (p.pack_ok && !dpack_bad) HIPCHK(c, hipMalloc((void**)&dpack_bad, sizeof(int32_t)));
+    HIPCHK(c, dmodel.ensure(sizeof(FeModel)));
+    if (p.fused) HIPCHK(c, dtables.ensure(sizeof(FeCompactTables)));
+    if (p.pack_ok) HIPCHK(c, dpack.ensure(sizeof(PackTable)));
+    if (p.pack_ok) HIPCHK(c, dpack_bad.ensure(sizeof(int32_t)));
     // (the lane front end's side buffer -- 139 MB at 65 536 robots -- is allocated by the first irlosc_frontend: a context that only
     // ever takes the fused path never needs it)
     for (Slot& s : c->slot) {      // the first model of the context: the slots' coordinate buffers
-        if (!s.qpos) HIPCHK(c, hipMalloc((void**)&s.qpos, (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
-        if (!s.qvel) HIPCHK(c, hipMalloc((void**)&s.qvel, (size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
+        HIPCHK(c, s.qpos.ensure((size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
+        HIPCHK(c, s.qvel.ensure((size_t)c->cfg.max_batch * c->cfg.n * sizeof(double)));
     }
     HIPCHK(c, hipMemcpyAsync(dmodel, &p.h, sizeof p.h, hipMemcpyHostToDevice, c->stream));
     if (p.fused) HIPCHK(c, hipMemcpyAsync(dtables, &p.tables, sizeof p.tables, hipMemcpyHostToDevice, c->stream));
@@ -1555,7 +1477,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
         for (Slot& s : c->slot) {
             if (s.coords <= 0) continue;
-            HIPCHK(c, ensure_qt(c, s));
+            HIPCHK(c, s.qt.ensure(qt_bytes(c)));
             HIPCHK(c, (hipError_t)launch_q_layout(s.qpos, s.qvel, s.qt, s.coords, c->cfg.n, c->stream));
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1591,7 +1513,7 @@ extern "C" int irlosc_upload_q(irlosc_ctx* c, int32_t slot, int32_t B, const dou
     // (only the fused path reads this layout; its buffer is allocated by the slot's first upload while the path is on, or by the
     //  irlosc_set_model that turns it on -- and, once it exists, refreshed by EVERY upload: a copy left stale while another model had
     //  the path switched off would be walked later)
-    if (c->model.fused) HIPCHK(c, ensure_qt(c, s));
+    if (c->model.fused) HIPCHK(c, s.qt.ensure(qt_bytes(c)));
     if (s.qt) HIPCHK(c, (hipError_t)launch_q_layout(s.qpos, s.qvel, s.qt, B, c->cfg.n, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.coords = B;
@@ -1609,7 +1531,7 @@ static int frontend_launch(irlosc_ctx* c, int slot, int B, const double* qpos = 
     if (!qpos) { qpos = s.qpos; qvel = s.qvel; }
     const hipStream_t st = cst ? cst : c->stream;
     Model& m = c->model;
-    if (m.fe_lane && !dev_alloc(m.fe_side, (((size_t)c->cfg.max_batch + 63) / 64) * frontend_lane_dual_ur5_side_doubles_per_wave() * sizeof(double)))
+    if (m.fe_lane && !got(m.fe_side.ensure((((size_t)c->cfg.max_batch + 63) / 64) * frontend_lane_dual_ur5_side_doubles_per_wave() * sizeof(double))))
         m.give_up_lane_walk();
     s.writing();
     int rc;
@@ -1693,8 +1615,8 @@ static int ft_launch(irlosc_ctx* c, const FtStep* s, int n, int B, hipStream_t s
 
 // The wrench buffer of step i of bank k's trains for a slot with a sensor feed (nullptr: out of device memory)
 static void* feed_wrench(irlosc_ctx* c, int k, int i) {
-    void*& w = c->bank[k].ftw[i];
-    if (!dev_alloc(w, (size_t)c->cfg.max_batch * c->cfg.ndev * 6 * c->esz)) {
+    DevBuf<void>& w = c->bank[k].ftw[i];
+    if (!got(w.ensure((size_t)c->cfg.max_batch * c->cfg.ndev * 6 * c->esz))) {
         fail(c, IRLOSC_ERR_HIP, "out of device memory for the wrench of the sensor feed");
         return nullptr;
     }
@@ -1991,12 +1913,7 @@ extern "C" int irlosc_set_sensordata(irlosc_ctx* c, int32_t slot, int32_t B, con
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t Bm = (size_t)c->cfg.max_batch, ns = (size_t)c->ft_n_sensor;
     s.end_feed();      // (none until the new one is in the buffer)
-    if (s.sens_cols < (int)ns) {
-        if (s.sens) HIPCHK(c, hipFree(s.sens));
-        s.sens = nullptr; s.sens_cols = 0;
-        HIPCHK(c, hipMalloc((void**)&s.sens, Bm * ns * sizeof(double)));
-        s.sens_cols = (int)ns;
-    }
+    HIPCHK(c, s.sens.reserve(Bm * ns * sizeof(double)));
     HIPCHK(c, hipMemcpyAsync(s.sens, sensordata, (size_t)B * ns * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.feed = B;
@@ -2018,9 +1935,9 @@ extern "C" int irlosc_step_from_q_device(irlosc_ctx* c, int32_t slot, int32_t B,
     const hipStream_t st = hip_stream ? (hipStream_t)hip_stream : c->stream;
     const bool fused = fused_ready(c, 1);      // (first call: allocates bank 0's exchange buffer / lane records on the context's stream)
     Slot& s = c->slot[slot];
-    if (fused) HIPCHK(c, ensure_qt(c, s));
+    if (fused) HIPCHK(c, s.qt.ensure(qt_bytes(c)));
     if (st != c->stream) {                     // ... and whatever else the context's stream holds comes first
-        if (!c->ev_dev) HIPCHK(c, hipEventCreateWithFlags(&c->ev_dev, hipEventDisableTiming));
+        HIPCHK(c, c->ev_dev.ensure(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(c->ev_dev, c->stream));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_dev, 0));
     }
@@ -2081,7 +1998,7 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     constexpr size_t TRACE_BYTES = (size_t)256 << 20;
     const size_t max_sample = (size_t)c->cfg.max_batch * c->cfg.ndev * 7 * sizeof(double);
     const int cap = (int)std::max<size_t>(1, TRACE_BYTES / max_sample);
-    if (nsamples && !dev_alloc(c->dtrace, (size_t)cap * max_sample))
+    if (nsamples && !got(c->dtrace.ensure((size_t)cap * max_sample)))
         return fail(c, IRLOSC_ERR_HIP, "out of device memory for the EE trace (%zu bytes)", (size_t)cap * max_sample);
     HIPCHK(c, hipMemsetAsync(c->dflags_any, 0, (size_t)B * sizeof(uint32_t), c->stream));
     int filled = 0, sent = 0;      // samples written / copied to the host
@@ -2128,8 +2045,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     if (!fused_ready(c, 1))
         return fail(c, IRLOSC_ERR_STATE, "no rollout on this context: the exchange buffers of the fused path could not be allocated (the path "
                     "is switched off; steps from joint coordinates run through dense records)");
-    HIPCHK(c, ensure_qt(c, c->slot[slot]));
-    if (!dev_alloc(c->dflags_any, (size_t)c->cfg.max_batch * sizeof(uint32_t))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for flags_any");
+    HIPCHK(c, c->slot[slot].qt.ensure(qt_bytes(c)));
+    if (!got(c->dflags_any.ensure((size_t)c->cfg.max_batch * sizeof(uint32_t)))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for flags_any");
     rc = rollout_ticks(c, slot, B, ticks, trace_every, ee_trace_host);
     if (!rc && u_host) {
         const hipError_t e = hipMemcpyAsync(u_host, c->du, (size_t)B * c->cfg.n * c->esz, hipMemcpyDeviceToHost, c->stream);
@@ -2188,9 +2105,7 @@ extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, cons
                 tab[per_robot ? ((size_t)(b / 64) * nd * wmax * 3 + e) * 64 + b % 64 : e] = xyz[(size_t)b * nd * wmax * 3 + e];
             }
     const size_t bytes = tab.size() * sizeof(double), state = (size_t)nd * c->cfg.max_batch * sizeof(int32_t);
-    if (s.wp_table && s.wp_table_bytes < bytes) { (void)hipFree(s.wp_table); s.wp_table = nullptr; s.wp_table_bytes = 0; }
-    if (!s.wp_table && dev_alloc(s.wp_table, bytes)) s.wp_table_bytes = bytes;
-    if (!s.wp_table || !dev_alloc(s.wp_index, state) || !dev_alloc(s.wp_arrivals, state) || !dev_alloc(s.wp_last, state))
+    if (!got(s.wp_table.reserve(bytes)) || !got(s.wp_index.ensure(state)) || !got(s.wp_arrivals.ensure(state)) || !got(s.wp_last.ensure(state)))
         return fail(c, IRLOSC_ERR_HIP, "out of device memory for the waypoint paths of slot %d (%zu bytes)", slot, bytes + 3 * state);
     HIPCHK(c, hipMemcpyAsync(s.wp_table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream));
     const WaypointArgs a = waypoint_args(c, s, B, *w, wmax, B, nullptr, 0);
@@ -2251,14 +2166,8 @@ extern "C" int irlosc_tick(irlosc_ctx* c, int32_t B, const void* M, const void* 
                           wrench ? b * nd * 6 * e : 0, tgt_vel ? b * nd * 6 * e : 0};
     size_t off[8], total = 0;
     for (int i = 0; i < 8; ++i) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
-    if (total > c->tick_in_bytes) {
-        if (c->tick_hin) HIPCHK(c, hipHostFree(c->tick_hin));
-        if (c->tick_din) HIPCHK(c, hipFree(c->tick_din));
-        c->tick_hin = c->tick_din = nullptr; c->tick_in_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->tick_hin, total, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc(&c->tick_din, total));
-        c->tick_in_bytes = total;
-    }
+    HIPCHK(c, c->tick_hin.reserve(total));
+    HIPCHK(c, c->tick_din.reserve(total));
     // output block: u | flags | the two words of the symmetry probe (they ride back in the one copy the tick makes anyway)
     const size_t ub = b * n * e, fl_off = (ub + 255) & ~(size_t)255, sym_off = (fl_off + b * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t out_total = sym_off + 2 * sizeof(int32_t);
@@ -2267,19 +2176,13 @@ extern "C" int irlosc_tick(irlosc_ctx* c, int32_t B, const void* M, const void* 
         int rch = symmetry_host(c, M, B);
         if (rch) return rch;
     }
-    if (out_total > c->tick_out_bytes) {
-        if (c->tick_hout) HIPCHK(c, hipHostFree(c->tick_hout));
-        if (c->tick_dout) HIPCHK(c, hipFree(c->tick_dout));
-        c->tick_hout = c->tick_dout = nullptr; c->tick_out_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->tick_hout, out_total, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc(&c->tick_dout, out_total));
-        c->tick_out_bytes = out_total;
-    }
-    unsigned char* hin = (unsigned char*)c->tick_hin;
-    unsigned char* din = (unsigned char*)c->tick_din;
+    HIPCHK(c, c->tick_hout.reserve(out_total));
+    HIPCHK(c, c->tick_dout.reserve(out_total));
+    unsigned char* hin = c->tick_hin;
+    unsigned char* din = c->tick_din;
     for (int i = 0; i < 8; ++i) if (sz[i]) memcpy(hin + off[i], src[i], sz[i]);
     HIPCHK(c, hipMemcpyAsync(din, hin, total, hipMemcpyHostToDevice, c->stream));
-    unsigned char* dout = (unsigned char*)c->tick_dout;
+    unsigned char* dout = c->tick_dout;
     uint32_t* dfl = (uint32_t*)(dout + fl_off);
     if (sym_dev) {
         int rcs = symmetry_probe(c, din + off[0], B, (int32_t*)(dout + sym_off), c->stream);
@@ -2288,14 +2191,15 @@ extern "C" int irlosc_tick(irlosc_ctx* c, int32_t B, const void* M, const void* 
     int rc = launch(c, B, StepInputs{din + off[0], din + off[1], din + off[2], sz[3] ? din + off[3] : nullptr, din + off[4], din + off[5],
                                      sz[7] ? din + off[7] : nullptr, sz[6] ? din + off[6] : nullptr}, dout, dfl, c->stream);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->tick_hout, dout, out_total, hipMemcpyDeviceToHost, c->stream));
+    unsigned char* hout = c->tick_hout;
+    HIPCHK(c, hipMemcpyAsync(hout, dout, out_total, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (sym_dev) {                                      // nothing is handed out for an asymmetric M
-        int rcs = symmetry_verdict(c, (const int32_t*)((unsigned char*)c->tick_hout + sym_off));
+        int rcs = symmetry_verdict(c, (const int32_t*)(hout + sym_off));
         if (rcs) return rcs;
     }
-    memcpy(u_host, c->tick_hout, ub);
-    if (flags_host) memcpy(flags_host, (unsigned char*)c->tick_hout + fl_off, b * sizeof(uint32_t));
+    memcpy(u_host, hout, ub);
+    if (flags_host) memcpy(flags_host, hout + fl_off, b * sizeof(uint32_t));
     return IRLOSC_OK;
 }
 
@@ -2347,8 +2251,8 @@ int rccl_load() {
 struct irlosc_comm {
     int device = 0, rank = 0, world = 1;
     ncclComm_t comm = nullptr;
-    hipStream_t stream = nullptr;
-    double* dbuf = nullptr;          // 2 doubles in, 2 doubles out, then `world` uint64 for the all-gather
+    Stream stream;
+    DevBuf<double> dbuf;             // 2 doubles in, 2 doubles out, then `world` uint64 for the all-gather
     std::string err;
 };
 
@@ -2400,8 +2304,8 @@ extern "C" int irlosc_comm_create(int32_t hip_device, int32_t rank, int32_t worl
     cm->device = hip_device; cm->rank = rank; cm->world = world;
     auto body = [&]() -> int {
         COMMCHK(cm, hipSetDevice(hip_device));
-        COMMCHK(cm, hipStreamCreateWithFlags(&cm->stream, hipStreamNonBlocking));
-        COMMCHK(cm, hipMalloc((void**)&cm->dbuf, (4 + (size_t)world + 1) * sizeof(double)));
+        COMMCHK(cm, cm->stream.ensure());
+        COMMCHK(cm, cm->dbuf.ensure((4 + (size_t)world + 1) * sizeof(double)));
         ncclUniqueId uid;
         memcpy(&uid, id, sizeof uid);
         NCCLCHK(cm, g_rccl.CommInitRank(&cm->comm, world, uid, rank));
@@ -2418,9 +2322,7 @@ extern "C" void irlosc_comm_destroy(irlosc_comm* cm) {
     (void)hipSetDevice(cm->device);
     if (cm->stream) (void)hipStreamSynchronize(cm->stream);
     if (cm->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(cm->comm);
-    if (cm->dbuf) (void)hipFree(cm->dbuf);
-    if (cm->stream) (void)hipStreamDestroy(cm->stream);
-    delete cm;
+    delete cm;      // (the buffer, then the stream)
 }
 
 extern "C" int irlosc_bench_allreduce(irlosc_comm* cm, double* steps_sum, double* elapsed_max) {
