@@ -506,6 +506,67 @@ IRLOSC_API int irlosc_set_waypoints(irlosc_ctx* ctx, int32_t slot, int32_t B, co
 IRLOSC_API int irlosc_download_waypoint_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* index, uint32_t* arrivals,
                                               int32_t* last_tick);
 
+/* ---- the WP / GRIP action list on the GPU: the insertion demo's fleet loop inside a rollout (csrc/osc_action.hpp) -----------------
+ * What action_sequence.py::FleetActionSequenceRunner.tick + after_step do on the host per tick, as one more small kernel of a rollout
+ * tick, between the walk (and the sensor feed's wrench) and the first OSC kernel: the target and gain changes it makes are seen by
+ * THIS tick's OSC step.  after_step -- the judgement of the state a plant step produced -- is the start of the FOLLOWING tick, because
+ * only the next walk has that state's EE pose.  Robot b on tick t since irlosc_set_action_list (a = its action, A = n_actions):
+ *   1. t > 0 and a < A:  err = 2-norm of calc_error(ee[active_dev], tgt[b][active_dev] as stored) (osc.py:101-118, all six entries,
+ *                        float64);  WP: err <= max_error[a] -> a += 1 (a NaN never advances);  GRIP: grip_left -= 1, <= 0 -> a += 1;
+ *                        a == A: finished_tick = t
+ *   2. t == 0:           start_xyz = EE xyz of active_dev
+ *   3. a < A, not yet entered:  gripper_force = gripper_force[a];
+ *                        WP:   tgt[b][passive_dev] = its EE xyz, with its EE quaternion (passive_hold_orientation) or passive_quat;
+ *                              tgt[b][active_dev] = pose[b][a], xyz replaced by start_xyz where xyz_from_start[a];  err = +inf
+ *                        GRIP: grip_left = grip_ticks[a]; targets stay
+ *   4. a < A and WP:     max_vel0 = max(min_speed[a], min(max_speed[a], kp[a] * err)) into word 9 (max_vel0) of active_dev's gain record
+ *                        of robot b, in the SLOT'S OWN gain copy [B][ndev][IRLOSC_GAIN_WORDS] (made from the context's gains by
+ *                        irlosc_set_action_list; the context's gains are never written, other slots and entry points see no change).
+ *                        max_vel0 persists through GRIP actions and after the list ends.
+ * A robot that has finished holds its last targets and gains.  NOT APPLIED: gripper_force is state only, as in
+ * FleetActionSequenceRunner -- the plant is untouched and no gripper joint is driven. */
+#define IRLOSC_MAX_ACTIONS 32
+#define IRLOSC_ACTION_WP   0
+#define IRLOSC_ACTION_GRIP 1
+typedef struct irlosc_action_list {
+    int32_t n_actions;                        /* A in [1, IRLOSC_MAX_ACTIONS] */
+    int32_t active_dev;                       /* device index (targets order) of the arm that runs the list */
+    int32_t passive_dev;                      /* the other arm, or -1: none, nothing of it is written */
+    int32_t passive_hold_orientation;         /* 1: a WP gives the passive arm its own EE quaternion; 0: passive_quat */
+    double passive_quat[4];                   /* w x y z, finite */
+    int32_t nb;                               /* 1 = one pose table for the fleet, B = a table per robot */
+    int32_t kind[IRLOSC_MAX_ACTIONS];         /* IRLOSC_ACTION_WP / IRLOSC_ACTION_GRIP */
+    int32_t xyz_from_start[IRLOSC_MAX_ACTIONS];   /* WP: 1 = target xyz is the active EE position of tick 0 ('start_pos') */
+    int32_t grip_ticks[IRLOSC_MAX_ACTIONS];   /* GRIP: >= 1 */
+    double kp[IRLOSC_MAX_ACTIONS];            /* WP: finite */
+    double max_error[IRLOSC_MAX_ACTIONS];     /* WP: finite */
+    double min_speed[IRLOSC_MAX_ACTIONS];     /* WP: finite, <= max_speed */
+    double max_speed[IRLOSC_MAX_ACTIONS];
+    double gripper_force[IRLOSC_MAX_ACTIONS]; /* finite; state only */
+} irlosc_action_list;
+/* Gives slot `slot`'s B robots the list: pose[nb][A][7] double (x y z qw qx qy qz; rows of GRIP actions are not read).  Every argument
+ * is checked before anything is touched (IRLOSC_ERR_ARG: n_actions outside [1, 32], a kind that is neither, device indices outside
+ * [0, ndev) or equal, hold flag / xyz_from_start not 0 / 1, nb not 1 or B, B < 1, a value that is not finite, min_speed > max_speed,
+ * grip_ticks < 1, pose NULL; the list in force stays, whole -- as it does when the call answers IRLOSC_ERR_STATE).  After
+ * irlosc_set_model, irlosc_set_gains and irlosc_set_targets for at least B robots on the slot (IRLOSC_ERR_STATE otherwise; also when
+ * the list has a WP and the gains in force have has_max_vel == 0 for active_dev: the limit would be ignored).  On success the slot
+ * has its gain copy (the context's gains broadcast or copied, null_kv with them) and the state is reset: action 0, nothing entered,
+ * err +inf, max_vel0 0, gripper_force 0, finished_tick -1, tick base 0.  desc == NULL clears the list (targets stay as they are).
+ * irlosc_set_gains, irlosc_set_targets on the slot, irlosc_set_waypoints on the slot and irlosc_set_model clear it too, and setting a
+ * list clears the slot's waypoint paths: targets are written by one entry point at a time.  Uploads of coordinates, records and
+ * sensor feeds leave it alone.  Only irlosc_rollout_from_q runs the list (on at most the B robots given here: IRLOSC_ERR_STATE
+ * beyond), with the slot's gain copy in place of the context's gains; every other step ignores both.  Buffers are allocated by the
+ * first use.  IRLOSC_ERR_HIP -- an allocation, a copy or the init launch failed -- is the one error that does NOT keep the list in
+ * force: the slot is left WITHOUT a list (its rollouts read the context's gains again; its targets stay as the earlier list last
+ * wrote them).  Synchronous. */
+IRLOSC_API int irlosc_set_action_list(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_action_list* desc, const double* pose);
+/* action, grip_left, finished_tick: int32 [B]; err, max_vel0, gripper_force: double [B]; any may be NULL.  THE STATE IS AS OF THE START
+ * OF THE LAST TICK RUN: the judgement of the state the last plant step produced happens on the next tick (a robot whose last step
+ * brought it within max_error still reports its WP, and finished_tick is the tick that found it done).  finished_tick: -1 until done.
+ * IRLOSC_ERR_STATE on a slot without a list, or with a list for fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_action_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* action, int32_t* grip_left, double* err,
+                                            double* max_vel0, double* gripper_force, int32_t* finished_tick);
+
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard
  * and NOTHING is exchanged per tick.  RCCL (over xGMI) is used once per benchmark: sum of the steps done, max of the

@@ -10,6 +10,8 @@ LIB_PATH = os.environ.get("IRLOSC_LIB", os.path.join(_HERE, "libirlosc.so"))   #
 
 MAX_DEV, MAX_N, MAX_K, GAIN_WORDS, MAX_BODIES = 4, 32, 16, 12, 64
 MAX_WAYPOINTS = 64
+MAX_ACTIONS = 32
+ACTION_WP, ACTION_GRIP = 0, 1
 F32, F64 = 0, 1
 USE_G, ADMITTANCE, NULLSPACE = 1, 2, 4
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_ROW16 = 0, 1, 3      # (2: the fp32-arithmetic kernel removed in ABI version 3)
@@ -27,7 +29,7 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_step_from_q", "irlosc_from_q_name", "irlosc_slot_structure", "irlosc_probe_structure", "irlosc_time_trains", "irlosc_giveup_counts",
            "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device",
            "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q",
-           "irlosc_set_waypoints", "irlosc_download_waypoint_state"]
+           "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -72,6 +74,15 @@ class Plant(C.Structure):
 class Waypoints(C.Structure):
     """struct irlosc_waypoints (include/irlosc.h): the waypoint paths of irlosc_set_waypoints."""
     _fields_ = [("count", C.c_int32 * MAX_DEV), ("threshold", C.c_double * MAX_DEV), ("loop", C.c_uint8 * MAX_DEV), ("nb", C.c_int32)]
+
+
+class ActionList(C.Structure):
+    """struct irlosc_action_list (include/irlosc.h): the WP / GRIP action list of irlosc_set_action_list."""
+    _fields_ = [("n_actions", C.c_int32), ("active_dev", C.c_int32), ("passive_dev", C.c_int32), ("passive_hold_orientation", C.c_int32),
+                ("passive_quat", C.c_double * 4), ("nb", C.c_int32),
+                ("kind", C.c_int32 * MAX_ACTIONS), ("xyz_from_start", C.c_int32 * MAX_ACTIONS), ("grip_ticks", C.c_int32 * MAX_ACTIONS),
+                ("kp", C.c_double * MAX_ACTIONS), ("max_error", C.c_double * MAX_ACTIONS), ("min_speed", C.c_double * MAX_ACTIONS),
+                ("max_speed", C.c_double * MAX_ACTIONS), ("gripper_force", C.c_double * MAX_ACTIONS)]
 
 
 class Cfg(C.Structure):
@@ -149,6 +160,8 @@ def load():
     lib.irlosc_download_q.argtypes = [vp, i32, i32, vp, vp]
     lib.irlosc_set_waypoints.argtypes = [vp, i32, i32, C.POINTER(Waypoints), vp]
     lib.irlosc_download_waypoint_state.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.irlosc_set_action_list.argtypes = [vp, i32, i32, C.POINTER(ActionList), vp]
+    lib.irlosc_download_action_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

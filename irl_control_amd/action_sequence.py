@@ -174,6 +174,34 @@ def _calc_error_batch(ee_pose, tgt_pose):
     return e
 
 
+def waypoint_target(obj, params, start_xyz):
+    """Target pose (x y z qw qx qy qz) of a WP action for one robot: `obj` its action objects ({name: {"pos", "quat", offsets,
+    "grip_yaw"}}), `start_xyz` the active arm's EE position at the start of the list ('start_pos').  The rule of
+    insertion_task.py:228-262 on object poses that are given instead of read from a simulator."""
+    offset = params.get("offset", [0.0, 0.0, 0.0])
+    txyz = params["target_xyz"]
+    if isinstance(txyz, str):
+        if txyz == "start_pos":
+            xyz = start_xyz
+        else:
+            o = obj[txyz]
+            xyz = np.asarray(o["pos"]) + np.asarray(o[offset] if isinstance(offset, str) else offset)
+    else:
+        xyz = np.asarray(txyz, dtype=np.float64) + np.asarray(offset, dtype=np.float64)
+    if "target_abg" in params:
+        tabg = params["target_abg"]
+        if isinstance(tabg, str):
+            o = obj[tabg]
+            grip_eul = DEFAULT_EE_ROT + [0, 0, np.deg2rad(o["grip_yaw"])]
+            R = quat2mat(o["quat"]) @ euler2mat(*grip_eul)
+            quat = euler2quat(*mat2euler(R))
+        else:
+            quat = euler2quat(*np.deg2rad(tabg))
+    else:
+        quat = DEFAULT_EE_QUAT
+    return np.concatenate([xyz, quat])
+
+
 class FleetActionSequenceRunner:
     """B robots run the SAME WP / GRIP action list, each on its own action objects (randomised poses), in lockstep on the
     batched controller: per tick one `BatchedOSC` step from joint coordinates (rigid-body front end on the GPU) with
@@ -215,29 +243,7 @@ class FleetActionSequenceRunner:
         self.ticks = 0
 
     def _waypoint_target(self, b, params, ee_pose_b):
-        obj = self.objects[b]
-        offset = params.get("offset", [0.0, 0.0, 0.0])
-        txyz = params["target_xyz"]
-        if isinstance(txyz, str):
-            if txyz == "start_pos":
-                xyz = self.start_pos[b]
-            else:
-                o = obj[txyz]
-                xyz = np.asarray(o["pos"]) + np.asarray(o[offset] if isinstance(offset, str) else offset)
-        else:
-            xyz = np.asarray(txyz, dtype=np.float64) + np.asarray(offset, dtype=np.float64)
-        if "target_abg" in params:
-            tabg = params["target_abg"]
-            if isinstance(tabg, str):
-                o = obj[tabg]
-                grip_eul = DEFAULT_EE_ROT + [0, 0, np.deg2rad(o["grip_yaw"])]
-                R = quat2mat(o["quat"]) @ euler2mat(*grip_eul)
-                quat = euler2quat(*mat2euler(R))
-            else:
-                quat = euler2quat(*np.deg2rad(tabg))
-        else:
-            quat = DEFAULT_EE_QUAT
-        return np.concatenate([xyz, quat])
+        return waypoint_target(self.objects[b], params, self.start_pos[b])
 
     def done(self):
         return self.action >= len(self.seq)
@@ -296,3 +302,94 @@ class FleetActionSequenceRunner:
                 self.grip_left[b] -= 1
                 if self.grip_left[b] <= 0:
                     self.action[b] += 1
+
+
+# ---- the same list as data: what BatchedOSC.set_action_list hands to the GPU (include/irlosc.h, csrc/osc_action.hpp) -----------
+def compile_action_list(sequence: List[Dict], objects: List[Dict], active_dev: int, passive_dev: int = -1, tick_seconds: float = 0.001,
+                        passive_hold_orientation: bool = False, passive_quat=None) -> Dict:
+    """The WP / GRIP list of FleetActionSequenceRunner as arrays: defaults from DEFAULT_PARAMS, per robot the pose table of its WP
+    actions (waypoint_target on its action objects; 'start_pos' becomes the flag xyz_from_start, its xyz is taken on tick 0), and
+    grip_ticks = max(1, round(gripper_duration / tick_seconds)).  -> the `desc` of action_list_tick / set_action_list."""
+    seq = [ActionSequenceRunner._with_defaults(copy.deepcopy(e), Action.WP if e["action"] == "WP" else Action.GRIP) for e in sequence]
+    A, B = len(seq), len(objects)
+    d = dict(n_actions=A, active_dev=int(active_dev), passive_dev=int(passive_dev), passive_hold_orientation=int(bool(passive_hold_orientation)),
+             passive_quat=np.asarray(DEFAULT_EE_QUAT if passive_quat is None else passive_quat, dtype=np.float64),
+             kind=np.zeros(A, np.int32), xyz_from_start=np.zeros(A, np.int32), grip_ticks=np.ones(A, np.int32),
+             kp=np.zeros(A), max_error=np.zeros(A), min_speed=np.zeros(A), max_speed=np.zeros(A), gripper_force=np.zeros(A),
+             pose=np.zeros((B, A, 7)))
+    d["pose"][:, :, 3] = 1.0                                          # (rows of GRIP actions are not read)
+    for a, p in enumerate(seq):
+        d["gripper_force"][a] = p["gripper_force"]
+        if p["action"] == "WP":
+            d["kind"][a] = Action.WP.value
+            d["xyz_from_start"][a] = int(isinstance(p["target_xyz"], str) and p["target_xyz"] == "start_pos")
+            d["kp"][a], d["max_error"][a] = p["kp"], p["max_error"]
+            d["min_speed"][a], d["max_speed"][a] = p["min_speed_xyz"], p["max_speed_xyz"]
+            for b in range(B):
+                d["pose"][b, a] = waypoint_target(objects[b], p, np.zeros(3))
+        else:
+            d["kind"][a] = Action.GRIP.value
+            d["grip_ticks"][a] = max(1, int(round(p["gripper_duration"] / tick_seconds)))
+    return d
+
+
+def action_list_state(B: int) -> Dict:
+    """The per-robot state of an action list as irlosc_set_action_list resets it."""
+    return dict(action=np.zeros(B, np.int32), entered=np.full(B, -1, np.int32), grip_left=np.zeros(B, np.int32),
+                err=np.full(B, np.inf), max_vel0=np.zeros(B), gripper_force=np.zeros(B), finished_tick=np.full(B, -1, np.int32),
+                start_xyz=np.zeros((B, 3)))
+
+
+def action_list_tick(state: Dict, ee, tgt, gains, desc: Dict, t: int):
+    """One tick of the action-list kernel (csrc/osc_action.hpp) in NumPy, in place: its four steps on rollout tick `t` of the list,
+    i.e. FleetActionSequenceRunner.after_step of the PREVIOUS tick (judged on `ee`, the EE poses of the state that tick's step
+    produced) followed by the bookkeeping of FleetActionSequenceRunner.tick.
+      state  action_list_state(B), advanced in place
+      ee     [B, ndev, 7] EE poses at the start of tick t
+      tgt    [B, ndev, 7] targets as stored (any float dtype; entered WP actions write it, values rounded to its dtype)
+      gains  [B, ndev, GAIN_WORDS] gain records as stored, or None: word 9 (max_vel0) of the active device is written
+      desc   compile_action_list(...)"""
+    A, ia, io = desc["n_actions"], desc["active_dev"], desc["passive_dev"]
+    ee = np.asarray(ee, dtype=np.float64)
+    B = len(ee)
+    st = state
+    if t > 0:
+        live = st["action"] < A
+        e = np.linalg.norm(_calc_error_batch(ee[:, ia], np.asarray(tgt[:, ia], dtype=np.float64)), axis=1)
+        for b in np.nonzero(live)[0]:
+            a = st["action"][b]
+            st["err"][b] = e[b]
+            if desc["kind"][a] == Action.WP.value:
+                nxt = st["err"][b] <= desc["max_error"][a]
+            else:
+                st["grip_left"][b] -= 1
+                nxt = st["grip_left"][b] <= 0
+            if nxt:
+                st["action"][b] += 1
+                if st["action"][b] == A:
+                    st["finished_tick"][b] = t
+    if t == 0:
+        st["start_xyz"][:] = ee[:, ia, :3]
+    pose = desc["pose"]
+    for b in range(B):
+        a = st["action"][b]
+        if a >= A:
+            continue
+        if st["entered"][b] != a:
+            st["entered"][b] = a
+            st["gripper_force"][b] = desc["gripper_force"][a]
+            if desc["kind"][a] == Action.WP.value:
+                if io >= 0:
+                    tgt[b, io, :3] = ee[b, io, :3]
+                    tgt[b, io, 3:] = ee[b, io, 3:] if desc["passive_hold_orientation"] else desc["passive_quat"]
+                tgt[b, ia] = pose[b if len(pose) > 1 else 0, a]
+                if desc["xyz_from_start"][a]:
+                    tgt[b, ia, :3] = st["start_xyz"][b]
+                st["err"][b] = np.inf
+            else:
+                st["grip_left"][b] = desc["grip_ticks"][a]
+        if desc["kind"][a] == Action.WP.value:
+            st["max_vel0"][b] = max(desc["min_speed"][a], min(desc["max_speed"][a], desc["kp"][a] * st["err"][b]))
+            if gains is not None:
+                gains[b, ia, 9] = st["max_vel0"][b]
+    return state

@@ -391,6 +391,60 @@ class BatchedOSC:
         self._chk(self.lib.irlosc_download_waypoint_state(self._h, slot, B, _lib.ptr(idx), _lib.ptr(arr), _lib.ptr(last)))
         return dict(index=idx, arrivals=arr, last_tick=last)
 
+    # -- the WP / GRIP action list of the rollout (irlosc_set_action_list / irlosc_download_action_state) ---------------------------
+    def set_action_list(self, sequence, objects=None, active_arm: str = "right", tick_seconds: float = 0.001,
+                        passive_hold_orientation: bool = False, slot: int = 0, passive_arm="auto"):
+        """The WP / GRIP list of action_sequence.FleetActionSequenceRunner for the slot's robots, run on the GPU by `rollout`: per
+        tick the active arm's error is judged, actions advance, an entered WP writes the slot's targets and the error-adaptive velocity
+        limit goes into the slot's own copy of the gains -- no host in between.  `sequence`: the list of action dicts (defaults from
+        action_sequence.DEFAULT_PARAMS), or a dict from action_sequence.compile_action_list; `objects`: per robot its action objects
+        (one entry: shared by the fleet).  `passive_arm`: "auto" = the other UR5 when the layout has it, None = no passive arm.
+        After set_model, set_gains and set_targets; resets the state.  sequence=None clears the list, as set_gains, set_targets,
+        set_waypoints and set_model do.  gripper_force is state only: no gripper joint is driven."""
+        from . import action_sequence as aseq
+        B = self._B[slot]
+        if sequence is None:
+            self._chk(self.lib.irlosc_set_action_list(self._h, slot, B, None, None))
+            return
+        if isinstance(sequence, dict):
+            d = sequence
+        else:
+            names = list(self.layout.dev_names)
+            arm = "ur5right" if active_arm == "right" else "ur5left"
+            other = "ur5left" if active_arm == "right" else "ur5right"
+            if passive_arm == "auto":
+                passive_arm = other if other in names else None
+            d = aseq.compile_action_list(sequence, objects if objects is not None else [{}], names.index(arm),
+                                         names.index(passive_arm) if passive_arm is not None else -1, tick_seconds, passive_hold_orientation)
+        A = int(d["n_actions"])
+        if not 1 <= A <= _lib.MAX_ACTIONS:
+            raise ValueError(f"an action list holds 1 to {_lib.MAX_ACTIONS} actions, got {A}")
+        pose = np.ascontiguousarray(d["pose"], dtype=np.float64)
+        if pose.ndim != 3 or pose.shape[1:] != (A, 7) or pose.shape[0] not in (1, B):
+            raise ValueError(f"pose: expected shape (1 or {B}, {A}, 7), got {pose.shape}")
+        desc = _lib.ActionList()
+        desc.n_actions, desc.active_dev, desc.passive_dev = A, int(d["active_dev"]), int(d["passive_dev"])
+        desc.passive_hold_orientation, desc.nb = int(d["passive_hold_orientation"]), pose.shape[0]
+        for i in range(4):
+            desc.passive_quat[i] = float(d["passive_quat"][i])
+        for a in range(A):
+            desc.kind[a], desc.xyz_from_start[a], desc.grip_ticks[a] = int(d["kind"][a]), int(d["xyz_from_start"][a]), int(d["grip_ticks"][a])
+            desc.kp[a], desc.max_error[a] = float(d["kp"][a]), float(d["max_error"][a])
+            desc.min_speed[a], desc.max_speed[a] = float(d["min_speed"][a]), float(d["max_speed"][a])
+            desc.gripper_force[a] = float(d["gripper_force"][a])
+        self._chk(self.lib.irlosc_set_action_list(self._h, slot, B, C.byref(desc), _lib.ptr(pose)))
+
+    def action_state(self, slot: int = 0):
+        """-> dict(action, grip_left, err, max_vel0, gripper_force, finished_tick), each [B]: where every robot stands in the slot's
+        action list AS OF THE START OF THE LAST TICK RUN (the state the last plant step produced is judged by the next tick);
+        action == number of actions: finished, on tick finished_tick (-1 until then).  (irlosc_download_action_state)"""
+        B = self._B[slot]
+        out = dict(action=np.empty(B, np.int32), grip_left=np.empty(B, np.int32), err=np.empty(B), max_vel0=np.empty(B),
+                   gripper_force=np.empty(B), finished_tick=np.empty(B, np.int32))
+        self._chk(self.lib.irlosc_download_action_state(self._h, slot, B, *[_lib.ptr(out[k]) for k in
+                                                                             ("action", "grip_left", "err", "max_vel0", "gripper_force", "finished_tick")]))
+        return out
+
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""
         B = self._B[first_slot] if B is None else B

@@ -26,6 +26,7 @@
 #include "osc_pack.hpp"
 #include "osc_plant.hpp"
 #include "osc_waypoint.hpp"
+#include "osc_action.hpp"
 #include "launchers.hpp"
 #include "dev_mem.hpp"
 
@@ -72,6 +73,16 @@ struct Slot {
     int wp_max = 0;
     int waypoints = 0;         // robots with paths (0 = none: a rollout tick launches no cycler)
     int wp_tick = 0;           // rollout ticks since irlosc_set_waypoints
+    // action list of the rollout (irlosc_set_action_list): per-robot state SoA over max_batch robots -- al_i: action, entered, grip_left,
+    // finished_tick; al_d: err, max_vel0, gripper_force, start_xyz[3] --, the pose table ([walk wave][A][7][64] per robot, [A][7] shared),
+    // the slot's own gains [actions][ndev][12] and null_kv [actions] in the context's dtype (the steps of its rollout read these per
+    // instance), allocated by the first use; the description in force
+    DevBuf<int32_t> al_i;
+    DevBuf<double> al_d, al_table;
+    DevBuf<void> al_gains, al_nullkv;
+    irlosc_action_list al{};
+    int actions = 0;           // robots with the list (0 = none: a rollout tick launches no action kernel and reads the context's gains)
+    int al_tick = 0;           // rollout ticks since irlosc_set_action_list
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -101,6 +112,14 @@ struct Slot {
     // The cycler ran behind a tick of a rollout.  (Marked once the whole tick is enqueued: if a launch behind the cycler fails, the
     // device state is one tick ahead of wp_tick -- on a context whose stream has already failed, where the rollout's result is void anyway.)
     void ticked() { ++wp_tick; }
+    // The action list of B robots is in the slot, its state reset by the kernel's init launch and its gain copy made.  A list and
+    // waypoint paths exclude each other: the list writes the targets from here on.
+    void listed(int B, const irlosc_action_list& d) { unpathed(); actions = B; al = d; al_tick = 0; }
+    // The list ends: cleared by the caller, the targets or the gains were written by their own entry points, paths took the targets
+    // over, the model changed, or its buffers failed.
+    void unlisted() { actions = 0; al_tick = 0; }
+    // The action kernel ran in a tick of a rollout (marked once the whole tick is enqueued, like ticked()).
+    void acted() { ++al_tick; }
     // pack_slot built the block of B robots from records it found eligible (lane_eligible: the tree verdict, so records > 0).
     void block_packed(int B) { packed = B; }
 };
@@ -482,6 +501,7 @@ extern "C" int irlosc_set_gains(irlosc_ctx* c, const double* gains, const double
     HIPCHK(c, hipMemcpyAsync(c->dnullkv, b.data(), b.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->gains_nb = nb;
+    for (Slot& s : c->slot) s.unlisted();      // their gain copies were made from the gains this call replaced
     return IRLOSC_OK;
 }
 
@@ -788,9 +808,10 @@ extern "C" int irlosc_set_targets(irlosc_ctx* c, int32_t slot, int32_t B, const 
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (B == 0) { s.targets = -1; s.unpathed(); return IRLOSC_OK; }
+    if (B == 0) { s.targets = -1; s.unpathed(); s.unlisted(); return IRLOSC_OK; }
     if (!tgt_pose) return fail(c, IRLOSC_ERR_ARG, "tgt_pose is NULL");
     s.unpathed();      // the targets are the caller's from here on: one entry point writes them at a time
+    s.unlisted();
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, nd = (size_t)c->cfg.ndev, e = c->esz;
     HIPCHK(c, hipMemcpyAsync(s.tgt, tgt_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
@@ -1471,7 +1492,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.unpathed(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.unpathed(); s.unlisted(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1638,10 +1659,38 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 // irlosc_rollout_from_q: the plant kernel behind the step (one step on bank 0), handed to the next train like the timing events
 // (irlosc_ctx::plant_next); trace: the device sample of this tick's EE poses, or nullptr
 // wp_tick: >= 0: the slot has waypoint paths and its cycler runs between the give-up pass and the plant, as this tick; -1: none
+// al_tick: >= 0: the slot has an action list, whose kernel runs between the walk and the first OSC kernel, as this tick, and the step
+// reads the slot's gain copy per instance; -1: none
 struct PlantCall {
     double* trace;
     int wp_tick;
+    int al_tick;
 };
+
+// The arguments of the slot's action kernel over B robots (init: the launch of irlosc_set_action_list; else a tick on exchange block xside)
+static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_action_list& d, const double* xside, int tick) {
+    ActionArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    a.xside = xside; a.tgt = s.tgt; a.gains = s.al_gains;
+    a.action = s.al_i; a.entered = s.al_i + Bm; a.grip_left = s.al_i + 2 * Bm; a.finished_tick = s.al_i + 3 * Bm;
+    a.err = s.al_d; a.max_vel0 = s.al_d + Bm; a.gripper_force = s.al_d + 2 * Bm; a.start_xyz = s.al_d + 3 * Bm;
+    a.table = s.al_table;
+    for (int i = 0; i < d.n_actions; ++i) {
+        a.kp[i] = d.kp[i]; a.max_error[i] = d.max_error[i]; a.min_speed[i] = d.min_speed[i]; a.max_speed[i] = d.max_speed[i];
+        a.force[i] = d.gripper_force[i]; a.grip_ticks[i] = d.grip_ticks[i];
+        a.kind[i] = (uint8_t)d.kind[i]; a.xyz_from_start[i] = (uint8_t)d.xyz_from_start[i];
+    }
+    for (int i = 0; i < 4; ++i) a.passive_quat[i] = d.passive_quat[i];
+    for (int i = 0; i < 7 && xside; ++i) {
+        a.ee_act[i] = c->model.tables.eetab[d.active_dev][i];
+        a.ee_pas[i] = d.passive_dev >= 0 ? c->model.tables.eetab[d.passive_dev][i] : 0;
+    }
+    a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.A = d.n_actions; a.per_robot = d.nb > 1;
+    a.n_entries = (int32_t)c->model.fe_xentries; a.tick = tick; a.init = xside ? 0 : 1;
+    a.active = d.active_dev; a.passive = d.passive_dev; a.hold = d.passive_hold_orientation;
+    return a;
+}
 
 // The arguments of the slot's waypoint cycler over B robots (init: the launch of irlosc_set_waypoints; else a tick on exchange block xside)
 static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, int wmax, int stride, const double* xside, int tick) {
@@ -1717,6 +1766,10 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
         StepInputs in = slot_inputs(s, wr);
         if (dv) { in.tgt = dv->tgt; in.tvel = dv->tvel; in.wrench = wr; }
         fill_params<T>(c, tr.p[i], B, in, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
+        if (pl && pl->al_tick >= 0) {      // a tick of a slot with an action list: its own gains, which the action kernel writes per robot
+            tr.p[i].gains = (const T*)s.al_gains.get(); tr.p[i].null_kv = (const T*)s.al_nullkv.get();
+            tr.p[i].gains_per_instance = 1;
+        }
         tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], qvel, c->model.dtables, c->span_next};
         ga.out[i] = slot_out<T>(s);
         ga.list[i] = bk.list[i];
@@ -1741,6 +1794,10 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     HIPCHK(c, (hipError_t)fused_walk(c).launch(c->model.dmodel, ft, n, st));
     int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
     if (rcw) return rcw;
+    if (pl && pl->al_tick >= 0) {      // the action list: its targets and velocity limit are this tick's, so in front of every OSC kernel
+        const Slot& s = c->slot[slots[0]];
+        HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s, B, s.al, bk.xside[0], pl->al_tick), st));
+    }
     if (use_lane) {
         if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
         HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
@@ -1772,6 +1829,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
     if (pl) c->slot[slots[0]].advanced(B);
     if (pl && pl->wp_tick >= 0) c->slot[slots[0]].ticked();
+    if (pl && pl->al_tick >= 0) c->slot[slots[0]].acted();
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2005,7 +2063,8 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     for (int t = 0; t < ticks; ++t) {
         const bool traced = nsamples && t % every == 0;
         const Slot& s = c->slot[slot];
-        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr, s.waypoints > 0 ? s.wp_tick : -1};
+        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr, s.waypoints > 0 ? s.wp_tick : -1,
+                           s.actions > 0 ? s.al_tick : -1};
         c->plant_next = &pl;
         const int rc = fused_resident(c, slot, B, 1);
         c->plant_next = nullptr;
@@ -2040,6 +2099,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     if (rc) return rc;
     if (c->slot[slot].waypoints > 0 && B > c->slot[slot].waypoints)
         return fail(c, IRLOSC_ERR_STATE, "slot %d: its waypoint paths cover %d robots, rollout asked for %d", slot, c->slot[slot].waypoints, B);
+    if (c->slot[slot].actions > 0 && B > c->slot[slot].actions)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its action list covers %d robots, rollout asked for %d", slot, c->slot[slot].actions, B);
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (!fused_ready(c, 1))
@@ -2094,6 +2155,7 @@ extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, cons
                     std::max(0, s.targets), B);
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     s.unpathed();      // (none until the new ones are in their buffers)
+    s.unlisted();      // the paths write the targets from here on: an action list of the slot ends
     // the table in the kernel's layout: per robot [walk wave][dev][w][3][64] (idle lanes and unlisted entries zero), shared as given
     const bool per_robot = w->nb > 1;
     const size_t waves = ((size_t)B + 63) / 64;
@@ -2139,6 +2201,121 @@ extern "C" int irlosc_download_waypoint_state(irlosc_ctx* c, int32_t slot, int32
         for (int b = 0; b < B; ++b)
             for (int d = 0; d < nd; ++d) dst[i][(size_t)b * nd + d] = h[(size_t)d * s.waypoints + b];
     }
+    return IRLOSC_OK;
+}
+
+// ---- the WP / GRIP action list of the rollout (osc_action.hpp) ---------------------------------------------------------------
+extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_action_list* d, const double* pose) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.unlisted(); return IRLOSC_OK; }
+    const int nd = c->cfg.ndev, A = d->n_actions;
+    if (A < 1 || A > IRLOSC_MAX_ACTIONS) return fail(c, IRLOSC_ERR_ARG, "action list: n_actions=%d out of [1,%d]", A, IRLOSC_MAX_ACTIONS);
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "action list: B=%d must be >= 1", B);
+    if (d->nb != 1 && d->nb != B) return fail(c, IRLOSC_ERR_ARG, "action list: nb=%d must be 1 or B=%d", d->nb, B);
+    if (d->active_dev < 0 || d->active_dev >= nd) return fail(c, IRLOSC_ERR_ARG, "action list: active_dev=%d out of [0,%d)", d->active_dev, nd);
+    if (d->passive_dev < -1 || d->passive_dev >= nd || d->passive_dev == d->active_dev)
+        return fail(c, IRLOSC_ERR_ARG, "action list: passive_dev=%d must be -1 or a device in [0,%d) other than active_dev", d->passive_dev, nd);
+    if (d->passive_hold_orientation != 0 && d->passive_hold_orientation != 1)
+        return fail(c, IRLOSC_ERR_ARG, "action list: passive_hold_orientation=%d must be 0 or 1", d->passive_hold_orientation);
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(d->passive_quat[i])) return fail(c, IRLOSC_ERR_ARG, "action list: passive_quat[%d] is not finite", i);
+    if (!pose) return fail(c, IRLOSC_ERR_ARG, "action list: pose is NULL");
+    bool has_wp = false;
+    for (int i = 0; i < A; ++i) {
+        if (d->kind[i] != IRLOSC_ACTION_WP && d->kind[i] != IRLOSC_ACTION_GRIP)
+            return fail(c, IRLOSC_ERR_ARG, "action list: kind[%d]=%d is neither WP nor GRIP", i, d->kind[i]);
+        if (!std::isfinite(d->gripper_force[i])) return fail(c, IRLOSC_ERR_ARG, "action list: gripper_force[%d] is not finite", i);
+        if (d->kind[i] == IRLOSC_ACTION_GRIP) {
+            if (d->grip_ticks[i] < 1) return fail(c, IRLOSC_ERR_ARG, "action list: grip_ticks[%d]=%d must be >= 1", i, d->grip_ticks[i]);
+            continue;
+        }
+        has_wp = true;
+        if (d->xyz_from_start[i] != 0 && d->xyz_from_start[i] != 1)
+            return fail(c, IRLOSC_ERR_ARG, "action list: xyz_from_start[%d]=%d must be 0 or 1", i, d->xyz_from_start[i]);
+        if (!std::isfinite(d->kp[i]) || !std::isfinite(d->max_error[i]) || !std::isfinite(d->min_speed[i]) || !std::isfinite(d->max_speed[i]))
+            return fail(c, IRLOSC_ERR_ARG, "action list: kp / max_error / min_speed / max_speed of action %d must be finite", i);
+        if (d->min_speed[i] > d->max_speed[i])
+            return fail(c, IRLOSC_ERR_ARG, "action list: min_speed[%d]=%g exceeds max_speed=%g", i, d->min_speed[i], d->max_speed[i]);
+        for (int b = 0; b < d->nb; ++b)
+            for (int w = 0; w < 7; ++w)
+                if (!std::isfinite(pose[((size_t)b * A + i) * 7 + w]))
+                    return fail(c, IRLOSC_ERR_ARG, "action list: pose of action %d, robot %d is not finite", i, b);
+    }
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (c->gains_nb == 0) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_gains has not been called");
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, action list given for %d: irlosc_set_targets first", slot,
+                    std::max(0, s.targets), B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    // the gains in force, as stored: checked for the velocity limit the list sets, then broadcast or copied into the slot's own
+    const size_t e = c->esz, rec = (size_t)nd * IRLOSC_GAIN_WORDS * e, nbg = (size_t)c->gains_nb;
+    std::vector<unsigned char> g(nbg * rec), nk(nbg * e);
+    HIPCHK(c, hipMemcpyAsync(g.data(), c->dgains, g.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nk.data(), c->dnullkv, nk.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    auto word = [&](size_t b, int dev, int w) {
+        const unsigned char* p = g.data() + b * rec + ((size_t)dev * IRLOSC_GAIN_WORDS + w) * e;
+        double v; float f;
+        if (e == 8) memcpy(&v, p, 8); else { memcpy(&f, p, 4); v = f; }
+        return v;
+    };
+    for (size_t b = 0; has_wp && b < std::min(nbg, (size_t)B); ++b)
+        if (word(b, d->active_dev, 11) == 0.0)
+            return fail(c, IRLOSC_ERR_STATE, "action list: the gains in force have has_max_vel == 0 for device %d (robot %zu): the velocity limit "
+                        "a WP sets would be ignored", d->active_dev, b);
+    s.unlisted();      // (none until the new one is in its buffers)
+    std::vector<unsigned char> gs((size_t)B * rec), nks((size_t)B * e);
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        memcpy(gs.data() + b * rec, g.data() + (nbg > 1 ? b : 0) * rec, rec);
+        memcpy(nks.data() + b * e, nk.data() + (nbg > 1 ? b : 0) * e, e);
+    }
+    // the pose table in the kernel's layout: per robot [walk wave][A][7][64] (idle lanes zero), shared as given
+    const bool per_robot = d->nb > 1;
+    const size_t waves = ((size_t)B + 63) / 64, Bm = (size_t)c->cfg.max_batch;
+    std::vector<double> tab(per_robot ? waves * A * 7 * 64 : (size_t)A * 7, 0.0);
+    for (int b = 0; b < d->nb; ++b)
+        for (int i = 0; i < A * 7; ++i)
+            tab[per_robot ? ((size_t)(b / 64) * A * 7 + i) * 64 + b % 64 : (size_t)i] = pose[(size_t)b * A * 7 + i];
+    const size_t bytes = tab.size() * sizeof(double);
+    if (!got(s.al_table.reserve(bytes)) || !got(s.al_i.ensure(4 * Bm * sizeof(int32_t))) || !got(s.al_d.ensure(6 * Bm * sizeof(double))) ||
+        !got(s.al_gains.ensure(Bm * rec)) || !got(s.al_nullkv.ensure(Bm * e)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the action list of slot %d", slot);
+    hipError_t ec = hipMemcpyAsync(s.al_table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    if (ec == hipSuccess) ec = hipMemcpyAsync(s.al_gains, gs.data(), gs.size(), hipMemcpyHostToDevice, c->stream);
+    if (ec == hipSuccess) ec = hipMemcpyAsync(s.al_nullkv, nks.data(), nks.size(), hipMemcpyHostToDevice, c->stream);
+    if (ec == hipSuccess) {
+        const ActionArgs a = action_args(c, s, B, *d, nullptr, 0);
+        ec = (hipError_t)(c->cfg.dtype == IRLOSC_F64 ? launch_actions<double>(a, c->stream) : launch_actions<float>(a, c->stream));
+    }
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when a copy or the launch failed: the vectors are the copies' sources)
+    HIPCHK(c, ec);
+    HIPCHK(c, es);
+    s.listed(B, *d);
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_action_state(irlosc_ctx* c, int32_t slot, int32_t B, int32_t* action, int32_t* grip_left, double* err,
+                                            double* max_vel0, double* gripper_force, int32_t* finished_tick) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Slot& s = c->slot[slot];
+    if (s.actions <= 0) return fail(c, IRLOSC_ERR_STATE, "slot %d has no action list (irlosc_set_action_list)", slot);
+    if (B > s.actions) return fail(c, IRLOSC_ERR_STATE, "slot %d: its action list covers %d robots, asked for %d", slot, s.actions, B);
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    int32_t* di[3] = {action, grip_left, finished_tick};
+    const size_t oi[3] = {0, 2 * Bm, 3 * Bm};
+    for (int i = 0; i < 3; ++i)
+        if (di[i]) HIPCHK(c, hipMemcpyAsync(di[i], s.al_i + oi[i], (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    double* dd[3] = {err, max_vel0, gripper_force};
+    for (int i = 0; i < 3; ++i)
+        if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], s.al_d + i * Bm, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }
 

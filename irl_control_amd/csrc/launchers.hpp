@@ -94,6 +94,12 @@ struct WaypointArgs;
 template <typename T>
 int launch_waypoints(const WaypointArgs& a, hipStream_t st);
 
+// tu_action.hip -- the WP / GRIP action list between the walk and the first OSC kernel of a rollout tick whose slot has one
+// (osc_action.hpp); T = record type (of the targets and of the slot's gain copy)
+struct ActionArgs;
+template <typename T>
+int launch_actions(const ActionArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;

@@ -1,0 +1,164 @@
+// The ACTION LIST of a rollout (irlosc_set_action_list): per tick and robot the WP / GRIP state machine of the insertion demo's fleet
+// form (action_sequence.py::FleetActionSequenceRunner.tick + after_step) -- judge the active arm's task error on this tick's EE pose,
+// advance, write the targets of an action that is entered, and set the error-adaptive velocity limit of the active arm in the slot's
+// own gain copy -- so that the OSC step of the SAME tick aims at them without the host in between.  It runs between the walk (and the
+// sensor feed's wrench) and the first OSC kernel of the tick; after_step, which needs the EE pose of the state the plant produced, is
+// the start of the following tick: only the next walk has that pose.
+//
+// One lane per robot, one block per walk wave (its 64 robots), like the waypoint cycler.  The EE pose of the active and the passive
+// device is seven coalesced 512-byte loads each of the tick's exchange block; the target record tgt[B][ndev][7] goes through an LDS
+// tile in the record type and is stored back -- the whole tile, untouched words bit for bit -- only by a wave in which a lane entered
+// a WP.  Per-robot state is SoA [field][stride]; a per-robot pose table is [walk wave][A][7][64], a shared one [A][7].  Idle lanes of a
+// ragged last wave neither load nor store.  The error is float64 (task_error6<double>, the target words converted to double), its
+// norm and the limit with every product and sum rounded on its own: the host can repeat them.
+//
+// Per robot on tick t of the list (A actions; a = action):
+//   1. t > 0 and a < A:  err = |calc_error(ee[active], tgt[active] as stored)|_2;  WP: err <= max_error[a] -> a += 1 (a NaN never advances);
+//                        GRIP: grip_left -= 1, <= 0 -> a += 1;  a == A: finished_tick = t
+//   2. t == 0:           start_xyz = EE xyz of the active device
+//   3. a < A and entered != a:  entered = a, gripper_force = gripper_force[a];  WP: passive target = its EE xyz + (its EE quaternion |
+//                        passive_quat), active target = pose a (xyz = start_xyz where xyz_from_start[a]), err = +inf;
+//                        GRIP: grip_left = grip_ticks[a], targets stay
+//   4. a < A and WP:     max_vel0 = max(min_speed[a], min(max_speed[a], kp[a] * err)) -> word 9 of the active device's gain record
+// A robot that has finished holds its last targets and gains.
+//
+// init = 1 (irlosc_set_action_list): action 0, entered -1, grip_left 0, err +inf, max_vel0 0, gripper_force 0, finished_tick -1,
+// start_xyz 0; neither the exchange block nor the targets are read.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/irlosc.h"
+#include "osc_common.hpp"
+
+namespace irlosc {
+
+struct ActionArgs {
+    const double* xside;      // the tick's exchange block [walk wave][n_entries][64] (init: not read)
+    void* tgt;                // [B][ndev][7] targets of the slot, record type
+    void* gains;              // [B][ndev][IRLOSC_GAIN_WORDS] the slot's gain copy, record type: word 9 of the active device in place
+    int32_t* action;          // [stride] each
+    int32_t* entered;
+    int32_t* grip_left;
+    int32_t* finished_tick;
+    double* err;
+    double* max_vel0;
+    double* gripper_force;
+    double* start_xyz;        // [3][stride]
+    const double* table;      // per_robot: [walk wave][A][7][64], else [A][7]
+    double kp[IRLOSC_MAX_ACTIONS], max_error[IRLOSC_MAX_ACTIONS], min_speed[IRLOSC_MAX_ACTIONS], max_speed[IRLOSC_MAX_ACTIONS];
+    double force[IRLOSC_MAX_ACTIONS];
+    double passive_quat[4];
+    int32_t grip_ticks[IRLOSC_MAX_ACTIONS];
+    uint8_t kind[IRLOSC_MAX_ACTIONS], xyz_from_start[IRLOSC_MAX_ACTIONS];
+    int32_t ee_act[7], ee_pas[7];       // exchange entries of the active / passive device's x y z qw qx qy qz
+    int32_t B, ndev, stride, A, per_robot, n_entries, tick, init;
+    int32_t active, passive, hold;      // device indices (passive -1: none); hold: the passive arm keeps its EE orientation
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
+    __shared__ T s_t[64 * IRLOSC_MAX_DEV * 7];      // the wave's target tile
+    const int lane = threadIdx.x;
+    const int b0 = (int)blockIdx.x * 64;
+    const int nvalid = min(64, a.B - b0);           // robots of this wave
+    const bool valid = lane < nvalid;
+    const size_t so = (size_t)b0 + lane;
+    if (a.init) {
+        if (valid) {
+            a.action[so] = 0; a.entered[so] = -1; a.grip_left[so] = 0; a.finished_tick[so] = -1;
+            a.err[so] = __builtin_huge_val(); a.max_vel0[so] = 0.0; a.gripper_force[so] = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = 0.0;
+        }
+        return;
+    }
+    const int row = a.ndev * 7;
+    T* __restrict__ tg = (T*)a.tgt + (size_t)b0 * row;
+    for (int t = 0; t < row; ++t) {
+        const int i = t * 64 + lane;
+        if (i < nvalid * row) s_t[i] = tg[i];
+    }
+    __syncthreads();
+    bool moved = false;
+    if (valid) {                                    // idle lanes load nothing
+        const int A = a.A;
+        const double* __restrict__ xs = a.xside + (size_t)blockIdx.x * a.n_entries * 64 + lane;
+        T* ta = s_t + lane * row + a.active * 7;
+        int act = a.action[so];
+        double err = a.err[so];
+        double ea[7];
+#pragma unroll
+        for (int c = 0; c < 7; ++c) ea[c] = xs[(size_t)a.ee_act[c] * 64];
+        if (a.tick > 0 && act < A) {                // after_step of the previous tick, on the state its plant step produced
+            double t7[7], e[6];
+#pragma unroll
+            for (int c = 0; c < 7; ++c) t7[c] = (double)ta[c];
+            task_error6<double>(ea, t7, true, true, e);
+            double s2 = __dmul_rn(e[0], e[0]);
+#pragma unroll
+            for (int c = 1; c < 6; ++c) s2 = __dadd_rn(s2, __dmul_rn(e[c], e[c]));
+            err = __dsqrt_rn(s2);
+            a.err[so] = err;
+            bool next;
+            if (a.kind[act] == 0) next = err <= a.max_error[act];      // NaN: stays
+            else {
+                const int gl = a.grip_left[so] - 1;
+                a.grip_left[so] = gl;
+                next = gl <= 0;
+            }
+            if (next) {
+                act += 1;
+                a.action[so] = act;
+                if (act == A) a.finished_tick[so] = a.tick;
+            }
+        }
+        double sx[3];
+        if (a.tick == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = sx[c] = ea[c];
+        }
+        if (act < A && a.entered[so] != act) {
+            a.entered[so] = act;
+            a.gripper_force[so] = a.force[act];
+            if (a.kind[act] == 0) {
+                if (a.passive >= 0) {
+                    T* tp = s_t + lane * row + a.passive * 7;
+#pragma unroll
+                    for (int c = 0; c < 7; ++c)
+                        if (c < 3 || a.hold) tp[c] = (T)xs[(size_t)a.ee_pas[c] * 64];
+                        else tp[c] = (T)a.passive_quat[c - 3];
+                }
+                const double* __restrict__ p = a.per_robot ? a.table + (((size_t)blockIdx.x * A + act) * 7) * 64 + lane : a.table + (size_t)act * 7;
+                const int cs = a.per_robot ? 64 : 1;
+                const bool from_start = a.xyz_from_start[act] != 0;
+                if (from_start && a.tick != 0) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) sx[c] = a.start_xyz[(size_t)c * a.stride + so];
+                }
+#pragma unroll
+                for (int c = 0; c < 7; ++c) ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)p[c * cs];
+                err = __builtin_huge_val();
+                a.err[so] = err;
+                moved = true;
+            } else {
+                a.grip_left[so] = a.grip_ticks[act];
+            }
+        }
+        if (act < A && a.kind[act] == 0) {          // the error-adaptive velocity limit of the active arm (insertion_task.py:293-295)
+            const double v = __dmul_rn(a.kp[act], err);
+            double m = v < a.max_speed[act] ? v : a.max_speed[act];          // min(max_speed, v) as the host evaluates it
+            m = m > a.min_speed[act] ? m : a.min_speed[act];                 // max(min_speed, m)
+            a.max_vel0[so] = m;
+            ((T*)a.gains)[(so * a.ndev + a.active) * IRLOSC_GAIN_WORDS + 9] = (T)m;
+        }
+    }
+    if (!__any(moved)) return;                      // (one wave per block: uniform over the block)
+    __syncthreads();
+    for (int t = 0; t < row; ++t) {
+        const int i = t * 64 + lane;
+        if (i < nvalid * row) tg[i] = s_t[i];
+    }
+}
+
+}  // namespace irlosc
