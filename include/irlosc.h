@@ -510,11 +510,14 @@ IRLOSC_API int irlosc_download_waypoint_state(irlosc_ctx* ctx, int32_t slot, int
  * What action_sequence.py::FleetActionSequenceRunner.tick + after_step do on the host per tick, as one more small kernel of a rollout
  * tick, between the walk (and the sensor feed's wrench) and the first OSC kernel: the target and gain changes it makes are seen by
  * THIS tick's OSC step.  after_step -- the judgement of the state a plant step produced -- is the start of the FOLLOWING tick, because
- * only the next walk has that state's EE pose.  Robot b on tick t since irlosc_set_action_list (a = its action, A = n_actions):
- *   1. t > 0 and a < A:  err = 2-norm of calc_error(ee[active_dev], tgt[b][active_dev] as stored) (osc.py:101-118, all six entries,
+ * only the next walk has that state's EE pose.  Robot b on tick t since irlosc_set_action_list (a = its action, A = n_actions).  A
+ * robot's list starts on the FIRST TICK THAT RUNS IT: tick 0 under rollouts over all B robots of the list, a later tick for a robot that
+ * earlier rollouts over fewer robots left out.  On that tick it is not judged, start_xyz is taken and action 0 is entered;
+ * finished_tick counts the slot's ticks since irlosc_set_action_list all the same.
+ *   1. not b's first tick and a < A:  err = 2-norm of calc_error(ee[active_dev], tgt[b][active_dev] as stored) (osc.py:101-118, all six entries,
  *                        float64);  WP: err <= max_error[a] -> a += 1 (a NaN never advances);  GRIP: grip_left -= 1, <= 0 -> a += 1;
  *                        a == A: finished_tick = t
- *   2. t == 0:           start_xyz = EE xyz of active_dev
+ *   2. b's first tick:   start_xyz = EE xyz of active_dev
  *   3. a < A, not yet entered:  gripper_force = gripper_force[a];
  *                        WP:   tgt[b][passive_dev] = its EE xyz, with its EE quaternion (passive_hold_orientation) or passive_quat;
  *                              tgt[b][active_dev] = pose[b][a], xyz replaced by start_xyz where xyz_from_start[a];  err = +inf
@@ -536,7 +539,7 @@ typedef struct irlosc_action_list {
     double passive_quat[4];                   /* w x y z, finite */
     int32_t nb;                               /* 1 = one pose table for the fleet, B = a table per robot */
     int32_t kind[IRLOSC_MAX_ACTIONS];         /* IRLOSC_ACTION_WP / IRLOSC_ACTION_GRIP */
-    int32_t xyz_from_start[IRLOSC_MAX_ACTIONS];   /* WP: 1 = target xyz is the active EE position of tick 0 ('start_pos') */
+    int32_t xyz_from_start[IRLOSC_MAX_ACTIONS];   /* WP: 1 = target xyz is the active EE position of the robot's first tick ('start_pos') */
     int32_t grip_ticks[IRLOSC_MAX_ACTIONS];   /* GRIP: >= 1 */
     double kp[IRLOSC_MAX_ACTIONS];            /* WP: finite */
     double max_error[IRLOSC_MAX_ACTIONS];     /* WP: finite */

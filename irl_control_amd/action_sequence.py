@@ -343,7 +343,9 @@ def action_list_state(B: int) -> Dict:
 def action_list_tick(state: Dict, ee, tgt, gains, desc: Dict, t: int):
     """One tick of the action-list kernel (csrc/osc_action.hpp) in NumPy, in place: its four steps on rollout tick `t` of the list,
     i.e. FleetActionSequenceRunner.after_step of the PREVIOUS tick (judged on `ee`, the EE poses of the state that tick's step
-    produced) followed by the bookkeeping of FleetActionSequenceRunner.tick.
+    produced) followed by the bookkeeping of FleetActionSequenceRunner.tick.  A robot's list starts on the first tick that runs it
+    (entered < 0: tick 0, or a later one when `ee` held fewer robots before): it is not judged then, its start_xyz is taken and action 0
+    is entered; finished_tick is `t`, the slot's count, all the same.
       state  action_list_state(B), advanced in place
       ee     [B, ndev, 7] EE poses at the start of tick t
       tgt    [B, ndev, 7] targets as stored (any float dtype; entered WP actions write it, values rounded to its dtype)
@@ -353,9 +355,10 @@ def action_list_tick(state: Dict, ee, tgt, gains, desc: Dict, t: int):
     ee = np.asarray(ee, dtype=np.float64)
     B = len(ee)
     st = state
-    if t > 0:
-        live = st["action"] < A
-        e = np.linalg.norm(_calc_error_batch(ee[:, ia], np.asarray(tgt[:, ia], dtype=np.float64)), axis=1)
+    first = st["entered"][:B] < 0
+    if not first.all():
+        live = (st["action"][:B] < A) & ~first
+        e = np.linalg.norm(_calc_error_batch(ee[:, ia], np.asarray(tgt[:B, ia], dtype=np.float64)), axis=1)
         for b in np.nonzero(live)[0]:
             a = st["action"][b]
             st["err"][b] = e[b]
@@ -368,8 +371,7 @@ def action_list_tick(state: Dict, ee, tgt, gains, desc: Dict, t: int):
                 st["action"][b] += 1
                 if st["action"][b] == A:
                     st["finished_tick"][b] = t
-    if t == 0:
-        st["start_xyz"][:] = ee[:, ia, :3]
+    st["start_xyz"][:B][first] = ee[first, ia, :3]
     pose = desc["pose"]
     for b in range(B):
         a = st["action"][b]
@@ -389,7 +391,8 @@ def action_list_tick(state: Dict, ee, tgt, gains, desc: Dict, t: int):
             else:
                 st["grip_left"][b] = desc["grip_ticks"][a]
         if desc["kind"][a] == Action.WP.value:
-            st["max_vel0"][b] = max(desc["min_speed"][a], min(desc["max_speed"][a], desc["kp"][a] * st["err"][b]))
+            with np.errstate(invalid="ignore"):      # (kp 0 on the tick a WP is entered: 0 x inf = NaN, which min() passes over like the kernel)
+                st["max_vel0"][b] = max(desc["min_speed"][a], min(desc["max_speed"][a], desc["kp"][a] * st["err"][b]))
             if gains is not None:
                 gains[b, ia, 9] = st["max_vel0"][b]
     return state

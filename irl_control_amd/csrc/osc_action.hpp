@@ -12,10 +12,12 @@
 // ragged last wave neither load nor store.  The error is float64 (task_error6<double>, the target words converted to double), its
 // norm and the limit with every product and sum rounded on its own: the host can repeat them.
 //
-// Per robot on tick t of the list (A actions; a = action):
-//   1. t > 0 and a < A:  err = |calc_error(ee[active], tgt[active] as stored)|_2;  WP: err <= max_error[a] -> a += 1 (a NaN never advances);
+// Per robot on tick t of the list (A actions; a = action).  A robot's list starts on the FIRST TICK THAT RUNS IT (entered < 0: nothing
+// entered yet) -- tick 0 for every robot of a rollout over the whole list, a later one for a robot that earlier, narrower rollouts left
+// out: on that tick it is not judged, start_xyz is taken and action 0 is entered.  finished_tick counts the slot's ticks all the same.
+//   1. not its first tick and a < A:  err = |calc_error(ee[active], tgt[active] as stored)|_2;  WP: err <= max_error[a] -> a += 1 (a NaN never advances);
 //                        GRIP: grip_left -= 1, <= 0 -> a += 1;  a == A: finished_tick = t
-//   2. t == 0:           start_xyz = EE xyz of the active device
+//   2. its first tick:   start_xyz = EE xyz of the active device
 //   3. a < A and entered != a:  entered = a, gripper_force = gripper_force[a];  WP: passive target = its EE xyz + (its EE quaternion |
 //                        passive_quat), active target = pose a (xyz = start_xyz where xyz_from_start[a]), err = +inf;
 //                        GRIP: grip_left = grip_ticks[a], targets stay
@@ -86,11 +88,13 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
         const double* __restrict__ xs = a.xside + (size_t)blockIdx.x * a.n_entries * 64 + lane;
         T* ta = s_t + lane * row + a.active * 7;
         int act = a.action[so];
+        const int ent = a.entered[so];
+        const bool first = ent < 0;                 // the first tick that runs this robot: tick 0, or later behind narrower rollouts
         double err = a.err[so];
         double ea[7];
 #pragma unroll
         for (int c = 0; c < 7; ++c) ea[c] = xs[(size_t)a.ee_act[c] * 64];
-        if (a.tick > 0 && act < A) {                // after_step of the previous tick, on the state its plant step produced
+        if (!first && act < A) {                    // after_step of the previous tick, on the state its plant step produced
             double t7[7], e[6];
 #pragma unroll
             for (int c = 0; c < 7; ++c) t7[c] = (double)ta[c];
@@ -114,11 +118,11 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
             }
         }
         double sx[3];
-        if (a.tick == 0) {
+        if (first) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = sx[c] = ea[c];
         }
-        if (act < A && a.entered[so] != act) {
+        if (act < A && ent != act) {
             a.entered[so] = act;
             a.gripper_force[so] = a.force[act];
             if (a.kind[act] == 0) {
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
                 const double* __restrict__ p = a.per_robot ? a.table + (((size_t)blockIdx.x * A + act) * 7) * 64 + lane : a.table + (size_t)act * 7;
                 const int cs = a.per_robot ? 64 : 1;
                 const bool from_start = a.xyz_from_start[act] != 0;
-                if (from_start && a.tick != 0) {
+                if (from_start && !first) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) sx[c] = a.start_xyz[(size_t)c * a.stride + so];
                 }

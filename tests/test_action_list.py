@@ -47,11 +47,15 @@ def base_gains(cfg):
     return synth.make_batch(cfg, 1, seed=0)[1]
 
 
-def make_ctx(B, dtype=F64, n_slots=1, cfg="k13"):
-    g = base_gains(cfg)
-    osc = BatchedOSC(synth.make_layout(cfg), B, dtype=dtype, n_slots=n_slots)
+def make_ctx(B, dtype=F64, n_slots=1, cfg="k13", max_batch=None, gains=None, feed=False):
+    """A context for B robots (max_batch: its capacity, default B) with the layout's base gains (gains: another gains dict, per instance
+    then with max_batch rows), the model, the plant and, with feed, the F/T sensors' description."""
+    g = base_gains(cfg) if gains is None else gains
+    osc = BatchedOSC(synth.make_layout(cfg), B if max_batch is None else max_batch, dtype=dtype, n_slots=n_slots)
     osc.set_gains(g["kp"], g["kv"], g["ko"], g["k"], g["d"], g["max_vel"], g["null_kv"])
     osc.set_model(RigidBodyModel.load("dual_ur5"))
+    if feed:
+        osc.set_ft_sensors()
     osc.set_plant(DT, DAMPING)
     return osc
 
@@ -73,33 +77,66 @@ def ee_start(q, qd, cfg):
 _SCEN = {}
 
 
-def scenario(B, cfg="k13", seed=0, fixed_speed=False, perturb=PERTURB, max_error=MAX_ERROR):
-    """-> dict(q, qd, tgt [B, ndev, 7]: the EE poses at the start, desc: the list WP, GRIP, WP, WP('start_pos') with per-robot poses --
-    EE poses of the active arm (ur5right) at start + uniform(-perturb, perturb) on its joints).  fixed_speed: min_speed == max_speed on
-    every WP.  Computed once per key and never written to."""
-    key = (B, cfg, seed, fixed_speed, perturb, max_error)
-    if key in _SCEN:
-        return _SCEN[key]
-    rng = np.random.default_rng(2000 + seed)
-    names = list(synth.make_layout(cfg).dev_names)
-    ia, io = names.index("ur5right"), names.index("ur5left") if "ur5left" in names else -1
+def start_state(B, rng):
+    """(q, qd) [B, 25]: both arms at their start configurations + uniform(-0.15, 0.15) rad per joint, at rest."""
     q = np.zeros((B, 25))
     q[:, RIGHT] = Q_RIGHT + rng.uniform(-0.15, 0.15, (B, 6))
     q[:, LEFT] = Q_LEFT + rng.uniform(-0.15, 0.15, (B, 6))
-    qd = np.zeros((B, 25))
+    return q, np.zeros((B, 25))
+
+
+def device_roles(cfg, active=None, passive=None):
+    """(active, passive) device indices of a list on layout cfg: as given, or by name -- the first ur5right, and the first ur5left where
+    the layout has one (else -1: no passive device)."""
+    names = list(synth.make_layout(cfg).dev_names)
+    ia = names.index("ur5right") if active is None else active
+    io = (names.index("ur5left") if "ur5left" in names else -1) if passive is None else passive
+    return ia, io
+
+
+def arm_joints(cfg, dev):
+    """The joints of the arm that device `dev` of layout cfg steers."""
+    return {"ur5right": RIGHT, "ur5left": LEFT}[synth.make_layout(cfg).dev_names[dev]]
+
+
+def default_list(fixed_speed=False, max_error=MAX_ERROR):
+    """The list WP, GRIP, WP, WP('start_pos') as the arrays of a description."""
     A = len(KINDS)
+    lo, hi = (SPEED_FIXED, SPEED_FIXED) if fixed_speed else SPEED_CLIP
+    return dict(kind=np.array(KINDS, np.int32), xyz_from_start=np.array([0, 0, 0, 1], np.int32), grip_ticks=np.array([1, GRIP_TICKS, 1, 1], np.int32),
+                kp=np.full(A, KP), max_error=np.array([max_error, 0.0, max_error, 1.5 * max_error]), min_speed=np.full(A, lo),
+                max_speed=np.array([hi, hi, min(hi, 1.0), hi]), gripper_force=np.array([0.0, 0.2, 0.0, -0.08]))
+
+
+def scenario(B, cfg="k13", seed=0, fixed_speed=False, perturb=PERTURB, max_error=MAX_ERROR, active=None, passive=None, hold=1,
+             passive_quat=None, shared=False, lst=None):
+    """-> dict(q, qd, tgt [B, ndev, 7]: the EE poses at the start, desc: the list WP, GRIP, WP, WP('start_pos') with per-robot poses --
+    EE poses of the active arm (ur5right) at start + uniform(-perturb, perturb) on its joints).  fixed_speed: min_speed == max_speed on
+    every WP.  active, passive: device indices (default: ur5right and ur5left by name); hold, passive_quat: the passive device's
+    orientation rule; shared: one pose table for the fleet (robot 0's); lst: another list (the arrays of default_list; its WP poses are
+    drawn the same way).  Computed once per key and never written to."""
+    key = (B, cfg, seed, fixed_speed, perturb, max_error, active, passive, hold, None if passive_quat is None else tuple(passive_quat), shared,
+           None if lst is None else tuple((k, tuple(np.asarray(v).tolist())) for k, v in sorted(lst.items())))
+    if key in _SCEN:
+        return _SCEN[key]
+    rng = np.random.default_rng(2000 + seed)
+    ia, io = device_roles(cfg, active, passive)
+    arm = arm_joints(cfg, ia)
+    q, qd = start_state(B, rng)
+    lst = default_list(fixed_speed, max_error) if lst is None else lst
+    A = len(lst["kind"])
     pose = np.zeros((B, A, 7))
     pose[:, :, 3] = 1.0
     tgt = ee_start(q, qd, cfg)
-    for a in (0, 2, 3):
+    for a in np.nonzero(np.asarray(lst["kind"]) == WP)[0]:
         g = q.copy()
-        g[:, RIGHT] += rng.uniform(-perturb, perturb, (B, 6))
+        g[:, arm] += rng.uniform(-perturb, perturb, (B, 6))
         pose[:, a] = ee_start(g, qd, cfg)[:, ia]
-    lo, hi = (SPEED_FIXED, SPEED_FIXED) if fixed_speed else SPEED_CLIP
-    desc = dict(n_actions=A, active_dev=ia, passive_dev=io, passive_hold_orientation=1, passive_quat=np.array(aseq.DEFAULT_EE_QUAT, dtype=F64),
-                kind=np.array(KINDS, np.int32), xyz_from_start=np.array([0, 0, 0, 1], np.int32), grip_ticks=np.array([1, GRIP_TICKS, 1, 1], np.int32),
-                kp=np.full(A, KP), max_error=np.array([max_error, 0.0, max_error, 1.5 * max_error]), min_speed=np.full(A, lo),
-                max_speed=np.array([hi, hi, min(hi, 1.0), hi]), gripper_force=np.array([0.0, 0.2, 0.0, -0.08]), pose=pose)
+    if shared:
+        pose = pose[:1].copy()
+    desc = dict(n_actions=A, active_dev=ia, passive_dev=io, passive_hold_orientation=int(hold),
+                passive_quat=np.array(aseq.DEFAULT_EE_QUAT if passive_quat is None else passive_quat, dtype=F64), pose=pose,
+                **{k: np.array(v) for k, v in lst.items()})
     for a in (q, qd, tgt, pose):
         a.setflags(write=False)
     _SCEN[key] = dict(q=q, qd=qd, tgt=tgt, desc=desc, cfg=cfg)
@@ -112,28 +149,33 @@ def fill(osc, sc, slot=0, rows=slice(None)):
 
 
 def sub_desc(desc, rows):
-    return dict(desc, pose=np.ascontiguousarray(desc["pose"][rows]))
+    return desc if len(desc["pose"]) == 1 else dict(desc, pose=np.ascontiguousarray(desc["pose"][rows]))
 
 
-def packed_gains(lay, cfg, B, dtype):
-    """The gain records [B, ndev, 12] as a context of `dtype` stores them."""
-    g = base_gains(cfg)
+def packed_gains(lay, cfg, B, dtype, gains=None):
+    """The gain records [B, ndev, 12] as a context of `dtype` stores them: the layout's base gains, or `gains` (per instance: B rows)."""
+    g = base_gains(cfg) if gains is None else gains
     return pack_gains(lay, g["kp"], g["kv"], g["ko"], g["k"], g["d"], np.broadcast_to(g["max_vel"], (B, lay.ndev, 2)))[0].astype(dtype)
 
 
-def host_loop(sc, dtype, T, q=None):
+def host_loop(sc, dtype, T, q=None, gains=None, tgt_vel=None, feed=None):
     """T x (set_gains per instance, set_targets, rollout(1)) on a context of its own, the bookkeeping by action_list_tick on the EE
-    poses at the start of every tick, targets and gains kept as the context stores them.  -> dict(out: the last tick's rollout result,
-    flags, state, tgt, gains, margin: the smallest |err - max_error| over every WP judgement of a robot in the list, entered: per
-    robot the set of actions it entered)."""
+    poses at the start of every tick, targets and gains kept as the context stores them.  gains: the base gains (default: the
+    layout's; per instance: B rows, of which the loop replaces word 9 only); tgt_vel [B, ndev, 6]: target velocities, set with the
+    targets on every tick; feed [B, n_sensor]: a constant sensor feed.  -> dict(out: the last tick's rollout result, flags, state,
+    tgt, gains, margin: the smallest |err - max_error| over every WP judgement of a robot in the list, entered: per robot the set of
+    actions it entered)."""
     cfg, desc = sc["cfg"], sc["desc"]
     q = np.array(sc["q"] if q is None else q)
     qd = np.array(sc["qd"])
     B = len(q)
-    osc = make_ctx(B, dtype, cfg=cfg)
-    lay, bg = osc.layout, base_gains(cfg)
+    osc = make_ctx(B, dtype, cfg=cfg, gains=gains, feed=feed is not None)
+    lay, bg = osc.layout, base_gains(cfg) if gains is None else gains
     tgt = np.array(sc["tgt"], dtype=dtype)
-    gains = packed_gains(lay, cfg, B, dtype)
+    gains = packed_gains(lay, cfg, B, dtype, gains)
+    if feed is not None:
+        osc.upload_q(q, qd)
+        osc.set_sensordata(feed)
     state = aseq.action_list_state(B)
     flags = np.zeros(B, np.uint32)
     margin, entered = np.inf, np.zeros((B, desc["n_actions"]), bool)
@@ -149,7 +191,7 @@ def host_loop(sc, dtype, T, q=None):
         entered[np.nonzero(live)[0], state["action"][live]] = True
         osc.set_gains(bg["kp"], bg["kv"], bg["ko"], bg["k"], bg["d"], gains[:, :, 9:11].astype(F64), bg["null_kv"])
         osc.upload_q(q, qd)
-        osc.set_targets(tgt)
+        osc.set_targets(tgt, tgt_vel)
         out = osc.rollout(1)
         flags |= out["flags_any"]
         q, qd = out["qpos"], out["qvel"]
@@ -164,21 +206,33 @@ def judged_err(ee, tgt, desc):
     return np.linalg.norm(aseq._calc_error_batch(ee[:, ia], tgt[:, ia].astype(F64)), axis=1)
 
 
-def device_list(sc, dtype, pieces, rows=slice(None), q=None):
-    """One context, the list on slot 0, rollout(p) for p in pieces.  -> dict(out: the last piece's result, flags, state, tgt-free)."""
+def device_list(sc, dtype, pieces, rows=slice(None), q=None, max_batch=None, gains=None, tgt_vel=None, feed=None, tgt=None, trace=False):
+    """One context, the list on slot 0, rollout(p) for p in pieces.  max_batch: the context's capacity (default: the robots run);
+    gains: its base gains (default: the layout's); tgt_vel, feed: target velocities and a constant sensor feed on the slot; tgt: the
+    slot's targets where they cover MORE robots than the list (given before the coordinates; default: the scenario's, for `rows`);
+    trace: every tick's EE poses.  -> dict(out: the last piece's result, outs: every piece's, flags, state, from_q_name, kernel_name,
+    trace [ticks, B, ndev, 7] or None)."""
     qq = np.array(sc["q"] if q is None else q)[rows]
-    osc = make_ctx(len(qq), dtype, cfg=sc["cfg"])
+    osc = make_ctx(len(qq), dtype, cfg=sc["cfg"], max_batch=max_batch, gains=gains, feed=feed is not None)
+    if tgt is not None:
+        osc.set_targets(tgt, tgt_vel)
     osc.upload_q(qq, sc["qd"][rows])
-    osc.set_targets(sc["tgt"][rows])
+    if tgt is None:
+        osc.set_targets(sc["tgt"][rows], None if tgt_vel is None else tgt_vel[rows])
+    if feed is not None:
+        osc.set_sensordata(feed[rows])
     osc.set_action_list(sub_desc(sc["desc"], rows))
     flags = np.zeros(len(qq), np.uint32)
+    traces, outs = [], []
     for p in pieces:
-        out = osc.rollout(p)
+        out = osc.rollout(p, trace_every=1 if trace else 0)
         flags |= out["flags_any"]
+        traces.append(out["ee_trace"])
+        outs.append(out)
     st = osc.action_state()
-    name = osc.from_q_name
+    names = osc.from_q_name, osc.kernel_name
     osc.close()
-    return dict(out=out, flags=flags, state=st, from_q_name=name)
+    return dict(out=out, outs=outs, flags=flags, state=st, from_q_name=names[0], kernel_name=names[1], trace=np.concatenate(traces) if trace else None)
 
 
 _RUNS = {}

@@ -150,3 +150,52 @@ def test_action_list_tick_is_the_fleet_runner_with_after_step_shifted_by_one_tic
         assert np.array_equal(state["action"], runner.action)
         assert np.all(state["action"][:B - 1] == 4) and state["action"][B - 1] == 0 and state["finished_tick"][B - 1] == -1
         assert len(set(state["finished_tick"][:B - 1])) >= 2 and state["finished_tick"][:B - 1].min() > 0
+
+
+# ---- robots that a narrower run left out start their list on the first tick that runs them ---------------------------------------
+def _closed_stream(state, ee, tgt, gains, desc, ticks, rows, ia):
+    """action_list_tick over `ticks` on the first `rows` robots of (state, ee, tgt, gains), the active arm of those robots moving half
+    of the way to its target's position after every tick (orientation kept: every pose of the list has the EE's own).  In place."""
+    for t in ticks:
+        aseq.action_list_tick(state, ee[:rows], tgt, gains, desc, t)
+        ee[:rows, ia, :3] += 0.5 * (tgt[:rows, ia, :3] - ee[:rows, ia, :3])
+
+
+def test_robots_that_start_three_ticks_late_equal_two_restatements_run_apart():
+    """B = 6, the list WP GRIP(2) WP WP('start_pos'): robots 0..2 run ticks 0..59, robots 3..5 only ticks 3..59 of the same state (what
+    irlosc_rollout_from_q over 3 robots and then over 6 does to a slot).  The late robots' list starts on tick 3: not judged there (their
+    targets are the EE poses they start from, which the rule of tick 0 alone would judge as arrived and skip action 0 unentered),
+    start_xyz taken there, action 0 entered.  Equal to the two halves run apart -- robots 0..2 for 60 ticks, robots 3..5 for 57 ticks
+    from tick 0 -- in every field, targets and gain words, finished_tick of the late half offset by 3."""
+    lay = synth.make_layout("k13")
+    _, gains, _ = synth.make_batch("k13", 1, seed=0)
+    B, H, T, LATE = 6, 3, 60, 3
+    rng = np.random.default_rng(11)
+    ia, io = 0, 1
+    ee0 = np.concatenate([rng.uniform(-0.5, 0.5, (B, lay.ndev, 3)), _unit(rng.normal(size=(B, lay.ndev, 4)))], axis=2)
+    pose = np.zeros((B, 4, 7))
+    for a in (0, 2, 3):
+        pose[:, a, :3] = ee0[:, ia, :3] + rng.uniform(0.05, 0.3, (B, 3)) * (a + 1)
+        pose[:, a, 3:] = ee0[:, ia, 3:]
+    desc = dict(n_actions=4, active_dev=ia, passive_dev=io, passive_hold_orientation=1, passive_quat=np.array(aseq.DEFAULT_EE_QUAT),
+                kind=np.array([0, 1, 0, 0], np.int32), xyz_from_start=np.array([0, 0, 0, 1], np.int32), grip_ticks=np.array([1, 2, 1, 1], np.int32),
+                kp=np.full(4, 2.0), max_error=np.full(4, 0.01), min_speed=np.full(4, 0.05), max_speed=np.full(4, 1.0),
+                gripper_force=np.array([0.0, 0.2, 0.1, -0.08]), pose=pose)
+    g0 = pack_gains(lay, gains["kp"], gains["kv"], gains["ko"], gains["k"], gains["d"], np.broadcast_to(gains["max_vel"], (B, lay.ndev, 2)))[0]
+
+    def fresh(rows):
+        return aseq.action_list_state(len(ee0[rows])), ee0[rows].copy(), ee0[rows].copy(), g0[rows].copy()
+
+    st, ee, tgt, g = fresh(slice(None))
+    _closed_stream(st, ee, tgt, g, desc, range(LATE), H, ia)
+    assert np.all(st["entered"][H:] == -1) and np.array_equal(tgt[H:], ee0[H:]) and np.array_equal(g[H:], g0[H:])
+    _closed_stream(st, ee, tgt, g, desc, range(LATE, T), B, ia)
+    for rows, ticks, off in ((slice(0, H), range(T), 0), (slice(H, B), range(T - LATE), LATE)):
+        s2, e2, t2, g2 = fresh(rows)
+        _closed_stream(s2, e2, t2, g2, dict(desc, pose=pose[rows]), ticks, len(e2), ia)
+        assert np.all(s2["action"] == 4) and s2["finished_tick"].min() > 0 and len(set(s2["finished_tick"])) >= 2
+        for key in st:
+            want = s2[key] + off if key == "finished_tick" else s2[key]
+            assert np.array_equal(st[key][rows], want), (key, rows)
+        assert np.array_equal(tgt[rows], t2) and np.array_equal(g[rows], g2) and np.array_equal(ee[rows], e2)
+    assert np.abs(st["start_xyz"][H:] - ee0[H:, ia, :3]).max() == 0
