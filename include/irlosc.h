@@ -471,6 +471,21 @@ IRLOSC_API int irlosc_rollout_from_q(irlosc_ctx* ctx, int32_t slot, int32_t B, i
  * it).  Synchronous. */
 IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, double* qpos, double* qvel);
 
+/* ---- ONE WRITER OF THE TARGETS: the program of a slot's rollouts -------------------------------------------------------------
+ * Inside a rollout the slot's targets are written by at most one PROGRAM: waypoint paths (irlosc_set_waypoints) or a WP / GRIP action
+ * list (irlosc_set_action_list), never both; outside one by irlosc_set_targets.  Targets are written by one entry point at a time:
+ *     irlosc_set_targets on the slot (B == 0 too), irlosc_set_model (all slots)        any program ends
+ *     irlosc_set_gains (all slots)                                                     a list ends (its gain copy is stale), paths stay
+ *     irlosc_set_waypoints with desc == NULL or all counts 0                           paths end, a list stays
+ *     irlosc_set_action_list with desc == NULL                                         a list ends, paths stay
+ *     a setter that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE                         nothing changes: the program in force stays, whole
+ *     a setter that succeeds                                                           its program replaces whatever was in force
+ *     a setter that answers IRLOSC_ERR_HIP (allocation, copy or init launch)           no program of its kind; irlosc_set_waypoints: none
+ * Uploads of coordinates, records and sensor feeds leave the program alone.  Only irlosc_rollout_from_q runs it (on at most the B
+ * robots it was set for: IRLOSC_ERR_STATE beyond); every other step ignores it and leaves its state as it is.  Its tick counts the
+ * slot's rollout ticks since its setter and continues across calls of irlosc_rollout_from_q.  Clearing a program leaves the targets
+ * as they are. */
+
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
  * the give-up pass and the plant.  Robot b, device d with W_d > 0 waypoints and index idx in [0, W_d] (idx == W_d: path finished,
@@ -495,11 +510,9 @@ typedef struct irlosc_waypoints {
  * resp. not > 0, loop not 0 / 1, nb not 1 or B, B < 1; the paths in force stay, whole -- as they do when the call answers
  * IRLOSC_ERR_STATE).  On success: idx = 0, arrivals = 0,
  * last_tick = -1 for every listed pair, tick base 0, and waypoint 0 is written into the xyz of the slot's targets of every listed
- * device.  desc == NULL or all counts 0 clears the slot's paths (its targets stay as they are).  irlosc_set_targets on the slot and
- * irlosc_set_model clear them too: targets are written by one entry point at a time; uploads of coordinates, records and sensor
- * feeds leave them alone.  Only irlosc_rollout_from_q runs the paths (on at most the B robots given here: IRLOSC_ERR_STATE beyond);
- * every other step ignores them and leaves their state as it is.  Buffers are allocated by the first use; IRLOSC_ERR_HIP when that
- * fails, and the slot is left without paths.  Synchronous. */
+ * device.  desc == NULL or all counts 0 clears the slot's paths.  What else ends them, what they end and who runs them: "one writer
+ * of the targets" above.  Buffers are allocated by the first use; IRLOSC_ERR_HIP when that fails, and the slot is left without
+ * paths.  Synchronous. */
 IRLOSC_API int irlosc_set_waypoints(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_waypoints* desc, const double* xyz);
 /* index, arrivals, last_tick: each [B][ndev], any may be NULL.  Devices without a list report index -1, arrivals 0, last_tick -1.
  * IRLOSC_ERR_STATE on a slot without paths, or with paths for fewer than B robots.  Synchronous. */
@@ -554,12 +567,9 @@ typedef struct irlosc_action_list {
  * irlosc_set_model, irlosc_set_gains and irlosc_set_targets for at least B robots on the slot (IRLOSC_ERR_STATE otherwise; also when
  * the list has a WP and the gains in force have has_max_vel == 0 for active_dev: the limit would be ignored).  On success the slot
  * has its gain copy (the context's gains broadcast or copied, null_kv with them) and the state is reset: action 0, nothing entered,
- * err +inf, max_vel0 0, gripper_force 0, finished_tick -1, tick base 0.  desc == NULL clears the list (targets stay as they are).
- * irlosc_set_gains, irlosc_set_targets on the slot, irlosc_set_waypoints on the slot and irlosc_set_model clear it too, and setting a
- * list clears the slot's waypoint paths: targets are written by one entry point at a time.  Uploads of coordinates, records and
- * sensor feeds leave it alone.  Only irlosc_rollout_from_q runs the list (on at most the B robots given here: IRLOSC_ERR_STATE
- * beyond), with the slot's gain copy in place of the context's gains; every other step ignores both.  Buffers are allocated by the
- * first use.  IRLOSC_ERR_HIP -- an allocation, a copy or the init launch failed -- is the one error that does NOT keep the list in
+ * err +inf, max_vel0 0, gripper_force 0, finished_tick -1, tick base 0.  desc == NULL clears the list.  What else ends it, what it
+ * ends and who runs it: "one writer of the targets" above; its rollouts read the slot's gain copy in place of the context's gains,
+ * every other step ignores both.  Buffers are allocated by the first use.  IRLOSC_ERR_HIP -- an allocation, a copy or the init launch failed -- is the one error that does NOT keep the list in
  * force: the slot is left WITHOUT a list (its rollouts read the context's gains again; its targets stay as the earlier list last
  * wrote them).  Synchronous. */
 IRLOSC_API int irlosc_set_action_list(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_action_list* desc, const double* pose);

@@ -355,7 +355,8 @@ class BatchedOSC:
         (`loop`) or finishes on the last one.  `xyz`: per device (layout order) a [W, 3] array (one path for the fleet), a [B, W, 3]
         array (a path per robot) or None (the device keeps the slot's target); W <= 64.  `threshold`, `loop`: one value or one per
         device.  After set_model and set_targets; writes waypoint 0 into the slot's targets and resets the state.  xyz=None (or all
-        None) clears the paths, as set_targets and set_model do."""
+        None) clears the paths and nothing else.  A slot has paths or an action list, never both; what else ends them: "one writer of
+        the targets" in include/irlosc.h."""
         L, B = self.layout, self._B[slot]
         paths = [None] * L.ndev if xyz is None else [None if p is None else np.asarray(p, dtype=np.float64) for p in xyz]
         if len(paths) != L.ndev:
@@ -399,8 +400,9 @@ class BatchedOSC:
         limit goes into the slot's own copy of the gains -- no host in between.  `sequence`: the list of action dicts (defaults from
         action_sequence.DEFAULT_PARAMS), or a dict from action_sequence.compile_action_list; `objects`: per robot its action objects
         (one entry: shared by the fleet).  `passive_arm`: "auto" = the other UR5 when the layout has it, None = no passive arm.
-        After set_model, set_gains and set_targets; resets the state.  sequence=None clears the list, as set_gains, set_targets,
-        set_waypoints and set_model do.  gripper_force is state only: no gripper joint is driven."""
+        After set_model, set_gains and set_targets; resets the state.  sequence=None clears the list and nothing else.  A slot has a
+        list or waypoint paths, never both; what else ends it: "one writer of the targets" in include/irlosc.h.  gripper_force is state
+        only: no gripper joint is driven."""
         from . import action_sequence as aseq
         B = self._B[slot]
         if sequence is None:

@@ -36,6 +36,35 @@ static_assert(FT_TRAIN == R16_TRAIN, "the sensor-feed wrench kernel covers a who
 
 static thread_local std::string g_create_error;
 
+// The program that writes a slot's targets inside a rollout, if any: waypoint paths (irlosc_set_waypoints, osc_waypoint.hpp) or the
+// WP / GRIP action list (irlosc_set_action_list, osc_action.hpp).  One entry point writes the targets at a time, so a slot has one
+// program at most -- `kind` says which: a list and paths exclude each other.  Written by the transitions below and by nothing else.
+struct Program {
+    enum Kind { NONE, PATHS, LIST };
+    Kind kind = NONE;          // (NONE: a rollout tick launches neither kernel and reads the context's gains)
+    int robots = 0, tick = 0;  // robots the program covers; rollout ticks since it came in force
+    irlosc_waypoints wp{};     // the description in force: of paths; of a list
+    irlosc_action_list al{};
+    // Device buffers, allocated by the first use and kept across programs: per-robot state SoA over max_batch robots (wp_i: index, arrivals,
+    // last_tick, [ndev][max_batch] each; al_i: action, entered, grip_left, finished_tick; al_d: err, max_vel0, gripper_force, start_xyz[3]), the
+    // table (walk_table), and a list's own gains [robots][ndev][12] and null_kv [robots] in the context's dtype (its rollout reads these per instance)
+    DevBuf<int32_t> wp_i, al_i;
+    DevBuf<double> wp_table, al_d, al_table;
+    DevBuf<void> al_gains, al_nullkv;
+
+    // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
+    void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
+    // A list of B robots is in force, its state reset by the kernel's init launch and its gain copy made: it writes the targets from here on.
+    void list(int B, const irlosc_action_list& d) { kind = LIST; robots = B; tick = 0; al = d; }
+    // The program ends: irlosc_set_targets wrote the targets, another program takes them over, the model changed, or its buffers failed.
+    void end() { kind = NONE; robots = 0; tick = 0; }
+    // The program ends if it is of this kind (its own setter cleared it; a list: the gains its copy was made from were replaced): one of the other kind stays whole
+    void end(Kind k) { if (kind == k) end(); }
+    // A tick of a rollout ran the program's kernel.  (Marked once the whole tick is enqueued: if a launch behind the kernel fails, the
+    // device state is one tick ahead of `tick` -- on a context whose stream has already failed, where the rollout's result is void anyway.)
+    void ticked() { ++tick; }
+};
+
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
 // (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
 // the fused path is on, sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
@@ -65,24 +94,7 @@ struct Slot {
     // bank, Bank::ftw)
     DevBuf<double> sens;       // (grown to max_batch x the description's n_sensor doubles)
     int feed = 0;              // robots of the feed (0 = no feed)
-    // waypoint paths of the rollout (irlosc_set_waypoints): per-robot state [ndev][waypoints] each, the table ([walk wave][dev][w][3][64]
-    // per robot, [dev][w][3] shared), allocated by the first use; the description in force and the widest list
-    DevBuf<int32_t> wp_index; DevBuf<uint32_t> wp_arrivals; DevBuf<int32_t> wp_last;
-    DevBuf<double> wp_table;
-    irlosc_waypoints wp{};
-    int wp_max = 0;
-    int waypoints = 0;         // robots with paths (0 = none: a rollout tick launches no cycler)
-    int wp_tick = 0;           // rollout ticks since irlosc_set_waypoints
-    // action list of the rollout (irlosc_set_action_list): per-robot state SoA over max_batch robots -- al_i: action, entered, grip_left,
-    // finished_tick; al_d: err, max_vel0, gripper_force, start_xyz[3] --, the pose table ([walk wave][A][7][64] per robot, [A][7] shared),
-    // the slot's own gains [actions][ndev][12] and null_kv [actions] in the context's dtype (the steps of its rollout read these per
-    // instance), allocated by the first use; the description in force
-    DevBuf<int32_t> al_i;
-    DevBuf<double> al_d, al_table;
-    DevBuf<void> al_gains, al_nullkv;
-    irlosc_action_list al{};
-    int actions = 0;           // robots with the list (0 = none: a rollout tick launches no action kernel and reads the context's gains)
-    int al_tick = 0;           // rollout ticks since irlosc_set_action_list
+    Program prog;              // what writes the targets inside a rollout
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -105,21 +117,6 @@ struct Slot {
     // The plant kernel of a rollout advanced the coordinates of B robots on the device: row-major and walk layout alike, so they stay the
     // slot's coordinates (targets and feed are not touched; the records went with the fused step of the tick: voided()).
     void advanced(int B) { coords = B; }
-    // Paths of B robots are in the slot, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
-    void pathed(int B, const irlosc_waypoints& d, int wmax) { waypoints = B; wp = d; wp_max = wmax; wp_tick = 0; }
-    // The paths end: cleared by the caller, the targets were written by irlosc_set_targets, the model changed, or their buffers failed.
-    void unpathed() { waypoints = 0; wp_tick = 0; }
-    // The cycler ran behind a tick of a rollout.  (Marked once the whole tick is enqueued: if a launch behind the cycler fails, the
-    // device state is one tick ahead of wp_tick -- on a context whose stream has already failed, where the rollout's result is void anyway.)
-    void ticked() { ++wp_tick; }
-    // The action list of B robots is in the slot, its state reset by the kernel's init launch and its gain copy made.  A list and
-    // waypoint paths exclude each other: the list writes the targets from here on.
-    void listed(int B, const irlosc_action_list& d) { unpathed(); actions = B; al = d; al_tick = 0; }
-    // The list ends: cleared by the caller, the targets or the gains were written by their own entry points, paths took the targets
-    // over, the model changed, or its buffers failed.
-    void unlisted() { actions = 0; al_tick = 0; }
-    // The action kernel ran in a tick of a rollout (marked once the whole tick is enqueued, like ticked()).
-    void acted() { ++al_tick; }
     // pack_slot built the block of B robots from records it found eligible (lane_eligible: the tree verdict, so records > 0).
     void block_packed(int B) { packed = B; }
 };
@@ -501,7 +498,7 @@ extern "C" int irlosc_set_gains(irlosc_ctx* c, const double* gains, const double
     HIPCHK(c, hipMemcpyAsync(c->dnullkv, b.data(), b.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->gains_nb = nb;
-    for (Slot& s : c->slot) s.unlisted();      // their gain copies were made from the gains this call replaced
+    for (Slot& s : c->slot) s.prog.end(Program::LIST);      // their gain copies were made from the gains this call replaced
     return IRLOSC_OK;
 }
 
@@ -808,10 +805,9 @@ extern "C" int irlosc_set_targets(irlosc_ctx* c, int32_t slot, int32_t B, const 
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (B == 0) { s.targets = -1; s.unpathed(); s.unlisted(); return IRLOSC_OK; }
+    if (B == 0) { s.targets = -1; s.prog.end(); return IRLOSC_OK; }
     if (!tgt_pose) return fail(c, IRLOSC_ERR_ARG, "tgt_pose is NULL");
-    s.unpathed();      // the targets are the caller's from here on: one entry point writes them at a time
-    s.unlisted();
+    s.prog.end();      // the targets are the caller's from here on: one entry point writes them at a time
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, nd = (size_t)c->cfg.ndev, e = c->esz;
     HIPCHK(c, hipMemcpyAsync(s.tgt, tgt_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
@@ -1492,7 +1488,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.unpathed(); s.unlisted(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1657,25 +1653,20 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 }
 
 // irlosc_rollout_from_q: the plant kernel behind the step (one step on bank 0), handed to the next train like the timing events
-// (irlosc_ctx::plant_next); trace: the device sample of this tick's EE poses, or nullptr
-// wp_tick: >= 0: the slot has waypoint paths and its cycler runs between the give-up pass and the plant, as this tick; -1: none
-// al_tick: >= 0: the slot has an action list, whose kernel runs between the walk and the first OSC kernel, as this tick, and the step
-// reads the slot's gain copy per instance; -1: none
-struct PlantCall {
-    double* trace;
-    int wp_tick;
-    int al_tick;
-};
+// (irlosc_ctx::plant_next); trace: the device sample of this tick's EE poses, or nullptr.  What else the tick runs, and as which
+// tick, is the slot's to say (Slot::prog).
+struct PlantCall { double* trace; };
 
 // The arguments of the slot's action kernel over B robots (init: the launch of irlosc_set_action_list; else a tick on exchange block xside)
 static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_action_list& d, const double* xside, int tick) {
+    const Program& p = s.prog;
     ActionArgs a;
     memset(&a, 0, sizeof a);
     const size_t Bm = (size_t)c->cfg.max_batch;
-    a.xside = xside; a.tgt = s.tgt; a.gains = s.al_gains;
-    a.action = s.al_i; a.entered = s.al_i + Bm; a.grip_left = s.al_i + 2 * Bm; a.finished_tick = s.al_i + 3 * Bm;
-    a.err = s.al_d; a.max_vel0 = s.al_d + Bm; a.gripper_force = s.al_d + 2 * Bm; a.start_xyz = s.al_d + 3 * Bm;
-    a.table = s.al_table;
+    a.xside = xside; a.tgt = s.tgt; a.gains = p.al_gains;
+    a.action = p.al_i; a.entered = p.al_i + Bm; a.grip_left = p.al_i + 2 * Bm; a.finished_tick = p.al_i + 3 * Bm;
+    a.err = p.al_d; a.max_vel0 = p.al_d + Bm; a.gripper_force = p.al_d + 2 * Bm; a.start_xyz = p.al_d + 3 * Bm;
+    a.table = p.al_table;
     for (int i = 0; i < d.n_actions; ++i) {
         a.kp[i] = d.kp[i]; a.max_error[i] = d.max_error[i]; a.min_speed[i] = d.min_speed[i]; a.max_speed[i] = d.max_speed[i];
         a.force[i] = d.gripper_force[i]; a.grip_ticks[i] = d.grip_ticks[i];
@@ -1693,20 +1684,58 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
 }
 
 // The arguments of the slot's waypoint cycler over B robots (init: the launch of irlosc_set_waypoints; else a tick on exchange block xside)
-static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, int wmax, int stride, const double* xside, int tick) {
+static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, const double* xside, int tick) {
     WaypointArgs a;
     memset(&a, 0, sizeof a);
-    a.xside = xside; a.tgt = s.tgt;
-    a.index = s.wp_index; a.arrivals = s.wp_arrivals; a.last_tick = s.wp_last; a.table = s.wp_table;
+    const size_t n = (size_t)c->cfg.ndev * c->cfg.max_batch;
+    a.xside = xside; a.tgt = s.tgt; a.table = s.prog.wp_table;
+    a.index = s.prog.wp_i; a.arrivals = (uint32_t*)(s.prog.wp_i + n); a.last_tick = s.prog.wp_i + 2 * n;
     for (int d = 0; d < c->cfg.ndev; ++d) {
         a.thr2[d] = w.threshold[d] * w.threshold[d];
         a.count[d] = w.count[d];
         a.loop[d] = w.loop[d];
         a.ee0[d] = xside ? c->model.tables.eetab[d][0] : 0;
+        a.wmax = std::max(a.wmax, w.count[d]);      // the widest list: the table's stride
     }
-    a.B = B; a.ndev = c->cfg.ndev; a.stride = stride; a.wmax = wmax; a.per_robot = w.nb > 1;
+    a.B = B; a.ndev = c->cfg.ndev; a.stride = c->cfg.max_batch; a.per_robot = w.nb > 1;
     a.n_entries = (int32_t)c->model.fe_xentries; a.tick = tick; a.init = xside ? 0 : 1;
     return a;
+}
+
+// The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
+static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
+    const Program& p = c->slot[slot].prog;
+    const bool paths = (need ? need : p.kind) == Program::PATHS;
+    if (need && p.kind != need)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d has no %s", slot, paths ? "waypoint paths (irlosc_set_waypoints)" : "action list (irlosc_set_action_list)");
+    if (p.kind && B > p.robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s %d robots, %sasked for %d", slot, paths ? "waypoint paths cover" : "action list covers",
+                    p.robots, need ? "" : "rollout ", B);
+    return IRLOSC_OK;
+}
+
+// A program's table [nb][E] in the layout its kernel walks: per robot [walk wave][E][64] (idle lanes zero), shared (nb == 1) as given
+static std::vector<double> walk_table(const double* t, int nb, size_t E) {
+    std::vector<double> tab(nb == 1 ? E : ((size_t)nb + 63) / 64 * E * 64, 0.0);
+    for (int b = 0; b < nb; ++b)
+        for (size_t e = 0; e < E; ++e) tab[nb == 1 ? e : ((size_t)(b / 64) * E + e) * 64 + b % 64] = t[(size_t)b * E + e];
+    return tab;
+}
+
+// The tail of a program's setter: its host arrays to the device and the init launch of its kernel on the context's stream -> the first
+// error.  Synchronises also when a copy or the launch failed: the host arrays are the copies' sources.  Only then is the program in force.
+struct HostCopy { void* dst; const void* src; size_t bytes; };
+template <typename Args>
+static int program_upload(irlosc_ctx* c, std::initializer_list<HostCopy> copies, int (*init64)(const Args&, hipStream_t),
+                          int (*init32)(const Args&, hipStream_t), const Args& a) {
+    hipError_t ec = hipSuccess;
+    for (const HostCopy& k : copies)
+        if (ec == hipSuccess) ec = hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->stream);
+    if (ec == hipSuccess) ec = (hipError_t)(c->cfg.dtype == IRLOSC_F64 ? init64 : init32)(a, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    HIPCHK(c, ec);
+    HIPCHK(c, es);
+    return IRLOSC_OK;
 }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
@@ -1741,6 +1770,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     }
     const irlosc_ctx::Bank& bk = c->bank[k];
     const hipStream_t st = dv ? dv->st : bk.st;
+    Slot& s0 = c->slot[slots[0]];      // (the slot of a rollout's tick)
+    const Program::Kind prog = pl ? s0.prog.kind : Program::NONE;      // what writes its targets inside the rollout
     FtStep fts[R16_TRAIN];
     int nft = 0;
     FeLaneTrain ft;
@@ -1766,8 +1797,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
         StepInputs in = slot_inputs(s, wr);
         if (dv) { in.tgt = dv->tgt; in.tvel = dv->tvel; in.wrench = wr; }
         fill_params<T>(c, tr.p[i], B, in, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
-        if (pl && pl->al_tick >= 0) {      // a tick of a slot with an action list: its own gains, which the action kernel writes per robot
-            tr.p[i].gains = (const T*)s.al_gains.get(); tr.p[i].null_kv = (const T*)s.al_nullkv.get();
+        if (prog == Program::LIST) {      // a tick of a slot with an action list: its own gains, which the action kernel writes per robot
+            tr.p[i].gains = (const T*)s.prog.al_gains.get(); tr.p[i].null_kv = (const T*)s.prog.al_nullkv.get();
             tr.p[i].gains_per_instance = 1;
         }
         tr.x[i] = Row16Extra{c->dzeros, bk.list[i], bk.count + i, bk.xside[i], qvel, c->model.dtables, c->span_next};
@@ -1794,10 +1825,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     HIPCHK(c, (hipError_t)fused_walk(c).launch(c->model.dmodel, ft, n, st));
     int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
     if (rcw) return rcw;
-    if (pl && pl->al_tick >= 0) {      // the action list: its targets and velocity limit are this tick's, so in front of every OSC kernel
-        const Slot& s = c->slot[slots[0]];
-        HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s, B, s.al, bk.xside[0], pl->al_tick), st));
-    }
+    if (prog == Program::LIST)      // the action list: its targets and velocity limit are this tick's, so in front of every OSC kernel
+        HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (use_lane) {
         if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
         HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
@@ -1806,16 +1835,13 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     }
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
-    if (pl && pl->wp_tick >= 0) {      // the targets move where an arm arrived: behind every OSC kernel of the tick, in front of the plant
-        const Slot& s = c->slot[slots[0]];
-        HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s, B, s.wp, s.wp_max, s.waypoints, bk.xside[0], pl->wp_tick), st));
-    }
+    if (prog == Program::PATHS)      // the targets move where an arm arrived: behind every OSC kernel of the tick, in front of the plant
+        HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s0, B, s0.prog.wp, bk.xside[0], s0.prog.tick), st));
     if (pl) {
-        const Slot& s = c->slot[slots[0]];
         PlantArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.xside = bk.xside[0]; pa.u = bk.u[0]; pa.flags = bk.flags[0];
-        pa.qt = s.qt; pa.qpos = s.qpos; pa.qvel = s.qvel;
+        pa.qt = s0.qt; pa.qpos = s0.qpos; pa.qvel = s0.qvel;
         pa.trace = pl->trace; pa.flags_any = c->dflags_any;
         pa.dt = c->plant.dt; pa.damping = c->plant.damping; pa.ctrl_mask = c->plant.ctrl_mask;
         pa.B = B; pa.ndev = c->cfg.ndev;
@@ -1827,9 +1853,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     // slots held before no longer belongs to one state.  They hold no records from here on -- irlosc_step / irlosc_step_resident
     // / irlosc_download_records on them fail with IRLOSC_ERR_STATE until irlosc_frontend / irlosc_upload* fills them again.
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
-    if (pl) c->slot[slots[0]].advanced(B);
-    if (pl && pl->wp_tick >= 0) c->slot[slots[0]].ticked();
-    if (pl && pl->al_tick >= 0) c->slot[slots[0]].acted();
+    if (pl) s0.advanced(B);
+    if (prog != Program::NONE) s0.prog.ticked();
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2062,9 +2087,7 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     int filled = 0, sent = 0;      // samples written / copied to the host
     for (int t = 0; t < ticks; ++t) {
         const bool traced = nsamples && t % every == 0;
-        const Slot& s = c->slot[slot];
-        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr, s.waypoints > 0 ? s.wp_tick : -1,
-                           s.actions > 0 ? s.al_tick : -1};
+        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr};
         c->plant_next = &pl;
         const int rc = fused_resident(c, slot, B, 1);
         c->plant_next = nullptr;
@@ -2096,11 +2119,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     if (c->cfg.n != plant_joints()) return fail(c, IRLOSC_ERR_STATE, "no rollout on this context: the plant kernel holds %d joints, n=%d", plant_joints(), c->cfg.n);
     rc = check_slot_q(c, slot, B);
     if (!rc) rc = check_slot_feed(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B);
     if (rc) return rc;
-    if (c->slot[slot].waypoints > 0 && B > c->slot[slot].waypoints)
-        return fail(c, IRLOSC_ERR_STATE, "slot %d: its waypoint paths cover %d robots, rollout asked for %d", slot, c->slot[slot].waypoints, B);
-    if (c->slot[slot].actions > 0 && B > c->slot[slot].actions)
-        return fail(c, IRLOSC_ERR_STATE, "slot %d: its action list covers %d robots, rollout asked for %d", slot, c->slot[slot].actions, B);
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (!fused_ready(c, 1))
@@ -2136,71 +2156,57 @@ extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, cons
             return fail(c, IRLOSC_ERR_ARG, "waypoints: count[%d]=%d out of [0,%d]", d, w->count[d], d < nd ? IRLOSC_MAX_WAYPOINTS : 0);
         wmax = std::max(wmax, (int)w->count[d]);
     }
-    if (!w || wmax == 0) { s.unpathed(); return IRLOSC_OK; }
+    if (!w || wmax == 0) { s.prog.end(Program::PATHS); return IRLOSC_OK; }
     if (B < 1) return fail(c, IRLOSC_ERR_ARG, "waypoints: B=%d must be >= 1", B);
     if (w->nb != 1 && w->nb != B) return fail(c, IRLOSC_ERR_ARG, "waypoints: nb=%d must be 1 or B=%d", w->nb, B);
     if (!xyz) return fail(c, IRLOSC_ERR_ARG, "waypoints: xyz is NULL");
+    // the table as given, but for entries no device lists: zero whatever the caller's array holds there
+    const size_t E = (size_t)nd * wmax * 3;
+    std::vector<double> dense((size_t)w->nb * E, 0.0);
     for (int d = 0; d < nd; ++d) {
         if (!w->count[d]) continue;
         if (!(std::isfinite(w->threshold[d]) && w->threshold[d] > 0.0))
             return fail(c, IRLOSC_ERR_ARG, "waypoints: threshold[%d]=%g must be finite and > 0", d, w->threshold[d]);
         if (w->loop[d] > 1) return fail(c, IRLOSC_ERR_ARG, "waypoints: loop[%d]=%d must be 0 or 1", d, (int)w->loop[d]);
         for (int b = 0; b < w->nb; ++b)
-            for (int i = 0; i < w->count[d] * 3; ++i)
-                if (!std::isfinite(xyz[(((size_t)b * nd + d) * wmax) * 3 + i]))
+            for (int i = 0; i < w->count[d] * 3; ++i) {
+                const size_t e = (((size_t)b * nd + d) * wmax) * 3 + i;
+                if (!std::isfinite(dense[e] = xyz[e]))
                     return fail(c, IRLOSC_ERR_ARG, "waypoints: waypoint %d of device %d, robot %d is not finite", i / 3, d, b);
+            }
     }
     if (B > std::max(0, s.targets))
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, waypoints given for %d: irlosc_set_targets first", slot,
                     std::max(0, s.targets), B);
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    s.unpathed();      // (none until the new ones are in their buffers)
-    s.unlisted();      // the paths write the targets from here on: an action list of the slot ends
-    // the table in the kernel's layout: per robot [walk wave][dev][w][3][64] (idle lanes and unlisted entries zero), shared as given
-    const bool per_robot = w->nb > 1;
-    const size_t waves = ((size_t)B + 63) / 64;
-    std::vector<double> tab(per_robot ? waves * nd * wmax * 3 * 64 : (size_t)nd * wmax * 3, 0.0);
-    for (int b = 0; b < w->nb; ++b)
-        for (int d = 0; d < nd; ++d)
-            for (int i = 0; i < w->count[d] * 3; ++i) {
-                const size_t e = ((size_t)d * wmax) * 3 + i;
-                tab[per_robot ? ((size_t)(b / 64) * nd * wmax * 3 + e) * 64 + b % 64 : e] = xyz[(size_t)b * nd * wmax * 3 + e];
-            }
-    const size_t bytes = tab.size() * sizeof(double), state = (size_t)nd * c->cfg.max_batch * sizeof(int32_t);
-    if (!got(s.wp_table.reserve(bytes)) || !got(s.wp_index.ensure(state)) || !got(s.wp_arrivals.ensure(state)) || !got(s.wp_last.ensure(state)))
-        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the waypoint paths of slot %d (%zu bytes)", slot, bytes + 3 * state);
-    HIPCHK(c, hipMemcpyAsync(s.wp_table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    const WaypointArgs a = waypoint_args(c, s, B, *w, wmax, B, nullptr, 0);
-    rc = c->cfg.dtype == IRLOSC_F64 ? launch_waypoints<double>(a, c->stream) : launch_waypoints<float>(a, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when the launch failed: `tab` is the copy's source)
-    HIPCHK(c, (hipError_t)rc);
-    HIPCHK(c, es);
-    s.pathed(B, *w, wmax);
-    return IRLOSC_OK;
+    Program& p = s.prog;
+    p.end();           // (none until the new ones are in their buffers; the paths write the targets from here on: an action list ends)
+    const std::vector<double> tab = walk_table(dense.data(), w->nb, E);
+    const size_t bytes = tab.size() * sizeof(double), state = (size_t)3 * nd * c->cfg.max_batch * sizeof(int32_t);
+    if (!got(p.wp_table.reserve(bytes)) || !got(p.wp_i.ensure(state)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the waypoint paths of slot %d (%zu bytes)", slot, bytes + state);
+    rc = program_upload(c, {{p.wp_table, tab.data(), bytes}}, launch_waypoints<double>, launch_waypoints<float>, waypoint_args(c, s, B, *w, nullptr, 0));
+    if (!rc) p.paths(B, *w);
+    return rc;
 }
 
 extern "C" int irlosc_download_waypoint_state(irlosc_ctx* c, int32_t slot, int32_t B, int32_t* index, uint32_t* arrivals, int32_t* last_tick) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B, Program::PATHS);
     if (rc) return rc;
-    const Slot& s = c->slot[slot];
-    if (s.waypoints <= 0) return fail(c, IRLOSC_ERR_STATE, "slot %d has no waypoint paths (irlosc_set_waypoints)", slot);
-    if (B > s.waypoints) return fail(c, IRLOSC_ERR_STATE, "slot %d: its waypoint paths cover %d robots, asked for %d", slot, s.waypoints, B);
+    const Program& p = c->slot[slot].prog;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    // SoA [ndev][waypoints] on the device -> [B][ndev] for the caller
-    const int nd = c->cfg.ndev;
-    const size_t n = (size_t)nd * s.waypoints;
-    std::vector<int32_t> h(n);
-    const void* src[3] = {s.wp_index, s.wp_arrivals, s.wp_last};
+    // SoA [3][ndev][max_batch] on the device -> [B][ndev] each for the caller
+    const size_t nd = (size_t)c->cfg.ndev, Bm = (size_t)c->cfg.max_batch;
+    std::vector<int32_t> h(3 * nd * Bm);
+    HIPCHK(c, hipMemcpyAsync(h.data(), p.wp_i, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     int32_t* dst[3] = {index, (int32_t*)arrivals, last_tick};
-    for (int i = 0; i < 3; ++i) {
-        if (!dst[i]) continue;
-        HIPCHK(c, hipMemcpyAsync(h.data(), src[i], n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (int b = 0; b < B; ++b)
-            for (int d = 0; d < nd; ++d) dst[i][(size_t)b * nd + d] = h[(size_t)d * s.waypoints + b];
-    }
+    for (size_t i = 0; i < 3; ++i)
+        for (size_t b = 0; dst[i] && b < (size_t)B; ++b)
+            for (size_t d = 0; d < nd; ++d) dst[i][b * nd + d] = h[(i * nd + d) * Bm + b];
     return IRLOSC_OK;
 }
 
@@ -2210,7 +2216,7 @@ extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, co
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (!d) { s.unlisted(); return IRLOSC_OK; }
+    if (!d) { s.prog.end(Program::LIST); return IRLOSC_OK; }
     const int nd = c->cfg.ndev, A = d->n_actions;
     if (A < 1 || A > IRLOSC_MAX_ACTIONS) return fail(c, IRLOSC_ERR_ARG, "action list: n_actions=%d out of [1,%d]", A, IRLOSC_MAX_ACTIONS);
     if (B < 1) return fail(c, IRLOSC_ERR_ARG, "action list: B=%d must be >= 1", B);
@@ -2266,55 +2272,41 @@ extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, co
         if (word(b, d->active_dev, 11) == 0.0)
             return fail(c, IRLOSC_ERR_STATE, "action list: the gains in force have has_max_vel == 0 for device %d (robot %zu): the velocity limit "
                         "a WP sets would be ignored", d->active_dev, b);
-    s.unlisted();      // (none until the new one is in its buffers)
+    Program& p = s.prog;
+    p.end(Program::LIST);      // (none until the new one is in its buffers; paths end when it is in force)
     std::vector<unsigned char> gs((size_t)B * rec), nks((size_t)B * e);
     for (size_t b = 0; b < (size_t)B; ++b) {
         memcpy(gs.data() + b * rec, g.data() + (nbg > 1 ? b : 0) * rec, rec);
         memcpy(nks.data() + b * e, nk.data() + (nbg > 1 ? b : 0) * e, e);
     }
-    // the pose table in the kernel's layout: per robot [walk wave][A][7][64] (idle lanes zero), shared as given
-    const bool per_robot = d->nb > 1;
-    const size_t waves = ((size_t)B + 63) / 64, Bm = (size_t)c->cfg.max_batch;
-    std::vector<double> tab(per_robot ? waves * A * 7 * 64 : (size_t)A * 7, 0.0);
-    for (int b = 0; b < d->nb; ++b)
-        for (int i = 0; i < A * 7; ++i)
-            tab[per_robot ? ((size_t)(b / 64) * A * 7 + i) * 64 + b % 64 : (size_t)i] = pose[(size_t)b * A * 7 + i];
-    const size_t bytes = tab.size() * sizeof(double);
-    if (!got(s.al_table.reserve(bytes)) || !got(s.al_i.ensure(4 * Bm * sizeof(int32_t))) || !got(s.al_d.ensure(6 * Bm * sizeof(double))) ||
-        !got(s.al_gains.ensure(Bm * rec)) || !got(s.al_nullkv.ensure(Bm * e)))
+    const std::vector<double> tab = walk_table(pose, d->nb, (size_t)A * 7);
+    const size_t bytes = tab.size() * sizeof(double), Bm = (size_t)c->cfg.max_batch;
+    if (!got(p.al_table.reserve(bytes)) || !got(p.al_i.ensure(4 * Bm * sizeof(int32_t))) || !got(p.al_d.ensure(6 * Bm * sizeof(double))) ||
+        !got(p.al_gains.ensure(Bm * rec)) || !got(p.al_nullkv.ensure(Bm * e)))
         return fail(c, IRLOSC_ERR_HIP, "out of device memory for the action list of slot %d", slot);
-    hipError_t ec = hipMemcpyAsync(s.al_table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
-    if (ec == hipSuccess) ec = hipMemcpyAsync(s.al_gains, gs.data(), gs.size(), hipMemcpyHostToDevice, c->stream);
-    if (ec == hipSuccess) ec = hipMemcpyAsync(s.al_nullkv, nks.data(), nks.size(), hipMemcpyHostToDevice, c->stream);
-    if (ec == hipSuccess) {
-        const ActionArgs a = action_args(c, s, B, *d, nullptr, 0);
-        ec = (hipError_t)(c->cfg.dtype == IRLOSC_F64 ? launch_actions<double>(a, c->stream) : launch_actions<float>(a, c->stream));
-    }
-    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when a copy or the launch failed: the vectors are the copies' sources)
-    HIPCHK(c, ec);
-    HIPCHK(c, es);
-    s.listed(B, *d);
-    return IRLOSC_OK;
+    rc = program_upload(c, {{p.al_table, tab.data(), bytes}, {p.al_gains, gs.data(), gs.size()}, {p.al_nullkv, nks.data(), nks.size()}},
+                        launch_actions<double>, launch_actions<float>, action_args(c, s, B, *d, nullptr, 0));
+    if (!rc) p.list(B, *d);
+    return rc;
 }
 
 extern "C" int irlosc_download_action_state(irlosc_ctx* c, int32_t slot, int32_t B, int32_t* action, int32_t* grip_left, double* err,
                                             double* max_vel0, double* gripper_force, int32_t* finished_tick) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B, Program::LIST);
     if (rc) return rc;
-    const Slot& s = c->slot[slot];
-    if (s.actions <= 0) return fail(c, IRLOSC_ERR_STATE, "slot %d has no action list (irlosc_set_action_list)", slot);
-    if (B > s.actions) return fail(c, IRLOSC_ERR_STATE, "slot %d: its action list covers %d robots, asked for %d", slot, s.actions, B);
+    const Program& p = c->slot[slot].prog;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t Bm = (size_t)c->cfg.max_batch;
     int32_t* di[3] = {action, grip_left, finished_tick};
     const size_t oi[3] = {0, 2 * Bm, 3 * Bm};
     for (int i = 0; i < 3; ++i)
-        if (di[i]) HIPCHK(c, hipMemcpyAsync(di[i], s.al_i + oi[i], (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (di[i]) HIPCHK(c, hipMemcpyAsync(di[i], p.al_i + oi[i], (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     double* dd[3] = {err, max_vel0, gripper_force};
     for (int i = 0; i < 3; ++i)
-        if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], s.al_d + i * Bm, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], p.al_d + i * Bm, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }

@@ -6,11 +6,10 @@
 // the start of the following tick: only the next walk has that pose.
 //
 // One lane per robot, one block per walk wave (its 64 robots), like the waypoint cycler.  The EE pose of the active and the passive
-// device is seven coalesced 512-byte loads each of the tick's exchange block; the target record tgt[B][ndev][7] goes through an LDS
-// tile in the record type and is stored back -- the whole tile, untouched words bit for bit -- only by a wave in which a lane entered
-// a WP.  Per-robot state is SoA [field][stride]; a per-robot pose table is [walk wave][A][7][64], a shared one [A][7].  Idle lanes of a
-// ragged last wave neither load nor store.  The error is float64 (task_error6<double>, the target words converted to double), its
-// norm and the limit with every product and sum rounded on its own: the host can repeat them.
+// device is seven coalesced 512-byte loads each of the tick's exchange block; the target record tgt[B][ndev][7] goes through the
+// wave's target tile (osc_common.hpp: its contract), stored by a wave in which a lane entered a WP.  Per-robot state is SoA
+// [field][stride]; a per-robot pose table is [walk wave][A][7][64], a shared one [A][7].  The error is float64 (task_error6<double>,
+// the target words converted to double), its norm and the limit with every product and sum rounded on its own: the host can repeat them.
 //
 // Per robot on tick t of the list (A actions; a = action).  A robot's list starts on the FIRST TICK THAT RUNS IT (entered < 0: nothing
 // entered yet) -- tick 0 for every robot of a rollout over the whole list, a later one for a robot that earlier, narrower rollouts left
@@ -77,11 +76,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
     }
     const int row = a.ndev * 7;
     T* __restrict__ tg = (T*)a.tgt + (size_t)b0 * row;
-    for (int t = 0; t < row; ++t) {
-        const int i = t * 64 + lane;
-        if (i < nvalid * row) s_t[i] = tg[i];
-    }
-    __syncthreads();
+    tgt_tile_load(s_t, tg, nvalid, row);
     bool moved = false;
     if (valid) {                                    // idle lanes load nothing
         const int A = a.A;
@@ -157,12 +152,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
             ((T*)a.gains)[(so * a.ndev + a.active) * IRLOSC_GAIN_WORDS + 9] = (T)m;
         }
     }
-    if (!__any(moved)) return;                      // (one wave per block: uniform over the block)
-    __syncthreads();
-    for (int t = 0; t < row; ++t) {
-        const int i = t * 64 + lane;
-        if (i < nvalid * row) tg[i] = s_t[i];
-    }
+    tgt_tile_store(tg, s_t, nvalid, row, moved);
 }
 
 }  // namespace irlosc

@@ -207,6 +207,29 @@ __device__ __forceinline__ T wave_max(T v) {
     return v;
 }
 
+// The TARGET TILE of the kernels that write a slot's targets inside a rollout (osc_waypoint.hpp, osc_action.hpp: one block per walk
+// wave, one lane per robot).  The target record tgt[B][ndev][7] is row-major in the record type T, a lane's words 7 ndev apart, so the
+// wave's tile -- the rows of its nvalid robots, tg = tgt + b0 * row, row = ndev * 7 -- goes through LDS.  The contract: the tile stays
+// in the record type and is stored whole, so a word no lane rewrote goes back bit for bit; it is stored only by a wave in which a lane
+// moved a target; idle lanes of a ragged last wave (nvalid < 64) neither load nor store: only the wave's robots' words are touched.
+template <typename T>
+__device__ __forceinline__ void tgt_tile_load(T* s_t, const T* tg, int nvalid, int row) {
+    for (int t = 0; t < row; ++t) {
+        const int i = t * 64 + (int)threadIdx.x;
+        if (i < nvalid * row) s_t[i] = tg[i];
+    }
+    __syncthreads();
+}
+template <typename T>
+__device__ __forceinline__ void tgt_tile_store(T* tg, const T* s_t, int nvalid, int row, bool moved) {
+    if (!__any(moved)) return;                      // (one wave per block: uniform over the block)
+    __syncthreads();
+    for (int t = 0; t < row; ++t) {
+        const int i = t * 64 + (int)threadIdx.x;
+        if (i < nvalid * row) tg[i] = s_t[i];
+    }
+}
+
 // zero pattern asked of dense records (osc_structure_kernel): bit c of mrow[j]: M[j][c] may be non-zero; bit c of jcols: column c of J
 struct StructureMasks { uint32_t mrow[32]; uint32_t jcols; };
 

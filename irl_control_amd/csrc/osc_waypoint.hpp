@@ -5,11 +5,10 @@
 // targets by then, and the plant touches neither the EE entries of the exchange block nor the targets.
 //
 // One lane per robot, one block per walk wave (its 64 robots), like the plant.  The EE position is three coalesced 512-byte loads of
-// the step's exchange block (entries PlantArgs::ee0 names: x y z follow each other); the target record tgt[B][ndev][7] is row-major
-// in the record type: a wave's tile goes through LDS, kept in the record type, and is stored back -- the whole tile, untouched words
-// bit for bit -- only when a lane of the wave moved its target.  Per-robot state is SoA [ndev][stride]; a per-robot table is
-// [walk wave][dev][w][3][64] (a lane's waypoint: three coalesced loads), a shared one [dev][w][3].  Idle lanes of a ragged last wave
-// store nothing.  The distance is float64 with every product and sum rounded on its own (no contraction): the host can repeat it.
+// the step's exchange block (entries PlantArgs::ee0 names: x y z follow each other); the target record tgt[B][ndev][7] goes through
+// the wave's target tile (osc_common.hpp: its contract), stored by a wave in which a lane moved its target.  Per-robot state is SoA
+// [ndev][stride]; a per-robot table is [walk wave][dev][w][3][64] (a lane's waypoint: three coalesced loads), a shared one
+// [dev][w][3].  The distance is float64 with every product and sum rounded on its own (no contraction): the host can repeat it.
 //
 // init = 1 (irlosc_set_waypoints): state = (0, 0, -1) for listed devices, (-1, 0, -1) for the others, and waypoint 0 into the
 // targets of every listed device; the exchange block is not read.
@@ -18,6 +17,7 @@
 #include <stdint.h>
 
 #include "../../include/irlosc.h"
+#include "osc_common.hpp"
 
 namespace irlosc {
 
@@ -44,11 +44,7 @@ __global__ __launch_bounds__(64) void osc_waypoint_kernel(const WaypointArgs a) 
     const bool valid = lane < nvalid;
     const int row = a.ndev * 7;
     T* __restrict__ tg = (T*)a.tgt + (size_t)b0 * row;
-    for (int t = 0; t < row; ++t) {
-        const int i = t * 64 + lane;
-        if (i < nvalid * row) s_t[i] = tg[i];
-    }
-    __syncthreads();
+    tgt_tile_load(s_t, tg, nvalid, row);
     bool moved = false;
     for (int d = 0; d < a.ndev; ++d) {
         const int W = a.count[d];
@@ -89,12 +85,7 @@ __global__ __launch_bounds__(64) void osc_waypoint_kernel(const WaypointArgs a) 
             moved = true;
         }
     }
-    if (!__any(moved)) return;                      // (one wave per block: uniform over the block)
-    __syncthreads();
-    for (int t = 0; t < row; ++t) {
-        const int i = t * 64 + lane;
-        if (i < nvalid * row) tg[i] = s_t[i];
-    }
+    tgt_tile_store(tg, s_t, nvalid, row, moved);
 }
 
 }  // namespace irlosc

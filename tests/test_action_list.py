@@ -552,6 +552,60 @@ def test_state_rules():
     assert state_rc() == ERR_STATE
     assert set_al() == 0 and state_rc() == 0
     assert lib.irlosc_download_waypoint_state(h, 0, B, None, None, None) == ERR_STATE
+    # one writer of the targets (the table in include/irlosc.h): what an entry point does not end stays whole.  A list is in force here.
+    n = B - 6
+    keys = ("action", "grip_left", "err", "max_vel0", "gripper_force", "finished_tick")
+    wp = _lib.Waypoints()
+    wp.count[0], wp.threshold[0], wp.loop[0], wp.nb = 1, 0.01, 1, B
+    wp_tab = np.zeros((B, lay.ndev, 1, 3))
+    wp_tab[:, 0, 0] = sc["tgt"][:, 0, :3]                # one waypoint for device 0: its EE position at the start
+
+    def set_wp(tab=wp_tab):
+        return lib.irlosc_set_waypoints(h, 0, B, C.byref(wp), _lib.ptr(tab))
+
+    def wp_rc():
+        return lib.irlosc_download_waypoint_state(h, 0, B, None, None, None)
+
+    def al_state(m):
+        out = dict(action=np.empty(m, np.int32), grip_left=np.empty(m, np.int32), err=np.empty(m), max_vel0=np.empty(m),
+                   gripper_force=np.empty(m), finished_tick=np.empty(m, np.int32))
+        assert lib.irlosc_download_action_state(h, 0, m, *[_lib.ptr(out[k]) for k in keys]) == 0
+        return out
+
+    # ... a NULL paths description ends only paths; a refused irlosc_set_waypoints changes nothing: IRLOSC_ERR_ARG (a NaN waypoint) ...
+    assert lib.irlosc_set_waypoints(h, 0, B, None, None) == 0 and state_rc() == 0
+    osc.rollout(3)
+    before = al_state(B)
+    nan_tab = wp_tab.copy()
+    nan_tab[B - 1, 0, 0, 1] = np.nan
+    assert set_wp(nan_tab) == ERR_ARG
+    after = al_state(B)
+    assert all(np.array_equal(before[k], after[k]) for k in keys)
+    # ... and IRLOSC_ERR_STATE (paths for more robots than the targets cover)
+    assert lib.irlosc_set_targets(h, 0, n, _lib.ptr(np.ascontiguousarray(sc["tgt"][:n])), None) == 0
+    assert set_al(n=n, p=np.ascontiguousarray(pose[:n]), nb=n) == 0
+    assert lib.irlosc_rollout_from_q(h, 0, n, 3, 0, None, None, None) == 0
+    before = al_state(n)
+    assert set_wp() == ERR_STATE and "irlosc_set_targets" in lib.irlosc_last_error(h).decode()
+    after = al_state(n)
+    assert all(np.array_equal(before[k], after[k]) for k in keys)
+    # paths that replace a list count their ticks from 0 (the list's counter stood at 3) ...
+    osc.set_targets(sc["tgt"])
+    osc.upload_q(sc["q"], sc["qd"])                      # (the narrower rollout left coordinates of n robots)
+    assert set_al() == 0
+    osc.rollout(3)
+    osc.upload_q(sc["q"], sc["qd"])                      # (back at the start: device 0 arrives on tick 0, and again on tick 1)
+    assert set_wp() == 0 and wp_rc() == 0 and state_rc() == ERR_STATE
+    osc.rollout(2)
+    before = osc.waypoint_state()
+    assert before["last_tick"][:, 0].min() >= 0 and before["last_tick"][:, 0].max() <= 1 and np.all(before["last_tick"][:, 1:] == -1)
+    # ... and irlosc_set_gains, a NULL list description and a refused irlosc_set_action_list leave them whole
+    assert lib.irlosc_set_gains(h, _lib.ptr(g), _lib.ptr(nk), nb) == 0 and wp_rc() == 0
+    assert lib.irlosc_set_action_list(h, 0, B, None, None) == 0 and wp_rc() == 0
+    assert set_al(n_actions=0) == ERR_ARG and wp_rc() == 0
+    after = osc.waypoint_state()
+    assert all(np.array_equal(before[k], after[k]) for k in before)
+    assert set_al() == 0 and state_rc() == 0 and wp_rc() == ERR_STATE
     osc.upload_q(sc["q"], sc["qd"])                      # uploads of coordinates leave the list alone
     assert state_rc() == 0
     osc.set_model(RigidBodyModel.load("dual_ur5"))
