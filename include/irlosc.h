@@ -452,7 +452,7 @@ typedef struct irlosc_plant {
 IRLOSC_API int irlosc_set_plant(irlosc_ctx* ctx, const irlosc_plant* plant);
 /* `ticks` (>= 1) dependent ticks on slot `slot`'s B robots, enqueued back to back on the context's stream, one host synchronisation
  * at the end.  A tick is one fused train of one step on bank 0 -- walk, the sensor feed's wrench if the slot has a feed (its readings
- * stay what irlosc_set_sensordata put there), OSC step, eigen pass, give-up pass -- and behind it the plant kernel.  Targets (target
+ * stay what irlosc_set_sensordata put there; a sensed push of the slot, irlosc_set_pushes, is taken off the wrench computed from them), OSC step, eigen pass, give-up pass -- and behind it the plant kernel.  Targets (target
  * velocities included) are the slot's, gains the context's.  The slot keeps B robots of coordinates, targets and feed; as after
  * every fused step it holds no dense records afterwards.
  *   trace_every > 0 and ee_trace_host != NULL: ee_trace_host[i][B][ndev][7] (double) = the EE poses at the START of tick
@@ -484,7 +484,11 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  * Uploads of coordinates, records and sensor feeds leave the program alone.  Only irlosc_rollout_from_q runs it (on at most the B
  * robots it was set for: IRLOSC_ERR_STATE beyond); every other step ignores it and leaves its state as it is.  Its tick counts the
  * slot's rollout ticks since its setter and continues across calls of irlosc_rollout_from_q.  Clearing a program leaves the targets
- * as they are. */
+ * as they are.
+ * EXTERNAL PUSHES (irlosc_set_pushes) write no targets, so they are no program: they coexist with paths and with a list, and neither
+ * ends the other.  What ends them: irlosc_set_pushes with desc == NULL, and irlosc_set_model (the exchange block's entry layout belongs
+ * to the model).  Uploads, irlosc_set_targets, irlosc_set_gains and sensor feeds leave them and their tick alone.  Like a program only
+ * irlosc_rollout_from_q runs them and advances their tick. */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -579,6 +583,50 @@ IRLOSC_API int irlosc_set_action_list(irlosc_ctx* ctx, int32_t slot, int32_t B, 
  * IRLOSC_ERR_STATE on a slot without a list, or with a list for fewer than B robots.  Synchronous. */
 IRLOSC_API int irlosc_download_action_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* action, int32_t* grip_left, double* err,
                                             double* max_vel0, double* gripper_force, int32_t* finished_tick);
+
+/* ---- external pushes on the plant, sensed by the F/T feed: admit_test / force_test inside a rollout (csrc/osc_push.hpp) ------------
+ * What examples/headless_loops.py::admit_test_loop does on the host -- xfrc_applied on a gripper body during a window of ticks, the
+ * F/T sensors reading the reaction after sim.step() (fakesim.ToyDynamics), the next `generate` yielding to it -- as up to two more
+ * small launches of a rollout tick.  The force is prescribed by the caller, as in the reference; there is no contact model.
+ * Robot b on tick t, counted in the slot's rollout ticks since irlosc_set_pushes (it continues across calls of irlosc_rollout_from_q):
+ *     W_d(t) = the sum, in ascending p, of wrench[b][p] over the pushes with dev[p] == d and tick0[p] <= t < tick1[p]: float64, the
+ *              first term taken as it is, every add rounded on its own.  W_d^apply takes the pushes with apply[p], W_d^sense those
+ *              with sense[p].
+ *   APPLY, behind the give-up pass and the waypoint cycler, in front of the plant kernel: for every device d with a non-empty
+ *     W_d^apply(t), in ascending d, and every hinge i above that device's EE body
+ *         bias_i <- bias_i - sum_{c = 0..5} J_d[c][i] W_d^apply(t)[c]          (an fma chain in ascending c)
+ *     in place on the tick's exchange block, so that the unchanged plant integrates M^-1 (u - bias - damping qvel + sum_d J_d^T W_d).
+ *     J_d is the EE body's Jacobian the walk left in the block (jacp rows, then jacr rows, at the body's FRAME ORIGIN), all six rows
+ *     whatever rows the layout controls.  The force therefore acts at the EE body's frame origin -- the point the controller
+ *     controls -- and the torque is a pure couple.  MuJoCo's xfrc_applied acts at the body's centre of mass, and the reference demo
+ *     pushes a gripper body below the EE: this is the contact-free stand-in, not MuJoCo.  Two devices that name one EE body sum.
+ *   SENSE, between the sensor feed's wrench kernel and every kernel that reads the wrench (action kernel, OSC kernels, give-up pass):
+ *     the reference reads the sensors after the step that felt the push, so the OSC step of tick t sees the push of tick t - 1.  On
+ *     tick t >= 1, for every device d with a non-empty W_d^sense(t - 1)
+ *         wrench[b][d][c] <- (T)((double)wrench[b][d][c] - W_d^sense(t - 1)[c])          (T: the context's dtype)
+ *     -- ToyDynamics' sign ("the reaction": s0 - xfrc_applied), taken in the world frame.  Only where the slot has a sensor feed and
+ *     the device a sensor; elsewhere `sense` changes nothing, as a feed changes nothing without IRLOSC_ADMITTANCE.  The slot's record
+ *     wrench is never written.
+ * A tick on which nothing is applied and nothing is sensed launches exactly the kernels a slot without pushes launches: the host
+ * knows the tick, the active sets are kernel arguments, there is no device-side tick state. */
+#define IRLOSC_MAX_PUSHES 8
+typedef struct irlosc_pushes {
+    int32_t n_pushes;                       /* P in [1, IRLOSC_MAX_PUSHES] */
+    int32_t nb;                             /* 1 = one wrench table for the fleet, B = a table per robot */
+    int32_t dev[IRLOSC_MAX_PUSHES];         /* target device (targets order) whose EE body is pushed */
+    int32_t tick0[IRLOSC_MAX_PUSHES];       /* active on ticks t with tick0 <= t < tick1; 0 <= tick0 < tick1 */
+    int32_t tick1[IRLOSC_MAX_PUSHES];
+    uint8_t apply[IRLOSC_MAX_PUSHES];       /* 1: acts on the plant */
+    uint8_t sense[IRLOSC_MAX_PUSHES];       /* 1: appears in the F/T wrench, one tick later */
+} irlosc_pushes;
+/* Gives slot `slot`'s B robots their pushes: wrench[nb][P][6] double, world frame, fx fy fz tx ty tz; tick base 0.  After
+ * irlosc_set_model (IRLOSC_ERR_STATE before).  Every argument is checked before anything is touched (IRLOSC_ERR_ARG: P outside [1, 8],
+ * dev outside [0, ndev), a window that is not 0 <= tick0 < tick1, apply or sense not 0 / 1 or both 0, nb not 1 or B, B < 1, wrench
+ * NULL or holding a value that is not finite; the pushes in force stay, whole).  desc == NULL clears the slot's pushes; what else ends
+ * them and who runs them: "one writer of the targets" above.  A rollout over more robots than the pushes cover answers
+ * IRLOSC_ERR_STATE.  The table is allocated by the first use and kept; IRLOSC_ERR_HIP -- the allocation or the copy failed -- leaves the
+ * slot without pushes.  Synchronous. */
+IRLOSC_API int irlosc_set_pushes(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_pushes* desc, const double* wrench);
 
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard

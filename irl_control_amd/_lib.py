@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("IRLOSC_LIB", os.path.join(_HERE, "libirlosc.so"))   #
 MAX_DEV, MAX_N, MAX_K, GAIN_WORDS, MAX_BODIES = 4, 32, 16, 12, 64
 MAX_WAYPOINTS = 64
 MAX_ACTIONS = 32
+MAX_PUSHES = 8
 ACTION_WP, ACTION_GRIP = 0, 1
 F32, F64 = 0, 1
 USE_G, ADMITTANCE, NULLSPACE = 1, 2, 4
@@ -29,7 +30,8 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_step_from_q", "irlosc_from_q_name", "irlosc_slot_structure", "irlosc_probe_structure", "irlosc_time_trains", "irlosc_giveup_counts",
            "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device",
            "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q",
-           "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state"]
+           "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state",
+           "irlosc_set_pushes"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -83,6 +85,12 @@ class ActionList(C.Structure):
                 ("kind", C.c_int32 * MAX_ACTIONS), ("xyz_from_start", C.c_int32 * MAX_ACTIONS), ("grip_ticks", C.c_int32 * MAX_ACTIONS),
                 ("kp", C.c_double * MAX_ACTIONS), ("max_error", C.c_double * MAX_ACTIONS), ("min_speed", C.c_double * MAX_ACTIONS),
                 ("max_speed", C.c_double * MAX_ACTIONS), ("gripper_force", C.c_double * MAX_ACTIONS)]
+
+
+class Pushes(C.Structure):
+    """struct irlosc_pushes (include/irlosc.h): the external pushes of irlosc_set_pushes."""
+    _fields_ = [("n_pushes", C.c_int32), ("nb", C.c_int32), ("dev", C.c_int32 * MAX_PUSHES), ("tick0", C.c_int32 * MAX_PUSHES),
+                ("tick1", C.c_int32 * MAX_PUSHES), ("apply", C.c_uint8 * MAX_PUSHES), ("sense", C.c_uint8 * MAX_PUSHES)]
 
 
 class Cfg(C.Structure):
@@ -162,6 +170,7 @@ def load():
     lib.irlosc_download_waypoint_state.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.irlosc_set_action_list.argtypes = [vp, i32, i32, C.POINTER(ActionList), vp]
     lib.irlosc_download_action_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.irlosc_set_pushes.argtypes = [vp, i32, i32, C.POINTER(Pushes), vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

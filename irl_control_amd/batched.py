@@ -447,6 +447,39 @@ class BatchedOSC:
                                                                              ("action", "grip_left", "err", "max_vel0", "gripper_force", "finished_tick")]))
         return out
 
+    # -- external pushes of the rollout (irlosc_set_pushes) ---------------------------------------------------------------------------
+    def set_pushes(self, pushes, wrench=None, slot: int = 0):
+        """External wrenches on EE bodies during windows of the slot's rollout ticks, as examples/headless_loops.py::admit_test_loop
+        sets xfrc_applied: `pushes` is a list of dict(dev=name_or_index, window=(tick0, tick1), apply=True, sense=True) -- active on the
+        ticks tick0 <= t < tick1 counted since this call (pushes.push_window_ticks maps the reference's window); `apply`: it acts on
+        the plant (at the EE body's frame origin), `sense`: the F/T wrench of the next tick carries its reaction (slots with a sensor
+        feed).  `wrench`: [P, 6] (one table for the fleet) or [B, P, 6], world frame, fx fy fz tx ty tz.  After set_model.  pushes=None
+        (or clear_pushes) ends them and nothing else; they coexist with waypoint paths and an action list."""
+        from . import pushes as _p
+        B = self._B[slot]
+        if pushes is None:
+            self._chk(self.lib.irlosc_set_pushes(self._h, slot, B, None, None))
+            return
+        P = len(pushes)
+        if not 1 <= P <= _lib.MAX_PUSHES:
+            raise ValueError(f"a slot holds 1 to {_lib.MAX_PUSHES} pushes, got {P}")
+        dev, t0, t1, ap, se = _p.normalise(pushes, self.layout.dev_names)
+        w = np.ascontiguousarray(wrench, dtype=np.float64)
+        if w.ndim == 2:
+            w = w[None]
+        if w.ndim != 3 or w.shape[1:] != (P, 6) or w.shape[0] not in (1, B):
+            raise ValueError(f"wrench: expected shape ({P}, 6) or ({B}, {P}, 6), got {np.shape(wrench)}")
+        desc = _lib.Pushes()
+        desc.n_pushes, desc.nb = P, w.shape[0]
+        for p in range(P):
+            desc.dev[p], desc.tick0[p], desc.tick1[p] = int(dev[p]), int(t0[p]), int(t1[p])
+            desc.apply[p], desc.sense[p] = int(ap[p]), int(se[p])
+        self._chk(self.lib.irlosc_set_pushes(self._h, slot, B, C.byref(desc), _lib.ptr(np.ascontiguousarray(w))))
+
+    def clear_pushes(self, slot: int = 0):
+        """Ends the slot's pushes (irlosc_set_pushes with desc == NULL); targets, programs and feeds are left alone."""
+        self.set_pushes(None, slot=slot)
+
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""
         B = self._B[first_slot] if B is None else B

@@ -27,6 +27,7 @@
 #include "osc_plant.hpp"
 #include "osc_waypoint.hpp"
 #include "osc_action.hpp"
+#include "osc_push.hpp"
 #include "launchers.hpp"
 #include "dev_mem.hpp"
 
@@ -65,6 +66,31 @@ struct Program {
     void ticked() { ++tick; }
 };
 
+// The external pushes of a slot's rollouts (irlosc_set_pushes, osc_push.hpp): wrenches on EE bodies during windows of ticks, applied
+// to the plant and / or taken off the sensor feed's wrench a tick later.  They write no targets, so they are no Program and live next
+// to one.  Written by the transitions below and by nothing else.
+struct Pushes {
+    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+    irlosc_pushes d{};         // the description in force
+    DevBuf<double> table;      // the wrenches (walk_table), allocated by the first use, kept across settings and grown on demand
+
+    // Pushes of B robots are in force, their table on the device.
+    void set(int B, const irlosc_pushes& desc) { robots = B; tick = 0; d = desc; }
+    // They end: their setter cleared them, the model changed (the block's entry layout is the model's), or their table failed.
+    void end() { robots = 0; tick = 0; }
+    // A tick of a rollout ran (with or without a launch of theirs: the windows are judged on the host).
+    void ticked() { if (robots) ++tick; }
+    // The pushes whose window holds tick t and that act on the plant / are read by the sensors: bit p
+    uint32_t active(int t, const uint8_t* which) const {
+        uint32_t m = 0;
+        for (int p = 0; robots && t >= 0 && p < d.n_pushes; ++p)
+            if (which[p] && d.tick0[p] <= t && t < d.tick1[p]) m |= 1u << p;
+        return m;
+    }
+    uint32_t applied() const { return active(tick, d.apply); }        // on this tick
+    uint32_t sensed() const { return active(tick - 1, d.sense); }     // on this tick: what the step of the tick before felt
+};
+
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
 // (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
 // the fused path is on, sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
@@ -95,6 +121,7 @@ struct Slot {
     DevBuf<double> sens;       // (grown to max_batch x the description's n_sensor doubles)
     int feed = 0;              // robots of the feed (0 = no feed)
     Program prog;              // what writes the targets inside a rollout
+    Pushes push;               // what pushes the plant inside a rollout
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -1488,7 +1515,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1702,6 +1729,20 @@ static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, con
     return a;
 }
 
+// The arguments of the slot's push kernel over B robots: the pushes of `active`, applied to exchange block xside or (xside == nullptr)
+// taken off the feed's wrench
+static PushArgs push_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t active, double* xside, void* wrench) {
+    const Pushes& p = s.push;
+    PushArgs a;
+    memset(&a, 0, sizeof a);
+    a.xside = xside; a.wrench = wrench; a.table = p.table;
+    a.B = B; a.ndev = c->cfg.ndev; a.P = p.d.n_pushes; a.per_robot = p.d.nb > 1;
+    a.apply = xside ? 1 : 0; a.active = active;
+    for (int i = 0; i < p.d.n_pushes; ++i) a.dev[i] = p.d.dev[i];
+    for (int d = 0; d < c->cfg.ndev; ++d) a.ee0[d] = c->model.tables.eetab[d][0];
+    return a;
+}
+
 // The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
 static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
     const Program& p = c->slot[slot].prog;
@@ -1772,6 +1813,11 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     const hipStream_t st = dv ? dv->st : bk.st;
     Slot& s0 = c->slot[slots[0]];      // (the slot of a rollout's tick)
     const Program::Kind prog = pl ? s0.prog.kind : Program::NONE;      // what writes its targets inside the rollout
+    // what pushes its plant on this tick, and what its sensors read of the tick before: where it has a feed and the device a sensor
+    const uint32_t push_apply = pl ? s0.push.applied() : 0u;
+    uint32_t push_sense = pl && s0.feed > 0 ? s0.push.sensed() : 0u;
+    for (int p = 0; push_sense && p < IRLOSC_MAX_PUSHES; ++p)
+        if (((push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) push_sense &= ~(1u << p);
     FtStep fts[R16_TRAIN];
     int nft = 0;
     FeLaneTrain ft;
@@ -1825,6 +1871,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     HIPCHK(c, (hipError_t)fused_walk(c).launch(c->model.dmodel, ft, n, st));
     int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
     if (rcw) return rcw;
+    if (push_sense)      // the sensed pushes: the reaction goes into the wrench ahead of every kernel that reads it
+        HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_sense, nullptr, fts[0].wrench), st));
     if (prog == Program::LIST)      // the action list: its targets and velocity limit are this tick's, so in front of every OSC kernel
         HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (use_lane) {
@@ -1837,6 +1885,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
     if (prog == Program::PATHS)      // the targets move where an arm arrived: behind every OSC kernel of the tick, in front of the plant
         HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s0, B, s0.prog.wp, bk.xside[0], s0.prog.tick), st));
+    if (push_apply)      // the applied pushes: into the bias entries of the block, which only the plant reads from here on
+        HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_apply, bk.xside[0], nullptr), st));
     if (pl) {
         PlantArgs pa;
         memset(&pa, 0, sizeof pa);
@@ -1855,6 +1905,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
     if (pl) s0.advanced(B);
     if (prog != Program::NONE) s0.prog.ticked();
+    if (pl) s0.push.ticked();
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2120,6 +2171,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     rc = check_slot_q(c, slot, B);
     if (!rc) rc = check_slot_feed(c, slot, B);
     if (!rc) rc = check_program(c, slot, B);
+    if (!rc && c->slot[slot].push.robots && B > c->slot[slot].push.robots)
+        rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its pushes cover %d robots, rollout asked for %d", slot, c->slot[slot].push.robots, B);
     if (rc) return rc;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
@@ -2207,6 +2260,44 @@ extern "C" int irlosc_download_waypoint_state(irlosc_ctx* c, int32_t slot, int32
     for (size_t i = 0; i < 3; ++i)
         for (size_t b = 0; dst[i] && b < (size_t)B; ++b)
             for (size_t d = 0; d < nd; ++d) dst[i][b * nd + d] = h[(i * nd + d) * Bm + b];
+    return IRLOSC_OK;
+}
+
+// ---- external pushes of the rollout (osc_push.hpp) ----------------------------------------------------------------------------
+extern "C" int irlosc_set_pushes(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_pushes* d, const double* wrench) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.push.end(); return IRLOSC_OK; }
+    const int nd = c->cfg.ndev, P = d->n_pushes;
+    if (P < 1 || P > IRLOSC_MAX_PUSHES) return fail(c, IRLOSC_ERR_ARG, "pushes: n_pushes=%d out of [1,%d]", P, IRLOSC_MAX_PUSHES);
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "pushes: B=%d must be >= 1", B);
+    if (d->nb != 1 && d->nb != B) return fail(c, IRLOSC_ERR_ARG, "pushes: nb=%d must be 1 or B=%d", d->nb, B);
+    for (int p = 0; p < P; ++p) {
+        if (d->dev[p] < 0 || d->dev[p] >= nd) return fail(c, IRLOSC_ERR_ARG, "pushes: dev[%d]=%d out of [0,%d)", p, d->dev[p], nd);
+        if (d->tick0[p] < 0 || d->tick0[p] >= d->tick1[p])
+            return fail(c, IRLOSC_ERR_ARG, "pushes: window [%d,%d) of push %d must hold 0 <= tick0 < tick1", d->tick0[p], d->tick1[p], p);
+        if (d->apply[p] > 1 || d->sense[p] > 1 || !(d->apply[p] | d->sense[p]))
+            return fail(c, IRLOSC_ERR_ARG, "pushes: apply[%d]=%d, sense[%d]=%d must be 0 or 1 and not both 0", p, (int)d->apply[p], p, (int)d->sense[p]);
+    }
+    if (!wrench) return fail(c, IRLOSC_ERR_ARG, "pushes: wrench is NULL");
+    const size_t E = (size_t)P * 6;
+    for (size_t i = 0; i < (size_t)d->nb * E; ++i)
+        if (!std::isfinite(wrench[i]))
+            return fail(c, IRLOSC_ERR_ARG, "pushes: wrench of push %zu, robot %zu is not finite", i % E / 6, i / E);
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Pushes& ps = s.push;
+    ps.end();          // (none until the new ones are in their table)
+    const std::vector<double> tab = walk_table(wrench, d->nb, E);
+    const size_t bytes = tab.size() * sizeof(double);
+    if (!got(ps.table.reserve(bytes))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for the pushes of slot %d (%zu bytes)", slot, bytes);
+    const hipError_t ec = hipMemcpyAsync(ps.table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when the copy failed: the host array is its source)
+    HIPCHK(c, ec);
+    HIPCHK(c, es);
+    ps.set(B, *d);
     return IRLOSC_OK;
 }
 

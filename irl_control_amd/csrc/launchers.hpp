@@ -100,6 +100,12 @@ struct ActionArgs;
 template <typename T>
 int launch_actions(const ActionArgs& a, hipStream_t st);
 
+// tu_push.hip -- the external pushes of a rollout tick whose slot has some active (osc_push.hpp): sense mode between the sensor feed's
+// wrench kernel and the first kernel that reads the wrench, apply mode in front of the plant; T = record type (of the wrench)
+struct PushArgs;
+template <typename T>
+int launch_pushes(const PushArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;
