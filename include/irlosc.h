@@ -439,7 +439,7 @@ IRLOSC_API int irlosc_step_from_q_device(irlosc_ctx* ctx, int32_t slot, int32_t 
  * What examples/closed_loop_headless.py does on the host per tick, as one more kernel behind a fused step from joint coordinates:
  *     rhs_j = (ctrl_mask bit j ? u_j : 0) - bias_j - damping qvel_j;   qacc = M^-1 rhs;   qvel += dt qacc;   qpos += dt qvel
  * from the M, bias the step's own walk left in its exchange buffer and the u the step computed, written back into the slot's
- * coordinates (row-major and walk layout alike).  NOT a simulator: no contacts, no joint limits, no equality constraints.  float64
+ * coordinates (row-major and walk layout alike).  NOT a simulator: no contacts (but the penalty walls of irlosc_set_walls), no joint limits, no equality constraints.  float64
  * arithmetic whatever the context's dtype (u is read in the context's dtype). */
 typedef struct irlosc_plant {
     double dt;               /* > 0, finite */
@@ -452,7 +452,7 @@ typedef struct irlosc_plant {
 IRLOSC_API int irlosc_set_plant(irlosc_ctx* ctx, const irlosc_plant* plant);
 /* `ticks` (>= 1) dependent ticks on slot `slot`'s B robots, enqueued back to back on the context's stream, one host synchronisation
  * at the end.  A tick is one fused train of one step on bank 0 -- walk, the sensor feed's wrench if the slot has a feed (its readings
- * stay what irlosc_set_sensordata put there; a sensed push of the slot, irlosc_set_pushes, is taken off the wrench computed from them), OSC step, eigen pass, give-up pass -- and behind it the plant kernel.  Targets (target
+ * stay what irlosc_set_sensordata put there; a sensed push of the slot, irlosc_set_pushes, and the force of its walls, irlosc_set_walls, are taken off the wrench computed from them), OSC step, eigen pass, give-up pass -- and behind it the plant kernel.  Targets (target
  * velocities included) are the slot's, gains the context's.  The slot keeps B robots of coordinates, targets and feed; as after
  * every fused step it holds no dense records afterwards.
  *   trace_every > 0 and ee_trace_host != NULL: ee_trace_host[i][B][ndev][7] (double) = the EE poses at the START of tick
@@ -488,7 +488,14 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  * EXTERNAL PUSHES (irlosc_set_pushes) write no targets, so they are no program: they coexist with paths and with a list, and neither
  * ends the other.  What ends them: irlosc_set_pushes with desc == NULL, and irlosc_set_model (the exchange block's entry layout belongs
  * to the model).  Uploads, irlosc_set_targets, irlosc_set_gains and sensor feeds leave them and their tick alone.  Like a program only
- * irlosc_rollout_from_q runs them and advances their tick. */
+ * irlosc_rollout_from_q runs them and advances their tick.
+ * COMPLIANT WALLS (irlosc_set_walls) write no targets either: they coexist with paths, a list and pushes, and none ends another.
+ *     irlosc_set_walls with desc == NULL, irlosc_set_model (all slots)                 walls end
+ *     irlosc_set_walls that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE                 nothing changes: the walls in force stay, whole
+ *     irlosc_set_walls that succeeds                                                   its walls replace those in force; state and tick reset
+ *     irlosc_set_walls that answers IRLOSC_ERR_HIP                                     no walls
+ *     everything else (uploads, targets, gains, feeds, programs, pushes, other steps)  leaves them, their state and their tick alone
+ * Only irlosc_rollout_from_q runs them and advances their tick. */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -627,6 +634,49 @@ typedef struct irlosc_pushes {
  * IRLOSC_ERR_STATE.  The table is allocated by the first use and kept; IRLOSC_ERR_HIP -- the allocation or the copy failed -- leaves the
  * slot without pushes.  Synchronous. */
 IRLOSC_API int irlosc_set_pushes(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_pushes* desc, const double* wrench);
+
+/* ---- compliant walls on EE bodies, sensed by the F/T feed: force_test's wall inside a rollout (csrc/osc_wall.hpp) ------------------
+ * In the reference's force_test the left arm walks a line of waypoints into a wall whose geom has solref="-900 -20": a direct spring
+ * (900) and damper (20).  Here a wall is a half-space with stiffness and damping, and the EE a sphere of radius r around the EE body's
+ * FRAME ORIGIN -- the point the controller controls.  The force is computed on the device, per robot and per tick, from the state the
+ * rollout itself produced: a closed loop.  It is NOT MuJoCo's soft constraint: no friction, no geometry beyond planes, one contact point.
+ * Robot b on tick t, counted in the slot's rollout ticks since irlosc_set_walls (it continues across calls of irlosc_rollout_from_q),
+ * wall w on device d, table row  nx ny nz off r k c 0  (n a unit vector of the world frame, n.x >= off the free side):
+ *     x   = the EE xyz of this tick's walk;   v_c = sum_i J_d[c][i] qvel_i, c = 0..2, over the hinges above the EE body in ascending i
+ *           (J_d: the EE body's jacp rows at its frame origin, qvel as this tick's walk read it)
+ *     g   = r - ((n0 x0 + n1 x1 + n2 x2) - off)        s = n0 v0 + n1 v1 + n2 v2        f = k g - c s
+ *     F_w = (g > 0 && f > 0) ? f n : 0
+ *     F_d(t) = the sum of F_w over the device's walls in ascending w, the first term taken as it is.
+ *   Float64 whatever the context's dtype; every product, add and subtract rounded on its own, sums left to right as written (the host
+ *   can repeat it: irl_control_amd/walls.py).  A wall never pulls.  A NaN anywhere gives no contact and no force.
+ *   APPLY, behind the give-up pass, the waypoint cycler and the pushes' APPLY, in front of the plant kernel: for devices in ascending d
+ *     and every hinge i above the EE body   bias_i <- fma(-J_d[2][i], F2, fma(-J_d[1][i], F1, fma(-J_d[0][i], F0, bias_i)))   in place
+ *     on the tick's exchange block.  A robot whose F_d is all zero has its bias left as it is.  F_d(t) goes into the per-robot state,
+ *     zeros included.
+ *   SENSE, between the pushes' SENSE and the action kernel, on every tick t >= 1, where the slot has a sensor feed and the device a
+ *     sensor:   wrench[b][d][c] <- (T)((double)wrench[b][d][c] - F_d(t - 1)[c]), c = 0..2; the torque words are untouched.  F_d(t - 1)
+ *     is the stored force of the last tick that ran robot b.
+ * State per robot and device, reset by the setter: force[3] (what the last tick applied), max_depth (the largest g > 0 seen, or 0),
+ * contact_ticks (ticks on which a wall of the device had g > 0), first_tick (the first such tick, or -1).
+ * A slot without walls launches exactly the kernels it launched before. */
+#define IRLOSC_MAX_WALLS 8
+typedef struct irlosc_walls {
+    int32_t n_walls;                        /* W in [1, IRLOSC_MAX_WALLS] */
+    int32_t nb;                             /* 1 = one table for the fleet, B = a table per robot */
+    int32_t dev[IRLOSC_MAX_WALLS];          /* target device (targets order) whose EE body the wall acts on */
+} irlosc_walls;
+/* Gives slot `slot`'s B robots their walls: table[nb][W][8] double, rows  nx ny nz off r k c 0.  After irlosc_set_model (IRLOSC_ERR_STATE
+ * before).  Every argument is checked before anything is touched (IRLOSC_ERR_ARG: W outside [1, 8], dev outside [0, ndev), nb not 1 or
+ * B, B < 1, table NULL or holding a value that is not finite, | |n|^2 - 1 | > 1e-12, r, k or c < 0; the walls in force stay, whole).
+ * desc == NULL clears the slot's walls; what else ends them and who runs them: "one writer of the targets" above.  A rollout over more
+ * robots than the walls cover answers IRLOSC_ERR_STATE.  Table and state are allocated by the first use and kept; IRLOSC_ERR_HIP -- an
+ * allocation or a copy failed -- leaves the slot without walls.  Synchronous. */
+IRLOSC_API int irlosc_set_walls(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_walls* desc, const double* table);
+/* The walls' per-robot state of the slot's first B robots: force[B][ndev][3], max_depth[B][ndev] (double), contact_ticks[B][ndev],
+ * first_tick[B][ndev] (int32); any may be NULL.  IRLOSC_ERR_STATE: the slot has no walls, or they cover fewer than B robots.
+ * Synchronous. */
+IRLOSC_API int irlosc_download_wall_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* force, double* max_depth,
+                                          int32_t* contact_ticks, int32_t* first_tick);
 
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard

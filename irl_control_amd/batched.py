@@ -480,6 +480,43 @@ class BatchedOSC:
         """Ends the slot's pushes (irlosc_set_pushes with desc == NULL); targets, programs and feeds are left alone."""
         self.set_pushes(None, slot=slot)
 
+    # -- compliant walls of the rollout (irlosc_set_walls / irlosc_download_wall_state) ------------------------------------------------
+    def set_walls(self, walls, slot: int = 0):
+        """Penalty walls on EE bodies inside the slot's rollouts, as the wall of the reference's force_test scene: `walls` is a list of
+        dict(dev=name_or_index, normal=(nx, ny, nz), offset= | point=, radius=0, stiffness=, damping=0), values scalars or per-robot
+        arrays (walls.normalise).  The EE is a sphere of `radius` around the EE body's frame origin; inside the half-space the force
+        stiffness x depth - damping x approach speed acts along the normal, never pulling, and the F/T wrench of the next tick carries
+        its reaction (slots with a sensor feed).  After set_model; resets the walls' state and tick.  walls=None (or clear_walls) ends
+        them and nothing else; they coexist with waypoint paths, an action list and pushes.  Not MuJoCo's soft constraint: no friction,
+        planes only, one contact point."""
+        from . import walls as _w
+        B = self._B[slot]
+        if walls is None:
+            self._chk(self.lib.irlosc_set_walls(self._h, slot, B, None, None))
+            return
+        dev, table = _w.normalise(walls, self.layout.dev_names, B)
+        desc = _lib.Walls()
+        desc.n_walls, desc.nb = len(dev), table.shape[0]
+        for w in range(len(dev)):
+            desc.dev[w] = int(dev[w])
+        self._chk(self.lib.irlosc_set_walls(self._h, slot, B, C.byref(desc), _lib.ptr(np.ascontiguousarray(table))))
+
+    def clear_walls(self, slot: int = 0):
+        """Ends the slot's walls (irlosc_set_walls with desc == NULL); targets, programs, pushes and feeds are left alone."""
+        self.set_walls(None, slot=slot)
+
+    def wall_state(self, slot: int = 0):
+        """-> dict(force [B, ndev, 3], max_depth [B, ndev], contact_ticks [B, ndev], first_tick [B, ndev]): per robot and device the
+        force the last rollout tick applied, the deepest penetration seen since set_walls (0: none), the ticks in contact and the first
+        of them (-1: none).  Devices without a wall report (0, 0, 0, -1).  (irlosc_download_wall_state)"""
+        L, B = self.layout, self._B[slot]
+        force = np.empty((B, L.ndev, 3), dtype=np.float64)
+        depth = np.empty((B, L.ndev), dtype=np.float64)
+        ticks = np.empty((B, L.ndev), dtype=np.int32)
+        first = np.empty((B, L.ndev), dtype=np.int32)
+        self._chk(self.lib.irlosc_download_wall_state(self._h, slot, B, _lib.ptr(force), _lib.ptr(depth), _lib.ptr(ticks), _lib.ptr(first)))
+        return dict(force=force, max_depth=depth, contact_ticks=ticks, first_tick=first)
+
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""
         B = self._B[first_slot] if B is None else B

@@ -28,6 +28,7 @@
 #include "osc_waypoint.hpp"
 #include "osc_action.hpp"
 #include "osc_push.hpp"
+#include "osc_wall.hpp"
 #include "launchers.hpp"
 #include "dev_mem.hpp"
 
@@ -91,6 +92,30 @@ struct Pushes {
     uint32_t sensed() const { return active(tick - 1, d.sense); }     // on this tick: what the step of the tick before felt
 };
 
+// The compliant walls of a slot's rollouts (irlosc_set_walls, osc_wall.hpp): penalty half-spaces on EE bodies, their force computed on
+// the device per robot and tick, applied to the plant and taken off the sensor feed's wrench a tick later.  They write no targets, so
+// they are no Program and live next to one and next to Pushes.  Written by the transitions below and by nothing else.
+struct Walls {
+    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+    irlosc_walls d{};          // the description in force
+    DevBuf<double> table;      // the rows (walk_table), allocated by the first use, kept across settings and grown on demand
+    DevBuf<double> st_d;       // state [4][ndev][max_batch]: force xyz, max_depth
+    DevBuf<int32_t> st_i;      // state [2][ndev][max_batch]: contact_ticks, first_tick
+
+    // Walls of B robots are in force, their table and their reset state on the device.
+    void set(int B, const irlosc_walls& desc) { robots = B; tick = 0; d = desc; }
+    // They end: their setter cleared them, the model changed (the block's entry layout is the model's), or their buffers failed.
+    void end() { robots = 0; tick = 0; }
+    // A tick of a rollout ran them.
+    void ticked() { if (robots) ++tick; }
+    // The devices that have a wall: bit d
+    uint32_t devices() const {
+        uint32_t m = 0;
+        for (int w = 0; robots && w < d.n_walls; ++w) m |= 1u << d.dev[w];
+        return m;
+    }
+};
+
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
 // (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
 // the fused path is on, sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
@@ -122,6 +147,7 @@ struct Slot {
     int feed = 0;              // robots of the feed (0 = no feed)
     Program prog;              // what writes the targets inside a rollout
     Pushes push;               // what pushes the plant inside a rollout
+    Walls walls;               // what the EE bodies run into inside a rollout
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -1515,7 +1541,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1743,6 +1769,23 @@ static PushArgs push_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t ac
     return a;
 }
 
+// The arguments of the slot's wall kernel over B robots: the devices of `devs`, applied to exchange block xside or (xside == nullptr)
+// their stored force taken off the feed's wrench
+static WallArgs wall_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t devs, double* xside, void* wrench) {
+    const Walls& w = s.walls;
+    const size_t plane = (size_t)c->cfg.ndev * c->cfg.max_batch;
+    WallArgs a;
+    memset(&a, 0, sizeof a);
+    a.xside = xside; a.qt = s.qt; a.wrench = wrench; a.table = w.table;
+    a.force = w.st_d; a.max_depth = w.st_d + 3 * plane;
+    a.contact_ticks = w.st_i; a.first_tick = w.st_i + plane;
+    a.B = B; a.ndev = c->cfg.ndev; a.W = w.d.n_walls; a.per_robot = w.d.nb > 1; a.stride = c->cfg.max_batch;
+    a.apply = xside ? 1 : 0; a.tick = w.tick; a.devs = devs;
+    for (int i = 0; i < w.d.n_walls; ++i) a.dev[i] = w.d.dev[i];
+    for (int d = 0; d < c->cfg.ndev; ++d) a.ee0[d] = c->model.tables.eetab[d][0];
+    return a;
+}
+
 // The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
 static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
     const Program& p = c->slot[slot].prog;
@@ -1818,6 +1861,11 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     uint32_t push_sense = pl && s0.feed > 0 ? s0.push.sensed() : 0u;
     for (int p = 0; push_sense && p < IRLOSC_MAX_PUSHES; ++p)
         if (((push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) push_sense &= ~(1u << p);
+    // the walls its EE bodies run into on this tick, and what its sensors read of their force of the tick before
+    const uint32_t wall_apply = pl ? s0.walls.devices() : 0u;
+    uint32_t wall_sense = pl && s0.feed > 0 && s0.walls.tick > 0 ? wall_apply : 0u;
+    for (int d = 0; wall_sense && d < c->cfg.ndev; ++d)
+        if (c->ft_f0[d] < 0) wall_sense &= ~(1u << d);
     FtStep fts[R16_TRAIN];
     int nft = 0;
     FeLaneTrain ft;
@@ -1873,6 +1921,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     if (rcw) return rcw;
     if (push_sense)      // the sensed pushes: the reaction goes into the wrench ahead of every kernel that reads it
         HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_sense, nullptr, fts[0].wrench), st));
+    if (wall_sense)      // the walls' force of the tick before, behind the pushes' reaction
+        HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, wall_sense, nullptr, fts[0].wrench), st));
     if (prog == Program::LIST)      // the action list: its targets and velocity limit are this tick's, so in front of every OSC kernel
         HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (use_lane) {
@@ -1887,6 +1937,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
         HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s0, B, s0.prog.wp, bk.xside[0], s0.prog.tick), st));
     if (push_apply)      // the applied pushes: into the bias entries of the block, which only the plant reads from here on
         HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_apply, bk.xside[0], nullptr), st));
+    if (wall_apply)      // the walls: their force from this tick's EE position and velocity, into the bias behind the pushes
+        HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, wall_apply, bk.xside[0], nullptr), st));
     if (pl) {
         PlantArgs pa;
         memset(&pa, 0, sizeof pa);
@@ -1905,7 +1957,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
     if (pl) s0.advanced(B);
     if (prog != Program::NONE) s0.prog.ticked();
-    if (pl) s0.push.ticked();
+    if (pl) { s0.push.ticked(); s0.walls.ticked(); }
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2173,6 +2225,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     if (!rc) rc = check_program(c, slot, B);
     if (!rc && c->slot[slot].push.robots && B > c->slot[slot].push.robots)
         rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its pushes cover %d robots, rollout asked for %d", slot, c->slot[slot].push.robots, B);
+    if (!rc && c->slot[slot].walls.robots && B > c->slot[slot].walls.robots)
+        rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its walls cover %d robots, rollout asked for %d", slot, c->slot[slot].walls.robots, B);
     if (rc) return rc;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
@@ -2298,6 +2352,79 @@ extern "C" int irlosc_set_pushes(irlosc_ctx* c, int32_t slot, int32_t B, const i
     HIPCHK(c, ec);
     HIPCHK(c, es);
     ps.set(B, *d);
+    return IRLOSC_OK;
+}
+
+// ---- compliant walls of the rollout (osc_wall.hpp) ------------------------------------------------------------------------------
+extern "C" int irlosc_set_walls(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_walls* d, const double* table) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.walls.end(); return IRLOSC_OK; }
+    const int nd = c->cfg.ndev, W = d->n_walls;
+    if (W < 1 || W > IRLOSC_MAX_WALLS) return fail(c, IRLOSC_ERR_ARG, "walls: n_walls=%d out of [1,%d]", W, IRLOSC_MAX_WALLS);
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "walls: B=%d must be >= 1", B);
+    if (d->nb != 1 && d->nb != B) return fail(c, IRLOSC_ERR_ARG, "walls: nb=%d must be 1 or B=%d", d->nb, B);
+    for (int w = 0; w < W; ++w)
+        if (d->dev[w] < 0 || d->dev[w] >= nd) return fail(c, IRLOSC_ERR_ARG, "walls: dev[%d]=%d out of [0,%d)", w, d->dev[w], nd);
+    if (!table) return fail(c, IRLOSC_ERR_ARG, "walls: table is NULL");
+    const size_t E = (size_t)W * 8;
+    for (size_t i = 0; i < (size_t)d->nb * E; ++i)
+        if (!std::isfinite(table[i]))
+            return fail(c, IRLOSC_ERR_ARG, "walls: word %zu of wall %zu, robot %zu is not finite", i % 8, i % E / 8, i / E);
+    for (size_t i = 0; i < (size_t)d->nb * W; ++i) {
+        const double* r = table + i * 8;
+        const double n2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+        if (std::fabs(n2 - 1.0) > 1e-12)
+            return fail(c, IRLOSC_ERR_ARG, "walls: the normal of wall %zu, robot %zu is no unit vector (|n|^2 - 1 = %g)", i % W, i / W, n2 - 1.0);
+        if (r[4] < 0.0 || r[5] < 0.0 || r[6] < 0.0)
+            return fail(c, IRLOSC_ERR_ARG, "walls: radius %g, stiffness %g, damping %g of wall %zu, robot %zu must be >= 0", r[4], r[5], r[6], i % W, i / W);
+    }
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Walls& ws = s.walls;
+    ws.end();          // (none until the new ones are in their table and their state is reset)
+    const std::vector<double> tab = walk_table(table, d->nb, E);
+    const size_t bytes = tab.size() * sizeof(double), plane = (size_t)nd * c->cfg.max_batch;
+    if (!got(ws.table.reserve(bytes)) || !got(ws.st_d.ensure(4 * plane * sizeof(double))) || !got(ws.st_i.ensure(2 * plane * sizeof(int32_t))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the walls of slot %d (%zu bytes)", slot, bytes + plane * 40);
+    hipError_t ec = hipMemcpyAsync(ws.table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    if (ec == hipSuccess) ec = hipMemsetAsync(ws.st_d, 0, 4 * plane * sizeof(double), c->stream);                      // force, max_depth = 0
+    if (ec == hipSuccess) ec = hipMemsetAsync(ws.st_i, 0, plane * sizeof(int32_t), c->stream);                         // contact_ticks = 0
+    if (ec == hipSuccess) ec = hipMemsetAsync(ws.st_i + plane, 0xff, plane * sizeof(int32_t), c->stream);              // first_tick = -1
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when a copy failed: the host array is its source)
+    HIPCHK(c, ec);
+    HIPCHK(c, es);
+    ws.set(B, *d);
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_wall_state(irlosc_ctx* c, int32_t slot, int32_t B, double* force, double* max_depth, int32_t* contact_ticks,
+                                          int32_t* first_tick) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Walls& ws = c->slot[slot].walls;
+    if (!ws.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d has no walls (irlosc_set_walls)", slot);
+    if (B > ws.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d: its walls cover %d robots, asked for %d", slot, ws.robots, B);
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    // SoA [4][ndev][max_batch] and [2][ndev][max_batch] on the device -> [B][ndev](,3) for the caller
+    const size_t nd = (size_t)c->cfg.ndev, Bm = (size_t)c->cfg.max_batch, plane = nd * Bm;
+    std::vector<double> hd(4 * plane);
+    std::vector<int32_t> hi(2 * plane);
+    HIPCHK(c, hipMemcpyAsync(hd.data(), ws.st_d, hd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hi.data(), ws.st_i, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < (size_t)B; ++b)
+        for (size_t d = 0; d < nd; ++d) {
+            const size_t so = d * Bm + b, o = b * nd + d;
+            for (size_t k = 0; force && k < 3; ++k) force[o * 3 + k] = hd[k * plane + so];
+            if (max_depth) max_depth[o] = hd[3 * plane + so];
+            if (contact_ticks) contact_ticks[o] = hi[so];
+            if (first_tick) first_tick[o] = hi[plane + so];
+        }
     return IRLOSC_OK;
 }
 

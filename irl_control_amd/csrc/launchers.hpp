@@ -106,6 +106,12 @@ struct PushArgs;
 template <typename T>
 int launch_pushes(const PushArgs& a, hipStream_t st);
 
+// tu_wall.hip -- the compliant walls of a rollout tick whose slot has some (osc_wall.hpp): sense mode behind the pushes' sense launch,
+// apply mode behind the pushes' apply launch, in front of the plant; T = record type (of the wrench)
+struct WallArgs;
+template <typename T>
+int launch_walls(const WallArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;
