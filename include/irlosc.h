@@ -439,7 +439,7 @@ IRLOSC_API int irlosc_step_from_q_device(irlosc_ctx* ctx, int32_t slot, int32_t 
  * What examples/closed_loop_headless.py does on the host per tick, as one more kernel behind a fused step from joint coordinates:
  *     rhs_j = (ctrl_mask bit j ? u_j : 0) - bias_j - damping qvel_j;   qacc = M^-1 rhs;   qvel += dt qacc;   qpos += dt qvel
  * from the M, bias the step's own walk left in its exchange buffer and the u the step computed, written back into the slot's
- * coordinates (row-major and walk layout alike).  NOT a simulator: no contacts (but the penalty walls of irlosc_set_walls), no joint limits, no equality constraints.  float64
+ * coordinates (row-major and walk layout alike).  NOT a simulator: no contacts (but the penalty walls of irlosc_set_walls), and joint limits, the gripper's equality rows and a driven gripper only as the penalty rows of irlosc_set_joints.  float64
  * arithmetic whatever the context's dtype (u is read in the context's dtype). */
 typedef struct irlosc_plant {
     double dt;               /* > 0, finite */
@@ -495,7 +495,15 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *     irlosc_set_walls that succeeds                                                   its walls replace those in force; state and tick reset
  *     irlosc_set_walls that answers IRLOSC_ERR_HIP                                     no walls
  *     everything else (uploads, targets, gains, feeds, programs, pushes, other steps)  leaves them, their state and their tick alone
- * Only irlosc_rollout_from_q runs them and advances their tick. */
+ * Only irlosc_rollout_from_q runs them and advances their tick.
+ * JOINT ROWS (irlosc_set_joints) write no targets either: they coexist with paths, a list, pushes and walls, and none ends another.
+ *     irlosc_set_joints with desc == NULL, irlosc_set_model (all slots)                rows end
+ *     irlosc_set_joints that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE                nothing changes: the rows in force stay, whole
+ *     irlosc_set_joints that succeeds                                                  its rows replace those in force; state and tick reset
+ *     irlosc_set_joints that answers IRLOSC_ERR_HIP                                    no rows
+ *     everything else (uploads, targets, gains, feeds, programs, pushes, walls, other steps)  leaves them, their state and their tick alone
+ * Only irlosc_rollout_from_q runs them and advances their tick.  An ACTION drive row reads the list in force on the tick it runs: with no
+ * list, or one whose active device is not the row's, it is idle and keeps its ctrl -- legal, because lists come and go. */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -550,8 +558,10 @@ IRLOSC_API int irlosc_download_waypoint_state(irlosc_ctx* ctx, int32_t slot, int
  *                        of robot b, in the SLOT'S OWN gain copy [B][ndev][IRLOSC_GAIN_WORDS] (made from the context's gains by
  *                        irlosc_set_action_list; the context's gains are never written, other slots and entry points see no change).
  *                        max_vel0 persists through GRIP actions and after the list ends.
- * A robot that has finished holds its last targets and gains.  NOT APPLIED: gripper_force is state only, as in
- * FleetActionSequenceRunner -- the plant is untouched and no gripper joint is driven. */
+ * A robot that has finished holds its last targets and gains.  gripper_force is state, as in FleetActionSequenceRunner; it drives a
+ * gripper where the slot has an ACTION drive row on active_dev (irlosc_set_joints): on every tick with a non-zero gripper_force the
+ * row's ctrl takes it, and gear x ctrl acts on the row's hinge in the plant step of the same tick.  Without such a row no gripper
+ * joint is driven. */
 #define IRLOSC_MAX_ACTIONS 32
 #define IRLOSC_ACTION_WP   0
 #define IRLOSC_ACTION_GRIP 1
@@ -569,7 +579,7 @@ typedef struct irlosc_action_list {
     double max_error[IRLOSC_MAX_ACTIONS];     /* WP: finite */
     double min_speed[IRLOSC_MAX_ACTIONS];     /* WP: finite, <= max_speed */
     double max_speed[IRLOSC_MAX_ACTIONS];
-    double gripper_force[IRLOSC_MAX_ACTIONS]; /* finite; state only */
+    double gripper_force[IRLOSC_MAX_ACTIONS]; /* finite; state, read by ACTION drive rows (irlosc_set_joints) */
 } irlosc_action_list;
 /* Gives slot `slot`'s B robots the list: pose[nb][A][7] double (x y z qw qx qy qz; rows of GRIP actions are not read).  Every argument
  * is checked before anything is touched (IRLOSC_ERR_ARG: n_actions outside [1, 32], a kind that is neither, device indices outside
@@ -677,6 +687,62 @@ IRLOSC_API int irlosc_set_walls(irlosc_ctx* ctx, int32_t slot, int32_t B, const 
  * Synchronous. */
 IRLOSC_API int irlosc_download_wall_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* force, double* max_depth,
                                           int32_t* contact_ticks, int32_t* first_tick);
+
+/* ---- joint rows: range stops, the gripper's equality rows and a driven gripper inside a rollout (csrc/osc_joint.hpp) ---------------
+ * Every hinge of the Dual-UR5 scene but the stand is limited, ten <equality><joint polycoef> rows tie each Robotiq finger linkage to its
+ * driven knuckle, and insertion_task.py::send_forces writes the gripper force into the motors on the two driven knuckles.  Here each is a
+ * ROW: a torque on one or two hinges computed on the device, per robot and per tick, from those hinges' own coordinates -- explicit
+ * penalties, NOT MuJoCo's soft-constraint solver, and no friction loss.  Robot b on a tick of irlosc_rollout_from_q, q / qd the
+ * coordinates at the start of the tick, row r with hinges a (and b) and table row t[8]:
+ *   IRLOSC_JOINT_LIMIT   t = lo hi k c 0 0 0 0     g_lo = lo - q_a, f_lo = k g_lo - c qd_a, t_lo = (g_lo > 0 && f_lo > 0) ? f_lo : 0
+ *                                                  g_hi = q_a - hi, f_hi = k g_hi + c qd_a, t_hi = (g_hi > 0 && f_hi > 0) ? f_hi : 0
+ *                        tau_a += t_lo - t_hi.   A stop never pulls; a NaN gives no contact and no force.
+ *   IRLOSC_JOINT_COUPLE  t = a0 a1 qa0 qb0 k c 0 0   hinge a is MuJoCo's joint1, the DEPENDENT y, hinge b its joint2, the x (linear
+ *                        polycoef only).  e = (q_a - qa0) - (a0 + a1 (q_b - qb0)), de = qd_a - a1 qd_b, f = k e + c de;
+ *                        tau_a -= f, tau_b += a1 f.  An f (or a1 f) that is not finite contributes nothing.  The joint1 = y reading
+ *                        follows MuJoCo's documentation; it has NOT been compared with MuJoCo on this project (MuJoCo is not installed).
+ *   IRLOSC_JOINT_DRIVE   t = gear value 0 0 0 0 0 0   source IRLOSC_JOINT_SRC_CONST: ctrl = value (per robot with a per-robot table).
+ *                        IRLOSC_JOINT_SRC_ACTION: ctrl is per-robot state, 0 after the setter, held across ticks; on a tick where the
+ *                        slot has an action list in force whose active_dev is the row's dev[r] and robot b's gripper_force state is
+ *                        non-zero, ctrl = gripper_force (the reference's `if gripper_force: ctrl[idx] = gripper_force`: a later action
+ *                        with force 0.0 keeps the grip).  The action kernel has run on the tick already, so a GRIP entered on tick t
+ *                        drives the plant step of tick t.  tau_a += gear ctrl; a ctrl or product that is not finite contributes nothing.
+ * tau_j sums the contributions to hinge j in ASCENDING ROW INDEX, the first taken as it is.  Float64 whatever the context's dtype; every
+ * product, add and subtract rounded on its own, nothing contracted (the host can repeat it: irl_control_amd/joints.py).  Then, behind the
+ * give-up pass, the waypoint cycler, the pushes' APPLY and the walls' APPLY and directly in front of the plant kernel, for every hinge
+ * with tau_j != 0:  bias_j <- bias_j - tau_j  in place on the tick's exchange block, so the plant integrates
+ * M^-1 (u - bias - damping qvel + tau).  The F/T feed's wrench does NOT see these forces: they act inside the gripper or at arm hinges,
+ * not at the site frame.
+ * State per robot, reset by the setter: tau[n] (what the last tick applied, zeros included); per row max_violation (the largest g > 0
+ * of a LIMIT or |e| of a COUPLE seen, 0 for a DRIVE), active_ticks (ticks with a non-zero contribution of the row), ctrl (DRIVE rows,
+ * else 0).  A slot without joint rows launches exactly the kernels it launched before. */
+#define IRLOSC_MAX_JOINT_ROWS 48
+#define IRLOSC_JOINT_LIMIT  0
+#define IRLOSC_JOINT_COUPLE 1
+#define IRLOSC_JOINT_DRIVE  2
+#define IRLOSC_JOINT_SRC_CONST  0
+#define IRLOSC_JOINT_SRC_ACTION 1
+typedef struct irlosc_joint_rows {
+    int32_t n_rows;                              /* R in [1, IRLOSC_MAX_JOINT_ROWS] */
+    int32_t per_robot;                           /* 0 = one table for the fleet, 1 = a table per robot */
+    int32_t kind[IRLOSC_MAX_JOINT_ROWS];         /* IRLOSC_JOINT_LIMIT / _COUPLE / _DRIVE */
+    int32_t joint_a[IRLOSC_MAX_JOINT_ROWS];      /* hinge index in [0, n) */
+    int32_t joint_b[IRLOSC_MAX_JOINT_ROWS];      /* COUPLE: the other hinge, != joint_a; else not read */
+    int32_t source[IRLOSC_MAX_JOINT_ROWS];       /* DRIVE: IRLOSC_JOINT_SRC_CONST / _ACTION; else not read */
+    int32_t dev[IRLOSC_MAX_JOINT_ROWS];          /* ACTION drive: the device (targets order) whose list drives it; else not read */
+} irlosc_joint_rows;
+/* Gives slot `slot`'s B robots their joint rows: table[per_robot ? B : 1][R][8] double.  After irlosc_set_model (IRLOSC_ERR_STATE
+ * before).  Every argument is checked before anything is touched (IRLOSC_ERR_ARG: R outside [1, 48], per_robot not 0 / 1, B < 1, an
+ * unknown kind or source, a hinge index outside [0, n), joint_a == joint_b on a COUPLE, dev of an ACTION drive outside [0, ndev), table
+ * NULL or holding a value that is not finite, lo >= hi, k or c < 0; the rows in force stay, whole).  desc == NULL clears the slot's
+ * rows; what else ends them and who runs them: "one writer of the targets" above.  A rollout over more robots than the rows cover
+ * answers IRLOSC_ERR_STATE.  Table and state are allocated by the first use and kept; IRLOSC_ERR_HIP -- an allocation or a copy failed
+ * -- leaves the slot without rows.  Synchronous. */
+IRLOSC_API int irlosc_set_joints(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_joint_rows* desc, const double* table);
+/* The rows' per-robot state of the slot's first B robots: tau[B][n], max_violation[B][R] (double), active_ticks[B][R] (int32),
+ * ctrl[B][R] (double); any may be NULL.  IRLOSC_ERR_STATE: the slot has no joint rows, or they cover fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_joint_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* tau, double* max_violation,
+                                           int32_t* active_ticks, double* ctrl);
 
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard

@@ -13,6 +13,9 @@ MAX_WAYPOINTS = 64
 MAX_ACTIONS = 32
 MAX_PUSHES = 8
 MAX_WALLS = 8
+MAX_JOINT_ROWS = 48
+JOINT_LIMIT, JOINT_COUPLE, JOINT_DRIVE = 0, 1, 2
+JOINT_SRC_CONST, JOINT_SRC_ACTION = 0, 1
 ACTION_WP, ACTION_GRIP = 0, 1
 F32, F64 = 0, 1
 USE_G, ADMITTANCE, NULLSPACE = 1, 2, 4
@@ -32,7 +35,8 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_kernel_class", "irlosc_set_ft_sensors", "irlosc_set_sensordata", "irlosc_step_from_q_device",
            "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q",
            "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state",
-           "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state"]
+           "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state", "irlosc_set_joints",
+           "irlosc_download_joint_state"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -97,6 +101,13 @@ class Pushes(C.Structure):
 class Walls(C.Structure):
     """struct irlosc_walls (include/irlosc.h): the compliant walls of irlosc_set_walls."""
     _fields_ = [("n_walls", C.c_int32), ("nb", C.c_int32), ("dev", C.c_int32 * MAX_WALLS)]
+
+
+class JointRows(C.Structure):
+    """struct irlosc_joint_rows (include/irlosc.h): the joint rows of irlosc_set_joints."""
+    _fields_ = [("n_rows", C.c_int32), ("per_robot", C.c_int32), ("kind", C.c_int32 * MAX_JOINT_ROWS),
+                ("joint_a", C.c_int32 * MAX_JOINT_ROWS), ("joint_b", C.c_int32 * MAX_JOINT_ROWS),
+                ("source", C.c_int32 * MAX_JOINT_ROWS), ("dev", C.c_int32 * MAX_JOINT_ROWS)]
 
 
 class Cfg(C.Structure):
@@ -179,6 +190,8 @@ def load():
     lib.irlosc_set_pushes.argtypes = [vp, i32, i32, C.POINTER(Pushes), vp]
     lib.irlosc_set_walls.argtypes = [vp, i32, i32, C.POINTER(Walls), vp]
     lib.irlosc_download_wall_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.irlosc_set_joints.argtypes = [vp, i32, i32, C.POINTER(JointRows), vp]
+    lib.irlosc_download_joint_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

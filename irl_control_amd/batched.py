@@ -32,6 +32,7 @@ class BatchedOSC:
                                    f"{self.lib.irlosc_last_error(None).decode()}")
         self._h = h
         self._B = [0] * self.n_slots
+        self._joint_rows = [0] * self.n_slots      # rows of each slot's set_joints (the width of joint_state's arrays)
         if kernel == _lib.KERNEL_AUTO and self.max_batch >= 1024 and self.kernel_class == _lib.CLASS_GENERIC:
             import warnings
             warnings.warn(f"layout (n={layout.n}, k={layout.k}, ndev={layout.ndev}) has no throughput kernel: "
@@ -208,6 +209,7 @@ class BatchedOSC:
         st = model.to_struct(list(names))
         self._chk(self.lib.irlosc_set_model(self._h, C.byref(st)))
         self._model = model
+        self._joint_rows = [0] * self.n_slots      # (irlosc_set_model ends every slot's joint rows)
 
     def upload_q(self, qpos, qvel, slot: int = 0):
         B = int(np.shape(qpos)[0])
@@ -315,7 +317,8 @@ class BatchedOSC:
     def set_plant(self, dt: float, damping: float = 0.0, actuated=None):
         """The plant of `rollout` (after set_model): qacc = M^-1 (u - bias - damping qvel), semi-implicit Euler with step `dt`.
         `actuated`: indices of the joints driven by u (default: all n, as examples/closed_loop_headless.py; the others see u = 0).
-        No contacts, no joint limits, no equality constraints.  set_model clears it."""
+        No contacts (but the penalty walls of set_walls); joint limits, the gripper's equality rows and a driven gripper only as
+        the penalty rows of set_joints (irlosc_set_joints).  set_model clears it."""
         n = self.layout.n
         idx = list(range(n)) if actuated is None else [int(j) for j in actuated]
         if any(j < 0 or j >= n for j in idx):
@@ -401,8 +404,8 @@ class BatchedOSC:
         action_sequence.DEFAULT_PARAMS), or a dict from action_sequence.compile_action_list; `objects`: per robot its action objects
         (one entry: shared by the fleet).  `passive_arm`: "auto" = the other UR5 when the layout has it, None = no passive arm.
         After set_model, set_gains and set_targets; resets the state.  sequence=None clears the list and nothing else.  A slot has a
-        list or waypoint paths, never both; what else ends it: "one writer of the targets" in include/irlosc.h.  gripper_force is state
-        only: no gripper joint is driven."""
+        list or waypoint paths, never both; what else ends it: "one writer of the targets" in include/irlosc.h.  gripper_force is state;
+        it drives a gripper where the slot has an action drive row on the active arm (set_joints)."""
         from . import action_sequence as aseq
         B = self._B[slot]
         if sequence is None:
@@ -516,6 +519,50 @@ class BatchedOSC:
         first = np.empty((B, L.ndev), dtype=np.int32)
         self._chk(self.lib.irlosc_download_wall_state(self._h, slot, B, _lib.ptr(force), _lib.ptr(depth), _lib.ptr(ticks), _lib.ptr(first)))
         return dict(force=force, max_depth=depth, contact_ticks=ticks, first_tick=first)
+
+    # -- joint rows of the rollout (irlosc_set_joints / irlosc_download_joint_state) --------------------------------------------------
+    def set_joints(self, rows, slot: int = 0):
+        """Joint-space forces inside the slot's rollouts: `rows` is a list of dicts (joints.normalise; joints.scene_rows builds the
+        Dual-UR5 set) -- kind="limit" (a range stop with stiffness and damping on one hinge), kind="couple" (a linear equality row
+        between two hinges, as the scene ties a finger linkage to its driven knuckle) or kind="drive" (gear x ctrl on one hinge, ctrl a
+        constant or the gripper_force of the slot's action list) -- hinges by name (after set_model) or index, values scalars or
+        per-robot arrays.  Every tick the rollout computes one torque per hinge from that hinge's coordinates and hands it to the plant.
+        Explicit penalties, not MuJoCo's soft constraints; the F/T feed does not see them.  After set_model; resets the rows' state and
+        tick.  rows=None (or clear_joints) ends them and nothing else; they coexist with waypoint paths, an action list, pushes and walls."""
+        from . import joints as _j
+        B = self._B[slot]
+        if rows is None:
+            self._chk(self.lib.irlosc_set_joints(self._h, slot, B, None, None))
+            self._joint_rows[slot] = 0
+            return
+        model = getattr(self, "_model", None)
+        names = model.joint_names if model is not None else [str(j) for j in range(self.layout.n)]
+        d, table = _j.normalise(rows, names, self.layout.dev_names, B)
+        desc = _lib.JointRows()
+        desc.n_rows, desc.per_robot = table.shape[1], int(d["per_robot"])
+        for r in range(table.shape[1]):
+            desc.kind[r], desc.joint_a[r], desc.joint_b[r] = int(d["kind"][r]), int(d["joint_a"][r]), int(d["joint_b"][r])
+            desc.source[r], desc.dev[r] = int(d["source"][r]), int(d["dev"][r])
+        self._chk(self.lib.irlosc_set_joints(self._h, slot, B, C.byref(desc), _lib.ptr(np.ascontiguousarray(table))))
+        self._joint_rows[slot] = table.shape[1]
+
+    def clear_joints(self, slot: int = 0):
+        """Ends the slot's joint rows (irlosc_set_joints with desc == NULL); targets, programs, pushes, walls and feeds are left alone."""
+        self.set_joints(None, slot=slot)
+
+    def joint_state(self, slot: int = 0):
+        """-> dict(tau [B, n], max_violation [B, R], active_ticks [B, R], ctrl [B, R]): per robot the torque per hinge the last rollout
+        tick applied, and per row the largest violation seen since set_joints (a LIMIT: how far outside its range, a COUPLE: |e|), the
+        ticks on which the row contributed and a DRIVE's ctrl.
+        (irlosc_download_joint_state)"""
+        L, B = self.layout, self._B[slot]
+        R = self._joint_rows[slot]
+        tau = np.empty((B, L.n), dtype=np.float64)
+        viol = np.empty((B, R), dtype=np.float64)
+        ticks = np.empty((B, R), dtype=np.int32)
+        ctrl = np.empty((B, R), dtype=np.float64)
+        self._chk(self.lib.irlosc_download_joint_state(self._h, slot, B, _lib.ptr(tau), _lib.ptr(viol), _lib.ptr(ticks), _lib.ptr(ctrl)))
+        return dict(tau=tau, max_violation=viol, active_ticks=ticks, ctrl=ctrl)
 
     def step_resident_from_q(self, iters: int, first_slot: int = 0, B: Optional[int] = None):
         """-> (ms_total, ms_per_step): `iters` x (front end + step) on resident joint coordinates, HIP-event timed."""

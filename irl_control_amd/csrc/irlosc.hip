@@ -29,6 +29,7 @@
 #include "osc_action.hpp"
 #include "osc_push.hpp"
 #include "osc_wall.hpp"
+#include "osc_joint.hpp"
 #include "launchers.hpp"
 #include "dev_mem.hpp"
 
@@ -116,6 +117,24 @@ struct Walls {
     }
 };
 
+// The joint rows of a slot's rollouts (irlosc_set_joints, osc_joint.hpp): range stops, finger couplings and gripper drives, one torque
+// per hinge computed on the device per robot and tick and taken off the bias in front of the plant.  They write no targets, so they are
+// no Program and live next to one, next to Pushes and next to Walls.  Written by the transitions below and by nothing else.
+struct Joints {
+    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+    irlosc_joint_rows d{};     // the description in force
+    DevBuf<double> table;      // the rows (walk_table), allocated by the first use, kept across settings and grown on demand
+    DevBuf<double> st_d;       // state [MAX_N + 2 R][max_batch]: tau[MAX_N] (the kernel writes its tree's NJ hinges), max_violation[R], ctrl[R]; grown on demand
+    DevBuf<int32_t> st_i;      // state [R][max_batch]: active_ticks
+
+    // Rows of B robots are in force, their table and their reset state on the device.
+    void set(int B, const irlosc_joint_rows& desc) { robots = B; tick = 0; d = desc; }
+    // They end: their setter cleared them, the model changed (hinge indices and the block's entry layout are the model's), or their buffers failed.
+    void end() { robots = 0; tick = 0; }
+    // A tick of a rollout ran them.
+    void ticked() { if (robots) ++tick; }
+};
+
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
 // (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
 // the fused path is on, sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
@@ -148,6 +167,7 @@ struct Slot {
     Program prog;              // what writes the targets inside a rollout
     Pushes push;               // what pushes the plant inside a rollout
     Walls walls;               // what the EE bodies run into inside a rollout
+    Joints joints;             // what acts on single hinges inside a rollout: stops, couplings, drives
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -1541,7 +1561,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1786,6 +1806,37 @@ static WallArgs wall_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t de
     return a;
 }
 
+// The arguments of the slot's joint-row kernel over B robots on exchange block xside: per hinge the rows that name it, in ascending row
+// (the accumulation order of osc_joint.hpp), and the ACTION drives that the list in force arms on this tick
+static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* xside) {
+    const Joints& j = s.joints;
+    const irlosc_joint_rows& d = j.d;
+    const size_t Bm = (size_t)c->cfg.max_batch, n = (size_t)c->cfg.n, N = IRLOSC_MAX_N;
+    JointArgs a;
+    memset(&a, 0, sizeof a);
+    a.xside = xside; a.qt = s.qt; a.table = j.table;
+    a.tau = j.st_d; a.max_violation = j.st_d + N * Bm; a.ctrl = j.st_d + (N + (size_t)d.n_rows) * Bm;
+    a.active_ticks = j.st_i;
+    a.B = B; a.R = d.n_rows; a.per_robot = d.per_robot; a.stride = (int32_t)Bm;
+    const bool list = s.prog.kind == Program::LIST;
+    a.gripper_force = list ? s.prog.al_d + 2 * Bm : nullptr;
+    int items = 0;
+    for (int h = 0; h < (int)n; ++h) {
+        a.first[h] = (uint8_t)items;
+        for (int r = 0; r < d.n_rows; ++r) {
+            if (d.joint_a[r] == h) a.item[items++] = (uint8_t)r;
+            else if (d.kind[r] == IRLOSC_JOINT_COUPLE && d.joint_b[r] == h) a.item[items++] = (uint8_t)(r | 0x80);
+        }
+    }
+    for (int h = (int)n; h <= IRLOSC_MAX_N; ++h) a.first[h] = (uint8_t)items;
+    for (int r = 0; r < d.n_rows; ++r) {
+        a.kind[r] = (uint8_t)d.kind[r]; a.ja[r] = (uint8_t)d.joint_a[r]; a.jb[r] = (uint8_t)d.joint_b[r]; a.source[r] = (uint8_t)d.source[r];
+        if (list && d.kind[r] == IRLOSC_JOINT_DRIVE && d.source[r] == IRLOSC_JOINT_SRC_ACTION && d.dev[r] == s.prog.al.active_dev)
+            a.armed |= (uint64_t)1 << r;
+    }
+    return a;
+}
+
 // The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
 static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
     const Program& p = c->slot[slot].prog;
@@ -1939,6 +1990,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
         HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_apply, bk.xside[0], nullptr), st));
     if (wall_apply)      // the walls: their force from this tick's EE position and velocity, into the bias behind the pushes
         HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, wall_apply, bk.xside[0], nullptr), st));
+    if (pl && s0.joints.robots)      // the joint rows: stops, couplings and drives from this tick's coordinates, into the bias behind the walls
+        HIPCHK(c, (hipError_t)launch_joints(joint_args(c, s0, B, bk.xside[0]), st));
     if (pl) {
         PlantArgs pa;
         memset(&pa, 0, sizeof pa);
@@ -1957,7 +2010,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
     if (pl) s0.advanced(B);
     if (prog != Program::NONE) s0.prog.ticked();
-    if (pl) { s0.push.ticked(); s0.walls.ticked(); }
+    if (pl) { s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); }
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2227,6 +2280,8 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
         rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its pushes cover %d robots, rollout asked for %d", slot, c->slot[slot].push.robots, B);
     if (!rc && c->slot[slot].walls.robots && B > c->slot[slot].walls.robots)
         rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its walls cover %d robots, rollout asked for %d", slot, c->slot[slot].walls.robots, B);
+    if (!rc && c->slot[slot].joints.robots && B > c->slot[slot].joints.robots)
+        rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its joint rows cover %d robots, rollout asked for %d", slot, c->slot[slot].joints.robots, B);
     if (rc) return rc;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
@@ -2425,6 +2480,96 @@ extern "C" int irlosc_download_wall_state(irlosc_ctx* c, int32_t slot, int32_t B
             if (contact_ticks) contact_ticks[o] = hi[so];
             if (first_tick) first_tick[o] = hi[plane + so];
         }
+    return IRLOSC_OK;
+}
+
+// ---- joint rows of the rollout (osc_joint.hpp) ------------------------------------------------------------------------------------
+extern "C" int irlosc_set_joints(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_joint_rows* d, const double* table) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.joints.end(); return IRLOSC_OK; }
+    const int n = c->cfg.n, nd = c->cfg.ndev, R = d->n_rows;
+    if (R < 1 || R > IRLOSC_MAX_JOINT_ROWS) return fail(c, IRLOSC_ERR_ARG, "joints: n_rows=%d out of [1,%d]", R, IRLOSC_MAX_JOINT_ROWS);
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "joints: B=%d must be >= 1", B);
+    if (d->per_robot != 0 && d->per_robot != 1) return fail(c, IRLOSC_ERR_ARG, "joints: per_robot=%d must be 0 or 1", d->per_robot);
+    for (int r = 0; r < R; ++r) {
+        const int k = d->kind[r];
+        if (k != IRLOSC_JOINT_LIMIT && k != IRLOSC_JOINT_COUPLE && k != IRLOSC_JOINT_DRIVE)
+            return fail(c, IRLOSC_ERR_ARG, "joints: kind[%d]=%d is unknown", r, k);
+        if (d->joint_a[r] < 0 || d->joint_a[r] >= n) return fail(c, IRLOSC_ERR_ARG, "joints: joint_a[%d]=%d out of [0,%d)", r, d->joint_a[r], n);
+        if (k == IRLOSC_JOINT_COUPLE) {
+            if (d->joint_b[r] < 0 || d->joint_b[r] >= n) return fail(c, IRLOSC_ERR_ARG, "joints: joint_b[%d]=%d out of [0,%d)", r, d->joint_b[r], n);
+            if (d->joint_b[r] == d->joint_a[r]) return fail(c, IRLOSC_ERR_ARG, "joints: row %d couples hinge %d with itself", r, d->joint_a[r]);
+        }
+        if (k == IRLOSC_JOINT_DRIVE) {
+            if (d->source[r] != IRLOSC_JOINT_SRC_CONST && d->source[r] != IRLOSC_JOINT_SRC_ACTION)
+                return fail(c, IRLOSC_ERR_ARG, "joints: source[%d]=%d is unknown", r, d->source[r]);
+            if (d->source[r] == IRLOSC_JOINT_SRC_ACTION && (d->dev[r] < 0 || d->dev[r] >= nd))
+                return fail(c, IRLOSC_ERR_ARG, "joints: dev[%d]=%d out of [0,%d)", r, d->dev[r], nd);
+        }
+    }
+    if (!table) return fail(c, IRLOSC_ERR_ARG, "joints: table is NULL");
+    const int nb = d->per_robot ? B : 1;
+    const size_t E = (size_t)R * 8;
+    for (size_t i = 0; i < (size_t)nb * E; ++i)
+        if (!std::isfinite(table[i]))
+            return fail(c, IRLOSC_ERR_ARG, "joints: word %zu of row %zu, robot %zu is not finite", i % 8, i % E / 8, i / E);
+    for (size_t i = 0; i < (size_t)nb * R; ++i) {
+        const double* t = table + i * 8;
+        const int k = d->kind[i % R];
+        if (k == IRLOSC_JOINT_LIMIT && !(t[0] < t[1]))
+            return fail(c, IRLOSC_ERR_ARG, "joints: the range [%g, %g] of row %zu, robot %zu is empty (lo >= hi)", t[0], t[1], i % R, i / R);
+        const double kk = k == IRLOSC_JOINT_LIMIT ? t[2] : t[4], cc = k == IRLOSC_JOINT_LIMIT ? t[3] : t[5];
+        if (k != IRLOSC_JOINT_DRIVE && (kk < 0.0 || cc < 0.0))
+            return fail(c, IRLOSC_ERR_ARG, "joints: stiffness %g, damping %g of row %zu, robot %zu must be >= 0", kk, cc, i % R, i / R);
+    }
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Joints& js = s.joints;
+    js.end();          // (none until the new ones are in their table and their state is reset)
+    const std::vector<double> tab = walk_table(table, nb, E);
+    const size_t bytes = tab.size() * sizeof(double), Bm = (size_t)c->cfg.max_batch;
+    const size_t nd_words = ((size_t)IRLOSC_MAX_N + 2 * (size_t)R) * Bm, ni_words = (size_t)R * Bm;
+    if (!got(js.table.reserve(bytes)) || !got(js.st_d.reserve(nd_words * sizeof(double))) || !got(js.st_i.reserve(ni_words * sizeof(int32_t))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the joint rows of slot %d (%zu bytes)", slot,
+                    bytes + nd_words * sizeof(double) + ni_words * sizeof(int32_t));
+    hipError_t ec = hipMemcpyAsync(js.table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
+    if (ec == hipSuccess) ec = hipMemsetAsync(js.st_d, 0, nd_words * sizeof(double), c->stream);      // tau, max_violation, ctrl = 0
+    if (ec == hipSuccess) ec = hipMemsetAsync(js.st_i, 0, ni_words * sizeof(int32_t), c->stream);     // active_ticks = 0
+    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when a copy failed: the host array is its source)
+    HIPCHK(c, ec);
+    HIPCHK(c, es);
+    js.set(B, *d);
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_joint_state(irlosc_ctx* c, int32_t slot, int32_t B, double* tau, double* max_violation, int32_t* active_ticks,
+                                           double* ctrl) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Joints& js = c->slot[slot].joints;
+    if (!js.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d has no joint rows (irlosc_set_joints)", slot);
+    if (B > js.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d: its joint rows cover %d robots, asked for %d", slot, js.robots, B);
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    // SoA [MAX_N + 2 R][max_batch] and [R][max_batch] on the device -> [B][n], [B][R] for the caller
+    const size_t n = (size_t)c->cfg.n, R = (size_t)js.d.n_rows, Bm = (size_t)c->cfg.max_batch, N = IRLOSC_MAX_N;
+    std::vector<double> hd((N + 2 * R) * Bm);
+    std::vector<int32_t> hi(R * Bm);
+    HIPCHK(c, hipMemcpyAsync(hd.data(), js.st_d, hd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hi.data(), js.st_i, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < (size_t)B; ++b) {
+        for (size_t j = 0; tau && j < n; ++j) tau[b * n + j] = hd[j * Bm + b];
+        for (size_t r = 0; r < R; ++r) {
+            if (max_violation) max_violation[b * R + r] = hd[(N + r) * Bm + b];
+            if (ctrl) ctrl[b * R + r] = hd[(N + R + r) * Bm + b];
+            if (active_ticks) active_ticks[b * R + r] = hi[r * Bm + b];
+        }
+    }
     return IRLOSC_OK;
 }
 

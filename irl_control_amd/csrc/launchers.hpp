@@ -112,6 +112,11 @@ struct WallArgs;
 template <typename T>
 int launch_walls(const WallArgs& a, hipStream_t st);
 
+// tu_joint.hip -- the joint rows of a rollout tick whose slot has some (osc_joint.hpp): range stops, finger couplings and gripper
+// drives as one torque per hinge, taken off the bias behind the walls' apply launch, directly in front of the plant
+struct JointArgs;
+int launch_joints(const JointArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;

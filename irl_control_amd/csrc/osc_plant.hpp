@@ -1,7 +1,8 @@
 // The contact-free PLANT of the fused path (irlosc_rollout_from_q): behind a fused step from joint coordinates, every robot's
 //     qacc = M^-1 (u - bias - damping qvel);   qvel += dt qacc;   qpos += dt qvel          (semi-implicit Euler)
 // written back into the slot's coordinates, so that the next tick's walk starts from them without the host in between.  Not a simulator:
-// no contacts, no joint limits, no equality constraints -- the plant examples/closed_loop_headless.py integrates in NumPy.
+// no contacts; joint limits, the gripper's equality rows and a driven gripper only as the penalty rows of irlosc_set_joints, which reach
+// this kernel through the bias (osc_joint.hpp) -- the plant examples/closed_loop_headless.py integrates in NumPy.
 //
 // One lane per robot, one block per walk wave (its 64 robots), float64 arithmetic whatever the record type.  Everything it needs is in
 // HBM after the step: the walk left the tree's non-zeros of M, the bias forces and the EE poses in the step's exchange block

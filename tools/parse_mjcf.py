@@ -4,6 +4,7 @@
 
     python tools/parse_mjcf.py                      # scenes/dual_ur5.xml -> models/dual_ur5.json
     python tools/parse_mjcf.py /root/reference/irl_control/scenes/ur5.xml ur5 arm=EE      # a second tree: models/ur5.json
+    python tools/parse_mjcf.py --joints tests/golden/dual_ur5_joints.json                 # the scene's joint-space rows, data only
 
 What is taken (scenes/dual_ur5.xml:51-265 in ir-lab/irl_control @ 2024_10_08): the body tree in MuJoCo's numbering
 (document order, depth first), each body's frame relative to its parent (pos + quat; `euler` attributes are converted
@@ -21,6 +22,11 @@ The signed-volume variant (compiler exactmeshinertia="true" / MuJoCo 3) is store
 for comparison: 0.314 kg instead of 0.343 kg per link, which moves the yaw inertia M[0][0] of the stand joint by 1e-4
 relative.  Only numbers leave this script: the STL stays in /root/reference.  Massless frames (ur_stand_dummy, ur_EE_*,
 EE_*) carry no geoms and are massless in MuJoCo too.
+
+--joints OUT writes what irl_control_amd/joints.py::scene_rows builds the rollout's joint rows from (irlosc_set_joints): per hinge
+name `limited` and `range`; the <equality><joint> rows as joint1, joint2, polycoef and the reference positions qpos0 of both hinges
+(the hinges' `ref`, 0 in this scene); the motors on finger hinges as actuator name, joint and gear.  A polycoef with a non-zero
+quadratic, cubic or quartic term is refused: the rows are linear.
 """
 import json
 import os
@@ -29,6 +35,11 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
+JOINTS_OUT = None
+if "--joints" in sys.argv:
+    _i = sys.argv.index("--joints")
+    JOINTS_OUT = sys.argv[_i + 1]
+    del sys.argv[_i:_i + 2]
 SRC = sys.argv[1] if len(sys.argv) > 1 else "/root/reference/irl_control/scenes/dual_ur5.xml"
 NAME = sys.argv[2] if len(sys.argv) > 2 else "dual_ur5"
 # device name -> end-effector body: the `EE:` entries of irl_control/robot_configs/default_xyz*.yaml for the Dual-UR5
@@ -144,8 +155,38 @@ def geoms_inertial(el, meshes, exact):
     return float(m_tot), c0.tolist(), mat_to_quat(V), w.tolist()
 
 
+def joints_fixture(root):
+    """The scene's joint-space rows as data: limits, equality couplings, the gripper motors."""
+    hinges = {}
+    for j in root.find("worldbody").iter("joint"):
+        if j.get("type", "hinge") != "hinge":
+            continue
+        hinges[j.get("name")] = dict(limited=j.get("limited", "false") == "true", range=vec(j.get("range"), 2, (0, 0)),
+                                     ref=float(j.get("ref", 0.0)))
+    eqs = []
+    eq = root.find("equality")
+    for e in (eq.findall("joint") if eq is not None else []):
+        pc = vec(e.get("polycoef"), 5, (0, 1, 0, 0, 0))
+        if any(c != 0.0 for c in pc[2:]):
+            sys.exit(f"equality {e.get('joint1')} / {e.get('joint2')}: polycoef {pc} has a non-zero quadratic, cubic or quartic term; "
+                     "the joint rows are linear")
+        j1, j2 = e.get("joint1"), e.get("joint2")
+        eqs.append(dict(joint1=j1, joint2=j2, polycoef=pc, qpos0=[hinges[j1]["ref"], hinges[j2]["ref"]]))
+    motors = [dict(name=a.get("name"), joint=a.get("joint"), gear=vec(a.get("gear"), 1, (1.0,))[0])       # (gear: its first entry)
+              for a in root.find("actuator") if a.tag == "motor" and a.get("name", "").startswith("gripper")]
+    out = dict(source=f"ir-lab/irl_control @ 2024_10_08, irl_control/scenes/{os.path.basename(SRC)}, via tools/parse_mjcf.py --joints",
+               joints={n: dict(limited=h["limited"], range=h["range"]) for n, h in hinges.items()}, equality=eqs, gripper_motors=motors)
+    with open(JOINTS_OUT, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(f"{sum(h['limited'] for h in hinges.values())} limited hinges of {len(hinges)}, {len(eqs)} equality rows, "
+          f"{len(motors)} gripper motors -> {JOINTS_OUT}")
+
+
 def main():
     root = ET.parse(SRC).getroot()
+    if JOINTS_OUT:
+        return joints_fixture(root)
     bodies, sites = [], []
     comp = root.find("compiler")
     meshdir = comp.get("meshdir", "") if comp is not None else ""
