@@ -48,12 +48,19 @@ struct Program {
     int robots = 0, tick = 0;  // robots the program covers; rollout ticks since it came in force
     irlosc_waypoints wp{};     // the description in force: of paths; of a list
     irlosc_action_list al{};
-    // Device buffers, allocated by the first use and kept across programs: per-robot state SoA over max_batch robots (wp_i: index, arrivals,
-    // last_tick, [ndev][max_batch] each; al_i: action, entered, grip_left, finished_tick; al_d: err, max_vel0, gripper_force, start_xyz[3]), the
+    // Device buffers, allocated by the first use and kept across programs: per-robot state SoA over max_batch robots (wp_i, al_i, al_d), the
     // table (walk_table), and a list's own gains [robots][ndev][12] and null_kv [robots] in the context's dtype (its rollout reads these per instance)
     DevBuf<int32_t> wp_i, al_i;
     DevBuf<double> wp_table, al_d, al_table;
     DevBuf<void> al_gains, al_nullkv;
+    // THE LAYOUT of the state -- the kernels' arguments, the setters' sizes and the downloads all ask here: wp_i in planes of `plane` =
+    // ndev x max_batch words; al_i and al_d in rows of Bm = max_batch words (start_xyz: three rows); and their sizes
+    int32_t* index(size_t) const { return wp_i; }  int32_t* arrivals(size_t plane) const { return wp_i + plane; }  int32_t* last_tick(size_t plane) const { return wp_i + 2 * plane; }
+    int32_t* action(size_t) const { return al_i; }  int32_t* entered(size_t Bm) const { return al_i + Bm; }  int32_t* grip_left(size_t Bm) const { return al_i + 2 * Bm; }
+    int32_t* finished_tick(size_t Bm) const { return al_i + 3 * Bm; }
+    double* err(size_t) const { return al_d; }  double* max_vel0(size_t Bm) const { return al_d + Bm; }  double* gripper_force(size_t Bm) const { return al_d + 2 * Bm; }
+    double* start_xyz(size_t Bm) const { return al_d + 3 * Bm; }
+    static size_t wp_words(size_t plane) { return 3 * plane; }  static size_t al_i_words(size_t Bm) { return 4 * Bm; }  static size_t al_d_words(size_t Bm) { return 6 * Bm; }
 
     // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
     void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
@@ -68,20 +75,25 @@ struct Program {
     void ticked() { ++tick; }
 };
 
-// The external pushes of a slot's rollouts (irlosc_set_pushes, osc_push.hpp): wrenches on EE bodies during windows of ticks, applied
-// to the plant and / or taken off the sensor feed's wrench a tick later.  They write no targets, so they are no Program and live next
-// to one.  Written by the transitions below and by nothing else.
-struct Pushes {
-    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
-    irlosc_pushes d{};         // the description in force
-    DevBuf<double> table;      // the wrenches (walk_table), allocated by the first use, kept across settings and grown on demand
-
-    // Pushes of B robots are in force, their table on the device.
-    void set(int B, const irlosc_pushes& desc) { robots = B; tick = 0; d = desc; }
-    // They end: their setter cleared them, the model changed (the block's entry layout is the model's), or their table failed.
+// What acts on the plant inside a slot's rollouts: external pushes, compliant walls, joint rows (below).  None of them writes targets, so
+// none is a Program: they live next to one and next to each other.  Each is written by its set(), by end() and ticked(), and by nothing else.
+struct PlantForce {
+    int robots = 0, tick = 0;  // robots it covers (0: none); rollout ticks since it came in force
+    DevBuf<double> table;      // its table (walk_table), allocated by the first use, kept across settings and grown on demand
+    // It ends: its setter cleared it, the model changed (hinge indices and the block's entry layout are the model's), or its buffers failed.
     void end() { robots = 0; tick = 0; }
-    // A tick of a rollout ran (with or without a launch of theirs: the windows are judged on the host).
+    // A tick of a rollout ran (with or without a launch of its own: the pushes' windows are judged on the host).
     void ticked() { if (robots) ++tick; }
+protected:
+    // It is in force for B robots, its table and (where it has some) its reset state on the device.
+    void in_force(int B) { robots = B; tick = 0; }
+};
+
+// The external pushes (irlosc_set_pushes, osc_push.hpp): wrenches on EE bodies during windows of ticks, applied to the plant and / or
+// taken off the sensor feed's wrench a tick later.
+struct Pushes : PlantForce {
+    irlosc_pushes d{};         // the description in force
+    void set(int B, const irlosc_pushes& desc) { in_force(B); d = desc; }
     // The pushes whose window holds tick t and that act on the plant / are read by the sensors: bit p
     uint32_t active(int t, const uint8_t* which) const {
         uint32_t m = 0;
@@ -93,22 +105,17 @@ struct Pushes {
     uint32_t sensed() const { return active(tick - 1, d.sense); }     // on this tick: what the step of the tick before felt
 };
 
-// The compliant walls of a slot's rollouts (irlosc_set_walls, osc_wall.hpp): penalty half-spaces on EE bodies, their force computed on
-// the device per robot and tick, applied to the plant and taken off the sensor feed's wrench a tick later.  They write no targets, so
-// they are no Program and live next to one and next to Pushes.  Written by the transitions below and by nothing else.
-struct Walls {
-    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+// The compliant walls (irlosc_set_walls, osc_wall.hpp): penalty half-spaces on EE bodies, their force computed on the device per robot
+// and tick, applied to the plant and taken off the sensor feed's wrench a tick later.
+struct Walls : PlantForce {
     irlosc_walls d{};          // the description in force
-    DevBuf<double> table;      // the rows (walk_table), allocated by the first use, kept across settings and grown on demand
-    DevBuf<double> st_d;       // state [4][ndev][max_batch]: force xyz, max_depth
-    DevBuf<int32_t> st_i;      // state [2][ndev][max_batch]: contact_ticks, first_tick
-
-    // Walls of B robots are in force, their table and their reset state on the device.
-    void set(int B, const irlosc_walls& desc) { robots = B; tick = 0; d = desc; }
-    // They end: their setter cleared them, the model changed (the block's entry layout is the model's), or their buffers failed.
-    void end() { robots = 0; tick = 0; }
-    // A tick of a rollout ran them.
-    void ticked() { if (robots) ++tick; }
+    DevBuf<double> st_d;       // per-robot state, allocated by the first use for max_batch robots: force xyz, max_depth
+    DevBuf<int32_t> st_i;      // ... contact_ticks, first_tick
+    // THE LAYOUT of the state: st_d / st_i in planes of `plane` = ndev x max_batch words (force: a plane per axis), and their sizes
+    double* force(size_t plane, size_t axis = 0) const { return st_d + axis * plane; }  double* max_depth(size_t plane) const { return st_d + 3 * plane; }
+    int32_t* contact_ticks(size_t) const { return st_i; }  int32_t* first_tick(size_t plane) const { return st_i + plane; }
+    static size_t d_words(size_t plane) { return 4 * plane; }  static size_t i_words(size_t plane) { return 2 * plane; }
+    void set(int B, const irlosc_walls& desc) { in_force(B); d = desc; }
     // The devices that have a wall: bit d
     uint32_t devices() const {
         uint32_t m = 0;
@@ -117,22 +124,17 @@ struct Walls {
     }
 };
 
-// The joint rows of a slot's rollouts (irlosc_set_joints, osc_joint.hpp): range stops, finger couplings and gripper drives, one torque
-// per hinge computed on the device per robot and tick and taken off the bias in front of the plant.  They write no targets, so they are
-// no Program and live next to one, next to Pushes and next to Walls.  Written by the transitions below and by nothing else.
-struct Joints {
-    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+// The joint rows (irlosc_set_joints, osc_joint.hpp): range stops, finger couplings and gripper drives, one torque per hinge computed
+// on the device per robot and tick and taken off the bias in front of the plant.
+struct Joints : PlantForce {
     irlosc_joint_rows d{};     // the description in force
-    DevBuf<double> table;      // the rows (walk_table), allocated by the first use, kept across settings and grown on demand
-    DevBuf<double> st_d;       // state [MAX_N + 2 R][max_batch]: tau[MAX_N] (the kernel writes its tree's NJ hinges), max_violation[R], ctrl[R]; grown on demand
-    DevBuf<int32_t> st_i;      // state [R][max_batch]: active_ticks
-
-    // Rows of B robots are in force, their table and their reset state on the device.
-    void set(int B, const irlosc_joint_rows& desc) { robots = B; tick = 0; d = desc; }
-    // They end: their setter cleared them, the model changed (hinge indices and the block's entry layout are the model's), or their buffers failed.
-    void end() { robots = 0; tick = 0; }
-    // A tick of a rollout ran them.
-    void ticked() { if (robots) ++tick; }
+    DevBuf<double> st_d;       // per-robot state, grown on demand: tau[MAX_N] (the kernel writes its tree's NJ hinges), max_violation[R], ctrl[R]
+    DevBuf<int32_t> st_i;      // ... active_ticks[R]
+    // THE LAYOUT of the state: st_d / st_i in rows of Bm = max_batch words, for R rows, and their sizes
+    double* tau(size_t) const { return st_d; }  double* max_violation(size_t Bm) const { return st_d + (size_t)IRLOSC_MAX_N * Bm; }
+    double* ctrl(size_t Bm, size_t R) const { return st_d + ((size_t)IRLOSC_MAX_N + R) * Bm; }  int32_t* active_ticks(size_t) const { return st_i; }
+    static size_t d_words(size_t Bm, size_t R) { return ((size_t)IRLOSC_MAX_N + 2 * R) * Bm; }  static size_t i_words(size_t Bm, size_t R) { return R * Bm; }
+    void set(int B, const irlosc_joint_rows& desc) { in_force(B); d = desc; }
 };
 
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
@@ -1730,6 +1732,9 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 // tick, is the slot's to say (Slot::prog).
 struct PlantCall { double* trace; };
 
+// The exchange entry of each device's EE pose (its x; y z qw qx qy qz follow): what the rollout's kernels find an EE body by
+static void fill_ee0(const irlosc_ctx* c, int32_t* ee0) { for (int d = 0; d < c->cfg.ndev; ++d) ee0[d] = c->model.tables.eetab[d][0]; }
+
 // The arguments of the slot's action kernel over B robots (init: the launch of irlosc_set_action_list; else a tick on exchange block xside)
 static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_action_list& d, const double* xside, int tick) {
     const Program& p = s.prog;
@@ -1737,8 +1742,8 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
     memset(&a, 0, sizeof a);
     const size_t Bm = (size_t)c->cfg.max_batch;
     a.xside = xside; a.tgt = s.tgt; a.gains = p.al_gains;
-    a.action = p.al_i; a.entered = p.al_i + Bm; a.grip_left = p.al_i + 2 * Bm; a.finished_tick = p.al_i + 3 * Bm;
-    a.err = p.al_d; a.max_vel0 = p.al_d + Bm; a.gripper_force = p.al_d + 2 * Bm; a.start_xyz = p.al_d + 3 * Bm;
+    a.action = p.action(Bm); a.entered = p.entered(Bm); a.grip_left = p.grip_left(Bm); a.finished_tick = p.finished_tick(Bm);
+    a.err = p.err(Bm); a.max_vel0 = p.max_vel0(Bm); a.gripper_force = p.gripper_force(Bm); a.start_xyz = p.start_xyz(Bm);
     a.table = p.al_table;
     for (int i = 0; i < d.n_actions; ++i) {
         a.kp[i] = d.kp[i]; a.max_error[i] = d.max_error[i]; a.min_speed[i] = d.min_speed[i]; a.max_speed[i] = d.max_speed[i];
@@ -1760,16 +1765,17 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
 static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, const double* xside, int tick) {
     WaypointArgs a;
     memset(&a, 0, sizeof a);
-    const size_t n = (size_t)c->cfg.ndev * c->cfg.max_batch;
-    a.xside = xside; a.tgt = s.tgt; a.table = s.prog.wp_table;
-    a.index = s.prog.wp_i; a.arrivals = (uint32_t*)(s.prog.wp_i + n); a.last_tick = s.prog.wp_i + 2 * n;
+    const Program& p = s.prog;
+    const size_t plane = (size_t)c->cfg.ndev * c->cfg.max_batch;
+    a.xside = xside; a.tgt = s.tgt; a.table = p.wp_table;
+    a.index = p.index(plane); a.arrivals = (uint32_t*)p.arrivals(plane); a.last_tick = p.last_tick(plane);
     for (int d = 0; d < c->cfg.ndev; ++d) {
         a.thr2[d] = w.threshold[d] * w.threshold[d];
         a.count[d] = w.count[d];
         a.loop[d] = w.loop[d];
-        a.ee0[d] = xside ? c->model.tables.eetab[d][0] : 0;
         a.wmax = std::max(a.wmax, w.count[d]);      // the widest list: the table's stride
     }
+    if (xside) fill_ee0(c, a.ee0);      // (the init launch reads no block)
     a.B = B; a.ndev = c->cfg.ndev; a.stride = c->cfg.max_batch; a.per_robot = w.nb > 1;
     a.n_entries = (int32_t)c->model.fe_xentries; a.tick = tick; a.init = xside ? 0 : 1;
     return a;
@@ -1785,7 +1791,7 @@ static PushArgs push_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t ac
     a.B = B; a.ndev = c->cfg.ndev; a.P = p.d.n_pushes; a.per_robot = p.d.nb > 1;
     a.apply = xside ? 1 : 0; a.active = active;
     for (int i = 0; i < p.d.n_pushes; ++i) a.dev[i] = p.d.dev[i];
-    for (int d = 0; d < c->cfg.ndev; ++d) a.ee0[d] = c->model.tables.eetab[d][0];
+    fill_ee0(c, a.ee0);
     return a;
 }
 
@@ -1797,12 +1803,11 @@ static WallArgs wall_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t de
     WallArgs a;
     memset(&a, 0, sizeof a);
     a.xside = xside; a.qt = s.qt; a.wrench = wrench; a.table = w.table;
-    a.force = w.st_d; a.max_depth = w.st_d + 3 * plane;
-    a.contact_ticks = w.st_i; a.first_tick = w.st_i + plane;
+    a.force = w.force(plane); a.max_depth = w.max_depth(plane); a.contact_ticks = w.contact_ticks(plane); a.first_tick = w.first_tick(plane);
     a.B = B; a.ndev = c->cfg.ndev; a.W = w.d.n_walls; a.per_robot = w.d.nb > 1; a.stride = c->cfg.max_batch;
     a.apply = xside ? 1 : 0; a.tick = w.tick; a.devs = devs;
     for (int i = 0; i < w.d.n_walls; ++i) a.dev[i] = w.d.dev[i];
-    for (int d = 0; d < c->cfg.ndev; ++d) a.ee0[d] = c->model.tables.eetab[d][0];
+    fill_ee0(c, a.ee0);
     return a;
 }
 
@@ -1811,15 +1816,14 @@ static WallArgs wall_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t de
 static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* xside) {
     const Joints& j = s.joints;
     const irlosc_joint_rows& d = j.d;
-    const size_t Bm = (size_t)c->cfg.max_batch, n = (size_t)c->cfg.n, N = IRLOSC_MAX_N;
+    const size_t Bm = (size_t)c->cfg.max_batch, n = (size_t)c->cfg.n;
     JointArgs a;
     memset(&a, 0, sizeof a);
     a.xside = xside; a.qt = s.qt; a.table = j.table;
-    a.tau = j.st_d; a.max_violation = j.st_d + N * Bm; a.ctrl = j.st_d + (N + (size_t)d.n_rows) * Bm;
-    a.active_ticks = j.st_i;
+    a.tau = j.tau(Bm); a.max_violation = j.max_violation(Bm); a.ctrl = j.ctrl(Bm, d.n_rows); a.active_ticks = j.active_ticks(Bm);
     a.B = B; a.R = d.n_rows; a.per_robot = d.per_robot; a.stride = (int32_t)Bm;
     const bool list = s.prog.kind == Program::LIST;
-    a.gripper_force = list ? s.prog.al_d + 2 * Bm : nullptr;
+    a.gripper_force = list ? s.prog.gripper_force(Bm) : nullptr;      // (the list's own state: what its ACTION drives read)
     int items = 0;
     for (int h = 0; h < (int)n; ++h) {
         a.first[h] = (uint8_t)items;
@@ -1837,16 +1841,31 @@ static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* x
     return a;
 }
 
+// The arguments of the plant kernel behind the tick's step on bank bk over B robots (trace: the device sample of its EE poses, or nullptr)
+static PlantArgs plant_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_ctx::Bank& bk, double* trace) {
+    PlantArgs a;
+    memset(&a, 0, sizeof a);
+    a.xside = bk.xside[0]; a.u = bk.u[0]; a.flags = bk.flags[0]; a.qt = s.qt; a.qpos = s.qpos; a.qvel = s.qvel;
+    a.trace = trace; a.flags_any = c->dflags_any; a.dt = c->plant.dt; a.damping = c->plant.damping; a.ctrl_mask = c->plant.ctrl_mask;
+    a.B = B; a.ndev = c->cfg.ndev; fill_ee0(c, a.ee0);
+    return a;
+}
+
+// What the slot has of one part (`robots` of `what`; 0: none) covers B robots.  With `setter` (a download) a slot that has none is refused,
+// by the name of the entry point that sets it; without (a rollout) it passes.
+static int check_covers(irlosc_ctx* c, int slot, int B, int robots, const char* what, const char* covers, const char* setter) {
+    if (setter && !robots) return fail(c, IRLOSC_ERR_STATE, "slot %d has no %s (%s)", slot, what, setter);
+    if (robots && B > robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s %s %d robots, %sasked for %d", slot, what, covers, robots, setter ? "" : "rollout ", B);
+    return IRLOSC_OK;
+}
+
 // The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
 static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
     const Program& p = c->slot[slot].prog;
     const bool paths = (need ? need : p.kind) == Program::PATHS;
-    if (need && p.kind != need)
-        return fail(c, IRLOSC_ERR_STATE, "slot %d has no %s", slot, paths ? "waypoint paths (irlosc_set_waypoints)" : "action list (irlosc_set_action_list)");
-    if (p.kind && B > p.robots)
-        return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s %d robots, %sasked for %d", slot, paths ? "waypoint paths cover" : "action list covers",
-                    p.robots, need ? "" : "rollout ", B);
-    return IRLOSC_OK;
+    return check_covers(c, slot, B, !need || p.kind == need ? p.robots : 0, paths ? "waypoint paths" : "action list", paths ? "cover" : "covers",
+                        !need ? nullptr : paths ? "irlosc_set_waypoints" : "irlosc_set_action_list");
 }
 
 // A program's table [nb][E] in the layout its kernel walks: per robot [walk wave][E][64] (idle lanes zero), shared (nb == 1) as given
@@ -1857,20 +1876,83 @@ static std::vector<double> walk_table(const double* t, int nb, size_t E) {
     return tab;
 }
 
-// The tail of a program's setter: its host arrays to the device and the init launch of its kernel on the context's stream -> the first
-// error.  Synchronises also when a copy or the launch failed: the host arrays are the copies' sources.  Only then is the program in force.
-struct HostCopy { void* dst; const void* src; size_t bytes; };
-template <typename Args>
-static int program_upload(irlosc_ctx* c, std::initializer_list<HostCopy> copies, int (*init64)(const Args&, hipStream_t),
-                          int (*init32)(const Args&, hipStream_t), const Args& a) {
+// The tail of every setter of a program or of what acts on the plant: host arrays to the device and fills with a byte value (src == nullptr)
+// as listed, then the init launch of a program's kernel if given, on the context's stream -> the first error.  Synchronises also when one of
+// them failed: the host arrays are the copies' sources.  Only then does the caller bring the part in force.
+struct Upload { void* dst; const void* src; size_t bytes; int byte; };
+template <typename Args = int>
+static int setter_upload(irlosc_ctx* c, std::initializer_list<Upload> ups, int (*init)(const Args&, hipStream_t) = nullptr, const Args* a = nullptr) {
     hipError_t ec = hipSuccess;
-    for (const HostCopy& k : copies)
-        if (ec == hipSuccess) ec = hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->stream);
-    if (ec == hipSuccess) ec = (hipError_t)(c->cfg.dtype == IRLOSC_F64 ? init64 : init32)(a, c->stream);
+    for (const Upload& k : ups)
+        if (ec == hipSuccess) ec = k.src ? hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(k.dst, k.byte, k.bytes, c->stream);
+    if (ec == hipSuccess && init) ec = (hipError_t)init(*a, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
     HIPCHK(c, ec);
     HIPCHK(c, es);
     return IRLOSC_OK;
+}
+
+// A download of per-robot state: `nd` doubles at sd and `ni` ints at si (either may be 0) to the host, one synchronise, then every Gather: row
+// p of the `count` rows [max_batch] from `src` on (the owner's accessor) goes to dst[b * ld + off + p * step], b < B (dst == NULL: skipped)
+template <typename T> struct Gather { T* dst; const T* src; size_t count, ld, off, step; };
+static int download_state(irlosc_ctx* c, int B, const double* sd, size_t nd, std::initializer_list<Gather<double>> gd, const int32_t* si,
+                          size_t ni, std::initializer_list<Gather<int32_t>> gi) {
+    std::vector<double> hd(nd);  std::vector<int32_t> hi(ni);
+    if (nd) HIPCHK(c, hipMemcpyAsync(hd.data(), sd, hd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (ni) HIPCHK(c, hipMemcpyAsync(hi.data(), si, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    auto gather = [&](const auto& h, const auto* dev, const auto& to) {
+        for (const auto& g : to)
+            for (size_t b = 0; g.dst && b < (size_t)B; ++b)
+                for (size_t p = 0; p < g.count; ++p) g.dst[b * g.ld + g.off + p * g.step] = h[(size_t)(g.src - dev) + p * Bm + b];
+    };
+    gather(hd, sd, gd); gather(hi, si, gi);
+    return IRLOSC_OK;
+}
+
+// What a tick of a rollout runs next to its fused step, decided once per tick from the slot (the default: no tick, nothing): the program that writes its
+// targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); rows
+struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; };
+static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
+    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0};
+    for (int p = 0; tp.push_sense && p < IRLOSC_MAX_PUSHES; ++p)
+        if (((tp.push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) tp.push_sense &= ~(1u << p);
+    if (s0.feed > 0 && s0.walls.tick > 0) tp.wall_sense = tp.wall_apply;
+    for (int d = 0; tp.wall_sense && d < c->cfg.ndev; ++d)
+        if (c->ft_f0[d] < 0) tp.wall_sense &= ~(1u << d);
+    return tp;
+}
+
+// THE ORDER OF A TICK'S LAUNCHES on the stream of bank 0 ([..]: where the plan has it; the unnamed lines are fused_train's own):
+//     the walk, the feed's wrench (ft_launch)
+//     tick_front:   [pushes SENSE: their reaction goes into the wrench ahead of every kernel that reads it] [walls SENSE: their force of the
+//                   tick before, behind it] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel]
+//     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
+//     tick_behind:  [waypoint cycler: the targets move where an arm arrived]; [pushes APPLY] [walls APPLY] [joint rows], each into the bias
+//                   entries of the block, which only the plant reads from here on; the plant: every robot has its u by then
+// What rests on this order alone: "pushes, then walls, then joint rows" on one bias entry of one tick.
+template <typename T>
+static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, const irlosc_ctx::Bank& bk, void* wrench, hipStream_t st) {
+    if (tp.push_sense) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_sense, nullptr, wrench), st));
+    if (tp.wall_sense) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_sense, nullptr, wrench), st));
+    if (tp.prog == Program::LIST) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
+    return IRLOSC_OK;
+}
+template <typename T>
+static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, const irlosc_ctx::Bank& bk, const PlantCall& pl, hipStream_t st) {
+    if (tp.prog == Program::PATHS) HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s0, B, s0.prog.wp, bk.xside[0], s0.prog.tick), st));
+    if (tp.push_apply) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_apply, bk.xside[0], nullptr), st));
+    if (tp.wall_apply) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_apply, bk.xside[0], nullptr), st));
+    if (tp.joints) HIPCHK(c, (hipError_t)launch_joints(joint_args(c, s0, B, bk.xside[0]), st));
+    HIPCHK(c, (hipError_t)launch_plant<T>(plant_args(c, s0, B, bk, pl.trace), st));
+    return IRLOSC_OK;
+}
+// The whole tick is enqueued: the slot's coordinates are the plant's, and what ran is a tick older (a slot without a program ticks none).
+static void tick_done(Slot& s0, int B, const TickPlan& tp) {
+    s0.advanced(B);
+    if (tp.prog != Program::NONE) s0.prog.ticked();
+    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked();      // (each ticks only where it is in force)
 }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
@@ -1891,8 +1973,7 @@ struct DevCall {
 // With `dv` (one step on bank 0) the caller's arrays replace every per-slot input -- coordinates (the walk reads the slot's dqt, which
 // the device entry has laid them out into), targets, sensordata -- and its u / flags the output set; the slot only lends scratch.
 // A step whose slot has a sensor feed gets its wrench from the feed (osc_ft_wrench between the walk and the OSC step).
-// With `pl` (one step on bank 0 of the slot's own inputs: a tick of irlosc_rollout_from_q) the plant kernel follows the give-up pass --
-// the robots the generic kernel finishes have their u by then -- and advances the slot's coordinates.
+// With `pl` (one step on bank 0 of the slot's own inputs: a tick of irlosc_rollout_from_q) tick_front and tick_behind run around the step (above).
 template <typename T>
 static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, const DevCall* dv, const PlantCall* pl = nullptr) {
     if (n < 1 || n > R16_TRAIN) return fail(c, IRLOSC_ERR_STATE, "train of %d steps", n);
@@ -1906,17 +1987,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     const irlosc_ctx::Bank& bk = c->bank[k];
     const hipStream_t st = dv ? dv->st : bk.st;
     Slot& s0 = c->slot[slots[0]];      // (the slot of a rollout's tick)
-    const Program::Kind prog = pl ? s0.prog.kind : Program::NONE;      // what writes its targets inside the rollout
-    // what pushes its plant on this tick, and what its sensors read of the tick before: where it has a feed and the device a sensor
-    const uint32_t push_apply = pl ? s0.push.applied() : 0u;
-    uint32_t push_sense = pl && s0.feed > 0 ? s0.push.sensed() : 0u;
-    for (int p = 0; push_sense && p < IRLOSC_MAX_PUSHES; ++p)
-        if (((push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) push_sense &= ~(1u << p);
-    // the walls its EE bodies run into on this tick, and what its sensors read of their force of the tick before
-    const uint32_t wall_apply = pl ? s0.walls.devices() : 0u;
-    uint32_t wall_sense = pl && s0.feed > 0 && s0.walls.tick > 0 ? wall_apply : 0u;
-    for (int d = 0; wall_sense && d < c->cfg.ndev; ++d)
-        if (c->ft_f0[d] < 0) wall_sense &= ~(1u << d);
+    const TickPlan tp = pl ? tick_plan(c, s0) : TickPlan{};
     FtStep fts[R16_TRAIN];
     int nft = 0;
     FeLaneTrain ft;
@@ -1942,7 +2013,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
         StepInputs in = slot_inputs(s, wr);
         if (dv) { in.tgt = dv->tgt; in.tvel = dv->tvel; in.wrench = wr; }
         fill_params<T>(c, tr.p[i], B, in, dv ? dv->u : bk.u[i], dv ? dv->flags : bk.flags[i]);
-        if (prog == Program::LIST) {      // a tick of a slot with an action list: its own gains, which the action kernel writes per robot
+        if (tp.prog == Program::LIST) {      // a tick of a slot with an action list: its own gains, which the action kernel writes per robot
             tr.p[i].gains = (const T*)s.prog.al_gains.get(); tr.p[i].null_kv = (const T*)s.prog.al_nullkv.get();
             tr.p[i].gains_per_instance = 1;
         }
@@ -1969,13 +2040,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     if (c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
     HIPCHK(c, (hipError_t)fused_walk(c).launch(c->model.dmodel, ft, n, st));
     int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
+    if (!rcw && pl) rcw = tick_front<T>(c, s0, B, tp, bk, nft ? fts[0].wrench : nullptr, st);
     if (rcw) return rcw;
-    if (push_sense)      // the sensed pushes: the reaction goes into the wrench ahead of every kernel that reads it
-        HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_sense, nullptr, fts[0].wrench), st));
-    if (wall_sense)      // the walls' force of the tick before, behind the pushes' reaction
-        HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, wall_sense, nullptr, fts[0].wrench), st));
-    if (prog == Program::LIST)      // the action list: its targets and velocity limit are this tick's, so in front of every OSC kernel
-        HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (use_lane) {
         if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
         HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
@@ -1984,33 +2050,13 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     }
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
-    if (prog == Program::PATHS)      // the targets move where an arm arrived: behind every OSC kernel of the tick, in front of the plant
-        HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s0, B, s0.prog.wp, bk.xside[0], s0.prog.tick), st));
-    if (push_apply)      // the applied pushes: into the bias entries of the block, which only the plant reads from here on
-        HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, push_apply, bk.xside[0], nullptr), st));
-    if (wall_apply)      // the walls: their force from this tick's EE position and velocity, into the bias behind the pushes
-        HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, wall_apply, bk.xside[0], nullptr), st));
-    if (pl && s0.joints.robots)      // the joint rows: stops, couplings and drives from this tick's coordinates, into the bias behind the walls
-        HIPCHK(c, (hipError_t)launch_joints(joint_args(c, s0, B, bk.xside[0]), st));
-    if (pl) {
-        PlantArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.xside = bk.xside[0]; pa.u = bk.u[0]; pa.flags = bk.flags[0];
-        pa.qt = s0.qt; pa.qpos = s0.qpos; pa.qvel = s0.qvel;
-        pa.trace = pl->trace; pa.flags_any = c->dflags_any;
-        pa.dt = c->plant.dt; pa.damping = c->plant.damping; pa.ctrl_mask = c->plant.ctrl_mask;
-        pa.B = B; pa.ndev = c->cfg.ndev;
-        for (int d = 0; d < c->cfg.ndev; ++d) pa.ee0[d] = c->model.tables.eetab[d][0];
-        HIPCHK(c, (hipError_t)launch_plant<T>(pa, st));
-    }
+    if (pl && (rcw = tick_behind<T>(c, s0, B, tp, bk, *pl, st))) return rcw;
     if (c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
     // The give-up pass wrote dense records of the robots on its lists into the slots (and nothing for the others): what the
     // slots held before no longer belongs to one state.  They hold no records from here on -- irlosc_step / irlosc_step_resident
     // / irlosc_download_records on them fail with IRLOSC_ERR_STATE until irlosc_frontend / irlosc_upload* fills them again.
     for (int i = 0; i < n; ++i) c->slot[slots[i]].voided();
-    if (pl) s0.advanced(B);
-    if (prog != Program::NONE) s0.prog.ticked();
-    if (pl) { s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); }
+    if (pl) tick_done(s0, B, tp);
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2276,12 +2322,9 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     rc = check_slot_q(c, slot, B);
     if (!rc) rc = check_slot_feed(c, slot, B);
     if (!rc) rc = check_program(c, slot, B);
-    if (!rc && c->slot[slot].push.robots && B > c->slot[slot].push.robots)
-        rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its pushes cover %d robots, rollout asked for %d", slot, c->slot[slot].push.robots, B);
-    if (!rc && c->slot[slot].walls.robots && B > c->slot[slot].walls.robots)
-        rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its walls cover %d robots, rollout asked for %d", slot, c->slot[slot].walls.robots, B);
-    if (!rc && c->slot[slot].joints.robots && B > c->slot[slot].joints.robots)
-        rc = fail(c, IRLOSC_ERR_STATE, "slot %d: its joint rows cover %d robots, rollout asked for %d", slot, c->slot[slot].joints.robots, B);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].push.robots, "pushes", "cover", nullptr);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].walls.robots, "walls", "cover", nullptr);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
     if (rc) return rc;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
@@ -2344,10 +2387,11 @@ extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, cons
     Program& p = s.prog;
     p.end();           // (none until the new ones are in their buffers; the paths write the targets from here on: an action list ends)
     const std::vector<double> tab = walk_table(dense.data(), w->nb, E);
-    const size_t bytes = tab.size() * sizeof(double), state = (size_t)3 * nd * c->cfg.max_batch * sizeof(int32_t);
+    const size_t bytes = tab.size() * sizeof(double), state = p.wp_words((size_t)nd * c->cfg.max_batch) * sizeof(int32_t);
     if (!got(p.wp_table.reserve(bytes)) || !got(p.wp_i.ensure(state)))
         return fail(c, IRLOSC_ERR_HIP, "out of device memory for the waypoint paths of slot %d (%zu bytes)", slot, bytes + state);
-    rc = program_upload(c, {{p.wp_table, tab.data(), bytes}}, launch_waypoints<double>, launch_waypoints<float>, waypoint_args(c, s, B, *w, nullptr, 0));
+    const WaypointArgs init = waypoint_args(c, s, B, *w, nullptr, 0);
+    rc = setter_upload(c, {{p.wp_table, tab.data(), bytes}}, c->cfg.dtype == IRLOSC_F64 ? launch_waypoints<double> : launch_waypoints<float>, &init);
     if (!rc) p.paths(B, *w);
     return rc;
 }
@@ -2360,16 +2404,9 @@ extern "C" int irlosc_download_waypoint_state(irlosc_ctx* c, int32_t slot, int32
     const Program& p = c->slot[slot].prog;
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    // SoA [3][ndev][max_batch] on the device -> [B][ndev] each for the caller
-    const size_t nd = (size_t)c->cfg.ndev, Bm = (size_t)c->cfg.max_batch;
-    std::vector<int32_t> h(3 * nd * Bm);
-    HIPCHK(c, hipMemcpyAsync(h.data(), p.wp_i, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int32_t* dst[3] = {index, (int32_t*)arrivals, last_tick};
-    for (size_t i = 0; i < 3; ++i)
-        for (size_t b = 0; dst[i] && b < (size_t)B; ++b)
-            for (size_t d = 0; d < nd; ++d) dst[i][b * nd + d] = h[(i * nd + d) * Bm + b];
-    return IRLOSC_OK;
+    const size_t nd = (size_t)c->cfg.ndev, plane = nd * c->cfg.max_batch;      // planes [ndev][max_batch] on the device -> [B][ndev] each for the caller
+    return download_state(c, B, nullptr, 0, {}, p.wp_i, p.wp_words(plane), {{index, p.index(plane), nd, nd, 0, 1},
+                          {(int32_t*)arrivals, p.arrivals(plane), nd, nd, 0, 1}, {last_tick, p.last_tick(plane), nd, nd, 0, 1}});
 }
 
 // ---- external pushes of the rollout (osc_push.hpp) ----------------------------------------------------------------------------
@@ -2402,12 +2439,9 @@ extern "C" int irlosc_set_pushes(irlosc_ctx* c, int32_t slot, int32_t B, const i
     const std::vector<double> tab = walk_table(wrench, d->nb, E);
     const size_t bytes = tab.size() * sizeof(double);
     if (!got(ps.table.reserve(bytes))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for the pushes of slot %d (%zu bytes)", slot, bytes);
-    const hipError_t ec = hipMemcpyAsync(ps.table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
-    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when the copy failed: the host array is its source)
-    HIPCHK(c, ec);
-    HIPCHK(c, es);
-    ps.set(B, *d);
-    return IRLOSC_OK;
+    rc = setter_upload(c, {{ps.table, tab.data(), bytes}});
+    if (!rc) ps.set(B, *d);
+    return rc;
 }
 
 // ---- compliant walls of the rollout (osc_wall.hpp) ------------------------------------------------------------------------------
@@ -2442,45 +2476,29 @@ extern "C" int irlosc_set_walls(irlosc_ctx* c, int32_t slot, int32_t B, const ir
     ws.end();          // (none until the new ones are in their table and their state is reset)
     const std::vector<double> tab = walk_table(table, d->nb, E);
     const size_t bytes = tab.size() * sizeof(double), plane = (size_t)nd * c->cfg.max_batch;
-    if (!got(ws.table.reserve(bytes)) || !got(ws.st_d.ensure(4 * plane * sizeof(double))) || !got(ws.st_i.ensure(2 * plane * sizeof(int32_t))))
-        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the walls of slot %d (%zu bytes)", slot, bytes + plane * 40);
-    hipError_t ec = hipMemcpyAsync(ws.table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
-    if (ec == hipSuccess) ec = hipMemsetAsync(ws.st_d, 0, 4 * plane * sizeof(double), c->stream);                      // force, max_depth = 0
-    if (ec == hipSuccess) ec = hipMemsetAsync(ws.st_i, 0, plane * sizeof(int32_t), c->stream);                         // contact_ticks = 0
-    if (ec == hipSuccess) ec = hipMemsetAsync(ws.st_i + plane, 0xff, plane * sizeof(int32_t), c->stream);              // first_tick = -1
-    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when a copy failed: the host array is its source)
-    HIPCHK(c, ec);
-    HIPCHK(c, es);
-    ws.set(B, *d);
-    return IRLOSC_OK;
+    const size_t d_bytes = ws.d_words(plane) * sizeof(double), i_bytes = ws.i_words(plane) * sizeof(int32_t);
+    if (!got(ws.table.reserve(bytes)) || !got(ws.st_d.ensure(d_bytes)) || !got(ws.st_i.ensure(i_bytes)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the walls of slot %d (%zu bytes)", slot, bytes + d_bytes + i_bytes);
+    rc = setter_upload(c, {{ws.table, tab.data(), bytes}, {ws.st_d, nullptr, d_bytes, 0},                // force, max_depth = 0
+                       {ws.contact_ticks(plane), nullptr, plane * sizeof(int32_t), 0},                   // contact_ticks = 0
+                       {ws.first_tick(plane), nullptr, plane * sizeof(int32_t), 0xff}});                 // first_tick = -1
+    if (!rc) ws.set(B, *d);
+    return rc;
 }
 
 extern "C" int irlosc_download_wall_state(irlosc_ctx* c, int32_t slot, int32_t B, double* force, double* max_depth, int32_t* contact_ticks,
                                           int32_t* first_tick) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].walls.robots, "walls", "cover", "irlosc_set_walls");
     if (rc) return rc;
     const Walls& ws = c->slot[slot].walls;
-    if (!ws.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d has no walls (irlosc_set_walls)", slot);
-    if (B > ws.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d: its walls cover %d robots, asked for %d", slot, ws.robots, B);
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    // SoA [4][ndev][max_batch] and [2][ndev][max_batch] on the device -> [B][ndev](,3) for the caller
-    const size_t nd = (size_t)c->cfg.ndev, Bm = (size_t)c->cfg.max_batch, plane = nd * Bm;
-    std::vector<double> hd(4 * plane);
-    std::vector<int32_t> hi(2 * plane);
-    HIPCHK(c, hipMemcpyAsync(hd.data(), ws.st_d, hd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hi.data(), ws.st_i, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t b = 0; b < (size_t)B; ++b)
-        for (size_t d = 0; d < nd; ++d) {
-            const size_t so = d * Bm + b, o = b * nd + d;
-            for (size_t k = 0; force && k < 3; ++k) force[o * 3 + k] = hd[k * plane + so];
-            if (max_depth) max_depth[o] = hd[3 * plane + so];
-            if (contact_ticks) contact_ticks[o] = hi[so];
-            if (first_tick) first_tick[o] = hi[plane + so];
-        }
-    return IRLOSC_OK;
+    const size_t nd = (size_t)c->cfg.ndev, plane = nd * c->cfg.max_batch;      // planes [ndev][max_batch] on the device -> [B][ndev](,3) for the caller
+    return download_state(c, B, ws.st_d, ws.d_words(plane), {{force, ws.force(plane, 0), nd, nd * 3, 0, 3}, {force, ws.force(plane, 1), nd, nd * 3, 1, 3},
+                          {force, ws.force(plane, 2), nd, nd * 3, 2, 3}, {max_depth, ws.max_depth(plane), nd, nd, 0, 1}},
+                          ws.st_i, ws.i_words(plane), {{contact_ticks, ws.contact_ticks(plane), nd, nd, 0, 1}, {first_tick, ws.first_tick(plane), nd, nd, 0, 1}});
 }
 
 // ---- joint rows of the rollout (osc_joint.hpp) ------------------------------------------------------------------------------------
@@ -2531,46 +2549,26 @@ extern "C" int irlosc_set_joints(irlosc_ctx* c, int32_t slot, int32_t B, const i
     js.end();          // (none until the new ones are in their table and their state is reset)
     const std::vector<double> tab = walk_table(table, nb, E);
     const size_t bytes = tab.size() * sizeof(double), Bm = (size_t)c->cfg.max_batch;
-    const size_t nd_words = ((size_t)IRLOSC_MAX_N + 2 * (size_t)R) * Bm, ni_words = (size_t)R * Bm;
-    if (!got(js.table.reserve(bytes)) || !got(js.st_d.reserve(nd_words * sizeof(double))) || !got(js.st_i.reserve(ni_words * sizeof(int32_t))))
-        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the joint rows of slot %d (%zu bytes)", slot,
-                    bytes + nd_words * sizeof(double) + ni_words * sizeof(int32_t));
-    hipError_t ec = hipMemcpyAsync(js.table, tab.data(), bytes, hipMemcpyHostToDevice, c->stream);
-    if (ec == hipSuccess) ec = hipMemsetAsync(js.st_d, 0, nd_words * sizeof(double), c->stream);      // tau, max_violation, ctrl = 0
-    if (ec == hipSuccess) ec = hipMemsetAsync(js.st_i, 0, ni_words * sizeof(int32_t), c->stream);     // active_ticks = 0
-    const hipError_t es = hipStreamSynchronize(c->stream);      // (also when a copy failed: the host array is its source)
-    HIPCHK(c, ec);
-    HIPCHK(c, es);
-    js.set(B, *d);
-    return IRLOSC_OK;
+    const size_t d_bytes = js.d_words(Bm, R) * sizeof(double), i_bytes = js.i_words(Bm, R) * sizeof(int32_t);
+    if (!got(js.table.reserve(bytes)) || !got(js.st_d.reserve(d_bytes)) || !got(js.st_i.reserve(i_bytes)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the joint rows of slot %d (%zu bytes)", slot, bytes + d_bytes + i_bytes);
+    rc = setter_upload(c, {{js.table, tab.data(), bytes}, {js.st_d, nullptr, d_bytes, 0}, {js.st_i, nullptr, i_bytes, 0}});      // every word of the state = 0
+    if (!rc) js.set(B, *d);
+    return rc;
 }
 
 extern "C" int irlosc_download_joint_state(irlosc_ctx* c, int32_t slot, int32_t B, double* tau, double* max_violation, int32_t* active_ticks,
                                            double* ctrl) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", "irlosc_set_joints");
     if (rc) return rc;
     const Joints& js = c->slot[slot].joints;
-    if (!js.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d has no joint rows (irlosc_set_joints)", slot);
-    if (B > js.robots) return fail(c, IRLOSC_ERR_STATE, "slot %d: its joint rows cover %d robots, asked for %d", slot, js.robots, B);
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
-    // SoA [MAX_N + 2 R][max_batch] and [R][max_batch] on the device -> [B][n], [B][R] for the caller
-    const size_t n = (size_t)c->cfg.n, R = (size_t)js.d.n_rows, Bm = (size_t)c->cfg.max_batch, N = IRLOSC_MAX_N;
-    std::vector<double> hd((N + 2 * R) * Bm);
-    std::vector<int32_t> hi(R * Bm);
-    HIPCHK(c, hipMemcpyAsync(hd.data(), js.st_d, hd.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hi.data(), js.st_i, hi.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (size_t b = 0; b < (size_t)B; ++b) {
-        for (size_t j = 0; tau && j < n; ++j) tau[b * n + j] = hd[j * Bm + b];
-        for (size_t r = 0; r < R; ++r) {
-            if (max_violation) max_violation[b * R + r] = hd[(N + r) * Bm + b];
-            if (ctrl) ctrl[b * R + r] = hd[(N + R + r) * Bm + b];
-            if (active_ticks) active_ticks[b * R + r] = hi[r * Bm + b];
-        }
-    }
-    return IRLOSC_OK;
+    const size_t n = (size_t)c->cfg.n, R = (size_t)js.d.n_rows, Bm = (size_t)c->cfg.max_batch;      // rows [max_batch] on the device -> [B][n], [B][R] for the caller
+    return download_state(c, B, js.st_d, js.d_words(Bm, R), {{tau, js.tau(Bm), n, n, 0, 1}, {max_violation, js.max_violation(Bm), R, R, 0, 1},
+                          {ctrl, js.ctrl(Bm, R), R, R, 0, 1}}, js.st_i, js.i_words(Bm, R), {{active_ticks, js.active_ticks(Bm), R, R, 0, 1}});
 }
 
 // ---- the WP / GRIP action list of the rollout (osc_action.hpp) ---------------------------------------------------------------
@@ -2644,11 +2642,12 @@ extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, co
     }
     const std::vector<double> tab = walk_table(pose, d->nb, (size_t)A * 7);
     const size_t bytes = tab.size() * sizeof(double), Bm = (size_t)c->cfg.max_batch;
-    if (!got(p.al_table.reserve(bytes)) || !got(p.al_i.ensure(4 * Bm * sizeof(int32_t))) || !got(p.al_d.ensure(6 * Bm * sizeof(double))) ||
+    if (!got(p.al_table.reserve(bytes)) || !got(p.al_i.ensure(p.al_i_words(Bm) * sizeof(int32_t))) || !got(p.al_d.ensure(p.al_d_words(Bm) * sizeof(double))) ||
         !got(p.al_gains.ensure(Bm * rec)) || !got(p.al_nullkv.ensure(Bm * e)))
         return fail(c, IRLOSC_ERR_HIP, "out of device memory for the action list of slot %d", slot);
-    rc = program_upload(c, {{p.al_table, tab.data(), bytes}, {p.al_gains, gs.data(), gs.size()}, {p.al_nullkv, nks.data(), nks.size()}},
-                        launch_actions<double>, launch_actions<float>, action_args(c, s, B, *d, nullptr, 0));
+    const ActionArgs init = action_args(c, s, B, *d, nullptr, 0);
+    rc = setter_upload(c, {{p.al_table, tab.data(), bytes}, {p.al_gains, gs.data(), gs.size()}, {p.al_nullkv, nks.data(), nks.size()}},
+                       c->cfg.dtype == IRLOSC_F64 ? launch_actions<double> : launch_actions<float>, &init);
     if (!rc) p.list(B, *d);
     return rc;
 }
@@ -2663,13 +2662,12 @@ extern "C" int irlosc_download_action_state(irlosc_ctx* c, int32_t slot, int32_t
     if (B == 0) return IRLOSC_OK;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t Bm = (size_t)c->cfg.max_batch;
-    int32_t* di[3] = {action, grip_left, finished_tick};
-    const size_t oi[3] = {0, 2 * Bm, 3 * Bm};
+    int32_t* di[3] = {action, grip_left, finished_tick};  const int32_t* si[3] = {p.action(Bm), p.grip_left(Bm), p.finished_tick(Bm)};
     for (int i = 0; i < 3; ++i)
-        if (di[i]) HIPCHK(c, hipMemcpyAsync(di[i], p.al_i + oi[i], (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    double* dd[3] = {err, max_vel0, gripper_force};
+        if (di[i]) HIPCHK(c, hipMemcpyAsync(di[i], si[i], (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    double* dd[3] = {err, max_vel0, gripper_force};  const double* sd[3] = {p.err(Bm), p.max_vel0(Bm), p.gripper_force(Bm)};
     for (int i = 0; i < 3; ++i)
-        if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], p.al_d + i * Bm, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], sd[i], (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }
