@@ -92,6 +92,13 @@ __device__ __forceinline__ void st_su(gptr ubase, const uint32_t voff, const dou
     *reinterpret_cast<gptr>(reinterpret_cast<__attribute__((address_space(1))) char*>(ubase) + voff) = v;
 }
 __device__ __forceinline__ void st_su(double* ubase, const uint32_t voff, const double v) { st_su((gptr)ubase, voff, v); }
+// the same form in LDS: a compile-time position in a __shared__ array + the lane's byte offset (the constant goes into the instruction)
+__device__ __forceinline__ double ld_lds(const double* sbase, const uint32_t voff) {
+    return *reinterpret_cast<const __attribute__((address_space(3))) double*>((const __attribute__((address_space(3))) char*)sbase + voff);
+}
+__device__ __forceinline__ void st_lds(double* sbase, const uint32_t voff, const double v) {
+    *reinterpret_cast<__attribute__((address_space(3))) double*>((__attribute__((address_space(3))) char*)sbase + voff) = v;
+}
 
 // Records of the flagged robots, transposed: [group of 64 records][entry][64] doubles -- what a lane writes and what a lane of the eigen
 // pass reads sits next to its neighbours' (slots of a wave's flagged lanes are consecutive: coalesced both ways).  Entries: the lower
@@ -209,6 +216,20 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     const uint32_t realm = lt.map.real;
     __shared__ double s_u[NJ * 65];                    // M dq as the hinges complete, then the torques: [hinge][64 robots + 1 pad]
     __shared__ double s_w[K * 64];                     // the task vector waits here across the recursion and the k x k stage
+    // -DIRLOSC_LANE_JPARK=1 (A/B builds, tools/build_variant.py; OFF in the product): the entries of J the recursion has consumed wait here
+    // for J^T t behind the k x k stage, as many as the SIMD's quarter of the CU's LDS holds next to s_u and s_w (one single-wave block per
+    // SIMD: 163 840 / 4 bytes each; 41 of 85 for rows (1, 6, 6), all 43 for (1, 3, 3)): [slot = Rec::jslot][64 robots], lane-contiguous like
+    // s_w, and only the entries beyond NPARK are read from the block a second time.  Measured: the kernel's FETCH_SIZE falls by the
+    // predicted 166 MB per train and the headline does not move with it -- alone it is 2.7 % SLOWER than reading J twice (the second read is
+    // 20 us behind the first and does not cost what its bytes say; the 82 LDS operations per wave do): profiles/NOTES.md, "Lane parking".
+#ifndef IRLOSC_LANE_JPARK
+#define IRLOSC_LANE_JPARK 0
+#endif
+    constexpr int LDS_SIMD = 163840 / 4;
+    constexpr int NPARK_FIT = (LDS_SIMD - (int)sizeof(s_u) - (int)sizeof(s_w)) / 512;
+    constexpr int NPARK = IRLOSC_LANE_JPARK ? (Rec<L>::n_j() < NPARK_FIT ? Rec<L>::n_j() : NPARK_FIT) : 0;
+    __shared__ double s_j[(NPARK > 0 ? NPARK : 1) * 64];
+    static_assert(sizeof(s_u) + sizeof(s_w) + (NPARK > 0 ? sizeof(s_j) : 0) <= LDS_SIMD, "four single-wave blocks share a CU's LDS");
     // -DIRLOSC_LANE_STAMPS (tools/build_variant.py; tools/phase_timing.py ... fromq with IRLOSC_PHASE_LANE=1): cycle stamps per phase into
     // p.dbg.  Compile-time only: a run-time `if (p.dbg)` around a stamp is a branch, and a branch inside the recursion lets the compiler
     // sink the arithmetic out of its pinned regions (see pin()).
@@ -412,6 +433,8 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
                 constexpr int r = decltype(rc)::value;
                 if constexpr (L::row_moved(r, j)) {
                     const double jv = Jv[r][j];
+                    constexpr int js = Rec<L>::jslot(r, j);     // (a constexpr variable first: inside an index the function runs at run time)
+                    if constexpr (js < NPARK) s_j[js * 64 + lane] = jv;      // (padding rows park the zero they loaded)
                     dx[r] = fma(jv, dq[j], dx[r]);
                     pin(dx[r]);
                     double t = jv;
@@ -448,9 +471,9 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
 #ifndef IRLOSC_LANE_JT_EARLY
 #define IRLOSC_LANE_JT_EARLY 0
 #endif
-    // The Jacobian entries once more, for J^T t behind the k x k stage (and for the records of the flagged robots).  Requested ahead of
-    // that stage their round trip would run under its ~2 000 instructions -- but 85 more live doubles next to the factor's 91 spill
-    // (1.3 kB of scratch): they are requested behind it.
+    // The Jacobian entries once more, for J^T t behind the k x k stage (and for the records of the flagged robots; with IRLOSC_LANE_JPARK
+    // the parked ones from LDS, the rest from the block).  Requested ahead of that stage their round trip would run under its ~2 000
+    // instructions -- but 85 more live doubles next to the factor's 91 spill (1.3 kB of scratch): they are requested behind it.
     double Jt[K][NJ];
     auto load_jt = [&]() {
         static_for<0, NJ>([&](auto jc) {
@@ -458,7 +481,11 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
             if constexpr (L::hinge_ee(j)) {
                 static_for<0, K>([&](auto rc) {
                     constexpr int r = decltype(rc)::value;
-                    if constexpr (L::row_moved(r, j)) Jt[r][j] = jload(rc, jc);
+                    if constexpr (L::row_moved(r, j)) {
+                        constexpr int js = Rec<L>::jslot(r, j);
+                        if constexpr (js < NPARK) Jt[r][j] = s_j[js * 64 + lane];      // (own slot: written by this lane in the recursion)
+                        else Jt[r][j] = jload(rc, jc);
+                    }
                 });
             }
         });
@@ -654,6 +681,17 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
     const int n = __builtin_amdgcn_readfirstlane(min(*es.rec_count, et.B));
     if (n < et.lane_min) return;            // (a thin list: osc_lane_eigen16_kernel below has this step)
     const int lane = threadIdx.x;
+    // The first IRLOSC_EIG_APARK entries of A wait here between the loads of a group; -DIRLOSC_EIG_APARK=0: every load_A reads the whole
+    // triangle from the record.  80 entries would fit the SIMD's quarter of the CU's LDS (one single-wave block per SIMD), but the count is
+    // set by the registers: the compiler pairs these reads (two entries into an aligned register quadruple) next to a full register file --
+    // scratch bytes per lane of the k = 13 instantiation at 0 / 24 / 48 / 56 / 64 / 80 entries: 148 / 484 / 0 / 124 / 188 / 204
+    // (single reads through volatile or asm: 380 / 852).  Check with tools/kernel_regs.py after any change to this kernel.
+#ifndef IRLOSC_EIG_APARK
+#define IRLOSC_EIG_APARK 48
+#endif
+    constexpr int APARK = NA < IRLOSC_EIG_APARK ? NA : IRLOSC_EIG_APARK;
+    __shared__ double s_a[(APARK > 0 ? APARK : 1) * 64];
+    static_assert(APARK == 0 || sizeof(s_a) <= 163840 / 4, "four single-wave blocks share a CU's LDS");
     for (int g = blockIdx.x; g * 64 < n; g += gridDim.x) {
         const bool live = g * 64 + lane < n;
         const double* __restrict__ rg = es.rec + (size_t)g * (R::E * 64);      // (uniform; the lane adds a 32-bit word offset)
@@ -665,13 +703,30 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
 #pragma unroll
         for (int r = 0; r < K; ++r) nr[r] = ((zrow >> r) & 1u) != 0;
         double Lf[NA], invd[K];
-        auto load_A = [&](double (&dst)[NA]) {
+        // FIRST = the group's first load: every entry from the record, the first APARK of them left in LDS on the way ([entry][64 lanes],
+        // addressed by the lane's byte offset vo + the instruction's constant: no address register of its own).  The later loads take those
+        // from LDS and only the remainder from the record.  A block's next group overwrites the array: one wave, LDS in program order.
+        // (Lanes past the list's end carry the last live lane's vo: they store what that lane stores, to the same address.)
+        auto load_A = [&](double (&dst)[NA], auto first) {
+            constexpr bool FIRST = decltype(first)::value;
             static_for<0, (NA + 7) / 8>([&](auto bc2) {
                 constexpr int e0 = 8 * decltype(bc2)::value;
-                const gcptr bp = sgpr_ptr(rg + e0 * 64);              // (eight entries within the instruction's offset field)
-                static_for<0, 8>([&](auto ec) { constexpr int e = e0 + decltype(ec)::value; if constexpr (e < NA) dst[e] = ld_su(bp + (e - e0) * 64, vo); });
+                if constexpr (FIRST || e0 + 8 > APARK) {
+                    const gcptr bp = sgpr_ptr(rg + e0 * 64);              // (eight entries within the instruction's offset field)
+                    static_for<0, 8>([&](auto ec) {
+                        constexpr int e = e0 + decltype(ec)::value;
+                        if constexpr (e < NA && (FIRST || e >= APARK)) dst[e] = ld_su(bp + (e - e0) * 64, vo);
+                    });
+                }
+            });
+            static_for<0, APARK>([&](auto ec) {               // (behind the requests: a store waits for its entry, not the next request for the store)
+                constexpr int e = decltype(ec)::value;
+                if constexpr (FIRST) st_lds(s_a + e * 64, vo, dst[e]);
+                else dst[e] = ld_lds(s_a + e * 64, vo);
             });
         };
+        constexpr std::true_type first_load{};
+        constexpr std::false_type reload{};
         auto factor = [&](double (&F)[NA], const double sigma, bool& pd) { ldl_inplace<L, true>(F, nr, invd, pd, sigma, nullptr, nullptr); };
         auto solve = [&](double (&z)[K]) {      // z <- (L~ D L~^T)^-1 z: the FMA chains of r16::solve16, per lane
             static_for<0, K - 1>([&](auto jc) {
@@ -691,7 +746,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
             for (int c = 0; c < K; ++c) { if (c & 1) s1 = fma(a[c], b2[c], s1); else s0 = fma(a[c], b2[c], s0); }
             return s0 + s1;
         };
-        load_A(Lf);
+        load_A(Lf, first_load);
         double nA2 = 0.0, lo = 0.0;
 #pragma unroll
         for (int r = 0; r < K; ++r) {
@@ -711,7 +766,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
             const bool use = live && broken;
             sigma = use ? hi * 0x1p-40 : 0.0;
             bool pd2;
-            load_A(Lf);
+            load_A(Lf, reload);
             factor(Lf, sigma, pd2);
             giveup = giveup || (use && !pd2);
         }
@@ -803,7 +858,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
             // Rayleigh-Ritz on the span of the candidates: H = V^T A V (4 x 4; unused vectors are zero), cyclic Jacobi, rotations applied to V
             double (&At)[NA] = Lf;              // (the factor is rebuilt behind this block: its registers hold A meanwhile)
             double h[NV][NV];
-            load_A(At);
+            load_A(At, reload);
             static_for<0, NV>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 double av[K];
@@ -871,7 +926,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
         for (int i = 0; i < NV; ++i) {
             cut[i] = below[i];
             if (__any(ask[i])) {
-                load_A(Lf);
+                load_A(Lf, reload);
 #pragma unroll
                 for (int e = 0; e < NA; ++e) Lf[e] = -Lf[e];
                 bool pdt;
@@ -881,7 +936,7 @@ __global__ __launch_bounds__(64, 1) void osc_lane_eigen_kernel(const EigTrain et
         }
         if (rr || wave_ask) {
             bool pd3;
-            load_A(Lf);
+            load_A(Lf, reload);
             factor(Lf, sigma, pd3);
         }
         int ncut = 0;
