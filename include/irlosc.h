@@ -472,15 +472,18 @@ IRLOSC_API int irlosc_rollout_from_q(irlosc_ctx* ctx, int32_t slot, int32_t B, i
 IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, double* qpos, double* qvel);
 
 /* ---- ONE WRITER OF THE TARGETS: the program of a slot's rollouts -------------------------------------------------------------
- * Inside a rollout the slot's targets are written by at most one PROGRAM: waypoint paths (irlosc_set_waypoints) or a WP / GRIP action
- * list (irlosc_set_action_list), never both; outside one by irlosc_set_targets.  Targets are written by one entry point at a time:
+ * Inside a rollout the slot's targets are written by at most one PROGRAM: waypoint paths (irlosc_set_waypoints), a WP / GRIP action
+ * list (irlosc_set_action_list) or a teleoperation stream (irlosc_set_teleop_stream), never two of them; outside one by
+ * irlosc_set_targets.  Targets are written by one entry point at a time:
  *     irlosc_set_targets on the slot (B == 0 too), irlosc_set_model (all slots)        any program ends
- *     irlosc_set_gains (all slots)                                                     a list ends (its gain copy is stale), paths stay
- *     irlosc_set_waypoints with desc == NULL or all counts 0                           paths end, a list stays
- *     irlosc_set_action_list with desc == NULL                                         a list ends, paths stay
+ *     irlosc_set_gains (all slots)                                                     a list ends (its gain copy is stale), paths and a stream stay
+ *     irlosc_set_waypoints with desc == NULL or all counts 0                           paths end, a list or a stream stays
+ *     irlosc_set_action_list with desc == NULL                                         a list ends, paths or a stream stay
+ *     irlosc_set_teleop_stream with desc == NULL                                       a stream ends, paths or a list stay
  *     a setter that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE                         nothing changes: the program in force stays, whole
  *     a setter that succeeds                                                           its program replaces whatever was in force
- *     a setter that answers IRLOSC_ERR_HIP (allocation, copy or init launch)           no program of its kind; irlosc_set_waypoints: none
+ *     a setter that answers IRLOSC_ERR_HIP (allocation, copy or init launch)           no program of its kind; irlosc_set_waypoints and
+ *                                                                                      irlosc_set_teleop_stream: none
  * Uploads of coordinates, records and sensor feeds leave the program alone.  Only irlosc_rollout_from_q runs it (on at most the B
  * robots it was set for: IRLOSC_ERR_STATE beyond); every other step ignores it and leaves its state as it is.  Its tick counts the
  * slot's rollout ticks since its setter and continues across calls of irlosc_rollout_from_q.  Clearing a program leaves the targets
@@ -600,6 +603,67 @@ IRLOSC_API int irlosc_set_action_list(irlosc_ctx* ctx, int32_t slot, int32_t B, 
  * IRLOSC_ERR_STATE on a slot without a list, or with a list for fewer than B robots.  Synchronous. */
 IRLOSC_API int irlosc_download_action_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* action, int32_t* grip_left, double* err,
                                             double* max_vel0, double* gripper_force, int32_t* finished_tick);
+
+/* ---- the space-mouse teleoperation stream on the GPU: a recorded session inside a rollout (csrc/osc_teleop.hpp) ------------------
+ * What examples/teleop_loops.py::space_mouse_loop does on the host per tick -- SpaceMouse.update_state() integrates the device's rate
+ * readings into a 6-DoF plate pose, the arms' targets ride on the plate and the base turns towards it -- as one more small kernel of a
+ * rollout tick, where the action list's goes: between the walk (and the sensor feed's wrench) and the first OSC kernel, so THIS tick's
+ * OSC step aims at the targets of this tick's reading (the reference: update_state(), then generate(), on one tick).  One stream can
+ * drive the whole fleet, or each robot can have its own.  Robot b on tick t, counted in the slot's rollout ticks since
+ * irlosc_set_teleop_stream and continuing across calls of irlosc_rollout_from_q; its reading r = readings[.][i], i = loop ? t mod T : t;
+ * pose (x y z roll pitch yaw), inc = increment (input_devices/space_mouse.py:30-38):
+ *     x += inc * r[0];  y += inc * r[1];  z += inc * r[2]                              -- each product and each sum rounded on its own
+ *     yaw = wrap(yaw - inc * r[5]);  pitch = wrap(pitch - inc * r[4]);  roll = wrap(roll + inc * r[3]);  wrap(a) = atan2(sin a, cos a)
+ *     q_p = euler2quat(pitch, roll, yaw, axes='rxyz') = qx(pitch) (x) qy(roll) (x) qz(yaw)    -- pitch and roll swapped, as in the reference;
+ *           with (cx, sx), (cy, sy), (cz, sz) the cosine and sine of pitch / 2, roll / 2, yaw / 2:
+ *           w = cx (cy cz) - sx (sy sz);  x = cx (sy sz) + sx (cy cz);  y = cx (sy cz) - sx (cy sz);  z = cx (cy sz) + sx (sy cz)
+ *     RIGID device d:    tgt xyz = p + R(q_p) off_xyz[d]   (R: quat2mat, rows summed left to right);
+ *                        tgt quat = q_p (x) off_quat[d]    (Hamilton product, terms left to right; no normalisation, no sign change)
+ *     HEADING device d:  h = atan2(y, x) + heading_offset[d];  tgt quat = (cos(h / 2), 0, 0, sin(h / 2));  the xyz words stay
+ *     NONE:              the device keeps the slot's target
+ * The arithmetic is float64 whatever the context's dtype; targets are stored as casts to it; target velocities are not touched.  The
+ * reference reaches the same rotations through mat2euler -> set_abg -> euler2quat: equal up to the quaternion's sign (1e-15), which
+ * calc_error's quat2euler does not see.  With loop == 0 the stream ENDS after T ticks: no kernel runs on ticks t >= T, pose and targets
+ * stay as tick T - 1 left them, the tick goes on counting.  A robot that a rollout over fewer robots leaves out keeps its pose and its
+ * targets and MISSES those readings: the reading index follows the slot's tick, not the robot's.  Nothing of the exchange block is read:
+ * a robot the plant has frozen (a NaN coordinate) is steered like every other.
+ * Not covered: examples/teleop_loops.py::ps_move_loop.  Its trigger switches ctrlr_dof_abg per tick, which changes k, and a context's
+ * layout is fixed when it is created. */
+#define IRLOSC_MAX_STREAM_TICKS 16384
+#define IRLOSC_TELEOP_NONE    0   /* the device keeps the slot's target */
+#define IRLOSC_TELEOP_RIGID   1   /* target pose = plate pose o (off_xyz, off_quat): all seven words written */
+#define IRLOSC_TELEOP_HEADING 2   /* quaternion = rotation about world z by atan2(y, x) + heading_offset; xyz words stay */
+typedef struct irlosc_teleop_stream {
+    int32_t ticks;                         /* T in [1, IRLOSC_MAX_STREAM_TICKS] */
+    int32_t nb;                            /* readings: 1 = one stream for the fleet, B = one per robot */
+    int32_t nb_origin;                     /* origin: 1 or B */
+    int32_t loop;                          /* 1: reading index = tick mod T; 0: the stream ends after T ticks */
+    double increment;                      /* finite (the reference: 0.0015) */
+    int32_t kind[IRLOSC_MAX_DEV];          /* IRLOSC_TELEOP_*; devices >= ndev: NONE; at least one device not NONE */
+    double off_xyz[IRLOSC_MAX_DEV][3];     /* RIGID: finite */
+    double off_quat[IRLOSC_MAX_DEV][4];    /* RIGID: w x y z, | |q|^2 - 1 | <= 1e-12 */
+    double heading_offset[IRLOSC_MAX_DEV]; /* HEADING: finite */
+} irlosc_teleop_stream;
+/* Gives slot `slot`'s B robots the stream: readings[nb][T][6] double (x y z roll pitch yaw rates), origin[nb_origin][6] double (the
+ * pose before tick 0).  Every argument is checked before anything is touched (IRLOSC_ERR_ARG: ticks outside [1, 16384], an unknown
+ * kind or one other than NONE on a device >= ndev, all kinds NONE, nb / nb_origin not 1 or B, loop not 0 / 1, a value that is not
+ * finite -- increment, a reading, an origin, a field of a device that reads it --, an off_quat of a RIGID device that is not of unit
+ * length, readings or origin NULL, B < 1; the program in force stays, whole -- as it does when the call answers IRLOSC_ERR_STATE).
+ * After irlosc_set_model and irlosc_set_targets for at least B robots on the slot (IRLOSC_ERR_STATE otherwise).  On success the stream
+ * replaces whatever program was in force, pose = origin and the tick base is 0; NO targets are written: the first tick does that.
+ * desc == NULL clears a stream (and leaves paths or a list alone).  What else ends it and who runs it: "one writer of the targets"
+ * above; irlosc_set_gains leaves it.  Buffers are allocated by the first use; IRLOSC_ERR_HIP -- an allocation, a copy or the init
+ * launch failed -- leaves the slot WITHOUT a program.  Per-robot readings take 48 T bytes of device memory per robot.  Synchronous. */
+IRLOSC_API int irlosc_set_teleop_stream(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_teleop_stream* desc, const double* readings,
+                                        const double* origin);
+/* pose: [B][6] double (x y z roll pitch yaw as the last tick that ran the robot left it; the origin before the first), tick: one int32
+ * (the slot's rollout ticks since the setter); either may be NULL.  IRLOSC_ERR_STATE on a slot without a stream, or with a stream for
+ * fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_teleop_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* pose, int32_t* tick);
+/* tgt_pose: [B][ndev][7] in the context's dtype: the slot's targets as they sit in HBM -- given by irlosc_set_targets, or written by the
+ * program of the slot's rollouts.  Works with or without a program.  IRLOSC_ERR_ARG: tgt_pose NULL; IRLOSC_ERR_STATE on a slot that
+ * holds targets for fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_targets(irlosc_ctx* ctx, int32_t slot, int32_t B, void* tgt_pose);
 
 /* ---- external pushes on the plant, sensed by the F/T feed: admit_test / force_test inside a rollout (csrc/osc_push.hpp) ------------
  * What examples/headless_loops.py::admit_test_loop does on the host -- xfrc_applied on a gripper body during a window of ticks, the

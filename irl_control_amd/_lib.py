@@ -17,6 +17,8 @@ MAX_JOINT_ROWS = 48
 JOINT_LIMIT, JOINT_COUPLE, JOINT_DRIVE = 0, 1, 2
 JOINT_SRC_CONST, JOINT_SRC_ACTION = 0, 1
 ACTION_WP, ACTION_GRIP = 0, 1
+MAX_STREAM_TICKS = 16384
+TELEOP_NONE, TELEOP_RIGID, TELEOP_HEADING = 0, 1, 2
 F32, F64 = 0, 1
 USE_G, ADMITTANCE, NULLSPACE = 1, 2, 4
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_ROW16 = 0, 1, 3      # (2: the fp32-arithmetic kernel removed in ABI version 3)
@@ -36,7 +38,7 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q",
            "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state",
            "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state", "irlosc_set_joints",
-           "irlosc_download_joint_state"]
+           "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets"]
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -90,6 +92,13 @@ class ActionList(C.Structure):
                 ("kind", C.c_int32 * MAX_ACTIONS), ("xyz_from_start", C.c_int32 * MAX_ACTIONS), ("grip_ticks", C.c_int32 * MAX_ACTIONS),
                 ("kp", C.c_double * MAX_ACTIONS), ("max_error", C.c_double * MAX_ACTIONS), ("min_speed", C.c_double * MAX_ACTIONS),
                 ("max_speed", C.c_double * MAX_ACTIONS), ("gripper_force", C.c_double * MAX_ACTIONS)]
+
+
+class TeleopStream(C.Structure):
+    """struct irlosc_teleop_stream (include/irlosc.h): the teleoperation stream of irlosc_set_teleop_stream."""
+    _fields_ = [("ticks", C.c_int32), ("nb", C.c_int32), ("nb_origin", C.c_int32), ("loop", C.c_int32), ("increment", C.c_double),
+                ("kind", C.c_int32 * MAX_DEV), ("off_xyz", (C.c_double * 3) * MAX_DEV), ("off_quat", (C.c_double * 4) * MAX_DEV),
+                ("heading_offset", C.c_double * MAX_DEV)]
 
 
 class Pushes(C.Structure):
@@ -187,6 +196,9 @@ def load():
     lib.irlosc_download_waypoint_state.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.irlosc_set_action_list.argtypes = [vp, i32, i32, C.POINTER(ActionList), vp]
     lib.irlosc_download_action_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.irlosc_set_teleop_stream.argtypes = [vp, i32, i32, C.POINTER(TeleopStream), vp, vp]
+    lib.irlosc_download_teleop_state.argtypes = [vp, i32, i32, vp, vp]
+    lib.irlosc_download_targets.argtypes = [vp, i32, i32, vp]
     lib.irlosc_set_pushes.argtypes = [vp, i32, i32, C.POINTER(Pushes), vp]
     lib.irlosc_set_walls.argtypes = [vp, i32, i32, C.POINTER(Walls), vp]
     lib.irlosc_download_wall_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]

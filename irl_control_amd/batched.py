@@ -358,7 +358,7 @@ class BatchedOSC:
         (`loop`) or finishes on the last one.  `xyz`: per device (layout order) a [W, 3] array (one path for the fleet), a [B, W, 3]
         array (a path per robot) or None (the device keeps the slot's target); W <= 64.  `threshold`, `loop`: one value or one per
         device.  After set_model and set_targets; writes waypoint 0 into the slot's targets and resets the state.  xyz=None (or all
-        None) clears the paths and nothing else.  A slot has paths or an action list, never both; what else ends them: "one writer of
+        None) clears the paths and nothing else.  A slot has one program -- paths, an action list or a teleoperation stream; what else ends them: "one writer of
         the targets" in include/irlosc.h."""
         L, B = self.layout, self._B[slot]
         paths = [None] * L.ndev if xyz is None else [None if p is None else np.asarray(p, dtype=np.float64) for p in xyz]
@@ -403,8 +403,8 @@ class BatchedOSC:
         limit goes into the slot's own copy of the gains -- no host in between.  `sequence`: the list of action dicts (defaults from
         action_sequence.DEFAULT_PARAMS), or a dict from action_sequence.compile_action_list; `objects`: per robot its action objects
         (one entry: shared by the fleet).  `passive_arm`: "auto" = the other UR5 when the layout has it, None = no passive arm.
-        After set_model, set_gains and set_targets; resets the state.  sequence=None clears the list and nothing else.  A slot has a
-        list or waypoint paths, never both; what else ends it: "one writer of the targets" in include/irlosc.h.  gripper_force is state;
+        After set_model, set_gains and set_targets; resets the state.  sequence=None clears the list and nothing else.  A slot has one
+        program -- a list, waypoint paths or a teleoperation stream; what else ends it: "one writer of the targets" in include/irlosc.h.  gripper_force is state;
         it drives a gripper where the slot has an action drive row on the active arm (set_joints)."""
         from . import action_sequence as aseq
         B = self._B[slot]
@@ -449,6 +449,59 @@ class BatchedOSC:
         self._chk(self.lib.irlosc_download_action_state(self._h, slot, B, *[_lib.ptr(out[k]) for k in
                                                                              ("action", "grip_left", "err", "max_vel0", "gripper_force", "finished_tick")]))
         return out
+
+    # -- the teleoperation stream of the rollout (irlosc_set_teleop_stream / irlosc_download_teleop_state / irlosc_download_targets) ----
+    def set_teleop_stream(self, readings, origin, rig=None, increment: float = 0.0015, loop: bool = False, slot: int = 0):
+        """A recorded space-mouse session for the slot's robots, replayed on the GPU by `rollout` as examples/teleop_loops.py::
+        space_mouse_loop runs it on the host: per tick the reading is integrated into the plate pose (SpaceMouse.update_state) and the
+        followers' targets are written in front of the same tick's OSC step.  `readings`: [T, 6] (one stream for the fleet) or
+        [B, T, 6] (one per robot), x y z roll pitch yaw rates, T <= 16384; `origin`: [6] or [B, 6], the pose before tick 0; `rig`: one
+        teleop.follower per device (default: teleop.space_mouse_rig, the demo's).  `loop`: start over after T ticks, else the stream
+        ends there and pose and targets stay.  After set_model and set_targets; resets pose and tick and writes no target (the first
+        tick does).  readings=None (or clear_teleop_stream) clears the stream and nothing else.  A slot has one program -- paths, an
+        action list or a stream; what else ends it: "one writer of the targets" in include/irlosc.h.  A robot that a narrower rollout
+        leaves out keeps its pose and misses those readings.  ps_move has no resident form (teleop.py)."""
+        from . import teleop as _t
+        B = self._B[slot]
+        if readings is None:
+            self._chk(self.lib.irlosc_set_teleop_stream(self._h, slot, B, None, None, None))
+            return
+        rd = np.ascontiguousarray(readings, dtype=np.float64)
+        if rd.ndim == 2:
+            rd = rd[None]
+        if rd.ndim != 3 or rd.shape[2] != 6 or rd.shape[1] < 1 or rd.shape[0] not in (1, B):
+            raise ValueError(f"readings: expected shape (T, 6) or ({B}, T, 6) with T >= 1, got {np.shape(readings)}")
+        og = np.ascontiguousarray(origin, dtype=np.float64)
+        if og.ndim == 1:
+            og = og[None]
+        if og.ndim != 2 or og.shape[1] != 6 or og.shape[0] not in (1, B):
+            raise ValueError(f"origin: expected shape (6,) or ({B}, 6), got {np.shape(origin)}")
+        rig = _t.space_mouse_rig(self.layout) if rig is None else list(rig)
+        if len(rig) != self.layout.ndev:
+            raise ValueError(f"rig: expected one follower per device ({self.layout.ndev}), got {len(rig)}")
+        desc = _t.to_struct(rig, rd.shape[1], rd.shape[0], og.shape[0], increment, loop)
+        self._chk(self.lib.irlosc_set_teleop_stream(self._h, slot, B, C.byref(desc), _lib.ptr(np.ascontiguousarray(rd)), _lib.ptr(np.ascontiguousarray(og))))
+
+    def clear_teleop_stream(self, slot: int = 0):
+        """Ends the slot's stream (irlosc_set_teleop_stream with desc == NULL); targets, paths and a list are left alone."""
+        self.set_teleop_stream(None, None, slot=slot)
+
+    def teleop_state(self, slot: int = 0):
+        """-> dict(pose [B, 6]: x y z roll pitch yaw of every robot's plate as the last tick that ran it left it (the origin before the
+        first), tick: the slot's rollout ticks since set_teleop_stream).  (irlosc_download_teleop_state)"""
+        B = self._B[slot]
+        pose = np.empty((B, 6), dtype=np.float64)
+        tick = C.c_int32(0)
+        self._chk(self.lib.irlosc_download_teleop_state(self._h, slot, B, _lib.ptr(pose), C.byref(tick)))
+        return dict(pose=pose, tick=int(tick.value))
+
+    def download_targets(self, slot: int = 0):
+        """-> the slot's targets [B, ndev, 7] in the context's dtype as they sit in HBM: given by set_targets, or written by the
+        program of its rollouts (irlosc_download_targets)."""
+        B = self._B[slot]
+        tgt = np.empty((B, self.layout.ndev, 7), dtype=self.dtype)
+        self._chk(self.lib.irlosc_download_targets(self._h, slot, B, _lib.ptr(tgt)))
+        return tgt
 
     # -- external pushes of the rollout (irlosc_set_pushes) ---------------------------------------------------------------------------
     def set_pushes(self, pushes, wrench=None, slot: int = 0):

@@ -27,6 +27,7 @@
 #include "osc_plant.hpp"
 #include "osc_waypoint.hpp"
 #include "osc_action.hpp"
+#include "osc_teleop.hpp"
 #include "osc_push.hpp"
 #include "osc_wall.hpp"
 #include "osc_joint.hpp"
@@ -39,19 +40,23 @@ static_assert(FT_TRAIN == R16_TRAIN, "the sensor-feed wrench kernel covers a who
 
 static thread_local std::string g_create_error;
 
-// The program that writes a slot's targets inside a rollout, if any: waypoint paths (irlosc_set_waypoints, osc_waypoint.hpp) or the
-// WP / GRIP action list (irlosc_set_action_list, osc_action.hpp).  One entry point writes the targets at a time, so a slot has one
-// program at most -- `kind` says which: a list and paths exclude each other.  Written by the transitions below and by nothing else.
+// The program that writes a slot's targets inside a rollout, if any: waypoint paths (irlosc_set_waypoints, osc_waypoint.hpp), the
+// WP / GRIP action list (irlosc_set_action_list, osc_action.hpp) or a teleoperation stream (irlosc_set_teleop_stream, osc_teleop.hpp).
+// One entry point writes the targets at a time, so a slot has one program at most -- `kind` says which: paths, a list and a stream
+// exclude each other.  Written by the transitions below and by nothing else.
 struct Program {
-    enum Kind { NONE, PATHS, LIST };
-    Kind kind = NONE;          // (NONE: a rollout tick launches neither kernel and reads the context's gains)
+    enum Kind { NONE, PATHS, LIST, STREAM };
+    Kind kind = NONE;          // (NONE: a rollout tick launches none of the kernels and reads the context's gains)
     int robots = 0, tick = 0;  // robots the program covers; rollout ticks since it came in force
-    irlosc_waypoints wp{};     // the description in force: of paths; of a list
+    irlosc_waypoints wp{};     // the description in force: of paths; of a list; of a stream
     irlosc_action_list al{};
+    irlosc_teleop_stream ts{};
+    std::vector<double> ts_shared;      // a shared stream's readings [T][6]: they travel as kernel arguments, tick by tick
     // Device buffers, allocated by the first use and kept across programs: per-robot state SoA over max_batch robots (wp_i, al_i, al_d), the
     // table (walk_table), and a list's own gains [robots][ndev][12] and null_kv [robots] in the context's dtype (its rollout reads these per instance)
+    // A stream: the pose SoA [6][max_batch] (ts_pose), per-robot readings (ts_table) and per-robot origins (ts_origin), both walk_table.
     DevBuf<int32_t> wp_i, al_i;
-    DevBuf<double> wp_table, al_d, al_table;
+    DevBuf<double> wp_table, al_d, al_table, ts_pose, ts_table, ts_origin;
     DevBuf<void> al_gains, al_nullkv;
     // THE LAYOUT of the state -- the kernels' arguments, the setters' sizes and the downloads all ask here: wp_i in planes of `plane` =
     // ndev x max_batch words; al_i and al_d in rows of Bm = max_batch words (start_xyz: three rows); and their sizes
@@ -60,12 +65,19 @@ struct Program {
     int32_t* finished_tick(size_t Bm) const { return al_i + 3 * Bm; }
     double* err(size_t) const { return al_d; }  double* max_vel0(size_t Bm) const { return al_d + Bm; }  double* gripper_force(size_t Bm) const { return al_d + 2 * Bm; }
     double* start_xyz(size_t Bm) const { return al_d + 3 * Bm; }
+    double* pose(size_t) const { return ts_pose; }      // (x y z roll pitch yaw: six rows of Bm words)
     static size_t wp_words(size_t plane) { return 3 * plane; }  static size_t al_i_words(size_t Bm) { return 4 * Bm; }  static size_t al_d_words(size_t Bm) { return 6 * Bm; }
+    static size_t ts_words(size_t Bm) { return 6 * Bm; }
 
     // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
     void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
     // A list of B robots is in force, its state reset by the kernel's init launch and its gain copy made: it writes the targets from here on.
     void list(int B, const irlosc_action_list& d) { kind = LIST; robots = B; tick = 0; al = d; }
+    // A stream over B robots is in force, their poses at the origins by the kernel's init launch (which wrote no target: the first tick
+    // does); `shared`: the readings of a stream for the whole fleet.
+    void stream(int B, const irlosc_teleop_stream& d, std::vector<double>&& shared) { kind = STREAM; robots = B; tick = 0; ts = d; ts_shared = std::move(shared); }
+    // The reading a stream takes on the tick to come: tick mod T of one that loops, none (-1) once one that does not has ended
+    int reading() const { return kind != STREAM ? -1 : ts.loop ? tick % ts.ticks : tick < ts.ticks ? tick : -1; }
     // The program ends: irlosc_set_targets wrote the targets, another program takes them over, the model changed, or its buffers failed.
     void end() { kind = NONE; robots = 0; tick = 0; }
     // The program ends if it is of this kind (its own setter cleared it; a list: the gains its copy was made from were replaced): one of the other kind stays whole
@@ -1761,6 +1773,27 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
     return a;
 }
 
+// The arguments of the slot's stream kernel over B robots: a tick on reading `index` of stream d, or (index < 0) the init launch of
+// irlosc_set_teleop_stream, which takes the origins (per robot: at ts_origin; shared: `shared`) where a tick takes the readings
+static TeleopArgs teleop_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_teleop_stream& d, const double* shared, int index) {
+    const Program& p = s.prog;
+    TeleopArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    a.init = index < 0;
+    a.per_robot = (a.init ? d.nb_origin : d.nb) > 1;
+    a.tgt = s.tgt; a.pose = p.pose(Bm); a.readings = a.init ? p.ts_origin : p.ts_table;
+    for (int i = 0; i < 6 && !a.per_robot; ++i) a.r[i] = shared[(a.init ? 0 : (size_t)index * 6) + i];
+    a.inc = d.increment;
+    for (int k = 0; k < c->cfg.ndev; ++k) {
+        a.kind[k] = d.kind[k]; a.heading[k] = d.heading_offset[k];
+        for (int i = 0; i < 3; ++i) a.off_xyz[k][i] = d.off_xyz[k][i];
+        for (int i = 0; i < 4; ++i) a.off_quat[k][i] = d.off_quat[k][i];
+    }
+    a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.T = d.ticks; a.index = a.init ? 0 : index;
+    return a;
+}
+
 // The arguments of the slot's waypoint cycler over B robots (init: the launch of irlosc_set_waypoints; else a tick on exchange block xside)
 static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, const double* xside, int tick) {
     WaypointArgs a;
@@ -1862,10 +1895,12 @@ static int check_covers(irlosc_ctx* c, int slot, int B, int robots, const char* 
 
 // The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
 static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
+    static const char* const what[] = {"", "waypoint paths", "action list", "teleoperation stream"};      // by Program::Kind
+    static const char* const covers[] = {"", "cover", "covers", "covers"};
+    static const char* const setter[] = {"", "irlosc_set_waypoints", "irlosc_set_action_list", "irlosc_set_teleop_stream"};
     const Program& p = c->slot[slot].prog;
-    const bool paths = (need ? need : p.kind) == Program::PATHS;
-    return check_covers(c, slot, B, !need || p.kind == need ? p.robots : 0, paths ? "waypoint paths" : "action list", paths ? "cover" : "covers",
-                        !need ? nullptr : paths ? "irlosc_set_waypoints" : "irlosc_set_action_list");
+    const Program::Kind k = need ? need : p.kind;
+    return check_covers(c, slot, B, !need || p.kind == need ? p.robots : 0, what[k], covers[k], need ? setter[k] : nullptr);
 }
 
 // A program's table [nb][E] in the layout its kernel walks: per robot [walk wave][E][64] (idle lanes zero), shared (nb == 1) as given
@@ -1877,14 +1912,14 @@ static std::vector<double> walk_table(const double* t, int nb, size_t E) {
 }
 
 // The tail of every setter of a program or of what acts on the plant: host arrays to the device and fills with a byte value (src == nullptr)
-// as listed, then the init launch of a program's kernel if given, on the context's stream -> the first error.  Synchronises also when one of
+// as listed (one of no bytes -- a table that stays on the host -- is skipped), then the init launch of a program's kernel if given, on the context's stream -> the first error.  Synchronises also when one of
 // them failed: the host arrays are the copies' sources.  Only then does the caller bring the part in force.
 struct Upload { void* dst; const void* src; size_t bytes; int byte; };
 template <typename Args = int>
 static int setter_upload(irlosc_ctx* c, std::initializer_list<Upload> ups, int (*init)(const Args&, hipStream_t) = nullptr, const Args* a = nullptr) {
     hipError_t ec = hipSuccess;
     for (const Upload& k : ups)
-        if (ec == hipSuccess) ec = k.src ? hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(k.dst, k.byte, k.bytes, c->stream);
+        if (ec == hipSuccess && k.bytes) ec = k.src ? hipMemcpyAsync(k.dst, k.src, k.bytes, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(k.dst, k.byte, k.bytes, c->stream);
     if (ec == hipSuccess && init) ec = (hipError_t)init(*a, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);
     HIPCHK(c, ec);
@@ -1913,9 +1948,10 @@ static int download_state(irlosc_ctx* c, int B, const double* sd, size_t nd, std
 
 // What a tick of a rollout runs next to its fused step, decided once per tick from the slot (the default: no tick, nothing): the program that writes its
 // targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); rows
-struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; };
+// it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on)
+struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; };
 static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
-    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0};
+    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading()};
     for (int p = 0; tp.push_sense && p < IRLOSC_MAX_PUSHES; ++p)
         if (((tp.push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) tp.push_sense &= ~(1u << p);
     if (s0.feed > 0 && s0.walls.tick > 0) tp.wall_sense = tp.wall_apply;
@@ -1927,7 +1963,8 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
 // THE ORDER OF A TICK'S LAUNCHES on the stream of bank 0 ([..]: where the plan has it; the unnamed lines are fused_train's own):
 //     the walk, the feed's wrench (ft_launch)
 //     tick_front:   [pushes SENSE: their reaction goes into the wrench ahead of every kernel that reads it] [walls SENSE: their force of the
-//                   tick before, behind it] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel]
+//                   tick before, behind it] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel
+//                   | stream kernel: its targets are this tick's too]
 //     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
 //     tick_behind:  [waypoint cycler: the targets move where an arm arrived]; [pushes APPLY] [walls APPLY] [joint rows], each into the bias
 //                   entries of the block, which only the plant reads from here on; the plant: every robot has its u by then
@@ -1937,6 +1974,7 @@ static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, 
     if (tp.push_sense) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_sense, nullptr, wrench), st));
     if (tp.wall_sense) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_sense, nullptr, wrench), st));
     if (tp.prog == Program::LIST) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
+    if (tp.reading >= 0) HIPCHK(c, (hipError_t)launch_teleop<T>(teleop_args(c, s0, B, s0.prog.ts, s0.prog.ts_shared.data(), tp.reading), st));
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2668,6 +2706,97 @@ extern "C" int irlosc_download_action_state(irlosc_ctx* c, int32_t slot, int32_t
     double* dd[3] = {err, max_vel0, gripper_force};  const double* sd[3] = {p.err(Bm), p.max_vel0(Bm), p.gripper_force(Bm)};
     for (int i = 0; i < 3; ++i)
         if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], sd[i], (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return IRLOSC_OK;
+}
+
+// ---- the teleoperation stream of the rollout (osc_teleop.hpp) -------------------------------------------------------------------
+extern "C" int irlosc_set_teleop_stream(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_teleop_stream* d, const double* readings,
+                                        const double* origin) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.prog.end(Program::STREAM); return IRLOSC_OK; }
+    const int nd = c->cfg.ndev, T = d->ticks;
+    if (T < 1 || T > IRLOSC_MAX_STREAM_TICKS) return fail(c, IRLOSC_ERR_ARG, "teleop stream: ticks=%d out of [1,%d]", T, IRLOSC_MAX_STREAM_TICKS);
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "teleop stream: B=%d must be >= 1", B);
+    if (d->nb != 1 && d->nb != B) return fail(c, IRLOSC_ERR_ARG, "teleop stream: nb=%d must be 1 or B=%d", d->nb, B);
+    if (d->nb_origin != 1 && d->nb_origin != B) return fail(c, IRLOSC_ERR_ARG, "teleop stream: nb_origin=%d must be 1 or B=%d", d->nb_origin, B);
+    if (d->loop != 0 && d->loop != 1) return fail(c, IRLOSC_ERR_ARG, "teleop stream: loop=%d must be 0 or 1", d->loop);
+    if (!std::isfinite(d->increment)) return fail(c, IRLOSC_ERR_ARG, "teleop stream: increment is not finite");
+    bool any = false;
+    for (int k = 0; k < IRLOSC_MAX_DEV; ++k) {
+        const int kind = d->kind[k];
+        if (kind != IRLOSC_TELEOP_NONE && kind != IRLOSC_TELEOP_RIGID && kind != IRLOSC_TELEOP_HEADING)
+            return fail(c, IRLOSC_ERR_ARG, "teleop stream: kind[%d]=%d is none of NONE, RIGID, HEADING", k, kind);
+        if (kind != IRLOSC_TELEOP_NONE && k >= nd) return fail(c, IRLOSC_ERR_ARG, "teleop stream: kind[%d]=%d on a device >= ndev=%d", k, kind, nd);
+        any = any || kind != IRLOSC_TELEOP_NONE;
+        if (kind == IRLOSC_TELEOP_RIGID) {
+            double n2 = 0.0;
+            for (int i = 0; i < 3; ++i)
+                if (!std::isfinite(d->off_xyz[k][i])) return fail(c, IRLOSC_ERR_ARG, "teleop stream: off_xyz[%d][%d] is not finite", k, i);
+            for (int i = 0; i < 4; ++i) n2 += d->off_quat[k][i] * d->off_quat[k][i];
+            if (!(std::fabs(n2 - 1.0) <= 1e-12))      // (a NaN or an infinity fails here too)
+                return fail(c, IRLOSC_ERR_ARG, "teleop stream: off_quat[%d] is not of unit length (|q|^2 = %.17g)", k, n2);
+        }
+        if (kind == IRLOSC_TELEOP_HEADING && !std::isfinite(d->heading_offset[k]))
+            return fail(c, IRLOSC_ERR_ARG, "teleop stream: heading_offset[%d] is not finite", k);
+    }
+    if (!any) return fail(c, IRLOSC_ERR_ARG, "teleop stream: every device has kind NONE");
+    if (!readings || !origin) return fail(c, IRLOSC_ERR_ARG, "teleop stream: %s is NULL", !readings ? "readings" : "origin");
+    const size_t E = (size_t)T * 6;
+    for (size_t i = 0; i < (size_t)d->nb * E; ++i)
+        if (!std::isfinite(readings[i])) return fail(c, IRLOSC_ERR_ARG, "teleop stream: reading %zu of robot %zu is not finite", i % E / 6, i / E);
+    for (size_t i = 0; i < (size_t)d->nb_origin * 6; ++i)
+        if (!std::isfinite(origin[i])) return fail(c, IRLOSC_ERR_ARG, "teleop stream: origin of robot %zu is not finite", i / 6);
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, teleop stream given for %d: irlosc_set_targets first", slot,
+                    std::max(0, s.targets), B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Program& p = s.prog;
+    p.end();           // (none until the new one is in its buffers; the stream writes the targets from here on: paths or a list end)
+    // what the init launch and the ticks read on the device: per-robot readings and origins; shared ones stay on the host
+    std::vector<double> tab, org, shared;
+    if (d->nb > 1) tab = walk_table(readings, d->nb, E); else shared.assign(readings, readings + E);
+    if (d->nb_origin > 1) org = walk_table(origin, d->nb_origin, 6);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    if (!got(p.ts_pose.ensure(p.ts_words(Bm) * sizeof(double))) || !got(p.ts_table.reserve(tab.size() * sizeof(double))) ||
+        !got(p.ts_origin.reserve(org.size() * sizeof(double))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the teleop stream of slot %d (%zu bytes)", slot,
+                    (p.ts_words(Bm) + tab.size() + org.size()) * sizeof(double));
+    const TeleopArgs init = teleop_args(c, s, B, *d, origin, -1);
+    const auto launch = c->cfg.dtype == IRLOSC_F64 ? launch_teleop<double> : launch_teleop<float>;
+    rc = setter_upload(c, {{p.ts_table, tab.data(), tab.size() * sizeof(double)}, {p.ts_origin, org.data(), org.size() * sizeof(double)}}, launch, &init);
+    if (!rc) p.stream(B, *d, std::move(shared));
+    return rc;
+}
+
+extern "C" int irlosc_download_teleop_state(irlosc_ctx* c, int32_t slot, int32_t B, double* pose, int32_t* tick) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B, Program::STREAM);
+    if (rc) return rc;
+    const Program& p = c->slot[slot].prog;
+    if (tick) *tick = p.tick;
+    if (B == 0 || !pose) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch;      // rows [max_batch] on the device -> [B][6] for the caller
+    return download_state(c, B, p.ts_pose, p.ts_words(Bm), {{pose, p.pose(Bm), 6, 6, 0, 1}}, nullptr, 0, {});
+}
+
+extern "C" int irlosc_download_targets(irlosc_ctx* c, int32_t slot, int32_t B, void* tgt_pose) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Slot& s = c->slot[slot];
+    if (!tgt_pose) return fail(c, IRLOSC_ERR_ARG, "tgt_pose is NULL");
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, asked for %d", slot, std::max(0, s.targets), B);
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    HIPCHK(c, hipMemcpyAsync(tgt_pose, s.tgt, (size_t)B * c->cfg.ndev * 7 * c->esz, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
 }

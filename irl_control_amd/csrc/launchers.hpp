@@ -100,6 +100,12 @@ struct ActionArgs;
 template <typename T>
 int launch_actions(const ActionArgs& a, hipStream_t st);
 
+// tu_teleop.hip -- the teleoperation stream where the action list's kernel goes, on a rollout tick whose slot has one and a reading
+// for the tick (osc_teleop.hpp); T = record type (of the targets)
+struct TeleopArgs;
+template <typename T>
+int launch_teleop(const TeleopArgs& a, hipStream_t st);
+
 // tu_push.hip -- the external pushes of a rollout tick whose slot has some active (osc_push.hpp): sense mode between the sensor feed's
 // wrench kernel and the first kernel that reads the wrench, apply mode in front of the plant; T = record type (of the wrench)
 struct PushArgs;

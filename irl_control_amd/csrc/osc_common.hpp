@@ -207,7 +207,7 @@ __device__ __forceinline__ T wave_max(T v) {
     return v;
 }
 
-// The TARGET TILE of the kernels that write a slot's targets inside a rollout (osc_waypoint.hpp, osc_action.hpp: one block per walk
+// The TARGET TILE of the kernels that write a slot's targets inside a rollout (osc_waypoint.hpp, osc_action.hpp, osc_teleop.hpp: one block per walk
 // wave, one lane per robot).  The target record tgt[B][ndev][7] is row-major in the record type T, a lane's words 7 ndev apart, so the
 // wave's tile -- the rows of its nvalid robots, tg = tgt + b0 * row, row = ndev * 7 -- goes through LDS.  The contract: the tile stays
 // in the record type and is stored whole, so a word no lane rewrote goes back bit for bit; it is stored only by a wave in which a lane
