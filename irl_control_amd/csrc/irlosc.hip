@@ -1074,9 +1074,6 @@ static int lane_train(irlosc_ctx* c, const KParams<double>* ps, const int* sl, i
     lt.map = c->model.lane_map;
     HIPCHK(c, hipMemsetAsync(bk.lane_count, 0, R16_TRAIN * sizeof(int32_t), st));
     if (first && c->tev_begin) HIPCHK(c, hipEventRecord(c->tev_begin, st));
-    // (A/B builds whose lane kernel takes the task rows from a pass: it writes them into the slot's block -- the same values for every
-    //  step of the slot, whichever bank runs it)
-    if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<double>(tr, n, st, 1));
     HIPCHK(c, (hipError_t)launch_lane_osc<double>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
     if (c->span_next) HIPCHK(c, (hipError_t)launch_span_end(c->span_next, st));      // (irlosc_time_trains: the step ends with its eigen pass)
     HIPCHK(c, (hipError_t)launch_row16_worklist<double>(tr, n, nullptr, st));
@@ -2080,12 +2077,8 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     int rcw = ft_launch(c, fts, nft, B, st);      // the sensor feed's wrench: read by every OSC kernel below (and the give-up pass)
     if (!rcw && pl) rcw = tick_front<T>(c, s0, B, tp, bk, nft ? fts[0].wrench : nullptr, st);
     if (rcw) return rcw;
-    if (use_lane) {
-        if (!lane_task_in_kernel()) HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st, 1));      // the task pass (A/B builds: the lane kernel computes the rows itself)
-        HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
-    } else {
-        HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st));
-    }
+    if (use_lane) HIPCHK(c, (hipError_t)launch_lane_osc<T>(tr, lt, n, c->model.lane_tier, lane_eig_blocks(), lane_eig_min(), st));
+    else HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st));      // (task pass + FROMQ kernel; the lane kernel computes the task rows itself)
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
     if (pl && (rcw = tick_behind<T>(c, s0, B, tp, bk, *pl, st))) return rcw;

@@ -203,7 +203,6 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     static_assert(TI::depth_first(), "hinges numbered depth first: a subtree is a run of indices");
     constexpr int BLK_E = TI::n_compact();
     constexpr int ZERO_E = TI::zero_index();
-    constexpr int TASK_E = TI::task_index(0);
     constexpr int NE = TI::n_pairs() + NJ;
     const KParams<TIN>& p = tr.p[blockIdx.y];
     const Row16Extra& x = tr.x[blockIdx.y];
@@ -216,20 +215,9 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     const uint32_t realm = lt.map.real;
     __shared__ double s_u[NJ * 65];                    // M dq as the hinges complete, then the torques: [hinge][64 robots + 1 pad]
     __shared__ double s_w[K * 64];                     // the task vector waits here across the recursion and the k x k stage
-    // -DIRLOSC_LANE_JPARK=1 (A/B builds, tools/build_variant.py; OFF in the product): the entries of J the recursion has consumed wait here
-    // for J^T t behind the k x k stage, as many as the SIMD's quarter of the CU's LDS holds next to s_u and s_w (one single-wave block per
-    // SIMD: 163 840 / 4 bytes each; 41 of 85 for rows (1, 6, 6), all 43 for (1, 3, 3)): [slot = Rec::jslot][64 robots], lane-contiguous like
-    // s_w, and only the entries beyond NPARK are read from the block a second time.  Measured: the kernel's FETCH_SIZE falls by the
-    // predicted 166 MB per train and the headline does not move with it -- alone it is 2.7 % SLOWER than reading J twice (the second read is
-    // 20 us behind the first and does not cost what its bytes say; the 82 LDS operations per wave do): profiles/NOTES.md, "Lane parking".
-#ifndef IRLOSC_LANE_JPARK
-#define IRLOSC_LANE_JPARK 0
-#endif
-    constexpr int LDS_SIMD = 163840 / 4;
-    constexpr int NPARK_FIT = (LDS_SIMD - (int)sizeof(s_u) - (int)sizeof(s_w)) / 512;
-    constexpr int NPARK = IRLOSC_LANE_JPARK ? (Rec<L>::n_j() < NPARK_FIT ? Rec<L>::n_j() : NPARK_FIT) : 0;
-    __shared__ double s_j[(NPARK > 0 ? NPARK : 1) * 64];
-    static_assert(sizeof(s_u) + sizeof(s_w) + (NPARK > 0 ? sizeof(s_j) : 0) <= LDS_SIMD, "four single-wave blocks share a CU's LDS");
+    // (J is NOT kept here between its two uses: parking the consumed entries in the LDS that is left was 2.7 % slower than reading them
+    //  from the block twice -- profiles/NOTES.md, "Lane parking")
+    static_assert(sizeof(s_u) + sizeof(s_w) <= 163840 / 4, "four single-wave blocks share a CU's LDS");
     // -DIRLOSC_LANE_STAMPS (tools/build_variant.py; tools/phase_timing.py ... fromq with IRLOSC_PHASE_LANE=1): cycle stamps per phase into
     // p.dbg.  Compile-time only: a run-time `if (p.dbg)` around a stamp is a branch, and a branch inside the recursion lets the compiler
     // sink the arithmetic out of its pinned regions (see pin()).
@@ -326,54 +314,36 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
 #endif
     constexpr int PFD = IRLOSC_LANE_PFD;
     static_for<0, PFD>([&](auto dc) { constexpr int j = NJ - 1 - decltype(dc)::value; if constexpr (j >= 0) fetch(std::integral_constant<int, (j >= 0 ? j : 0)>{}); });
-#ifndef IRLOSC_LANE_TASK_IN
-#define IRLOSC_LANE_TASK_IN 1
-#endif
-    if constexpr (IRLOSC_LANE_TASK_IN) {
-        // Part 1 of the task signal -- calc_error, velocity limit, gains, stiffness (osc.py:101-118,70-99,160-168) [+ the wrench,
-        // osc.py:184-185] -- computed HERE, device by device, while the first rows of M are on their way: this wave has nothing else to do
-        // until they arrive (one wave per SIMD), so the ~450 instructions per device are free, and the task pass (58 us per train, 230 MB
-        // of traffic) is not launched at all.  The rows themselves are r16::gained_error6, as in that pass; they go to their CANONICAL
-        // positions in LDS (padding rows: zero).
+    // Part 1 of the task signal -- calc_error, velocity limit, gains, stiffness (osc.py:101-118,70-99,160-168) [+ the wrench,
+    // osc.py:184-185] -- computed HERE, device by device, while the first rows of M are on their way: this wave has nothing else to do
+    // until they arrive (one wave per SIMD), so the ~450 instructions per device are free, and no task pass (58 us per train, 230 MB of
+    // traffic) runs ahead of this kernel.  The rows themselves are r16::gained_error6, as in that pass; they go to their CANONICAL
+    // positions in LDS (padding rows: zero), where they wait across the recursion and the k x k stage.  (Taking the rows from the task
+    // pass's entries of the block instead measured slower: profiles/NOTES.md, "The task pass as a kernel of its own again".)
 #pragma unroll
-        for (int r = 0; r < K; ++r) s_w[r * 64 + lane] = 0.0;
+    for (int r = 0; r < K; ++r) s_w[r * 64 + lane] = 0.0;
 #pragma unroll 1
-        for (int dv = 0; dv < nd; ++dv) {
-            const DevMeta dm = p.dev[dv];
-            const int e0 = lt.map.ee_e0[dv];
-            const TIN* __restrict__ tgp = p.tgt + ((size_t)bc * nd + dv) * 7;
-            const TIN* __restrict__ gp = p.gains + (p.gains_per_instance ? (size_t)bc * nd * IRLOSC_GAIN_WORDS : 0) + dv * IRLOSC_GAIN_WORDS;
-            const TIN* __restrict__ wp = wbase + wsel * (((size_t)bc * nd + dv) * 6);
-            double ee[7], tg[7], g[IRLOSC_GAIN_WORDS], wr6[6];
+    for (int dv = 0; dv < nd; ++dv) {
+        const DevMeta dm = p.dev[dv];
+        const int e0 = lt.map.ee_e0[dv];
+        const TIN* __restrict__ tgp = p.tgt + ((size_t)bc * nd + dv) * 7;
+        const TIN* __restrict__ gp = p.gains + (p.gains_per_instance ? (size_t)bc * nd * IRLOSC_GAIN_WORDS : 0) + dv * IRLOSC_GAIN_WORDS;
+        const TIN* __restrict__ wp = wbase + wsel * (((size_t)bc * nd + dv) * 6);
+        double ee[7], tg[7], g[IRLOSC_GAIN_WORDS], wr6[6];
 #pragma unroll
-            for (int i = 0; i < 7; ++i) ee[i] = col[(size_t)(unsigned)(e0 + i) * 64];
+        for (int i = 0; i < 7; ++i) ee[i] = col[(size_t)(unsigned)(e0 + i) * 64];
 #pragma unroll
-            for (int i = 0; i < 7; ++i) tg[i] = (double)tgp[i];
+        for (int i = 0; i < 7; ++i) tg[i] = (double)tgp[i];
 #pragma unroll
-            for (int i = 0; i < IRLOSC_GAIN_WORDS; ++i) g[i] = (double)gp[i];
+        for (int i = 0; i < IRLOSC_GAIN_WORDS; ++i) g[i] = (double)gp[i];
 #pragma unroll
-            for (int i = 0; i < 6; ++i) wr6[i] = (double)wp[wsel * i];
-            double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            r16::gained_error6(dm.calc, ee, tg, g, e);
-            int cnt = 0;
+        for (int i = 0; i < 6; ++i) wr6[i] = (double)wp[wsel * i];
+        double e[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        r16::gained_error6(dm.calc, ee, tg, g, e);
+        int cnt = 0;
 #pragma unroll
-            for (int i = 0; i < 6; ++i)
-                if (dm.dofmask & (1u << i)) { s_w[lt.map.canon[dm.row0 + cnt] * 64 + lane] = e[i] + wr6[i]; ++cnt; }
-        }
-    } else
-    {   // Part 1 of the task signal [+ the wrench]: u_task_all + ext_f (osc.py:184-185), canonical order (padding: the entry of zeros;
-        // device 0, component 0 -- a valid address, times zero).  Requested behind the first rows of M -- one round trip for all of it --
-        // and parked in LDS: the values are next needed behind the k x k stage, and any register they held on the way was spilled, load
-        // by load, each waited for on the spot (13 to 26 round trips per wave).
-        double wt[K], wrv[K];
-#pragma unroll
-        for (int r = 0; r < K; ++r) {
-            const int e = ZERO_E + rm[r] * (TASK_E - ZERO_E + lt.map.ext[r]);
-            wt[r] = col[(size_t)(unsigned)e * 64];
-            wrv[r] = (double)wbase[wsel * (((size_t)bc * nd + lt.map.dev[r]) * 6 + lt.map.comp[r])];
-        }
-#pragma unroll
-        for (int r = 0; r < K; ++r) s_w[r * 64 + lane] = fma((double)rm[r], wrv[r], wt[r]);
+        for (int i = 0; i < 6; ++i)
+            if (dm.dofmask & (1u << i)) { s_w[lt.map.canon[dm.row0 + cnt] * 64 + lane] = e[i] + wr6[i]; ++cnt; }
     }
 
     LANE_TS(1);
@@ -433,8 +403,6 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
                 constexpr int r = decltype(rc)::value;
                 if constexpr (L::row_moved(r, j)) {
                     const double jv = Jv[r][j];
-                    constexpr int js = Rec<L>::jslot(r, j);     // (a constexpr variable first: inside an index the function runs at run time)
-                    if constexpr (js < NPARK) s_j[js * 64 + lane] = jv;      // (padding rows park the zero they loaded)
                     dx[r] = fma(jv, dq[j], dx[r]);
                     pin(dx[r]);
                     double t = jv;
@@ -468,30 +436,6 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
         }
     });
     __builtin_amdgcn_sched_barrier(0);
-#ifndef IRLOSC_LANE_JT_EARLY
-#define IRLOSC_LANE_JT_EARLY 0
-#endif
-    // The Jacobian entries once more, for J^T t behind the k x k stage (and for the records of the flagged robots; with IRLOSC_LANE_JPARK
-    // the parked ones from LDS, the rest from the block).  Requested ahead of that stage their round trip would run under its ~2 000
-    // instructions -- but 85 more live doubles next to the factor's 91 spill (1.3 kB of scratch): they are requested behind it.
-    double Jt[K][NJ];
-    auto load_jt = [&]() {
-        static_for<0, NJ>([&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            if constexpr (L::hinge_ee(j)) {
-                static_for<0, K>([&](auto rc) {
-                    constexpr int r = decltype(rc)::value;
-                    if constexpr (L::row_moved(r, j)) {
-                        constexpr int js = Rec<L>::jslot(r, j);
-                        if constexpr (js < NPARK) Jt[r][j] = s_j[js * 64 + lane];      // (own slot: written by this lane in the recursion)
-                        else Jt[r][j] = jload(rc, jc);
-                    }
-                });
-            }
-        });
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    if constexpr (IRLOSC_LANE_JT_EARLY == 1) load_jt();
 
     LANE_TS(2);
     uint32_t flags = npd ? IRLOSC_FLAG_M_NOT_PD : 0u;
@@ -548,7 +492,6 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     static_for<0, K>([&](auto cc) { constexpr int c = decltype(cc)::value; t[c] = plain ? t[c] : 0.0; });      // the eigen pass adds its own J^T t
     __builtin_amdgcn_sched_barrier(0);
     LANE_TS(3);
-    if constexpr (IRLOSC_LANE_JT_EARLY == 2) load_jt();      // (in flight while the records are written)
     // ---- the robots the certificate does not clear get a record for the eigen pass: slot from one atomic per wave ---------------------
     const bool hand = !plain && live;
     const unsigned long long hm = __ballot(hand);
@@ -590,9 +533,21 @@ __global__ __launch_bounds__(64, 1) void osc_lane_kernel(const Row16Train<TIN> t
     }
     __builtin_amdgcn_sched_barrier(0);
     LANE_TS(4);
-    // ---- J^T t, hinge by hinge, behind the records' A (the factor is dead by now: its 91 entries and these 85 do not fit the
-    // architectural registers together); the flagged robots leave the entries that can be non-zero in their record
-    if constexpr (IRLOSC_LANE_JT_EARLY == 0) load_jt();
+    // ---- J^T t, hinge by hinge; the flagged robots leave the entries that can be non-zero in their record.  The Jacobian entries are
+    // read from the block once more, and only HERE, behind the records' A, where the factor is dead: requested ahead of the k x k stage,
+    // or behind it while the records are written, their round trip would run under other work -- but these 85 doubles next to the
+    // factor's 91 do not fit the architectural registers together and spill (1.3 kB of scratch).
+    double Jt[K][NJ];
+    static_for<0, NJ>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        if constexpr (L::hinge_ee(j)) {
+            static_for<0, K>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                if constexpr (L::row_moved(r, j)) Jt[r][j] = jload(rc, jc);
+            });
+        }
+    });
+    __builtin_amdgcn_sched_barrier(0);
     double jt[NJ];
     static_for<0, NJ>([&](auto jc) {
         constexpr int j = decltype(jc)::value;

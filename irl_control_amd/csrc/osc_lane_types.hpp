@@ -7,7 +7,9 @@
 namespace irlosc {
 namespace lane {
 
-// What the host derives from the layout (irlosc_set_model): uniform over the launch, read as scalars
+// What the host derives from the layout (irlosc_set_model): uniform over the launch, read as scalars.  (ext and dev are no longer read by
+// a kernel, only by lane_plan while it builds the map; they keep their place because the struct is a kernel argument -- dropping them
+// moves every scalar load offset behind them and is a change of the machine code to be made, and diffed, on its own.)
 struct RowMap {
     uint32_t real;                  // bit r: canonical row r is a task row of the layout (else padding)
     int32_t comp[IRLOSC_MAX_K];     // component 0..5 of (jacp, jacr) the row takes (device.py:131-132); 0 for padding

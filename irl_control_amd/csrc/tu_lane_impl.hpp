@@ -53,9 +53,6 @@ int launch_lane_osc<IRLOSC_LANE_TIN>(const Row16Train<IRLOSC_LANE_TIN>& tr, cons
 }
 
 #ifdef IRLOSC_LANE_PLAN
-// does the lane kernel compute part 1 of the task signal itself (then no task pass is launched ahead of it)?
-int lane_task_in_kernel() { return IRLOSC_LANE_TASK_IN; }
-
 // Which instantiation takes a layout, and its row map: the task rows grouped by end-effector body (candidates of the compiled tree in
 // body order), each group padded to the tier's rows.  -1: no instantiation (an EE body that is not a candidate cannot happen on a
 // model that matched the tree; more rows on one body than any tier holds can: e.g. a base asked for three rotations) -- the fused

@@ -43,18 +43,16 @@ int launch_row16(const Row16Train<TIN>& tr, int nsteps, bool tree, hipStream_t s
 // factorisation in the tree-structured form of the compiled Dual-UR5 shape.  Blocks of FOUR waves (256 threads): block x takes
 // robots 16 (x % 4) .. of walk wave x / 4, i.e. one 128-byte line of every entry of that wave's exchange block.
 template <typename TIN>
-int launch_row16_fromq(const Row16Train<TIN>& tr, int nsteps, hipStream_t st, int parts) {
+int launch_row16_fromq(const Row16Train<TIN>& tr, int nsteps, hipStream_t st) {
     const KParams<TIN>& p = tr.p[0];
     if (p.B <= 0 || nsteps <= 0) return 0;
     const int waves = (p.B + 63) / 64;
     const dim3 grid(waves * 4, nsteps), tgrid(waves, nsteps);      // the task pass first: one lane per robot, block = walk wave
-    if (p.padded) return launch_row16_pad_fromq<TIN>(tr, nsteps, st, parts);
-    int rc = 0;
-    if (parts & 1)
-        rc = exact_dispatch(tr, [&](auto s) {
-            hipLaunchKernelGGL((osc_task_rows_fromq_kernel<decltype(s)::k, decltype(s)::ndev, TIN, TopoDualUr5>), tgrid, dim3(64 * decltype(s)::ndev), 0, st, tr);
-        });
-    if (rc || !(parts & 2)) return rc;
+    if (p.padded) return launch_row16_pad_fromq<TIN>(tr, nsteps, st);
+    const int rc = exact_dispatch(tr, [&](auto s) {
+        hipLaunchKernelGGL((osc_task_rows_fromq_kernel<decltype(s)::k, decltype(s)::ndev, TIN, TopoDualUr5>), tgrid, dim3(64 * decltype(s)::ndev), 0, st, tr);
+    });
+    if (rc) return rc;
     return exact_dispatch(tr, [&](auto s) {
         hipLaunchKernelGGL((osc_row16_kernel<decltype(s)::k, decltype(s)::ndev, TIN, 25, true, TopoDualUr5>), grid, dim3(256), 0, st, tr);
     });
@@ -70,7 +68,7 @@ int launch_row16_worklist(const Row16Train<TIN>& tr, int nsteps, int32_t* reset,
 }
 
 template int launch_row16<IRLOSC_R16_TIN>(const Row16Train<IRLOSC_R16_TIN>&, int, bool, hipStream_t);
-template int launch_row16_fromq<IRLOSC_R16_TIN>(const Row16Train<IRLOSC_R16_TIN>&, int, hipStream_t, int);
+template int launch_row16_fromq<IRLOSC_R16_TIN>(const Row16Train<IRLOSC_R16_TIN>&, int, hipStream_t);
 template int launch_row16_worklist<IRLOSC_R16_TIN>(const Row16Train<IRLOSC_R16_TIN>&, int, int32_t*, hipStream_t);
 
 #ifdef IRLOSC_R16_TREE_MASKS      // (one definition in the library)

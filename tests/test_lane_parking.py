@@ -1,9 +1,8 @@
-"""The lane-form eigen pass parks the head of A's triangle in LDS at a group's first load and reloads only the tail from the record;
-the lane kernel can park the entries of J its recursion has consumed the same way (-DIRLOSC_LANE_JPARK=1, an A/B build: off in the
-product, csrc/osc_lane.hpp).  The parked values are the doubles that used to be read again, so nothing may change -- and nothing
-parked may survive from one step, slot, block or group of records to the next.  Held here at the shapes where that could go wrong,
-whichever of the two is compiled in: a last wave with 37 live lanes, both tiers (k7: every entry of J and of A fits), trains on both
-banks, the fused path's blocks, and a block of the eigen pass that takes a second group of records into the LDS of its first."""
+"""The lane-form eigen pass parks the head of A's triangle in LDS at a group's first load and reloads only the tail from the record
+(csrc/osc_lane.hpp).  The parked values are the doubles that used to be read again, so nothing may change -- and nothing parked may
+survive from one step, slot, block or group of records to the next.  Held here at the shapes where the eigen pass's parking could go
+wrong: a last wave with 37 live lanes, both tiers (k7: every entry of A fits), trains on both banks, the fused path's blocks, and a
+block of the eigen pass that takes a second group of records into the LDS of its first."""
 import os
 import subprocess
 import sys
