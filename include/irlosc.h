@@ -808,6 +808,60 @@ IRLOSC_API int irlosc_set_joints(irlosc_ctx* ctx, int32_t slot, int32_t B, const
 IRLOSC_API int irlosc_download_joint_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* tau, double* max_violation,
                                            int32_t* active_ticks, double* ctrl);
 
+/* ---- the episode log: every logged tick's observations and torques, gathered on the GPU (csrc/osc_log.hpp) -------------------------
+ * irlosc_rollout_from_q hands back the EE poses and nothing else per tick.  A LOG hands back, per logged tick and per logged robot, the
+ * channels the caller picks -- the (observation, action) pairs a policy is trained from -- without cutting the rollout into one-tick
+ * calls.  Everything is a double; widening the float32 words of a float32 context (u, targets, wrench) and the uint32 flags is exact,
+ * and the host recovers the original bits by casting back.
+ *   FRONT channels, gathered directly behind the give-up pass and in front of the waypoint cycler -- the state the OSC step used, the
+ *     targets and the wrench it saw, the torques it produced.  A list's or a stream's targets of the tick are in the sample (they are
+ *     written in front of the OSC step); a waypoint that the cycler advances on this tick shows up in the next sample.
+ *   BACK channels (WALL_FORCE, JOINT_TAU), gathered behind the joint rows and directly in front of the plant: the `force` and `tau` that
+ *     irlosc_download_wall_state / irlosc_download_joint_state would read behind this tick.
+ * The log only reads: coordinates, torques, flags, programs, pushes, walls and rows of a logged rollout are bit for bit those of the
+ * unlogged one, all tick counts continue as there, and the order of a tick's launches (pushes, then walls, then joint rows on one bias
+ * entry) is unchanged.  A rollout without a log launches exactly the kernels it launched before. */
+#define IRLOSC_LOG_QPOS        1u   /* [R][n]        coordinates at the START of the tick: what the tick's walk read            */
+#define IRLOSC_LOG_QVEL        2u   /* [R][n]                                                                                    */
+#define IRLOSC_LOG_EE_POSE     4u   /* [R][ndev][7]  the walk's EE poses: the words irlosc_rollout_from_q's ee_trace carries     */
+#define IRLOSC_LOG_TARGETS     8u   /* [R][ndev][7]  as the tick's OSC step read them, widened to double                         */
+#define IRLOSC_LOG_WRENCH     16u   /* [R][ndev][6]  the feed's wrench as the OSC step read it (after every SENSE), widened      */
+#define IRLOSC_LOG_U          32u   /* [R][n]        the tick's torques (give-up pass included), widened                         */
+#define IRLOSC_LOG_FLAGS      64u   /* [R][1]        the step's flag word of the tick as a double (not what the plant adds)      */
+#define IRLOSC_LOG_WALL_FORCE 128u  /* [R][ndev][3]  F_d(t) the walls applied on this tick                                       */
+#define IRLOSC_LOG_JOINT_TAU  256u  /* [R][n]        tau the joint rows applied on this tick                                     */
+typedef struct irlosc_log {
+    uint32_t channels;      /* OR of the above, not 0, no other bit */
+    int32_t  every;         /* >= 1: ticks 0, every, 2 every, ... of THIS call are logged (as trace_every counts) */
+    int32_t  n_robots;      /* R: 0 or B with robots == NULL (all B), else the length of robots[] in [1, B] */
+    int32_t  reserved;      /* 0 */
+    uint64_t buffer_bytes;  /* device ring, 0 = 256 MiB; else it must hold at least two samples */
+} irlosc_log;
+/* A SAMPLE is the concatenation, in ascending bit order, of the asked channels' planes, each a dense row-major [R][w] array of doubles
+ * (channel-major on purpose: a block's 64 robots own 64 w consecutive doubles of a plane, so the kernel's stores are coalesced tiles).
+ * Context-free: offset[i] = where the plane of channel bit i starts inside a sample, in doubles (-1 for a channel not asked for), and
+ * *sample_words = the sample's size.  IRLOSC_ERR_ARG: channels 0 or with an unknown bit, R < 1, n outside [1, IRLOSC_MAX_N], ndev
+ * outside [1, IRLOSC_MAX_DEV], offset or sample_words NULL. */
+IRLOSC_API int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int32_t R, int64_t offset[9], int64_t* sample_words);
+/* irlosc_rollout_from_q with a log in place of the EE trace: log_host[ceil(ticks / every)][sample_words] (double), one sample per logged
+ * tick of the R robots of `robots` (strictly ascending, in [0, B); NULL: all B).  log == NULL is
+ * irlosc_rollout_from_q(ctx, slot, B, ticks, 0, NULL, u_host, flags_any_host); robots and log_host are not read then.
+ * The samples are gathered into a device ring the context owns (allocated by the first use, regrown on demand; with buffer_bytes == 0
+ * it is 256 MiB, or two samples where those are larger).  The ring has two halves of whole samples, and a half holds what drains in
+ * one piece -- 32 MiB, or one sample where that is larger.  A full half, and the last one, crosses PCIe on a stream of its own into a
+ * pinned block while the following ticks fill the other half on the context's stream; the host copies a pinned block into log_host
+ * when it needs the block again, and at the end.  Ticks keep running while a half is on the link; the rollout waits only where a half
+ * would be refilled before it has left.
+ * Every argument is checked before anything is enqueued, sizes in 64 bits; after a refusal the slot is exactly as it was: no tick ran.
+ *   IRLOSC_ERR_ARG    what irlosc_log_layout refuses; every < 1; reserved != 0; robots == NULL with n_robots not 0 or B; robots given with
+ *                     n_robots outside [1, B], not strictly ascending or outside [0, B); log_host NULL; a buffer_bytes != 0 that
+ *                     holds fewer than two samples
+ *   IRLOSC_ERR_STATE  what irlosc_rollout_from_q refuses; IRLOSC_LOG_WRENCH on a slot without a sensor feed; IRLOSC_LOG_WALL_FORCE on a
+ *                     slot without walls; IRLOSC_LOG_JOINT_TAU on a slot without joint rows (each covers B robots, as every rollout asks)
+ * A robot that is frozen on a tick is logged like any other: its coordinates repeat, its u and flags are what the step produced. */
+IRLOSC_API int irlosc_rollout_from_q_logged(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t ticks, const irlosc_log* log,
+                                            const int32_t* robots, double* log_host, void* u_host, uint32_t* flags_any_host);
+
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard
  * and NOTHING is exchanged per tick.  RCCL (over xGMI) is used once per benchmark: sum of the steps done, max of the

@@ -38,7 +38,9 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_slot_route", "irlosc_set_plant", "irlosc_rollout_from_q", "irlosc_download_q",
            "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state",
            "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state", "irlosc_set_joints",
-           "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets"]
+           "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets",
+           "irlosc_log_layout", "irlosc_rollout_from_q_logged"]
+LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -119,6 +121,12 @@ class JointRows(C.Structure):
                 ("source", C.c_int32 * MAX_JOINT_ROWS), ("dev", C.c_int32 * MAX_JOINT_ROWS)]
 
 
+class Log(C.Structure):
+    """struct irlosc_log (include/irlosc.h): the episode log of irlosc_rollout_from_q_logged."""
+    _fields_ = [("channels", C.c_uint32), ("every", C.c_int32), ("n_robots", C.c_int32), ("reserved", C.c_int32),
+                ("buffer_bytes", C.c_uint64)]
+
+
 class Cfg(C.Structure):
     _fields_ = [("hip_device", C.c_int32), ("dtype", C.c_int32), ("max_batch", C.c_int32),
                 ("n_slots", C.c_int32), ("n", C.c_int32), ("ndev", C.c_int32),
@@ -192,6 +200,8 @@ def load():
     lib.irlosc_set_plant.argtypes = [vp, C.POINTER(Plant)]
     lib.irlosc_rollout_from_q.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     lib.irlosc_download_q.argtypes = [vp, i32, i32, vp, vp]
+    lib.irlosc_log_layout.argtypes = [i32, i32, C.c_uint32, i32, vp, vp]
+    lib.irlosc_rollout_from_q_logged.argtypes = [vp, i32, i32, i32, C.POINTER(Log), vp, vp, vp, vp]
     lib.irlosc_set_waypoints.argtypes = [vp, i32, i32, C.POINTER(Waypoints), vp]
     lib.irlosc_download_waypoint_state.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.irlosc_set_action_list.argtypes = [vp, i32, i32, C.POINTER(ActionList), vp]

@@ -343,6 +343,39 @@ class BatchedOSC:
         qpos, qvel = self.download_q(slot)
         return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=tr)
 
+    def rollout_logged(self, ticks: int, channels, every: int = 1, robots=None, slot: int = 0, buffer_bytes: int = 0):
+        """`rollout` with an episode log (irlosc_rollout_from_q_logged): on ticks 0, every, 2 every, ... of this call the `channels`
+        (names of rollout_log.CHANNELS, or an OR of their bits) of `robots` (strictly ascending indices; None: all B) are gathered on
+        the GPU and drained to the host while the following ticks run.  channels=None runs the entry point without a log.
+        -> `rollout`'s dict (ee_trace None) plus log: dict of named arrays [S, R, ...] (rollout_log.split) and log_ticks: the S ticks
+        they belong to.  `buffer_bytes`: the device ring (0: 256 MiB; else at least two samples)."""
+        from . import rollout_log
+        L, B = self.layout, self._B[slot]
+        ticks = int(ticks)
+        u = np.empty((B, L.n), dtype=self.dtype)
+        fl = np.empty(B, dtype=np.uint32)
+        lg = idx = buf = None
+        log, log_ticks = None, None
+        if channels is not None:
+            m = rollout_log.mask(channels)
+            every = int(every)
+            if robots is not None:
+                idx = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+            R = B if idx is None else len(idx)
+            lg = _lib.Log(m & 0xFFFFFFFF, every, 0 if idx is None else R, 0, int(buffer_bytes))
+            S = -(-ticks // every) if every > 0 and ticks > 0 else 0
+            words = 0
+            if S and R >= 1 and m and not m & ~rollout_log.ALL:
+                words = rollout_log.layout(L.n, L.ndev, m, R)[1]
+            buf = np.empty((S, words), dtype=np.float64)
+        self._chk(self.lib.irlosc_rollout_from_q_logged(self._h, slot, B, ticks, C.byref(lg) if lg is not None else None, _lib.ptr(idx),
+                                                        _lib.ptr(buf), _lib.ptr(u), _lib.ptr(fl)))
+        if buf is not None:
+            log = rollout_log.split(buf, L.n, L.ndev, m, R, dtype=self.dtype) if B else {}
+            log_ticks = np.arange(0, ticks, every, dtype=np.int64)
+        qpos, qvel = self.download_q(slot)
+        return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=None, log=log, log_ticks=log_ticks)
+
     def download_q(self, slot: int = 0):
         """-> (qpos, qvel) [B, n] float64 of the slot as they sit in HBM: uploaded, or advanced by `rollout` (irlosc_download_q)."""
         B = self._B[slot]

@@ -31,6 +31,7 @@
 #include "osc_push.hpp"
 #include "osc_wall.hpp"
 #include "osc_joint.hpp"
+#include "osc_log.hpp"
 #include "launchers.hpp"
 #include "dev_mem.hpp"
 
@@ -277,6 +278,7 @@ struct irlosc_ctx {
     int k = 0;
     size_t esz = 4;
     Stream stream;                     // (declared ahead of everything enqueued on it: destroyed last)
+    Stream log_stream;                 // irlosc_rollout_from_q_logged: the stream a half of the log's ring drains on
     Event ev0, ev1;
     std::vector<Slot> slot;            // resident inputs, one set per slot
     int nsets = 1;                     // output sets of bank 0: step i of a row16 train writes set i; the generic path only ever uses set 0
@@ -336,6 +338,13 @@ struct irlosc_ctx {
     irlosc_plant plant{};
     DevBuf<uint32_t> dflags_any;
     DevBuf<double> dtrace;
+    // irlosc_rollout_from_q_logged: the device ring of the episode log (two halves of whole samples), the index list of the logged robots,
+    // and per half the pinned block it drains into with its events: `full` on the rollout's stream behind the half's last sample,
+    // `drained` on log_stream behind its copy
+    DevBuf<double> dlog;
+    DevBuf<int32_t> dlog_robots;
+    PinnedBuf log_stage[2];
+    Event log_full[2], log_drained[2];
     DevBuf<int32_t> dsym;     // symmetry probe of the throughput paths: {count, first instance}
     // Tree-structured factorisation on dense records (row16 kernel), for slots whose records carry the tree's zeros (Slot::tree)
     int tree_enabled = 1;              // IRLOSC_TREE=0 turns the form off (A/B measurements)
@@ -1738,8 +1747,11 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 
 // irlosc_rollout_from_q: the plant kernel behind the step (one step on bank 0), handed to the next train like the timing events
 // (irlosc_ctx::plant_next); trace: the device sample of this tick's EE poses, or nullptr.  What else the tick runs, and as which
-// tick, is the slot's to say (Slot::prog).
-struct PlantCall { double* trace; };
+// tick, is the slot's to say (Slot::prog).  log: the episode log's sample of this tick (irlosc_rollout_from_q_logged), or nullptr.
+// A logged tick: the ring's sample it fills, the event its first log launch waits for on the tick's stream (the half it starts was still
+// draining: the copy that empties it; else null), and what stays the same over the call -- channels, robots (device, or nullptr: all), layout
+struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };
+struct PlantCall { double* trace; const LogCall* log; };
 
 // The exchange entry of each device's EE pose (its x; y z qw qx qy qz follow): what the rollout's kernels find an EE body by
 static void fill_ee0(const irlosc_ctx* c, int32_t* ee0) { for (int d = 0; d < c->cfg.ndev; ++d) ee0[d] = c->model.tables.eetab[d][0]; }
@@ -1881,6 +1893,21 @@ static PlantArgs plant_args(const irlosc_ctx* c, const Slot& s, int B, const irl
     return a;
 }
 
+// The arguments of a log launch of the tick's step on bank bk: the channels of `mask` out of the log's (the front or the back ones; none: no
+// launch), wrench: the feed's wrench of the tick (or nullptr: the slot has no feed, and the log no WRENCH channel)
+static LogArgs log_args(const irlosc_ctx* c, const Slot& s, const irlosc_ctx::Bank& bk, const LogCall& lg, uint32_t mask, const void* wrench) {
+    LogArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    a.sample = lg.sample; a.robots = lg.robots; a.mask = lg.channels & mask;
+    for (int i = 0; i < LOG_CHANNELS; ++i) a.off[i] = lg.off[i];
+    a.qpos = s.qpos; a.qvel = s.qvel; a.xside = bk.xside[0]; a.tgt = s.tgt; a.wrench = wrench; a.u = bk.u[0]; a.flags = bk.flags[0];
+    a.wall_force = s.walls.force((size_t)c->cfg.ndev * Bm); a.joint_tau = s.joints.tau(Bm);
+    a.R = lg.R; a.n = c->cfg.n; a.ndev = c->cfg.ndev; a.n_entries = (int32_t)c->model.fe_xentries; a.stride = (int32_t)Bm;
+    fill_ee0(c, a.ee0);
+    return a;
+}
+
 // What the slot has of one part (`robots` of `what`; 0: none) covers B robots.  With `setter` (a download) a slot that has none is refused,
 // by the name of the entry point that sets it; without (a rollout) it passes.
 static int check_covers(irlosc_ctx* c, int slot, int B, int robots, const char* what, const char* covers, const char* setter) {
@@ -1963,8 +1990,13 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
 //                   tick before, behind it] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel
 //                   | stream kernel: its targets are this tick's too]
 //     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
+//     [log FRONT (a logged tick): coordinates, EE poses, targets, wrench, u and flags as the step used and left them -- behind the give-up
+//                   pass, which completes u; in front of the cycler, which moves the targets, and of the plant, which moves the
+//                   coordinates and overwrites the block's M entries (the EE entries it leaves alone; the order does not lean on that)]
 //     tick_behind:  [waypoint cycler: the targets move where an arm arrived]; [pushes APPLY] [walls APPLY] [joint rows], each into the bias
-//                   entries of the block, which only the plant reads from here on; the plant: every robot has its u by then
+//                   entries of the block, which only the plant reads from here on; [log BACK (a logged tick with WALL_FORCE or JOINT_TAU):
+//                   the force / tau planes the two launches ahead of it just wrote]; the plant: every robot has its u by then
+// The log launches only read, and write nothing but their sample of the ring.
 // What rests on this order alone: "pushes, then walls, then joint rows" on one bias entry of one tick.
 template <typename T>
 static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, const irlosc_ctx::Bank& bk, void* wrench, hipStream_t st) {
@@ -1980,6 +2012,7 @@ static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp,
     if (tp.push_apply) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_apply, bk.xside[0], nullptr), st));
     if (tp.wall_apply) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_apply, bk.xside[0], nullptr), st));
     if (tp.joints) HIPCHK(c, (hipError_t)launch_joints(joint_args(c, s0, B, bk.xside[0]), st));
+    if (pl.log && (pl.log->channels & LOG_BACK)) HIPCHK(c, (hipError_t)launch_log<T>(log_args(c, s0, bk, *pl.log, LOG_BACK, nullptr), st));
     HIPCHK(c, (hipError_t)launch_plant<T>(plant_args(c, s0, B, bk, pl.trace), st));
     return IRLOSC_OK;
 }
@@ -2081,6 +2114,10 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     else HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st));      // (task pass + FROMQ kernel; the lane kernel computes the task rows itself)
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
+    if (pl && pl->log) {      // the log's front launch; the first into a half of the ring that was draining waits for its copy
+        if (pl->log->wait) HIPCHK(c, hipStreamWaitEvent(st, pl->log->wait, 0));
+        HIPCHK(c, (hipError_t)launch_log<T>(log_args(c, s0, bk, *pl->log, LOG_FRONT, nft ? fts[0].wrench : nullptr), st));
+    }
     if (pl && (rcw = tick_behind<T>(c, s0, B, tp, bk, *pl, st))) return rcw;
     if (c->tev_end) HIPCHK(c, hipEventRecord(c->tev_end, st));
     // The give-up pass wrote dense records of the robots on its lists into the slots (and nothing for the others): what the
@@ -2306,8 +2343,57 @@ extern "C" int irlosc_download_q(irlosc_ctx* c, int32_t slot, int32_t B, double*
     return IRLOSC_OK;
 }
 
-// The ticks of a rollout, enqueued; the caller synchronises (also after an error: earlier ticks are in flight).
-static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, double* trace_host) {
+// The episode log of one call of irlosc_rollout_from_q_logged: what every logged tick's LogCall shares, where the samples go on the host, the
+// ring's shape (two halves of `hcap` samples of `words` doubles), and per half what is on its way: samples first .. first + count - 1 in
+// the half's pinned block behind its `drained` event (count 0: nothing), and whether the half has been drained before in this call
+struct LogRun {
+    LogCall call{};
+    int every = 1, nsamples = 0, hcap = 1;
+    size_t words = 0;
+    double* host = nullptr;
+    struct { int first = 0, count = 0; bool drained = false; } half[2];
+};
+
+// The samples of half h that are on their way arrive in log_host: the host waits for the half's copy (keep: and copies the pinned block on)
+static int log_collect(irlosc_ctx* c, LogRun& lr, int h, bool keep = true) {
+    if (!lr.half[h].count) return IRLOSC_OK;
+    const int first = lr.half[h].first, count = lr.half[h].count;
+    lr.half[h].count = 0;
+    HIPCHK(c, hipEventSynchronize(c->log_drained[h]));
+    if (keep) memcpy(lr.host + (size_t)first * lr.words, (const unsigned char*)c->log_stage[h], (size_t)count * lr.words * sizeof(double));
+    return IRLOSC_OK;
+}
+
+// Half h holds samples first .. first + count - 1: they leave on log_stream behind the ticks that wrote them, into the half's pinned block
+// (which the host empties first if its last load is still there), while the rollout's stream goes on into the other half
+static int log_drain(irlosc_ctx* c, LogRun& lr, int h, int first, int count) {
+    HIPCHK(c, hipEventRecord(c->log_full[h], c->stream));
+    const int rc = log_collect(c, lr, h);
+    if (rc) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->log_stream, c->log_full[h], 0));
+    HIPCHK(c, hipMemcpyAsync((unsigned char*)c->log_stage[h], c->dlog + (size_t)h * lr.hcap * lr.words, (size_t)count * lr.words * sizeof(double),
+                             hipMemcpyDeviceToHost, c->log_stream));
+    HIPCHK(c, hipEventRecord(c->log_drained[h], c->log_stream));
+    lr.half[h].first = first; lr.half[h].count = count; lr.half[h].drained = true;
+    return IRLOSC_OK;
+}
+
+// The end of a logged call, error or not: both halves arrive (rc != 0: are waited for and dropped) and log_stream is joined -> rc, or the
+// first error here.  The caller joins the rollout's stream.
+static int log_join(irlosc_ctx* c, LogRun& lr, int rc) {
+    const int older = lr.half[0].count && lr.half[1].count && lr.half[1].first < lr.half[0].first ? 1 : 0;
+    for (int i = 0; i < 2; ++i) {
+        const int e = log_collect(c, lr, i ? 1 - older : older, rc == IRLOSC_OK);
+        if (e && !rc) rc = e;
+    }
+    const hipError_t es = hipStreamSynchronize(c->log_stream);
+    if (es != hipSuccess && !rc) rc = fail(c, IRLOSC_ERR_HIP, "hipStreamSynchronize of the log's stream failed: %s", hipGetErrorString(es));
+    return rc;
+}
+
+// The ticks of a rollout, enqueued; the caller synchronises (also after an error: earlier ticks are in flight) and, with a log, joins it
+// (log_join).  One frame for the unlogged and the logged entry point: lr == nullptr is the rollout without a log.
+static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, double* trace_host, LogRun* lr = nullptr) {
     const size_t sample = (size_t)B * c->cfg.ndev * 7;      // doubles
     const int nsamples = every > 0 && trace_host ? (ticks + every - 1) / every : 0;
     // the trace's device buffer: whole samples up to TRACE_BYTES, at least one; a chunk goes to the host when it is full
@@ -2318,13 +2404,24 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
         return fail(c, IRLOSC_ERR_HIP, "out of device memory for the EE trace (%zu bytes)", (size_t)cap * max_sample);
     HIPCHK(c, hipMemsetAsync(c->dflags_any, 0, (size_t)B * sizeof(uint32_t), c->stream));
     int filled = 0, sent = 0;      // samples written / copied to the host
+    int logged_n = 0;              // samples of the log written
     for (int t = 0; t < ticks; ++t) {
         const bool traced = nsamples && t % every == 0;
-        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr};
+        const bool logged = lr && t % lr->every == 0;
+        const int lh = logged ? (logged_n / lr->hcap) % 2 : 0, lpos = logged ? logged_n % lr->hcap : 0;      // the log's half and place in it
+        if (logged) {
+            lr->call.sample = c->dlog + ((size_t)lh * lr->hcap + lpos) * lr->words;
+            lr->call.wait = lpos == 0 && lr->half[lh].drained ? (hipEvent_t)c->log_drained[lh] : nullptr;
+        }
+        const PlantCall pl{traced ? c->dtrace + (size_t)(filled % cap) * sample : nullptr, logged ? &lr->call : nullptr};
         c->plant_next = &pl;
         const int rc = fused_resident(c, slot, B, 1);
         c->plant_next = nullptr;
         if (rc) return rc;
+        if (logged && (++logged_n % lr->hcap == 0 || logged_n == lr->nsamples)) {      // the half is full, or holds the last sample
+            const int rcl = log_drain(c, *lr, lh, logged_n - 1 - lpos, lpos + 1);
+            if (rcl) return rcl;
+        }
         if (traced && (++filled % cap == 0 || filled == nsamples)) {
             HIPCHK(c, hipMemcpyAsync(trace_host + (size_t)sent * sample, c->dtrace, (size_t)(filled - sent) * sample * sizeof(double),
                                      hipMemcpyDeviceToHost, c->stream));
@@ -2334,8 +2431,78 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     return IRLOSC_OK;
 }
 
-extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, int32_t trace_every, double* ee_trace_host,
-                                     void* u_host, uint32_t* flags_any_host) {
+extern "C" int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int32_t R, int64_t offset[9], int64_t* sample_words) {
+    if (!offset || !sample_words) return fail(nullptr, IRLOSC_ERR_ARG, "log: offset and sample_words are required");
+    if (channels == 0 || (channels & ~(LOG_FRONT | LOG_BACK))) return fail(nullptr, IRLOSC_ERR_ARG, "log: channels=0x%x must be a non-empty OR of the IRLOSC_LOG_* bits", channels);
+    if (R < 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: R=%d must be >= 1", R);
+    if (n < 1 || n > IRLOSC_MAX_N) return fail(nullptr, IRLOSC_ERR_ARG, "log: n=%d out of [1,%d]", n, IRLOSC_MAX_N);
+    if (ndev < 1 || ndev > IRLOSC_MAX_DEV) return fail(nullptr, IRLOSC_ERR_ARG, "log: ndev=%d out of [1,%d]", ndev, IRLOSC_MAX_DEV);
+    int64_t words = 0;
+    for (int i = 0; i < LOG_CHANNELS; ++i) {
+        offset[i] = (channels >> i) & 1u ? words : -1;
+        if ((channels >> i) & 1u) words += (int64_t)R * log_width(i, n, ndev);
+    }
+    *sample_words = words;
+    return IRLOSC_OK;
+}
+
+// The log of a call, checked against the slot (every refusal ahead of the first allocation or launch) and planned into lr; B >= 1
+static int log_plan(irlosc_ctx* c, int slot, int B, int ticks, const irlosc_log* log, const int32_t* robots, double* log_host, LogRun& lr) {
+    if (log->every < 1) return fail(c, IRLOSC_ERR_ARG, "log: every=%d must be >= 1", log->every);
+    if (log->reserved != 0) return fail(c, IRLOSC_ERR_ARG, "log: reserved must be 0");
+    if (!log_host) return fail(c, IRLOSC_ERR_ARG, "log: log_host is NULL");
+    if (!robots && log->n_robots != 0 && log->n_robots != B)
+        return fail(c, IRLOSC_ERR_ARG, "log: n_robots=%d without robots[] must be 0 or B=%d", log->n_robots, B);
+    if (robots && (log->n_robots < 1 || log->n_robots > B)) return fail(c, IRLOSC_ERR_ARG, "log: n_robots=%d out of [1,%d]", log->n_robots, B);
+    const int R = robots ? log->n_robots : B;
+    for (int i = 0; robots && i < R; ++i)
+        if (robots[i] < 0 || robots[i] >= B || (i && robots[i] <= robots[i - 1]))
+            return fail(c, IRLOSC_ERR_ARG, "log: robots[%d]=%d: the list must be strictly ascending in [0,%d)", i, robots[i], B);
+    int64_t words = 0;
+    if (irlosc_log_layout(c->cfg.n, c->cfg.ndev, log->channels, R, lr.call.off, &words)) return fail(c, IRLOSC_ERR_ARG, "%s", irlosc_last_error(nullptr));
+    const uint64_t sb = (uint64_t)words * sizeof(double);      // (R <= max_batch, 170 words a robot at most: far from 2^63)
+    if (log->buffer_bytes && log->buffer_bytes / 2 < sb)
+        return fail(c, IRLOSC_ERR_ARG, "log: buffer_bytes=%llu holds fewer than two samples of %llu bytes", (unsigned long long)log->buffer_bytes, (unsigned long long)sb);
+    const Slot& s = c->slot[slot];
+    if ((log->channels & IRLOSC_LOG_WRENCH) && s.feed <= 0) return fail(c, IRLOSC_ERR_STATE, "log: IRLOSC_LOG_WRENCH on slot %d, which has no sensor feed (irlosc_set_sensordata)", slot);
+    if ((log->channels & IRLOSC_LOG_WALL_FORCE) && !s.walls.robots) return fail(c, IRLOSC_ERR_STATE, "log: IRLOSC_LOG_WALL_FORCE on slot %d, which has no walls (irlosc_set_walls)", slot);
+    if ((log->channels & IRLOSC_LOG_JOINT_TAU) && !s.joints.robots) return fail(c, IRLOSC_ERR_STATE, "log: IRLOSC_LOG_JOINT_TAU on slot %d, which has no joint rows (irlosc_set_joints)", slot);
+    // the ring: two halves of whole samples; a half holds what drains in one piece (DRAIN_BYTES, or one sample where that is larger: short
+    // pieces keep the last one, which nothing overlaps, short), never more than the ring's half or the call's samples
+    constexpr uint64_t RING_BYTES = (uint64_t)256 << 20, DRAIN_BYTES = (uint64_t)32 << 20;
+    const uint64_t ring = log->buffer_bytes ? log->buffer_bytes : std::max(RING_BYTES, 2 * sb);
+    lr.every = log->every;
+    lr.nsamples = (ticks + log->every - 1) / log->every;
+    lr.hcap = (int)std::min<uint64_t>(std::min(ring / 2 / sb, std::max<uint64_t>(1, DRAIN_BYTES / sb)), (uint64_t)lr.nsamples);
+    lr.words = (size_t)words;
+    lr.host = log_host;
+    lr.call.channels = log->channels; lr.call.R = R;
+    return IRLOSC_OK;
+}
+
+// The log's buffers for the call lr plans: ring, pinned blocks, stream and events (each made by the first use, grown on demand), and the
+// index list on the device
+static int log_buffers(irlosc_ctx* c, const int32_t* robots, LogRun& lr) {
+    const size_t half = (size_t)lr.hcap * lr.words * sizeof(double);
+    if (!got(c->dlog.reserve(2 * half))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for the log's ring (%zu bytes)", 2 * half);
+    for (int h = 0; h < (lr.nsamples > lr.hcap ? 2 : 1); ++h)
+        if (!got(c->log_stage[h].reserve(half))) return fail(c, IRLOSC_ERR_HIP, "out of pinned host memory for the log (%zu bytes)", half);
+    HIPCHK(c, c->log_stream.ensure());
+    for (int h = 0; h < 2; ++h) {
+        HIPCHK(c, c->log_full[h].ensure(hipEventDisableTiming));
+        HIPCHK(c, c->log_drained[h].ensure(hipEventDisableTiming));
+    }
+    if (robots) {
+        if (!got(c->dlog_robots.reserve((size_t)c->cfg.max_batch * sizeof(int32_t)))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for the log's robot list");
+        HIPCHK(c, hipMemcpyAsync(c->dlog_robots, robots, (size_t)lr.call.R * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        lr.call.robots = c->dlog_robots;
+    }
+    return IRLOSC_OK;
+}
+
+// Both rollout entry points: the EE trace (irlosc_rollout_from_q) or the episode log (irlosc_rollout_from_q_logged), or neither
+static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, int32_t trace_every, double* ee_trace_host, const irlosc_log* log,
+                        const int32_t* robots, double* log_host, void* u_host, uint32_t* flags_any_host) {
     if (!c) return IRLOSC_ERR_ARG;
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
@@ -2358,13 +2525,18 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
     if (rc) return rc;
     if (B == 0) return IRLOSC_OK;
+    LogRun lr;
+    if (log && (rc = log_plan(c, slot, B, ticks, log, robots, log_host, lr))) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     if (!fused_ready(c, 1))
         return fail(c, IRLOSC_ERR_STATE, "no rollout on this context: the exchange buffers of the fused path could not be allocated (the path "
                     "is switched off; steps from joint coordinates run through dense records)");
     HIPCHK(c, c->slot[slot].qt.ensure(qt_bytes(c)));
     if (!got(c->dflags_any.ensure((size_t)c->cfg.max_batch * sizeof(uint32_t)))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for flags_any");
-    rc = rollout_ticks(c, slot, B, ticks, trace_every, ee_trace_host);
+    // (from here on work may be in flight: every path below joins the streams before it returns)
+    if (log) rc = log_buffers(c, robots, lr);
+    if (!rc) rc = rollout_ticks(c, slot, B, ticks, trace_every, ee_trace_host, log ? &lr : nullptr);
+    if (log && c->log_stream) rc = log_join(c, lr, rc);
     if (!rc && u_host) {
         const hipError_t e = hipMemcpyAsync(u_host, c->du, (size_t)B * c->cfg.n * c->esz, hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) rc = fail(c, IRLOSC_ERR_HIP, "copy of u failed: %s", hipGetErrorString(e));
@@ -2376,6 +2548,16 @@ extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int
     const hipError_t es = hipStreamSynchronize(c->stream);
     if (es != hipSuccess && !rc) rc = fail(c, IRLOSC_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(es));
     return rc;
+}
+
+extern "C" int irlosc_rollout_from_q(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, int32_t trace_every, double* ee_trace_host,
+                                     void* u_host, uint32_t* flags_any_host) {
+    return rollout_call(c, slot, B, ticks, trace_every, ee_trace_host, nullptr, nullptr, nullptr, u_host, flags_any_host);
+}
+
+extern "C" int irlosc_rollout_from_q_logged(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, const irlosc_log* log, const int32_t* robots,
+                                            double* log_host, void* u_host, uint32_t* flags_any_host) {
+    return rollout_call(c, slot, B, ticks, 0, nullptr, log, robots, log_host, u_host, flags_any_host);
 }
 
 // ---- waypoint paths of the rollout (osc_waypoint.hpp) -----------------------------------------------------------------------

@@ -122,6 +122,12 @@ int launch_walls(const WallArgs& a, hipStream_t st);
 struct JointArgs;
 int launch_joints(const JointArgs& a, hipStream_t st);
 
+// tu_log.hip -- the episode log of a logged rollout tick (osc_log.hpp): the front launch behind the give-up pass, the back launch (the
+// walls' and rows' planes) directly in front of the plant; T = record type (of u, the targets and the wrench)
+struct LogArgs;
+template <typename T>
+int launch_log(const LogArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;

@@ -1,0 +1,74 @@
+"""The episode log of a rollout on the host (include/irlosc.h, "the episode log"): the channel names, a NumPy mirror of
+irlosc_log_layout, and split(), which turns the raw buffer of irlosc_rollout_from_q_logged into named arrays."""
+import numpy as np
+
+# channel names in bit order: bit i of irlosc_log.channels is CHANNELS[i] (IRLOSC_LOG_QPOS = 1 << 0, ...)
+CHANNELS = ("qpos", "qvel", "ee_pose", "targets", "wrench", "u", "flags", "wall_force", "joint_tau")
+BITS = {name: 1 << i for i, name in enumerate(CHANNELS)}
+ALL = (1 << len(CHANNELS)) - 1
+MAX_N, MAX_DEV = 32, 4
+
+
+def mask(channels) -> int:
+    """An OR of IRLOSC_LOG_* bits from an int or from names ("qpos", ...)."""
+    if isinstance(channels, (int, np.integer)):
+        return int(channels)
+    if isinstance(channels, str):
+        channels = [channels]
+    m = 0
+    for name in channels:
+        if name not in BITS:
+            raise ValueError(f"unknown log channel {name!r}: one of {CHANNELS}")
+        m |= BITS[name]
+    return m
+
+
+def names(channels) -> tuple:
+    """The names of the channels of a mask, in bit order."""
+    m = mask(channels)
+    return tuple(name for i, name in enumerate(CHANNELS) if (m >> i) & 1)
+
+
+def shape(name: str, n: int, ndev: int) -> tuple:
+    """The per-robot shape of a channel: its plane is [R, *shape]."""
+    return {"qpos": (n,), "qvel": (n,), "ee_pose": (ndev, 7), "targets": (ndev, 7), "wrench": (ndev, 6), "u": (n,), "flags": (),
+            "wall_force": (ndev, 3), "joint_tau": (n,)}[name]
+
+
+def layout(n: int, ndev: int, channels, R: int):
+    """-> (offset[9] int64, sample_words) as irlosc_log_layout gives them: where each channel's plane [R][w] starts inside a sample, in
+    doubles (-1: not asked for), and the sample's size.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
+    m = mask(channels)
+    if m == 0 or m & ~ALL:
+        raise ValueError(f"channels=0x{m:x} must be a non-empty OR of the IRLOSC_LOG_* bits")
+    if R < 1 or not 1 <= n <= MAX_N or not 1 <= ndev <= MAX_DEV:
+        raise ValueError(f"R={R}, n={n}, ndev={ndev} out of range")
+    off = np.full(len(CHANNELS), -1, dtype=np.int64)
+    words = 0
+    for i, name in enumerate(CHANNELS):
+        if (m >> i) & 1:
+            off[i] = words
+            words += R * int(np.prod(shape(name, n, ndev), dtype=np.int64))
+    return off, words
+
+
+def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64) -> dict:
+    """The raw log buffer [S, sample_words] (float64) as named arrays [S, R, ...].  u, targets and wrench come back in `dtype` (the
+    context's: the cast undoes the exact widening), flags as uint32, everything else float64."""
+    off, words = layout(n, ndev, channels, R)
+    buf = np.asarray(buf, dtype=np.float64).reshape(-1, words)
+    out = {}
+    for i, name in enumerate(CHANNELS):
+        if off[i] < 0:
+            continue
+        shp = shape(name, n, ndev)
+        w = int(np.prod(shp, dtype=np.int64))
+        a = buf[:, off[i]:off[i] + R * w].reshape((buf.shape[0], R) + shp)
+        if name in ("u", "targets", "wrench"):
+            a = a.astype(dtype)
+        elif name == "flags":
+            a = a.astype(np.uint32)
+        else:
+            a = a.copy()
+        out[name] = a
+    return out
