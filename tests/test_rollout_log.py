@@ -1,6 +1,7 @@
 """The episode log of a rollout (-m gpu): irlosc_rollout_from_q_logged against the path callers had before it -- rollout(1) T times from
 the same start with downloads around each tick.  Unless a tolerance is named every comparison is == on bits: widening to double is exact
-and both runs execute the same kernels on the same inputs."""
+and both runs execute the same kernels on the same inputs.
+Other layouts, the row16 FROMQ form and contexts wider than B: tests/test_rollout_log_layouts.py."""
 import ctypes as C
 
 import numpy as np
