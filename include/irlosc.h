@@ -506,7 +506,21 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *     irlosc_set_joints that answers IRLOSC_ERR_HIP                                    no rows
  *     everything else (uploads, targets, gains, feeds, programs, pushes, walls, other steps)  leaves them, their state and their tick alone
  * Only irlosc_rollout_from_q runs them and advances their tick.  An ACTION drive row reads the list in force on the tick it runs: with no
- * list, or one whose active device is not the row's, it is idle and keeps its ctrl -- legal, because lists come and go. */
+ * list, or one whose active device is not the row's, it is idle and keeps its ctrl -- legal, because lists come and go.
+ * EPISODES (irlosc_set_episodes) write targets only where they put a robot back to its start, so they are no program either: they live
+ * next to paths or a list, walls and joint rows, but their snapshot and their resets belong to the program and the targets they were set on.
+ *     irlosc_set_episodes with desc == NULL, irlosc_set_model (all slots)              episodes end
+ *     irlosc_set_targets on the slot (B == 0 too)                                      episodes end: the snapshot is stale
+ *     a setter of the slot's program that succeeds, or that ends the program in force
+ *     (irlosc_set_waypoints, irlosc_set_action_list; irlosc_set_gains where it ends a list)   episodes end
+ *     irlosc_set_episodes that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE              nothing changes: the episodes in force stay, whole
+ *     irlosc_set_episodes that succeeds                                                its episodes replace those in force; state and tick reset
+ *     irlosc_set_episodes that answers IRLOSC_ERR_HIP                                  no episodes
+ *     irlosc_set_teleop_stream, irlosc_set_pushes on a slot with episodes              REFUSED (IRLOSC_ERR_STATE), as irlosc_set_episodes is on a
+ *                                                                                      slot with a stream or with pushes: the reading index and
+ *                                                                                      the windows are the slot's ticks, not a robot's
+ *     everything else (uploads of coordinates, feeds, gains without a list, walls, joint rows, other steps)  leaves them alone
+ * Only irlosc_rollout_from_q and irlosc_rollout_from_q_logged run them and advance their tick. */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -861,6 +875,72 @@ IRLOSC_API int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int
  * A robot that is frozen on a tick is logged like any other: its coordinates repeat, its u and flags are what the step produced. */
 IRLOSC_API int irlosc_rollout_from_q_logged(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t ticks, const irlosc_log* log,
                                             const int32_t* robots, double* log_host, void* u_host, uint32_t* flags_any_host);
+
+/* ---- episodes: per-robot resets on the GPU and an early exit of the rollout (csrc/osc_episode.hpp) -----------------------------------
+ * A rollout is one episode per robot per call unless the slot has EPISODES: then a robot whose episode has ended starts over on the
+ * device while its neighbours go on, and a call can end as soon as every robot is through.  One more small kernel per tick, behind the
+ * plant (which wrote the coordinates a reset replaces): the last launch of the tick.  Per covered robot the device keeps
+ *     count        episodes ended so far
+ *     age          ticks the running episode has been run (only ticks that run the robot count: a rollout over fewer robots does not
+ *                  age those it leaves out -- the list's own "first tick that runs it" rule)
+ *     start_tick   the episodes' tick on which the running episode first ran (-1: it has not run yet)
+ *     a ring of the last `records` ended episodes: start_tick, length (= age), outcome, start index | variant index << 16
+ * and judges it on every tick that runs it.  The episode ENDS on that tick when
+ *     FINISHED, with end_on_finish:  a LIST: the robot's finished_tick >= 0;  PATHS: every listed device with loop == 0 has index == W_d,
+ *                                    and there is such a device;  no program: never
+ *     TIMEOUT, with max_ticks > 0:   age == max_ticks.  A robot that finishes on the tick of its timeout is FINISHED.
+ * Then its record is written and count += 1, and with max_episodes == 0 || count < max_episodes the robot is RESET, else PARKED: never
+ * judged again, it carries on exactly as a finished robot does without episodes.  A reset leaves the robot as the setters' init launches
+ * would: coordinates (walk layout, row-major qpos and qvel) = start state count mod S; its whole target row = the snapshot taken by
+ * irlosc_set_episodes (PATHS: waypoint 0 of every listed device on top); a list's state as irlosc_set_action_list leaves it, word 9 of
+ * the active device in the slot's gain copy taken again from the context's gains and, with V > 0 pose variants, the robot's lines of the
+ * list's pose table rewritten with variant count mod V; the paths' state (0, 0, -1); walls: force, max_depth, contact_ticks 0,
+ * first_tick -1 (the SENSE launch of the next tick subtracts +0.0: the feed's wrench keeps its bits); joint rows: tau, max_violation,
+ * active_ticks 0 and ctrl 0 (an ACTION drive lets go).  The next tick is the first tick of a fresh rollout for that robot.  Tick-valued
+ * state (finished_tick, last_tick, first_tick) keeps counting its owner's ticks: subtract the episode's start_tick.
+ * EARLY EXIT.  poll_every = P > 0: after the ticks P - 1, 2 P - 1, ... of a call the number of robots of the call that are not parked
+ * goes to pinned host memory behind an event on the rollout's stream; before enqueuing tick m P (m >= 2) the host WAITS for the copy
+ * made after tick (m - 1) P - 1 and ends the call there if it is zero.  Waiting, not polling: the ticks a call runs are a function of
+ * its inputs.  With D the tick of the call on which its last robot parks (-1: all were parked before it):
+ *     ticks_run = min(ticks, (max(1, ceil((D + 1) / P)) + 1) P);   ticks where no such tick exists, or with P == 0.
+ * An unlogged and a logged call exit alike; a logged one drains the samples of the half it stopped in and leaves the rows of log_host
+ * beyond the ticks run unwritten; u_host / flags_any_host are those of the last tick run.  Without episodes, or with poll_every == 0,
+ * a rollout enqueues exactly what it enqueued before. */
+#define IRLOSC_EPISODE_FINISHED 1
+#define IRLOSC_EPISODE_TIMEOUT  2
+#define IRLOSC_MAX_EPISODE_RECORDS 16
+#define IRLOSC_MAX_EPISODE_STARTS  4096       /* start states and pose variants, each */
+typedef struct irlosc_episodes {
+    int32_t max_ticks;          /* >= 0: 0 = no timeout */
+    int32_t end_on_finish;      /* 0 / 1 */
+    int32_t max_episodes;       /* >= 0: 0 = no limit; else a robot parks when it has ended this many */
+    int32_t n_starts;           /* S in [1, IRLOSC_MAX_EPISODE_STARTS] */
+    int32_t starts_per_robot;   /* 0: one set of S start states for the fleet, 1: a set per robot */
+    int32_t n_variants;         /* V in [0, IRLOSC_MAX_EPISODE_STARTS]: pose variants of the slot's action list (0: its table stays) */
+    int32_t records;            /* ring length in [1, IRLOSC_MAX_EPISODE_RECORDS] */
+    int32_t poll_every;         /* P >= 0: 0 = never exit early */
+    int32_t reserved;           /* 0 */
+} irlosc_episodes;
+/* Gives slot `slot`'s B robots their episodes: qpos0, qvel0 [starts_per_robot ? B : 1][S][n] double, poses [V][B][A][7] double (A: the
+ * list's n_actions; rows of GRIP actions are not read; NULL with V == 0).  Every argument is checked before anything is touched
+ * (IRLOSC_ERR_ARG: a field outside its range above, reserved != 0, B < 1, qpos0 / qvel0 NULL or poses NULL with V > 0, a start state or
+ * the pose of a WP that is not finite).  IRLOSC_ERR_STATE, with the reason, and the episodes in force stay: no model; targets, or the
+ * slot's program, walls or joint rows covering fewer than B robots; a context whose n is not the rollout's; a teleoperation stream or
+ * pushes on the slot (and those two setters are refused on a slot with episodes); V > 0 without an action list, or with one whose pose
+ * table is shared by the fleet (nb == 1 for more than one robot).  On success: count 0, age 0, start_tick -1, tick base 0, the ring
+ * zero, the snapshot of the slot's targets taken, start state 0 written into the coordinates of the B robots (as irlosc_set_waypoints
+ * writes waypoint 0 into the targets: the slot then has coordinates for B robots) and variant 0 into the list's pose table.  The
+ * program's own state is NOT reset: set the program, then its episodes.  desc == NULL ends the episodes; what else ends them: "one
+ * writer of the targets" above.  Buffers are allocated by the first use; IRLOSC_ERR_HIP leaves the slot without episodes.  Synchronous. */
+IRLOSC_API int irlosc_set_episodes(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_episodes* desc, const double* qpos0,
+                                   const double* qvel0, const double* poses);
+/* count, age, start_tick: int32 [B]; running: one int32, the robots of the first B that are not parked; records [B][records][4] int32
+ * (start_tick, length, outcome, start index | variant index << 16), entry e of a robot being its episode e' = the largest e' < count
+ * with e' mod records == e (entries >= count: zero); ticks_run: one int32, the ticks the slot's last rollout call ran.  Any may be NULL.
+ * IRLOSC_ERR_STATE on a slot without episodes, or with episodes for fewer than B robots -- but B == 0 answers ticks_run on any slot.
+ * Synchronous. */
+IRLOSC_API int irlosc_download_episode_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* count, int32_t* age, int32_t* start_tick,
+                                             int32_t* running, int32_t* records, int32_t* ticks_run);
 
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard

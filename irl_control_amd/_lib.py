@@ -39,8 +39,10 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state",
            "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state", "irlosc_set_joints",
            "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets",
-           "irlosc_log_layout", "irlosc_rollout_from_q_logged"]
+           "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
+EPISODE_FINISHED, EPISODE_TIMEOUT = 1, 2
+MAX_EPISODE_RECORDS, MAX_EPISODE_STARTS = 16, 4096
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
 ROUTE_NONE, ROUTE_GENERIC, ROUTE_ROW16, ROUTE_ROW16_TREE, ROUTE_LANE = 0, 1, 2, 3, 4
@@ -125,6 +127,13 @@ class Log(C.Structure):
     """struct irlosc_log (include/irlosc.h): the episode log of irlosc_rollout_from_q_logged."""
     _fields_ = [("channels", C.c_uint32), ("every", C.c_int32), ("n_robots", C.c_int32), ("reserved", C.c_int32),
                 ("buffer_bytes", C.c_uint64)]
+
+
+class Episodes(C.Structure):
+    """struct irlosc_episodes (include/irlosc.h): the episodes of irlosc_set_episodes."""
+    _fields_ = [("max_ticks", C.c_int32), ("end_on_finish", C.c_int32), ("max_episodes", C.c_int32), ("n_starts", C.c_int32),
+                ("starts_per_robot", C.c_int32), ("n_variants", C.c_int32), ("records", C.c_int32), ("poll_every", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class Cfg(C.Structure):
@@ -214,6 +223,8 @@ def load():
     lib.irlosc_download_wall_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.irlosc_set_joints.argtypes = [vp, i32, i32, C.POINTER(JointRows), vp]
     lib.irlosc_download_joint_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.irlosc_set_episodes.argtypes = [vp, i32, i32, C.POINTER(Episodes), vp, vp, vp]
+    lib.irlosc_download_episode_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

@@ -33,6 +33,7 @@ class BatchedOSC:
         self._h = h
         self._B = [0] * self.n_slots
         self._joint_rows = [0] * self.n_slots      # rows of each slot's set_joints (the width of joint_state's arrays)
+        self._episode_records = [1] * self.n_slots      # ring length of each slot's set_episodes (the width of episode_state's records)
         if kernel == _lib.KERNEL_AUTO and self.max_batch >= 1024 and self.kernel_class == _lib.CLASS_GENERIC:
             import warnings
             warnings.warn(f"layout (n={layout.n}, k={layout.k}, ndev={layout.ndev}) has no throughput kernel: "
@@ -340,8 +341,17 @@ class BatchedOSC:
         fl = np.empty(B, dtype=np.uint32)
         tr = np.empty((-(-ticks // trace_every), B, L.ndev, 7), dtype=np.float64) if trace_every > 0 and ticks > 0 else None
         self._chk(self.lib.irlosc_rollout_from_q(self._h, slot, B, ticks, trace_every, _lib.ptr(tr), _lib.ptr(u), _lib.ptr(fl)))
+        run = self._ticks_run(slot)
+        if tr is not None and run < ticks:
+            tr = tr[:-(-run // trace_every)]
         qpos, qvel = self.download_q(slot)
-        return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=tr)
+        return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=tr, ticks_run=run)
+
+    def _ticks_run(self, slot: int) -> int:
+        """The ticks the slot's last rollout call ran: fewer than asked where its episodes exited early (set_episodes, poll_every)."""
+        run = C.c_int32(0)
+        self._chk(self.lib.irlosc_download_episode_state(self._h, slot, 0, None, None, None, None, None, C.byref(run)))
+        return int(run.value)
 
     def rollout_logged(self, ticks: int, channels, every: int = 1, robots=None, slot: int = 0, buffer_bytes: int = 0):
         """`rollout` with an episode log (irlosc_rollout_from_q_logged): on ticks 0, every, 2 every, ... of this call the `channels`
@@ -370,11 +380,60 @@ class BatchedOSC:
             buf = np.empty((S, words), dtype=np.float64)
         self._chk(self.lib.irlosc_rollout_from_q_logged(self._h, slot, B, ticks, C.byref(lg) if lg is not None else None, _lib.ptr(idx),
                                                         _lib.ptr(buf), _lib.ptr(u), _lib.ptr(fl)))
+        run = self._ticks_run(slot)
         if buf is not None:
-            log = rollout_log.split(buf, L.n, L.ndev, m, R, dtype=self.dtype) if B else {}
-            log_ticks = np.arange(0, ticks, every, dtype=np.int64)
+            log_ticks = np.arange(0, min(ticks, run) if B else ticks, every, dtype=np.int64)      # (an early exit: the rows of the ticks run)
+            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype) if B else {}
         qpos, qvel = self.download_q(slot)
-        return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=None, log=log, log_ticks=log_ticks)
+        return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=None, log=log, log_ticks=log_ticks, ticks_run=run)
+
+    # -- episodes of the rollout (irlosc_set_episodes / irlosc_download_episode_state) ------------------------------------------------
+    def set_episodes(self, qpos0, qvel0=None, max_ticks: int = 0, end_on_finish: bool = True, max_episodes: int = 0, poses=None,
+                     records: int = 4, poll_every: int = 0, slot: int = 0):
+        """Episodes for the slot's robots, ended and restarted on the GPU by `rollout` / `rollout_logged`: a robot whose list or
+        non-looping paths are through (`end_on_finish`) or that has run `max_ticks` ticks (0: no limit) gets its record written and starts
+        over -- coordinates from its next start state, targets from the snapshot taken here, the program's, walls' and joint rows' state
+        as their setters leave it -- while its neighbours go on; after `max_episodes` (0: no limit) it parks.  `qpos0`, `qvel0`:
+        [S, n] (start states shared by the fleet) or [B, S, n] (per robot; qvel0 None: at rest); episode e starts from state e mod S.
+        `poses`: [V, B, A, 7] pose variants of the slot's action list (episode e runs variant e mod V; needs a per-robot pose table), or
+        None.  `records`: how many ended episodes per robot episode_state keeps (1 .. 16).  `poll_every` = P > 0: the call ends early,
+        at a multiple of P ticks, once every robot is parked (ticks_run in the result; episodes.ticks_run is the formula).  After
+        set_model, set_targets and the program; writes start state 0 into the slot's coordinates.  qpos0=None (or clear_episodes) ends
+        them.  Refused next to a teleoperation stream or pushes; what else ends them: "one writer of the targets" in include/irlosc.h."""
+        B = self._B[slot]
+        if qpos0 is None:
+            self._chk(self.lib.irlosc_set_episodes(self._h, slot, B, None, None, None, None))
+            return
+        n = self.layout.n
+        q0 = np.ascontiguousarray(qpos0, dtype=np.float64)
+        if not (q0.ndim in (2, 3) and q0.shape[-1] == n and q0.shape[-2] >= 1 and (q0.ndim == 2 or q0.shape[0] == B)):
+            raise ValueError(f"qpos0: expected shape (S, {n}) or ({B}, S, {n}) with S >= 1, got {q0.shape}")
+        v0 = np.zeros_like(q0) if qvel0 is None else np.ascontiguousarray(qvel0, dtype=np.float64)
+        if v0.shape != q0.shape:
+            raise ValueError(f"qvel0: expected shape {q0.shape}, got {v0.shape}")
+        ps = None if poses is None else np.ascontiguousarray(poses, dtype=np.float64)
+        if ps is not None and not (ps.ndim == 4 and ps.shape[0] >= 1 and ps.shape[1] == B and ps.shape[3] == 7):
+            raise ValueError(f"poses: expected shape (V, {B}, A, 7) with V >= 1, got {ps.shape}")
+        desc = _lib.Episodes(int(max_ticks), int(bool(end_on_finish)), int(max_episodes), q0.shape[-2], int(q0.ndim == 3),
+                             0 if ps is None else ps.shape[0], int(records), int(poll_every), 0)
+        self._chk(self.lib.irlosc_set_episodes(self._h, slot, B, C.byref(desc), _lib.ptr(q0), _lib.ptr(v0), _lib.ptr(ps)))
+        self._episode_records[slot] = int(records)
+
+    def clear_episodes(self, slot: int = 0):
+        """Ends the slot's episodes (irlosc_set_episodes with desc == NULL); everything else is left alone."""
+        self.set_episodes(None, slot=slot)
+
+    def episode_state(self, slot: int = 0):
+        """-> dict(count, age, start_tick: [B]; running: robots not parked; records [B, R, 4] int32: start_tick, length, outcome
+        (_lib.EPISODE_FINISHED / _TIMEOUT), start index | variant index << 16 of the robot's last R ended episodes, episode e at entry
+        e mod R; ticks_run: the ticks the slot's last rollout call ran).  (irlosc_download_episode_state)"""
+        B, R = self._B[slot], self._episode_records[slot]
+        out = dict(count=np.empty(B, np.int32), age=np.empty(B, np.int32), start_tick=np.empty(B, np.int32))
+        rec = np.empty((B, R, 4), dtype=np.int32)
+        running, run = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.irlosc_download_episode_state(self._h, slot, B, _lib.ptr(out["count"]), _lib.ptr(out["age"]), _lib.ptr(out["start_tick"]),
+                                                         C.byref(running), _lib.ptr(rec), C.byref(run)))
+        return dict(out, running=int(running.value), records=rec, ticks_run=int(run.value))
 
     def download_q(self, slot: int = 0):
         """-> (qpos, qvel) [B, n] float64 of the slot as they sit in HBM: uploaded, or advanced by `rollout` (irlosc_download_q)."""

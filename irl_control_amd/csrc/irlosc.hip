@@ -32,6 +32,7 @@
 #include "osc_wall.hpp"
 #include "osc_joint.hpp"
 #include "osc_log.hpp"
+#include "osc_episode.hpp"
 #include "launchers.hpp"
 #include "dev_mem.hpp"
 
@@ -150,6 +151,33 @@ struct Joints : PlantForce {
     void set(int B, const irlosc_joint_rows& desc) { in_force(B); d = desc; }
 };
 
+// The episodes (irlosc_set_episodes, osc_episode.hpp): per robot the judgement whether its running episode has ended, its record and its
+// reset on the device, and per wave the robots still running for the early exit.  They write no targets but a reset robot's snapshot row,
+// so they are no Program: they live next to one.  Written by laid_out(), set(), end() and ticked(), and by nothing else.
+struct Episodes {
+    irlosc_episodes d{};       // the description in force
+    int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+    int starts_per_robot = 0, list_per_robot = 0;      // the layouts of `starts` and of the list's pose table (a lone robot's: the shared one)
+    size_t vstride = 0;        // doubles between two variants' tables
+    DevBuf<int32_t> st_i;      // per-robot state, allocated by the first use for max_batch robots: count, age, start_tick, the ring
+    DevBuf<int32_t> running;   // [walk waves of max_batch]
+    DevBuf<void> snap;         // the targets' snapshot [max_batch][ndev][7], record type
+    DevBuf<double> starts, variants;      // the start states and the pose variants (walk_table), grown on demand
+    // THE LAYOUT of the state: rows of Bm = max_batch words; the ring [IRLOSC_MAX_EPISODE_RECORDS][4][Bm] behind them
+    int32_t* count(size_t) const { return st_i; }  int32_t* age(size_t Bm) const { return st_i + Bm; }  int32_t* start_tick(size_t Bm) const { return st_i + 2 * Bm; }
+    int32_t* ring(size_t Bm) const { return st_i + 3 * Bm; }
+    static size_t i_words(size_t Bm) { return (3 + 4 * (size_t)IRLOSC_MAX_EPISODE_RECORDS) * Bm; }
+    // Episodes of B robots are in force: tables, snapshot and reset state on the device.  (They belong to the program in force with them:
+    // every transition that ends or replaces it ends them.)
+    void set(int B, const irlosc_episodes& desc) { robots = B; tick = 0; d = desc; }
+    // The tables of the episodes to come are laid out like this (ahead of the init launch, which reads them; none are in force meanwhile)
+    void laid_out(int starts_pr, int list_pr, size_t vs) { starts_per_robot = starts_pr; list_per_robot = list_pr; vstride = vs; }
+    // They end: their setter cleared them, the model changed, the targets or the program they were set on changed, or their buffers failed.
+    void end() { robots = 0; tick = 0; }
+    // A tick of a rollout ran their kernel.
+    void ticked() { if (robots) ++tick; }
+};
+
 // One slot of a context: the resident inputs of a step, grouped by what they describe.  Records and targets come with the context
 // (create_impl); the other buffers are allocated by their first use -- qpos / qvel by the first irlosc_set_model, qt by the first use while
 // the fused path is on, sens by the slot's first feed, blk / blk_dq by its first pack.  Counts: 0 = nothing yet, -1 = an
@@ -183,6 +211,8 @@ struct Slot {
     Pushes push;               // what pushes the plant inside a rollout
     Walls walls;               // what the EE bodies run into inside a rollout
     Joints joints;             // what acts on single hinges inside a rollout: stops, couplings, drives
+    Episodes episodes;         // what ends and restarts single robots inside a rollout
+    int ticks_run = 0;         // ticks the last rollout call on the slot ran (fewer than asked: an early exit of its episodes)
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -205,6 +235,8 @@ struct Slot {
     // The plant kernel of a rollout advanced the coordinates of B robots on the device: row-major and walk layout alike, so they stay the
     // slot's coordinates (targets and feed are not touched; the records went with the fused step of the tick: voided()).
     void advanced(int B) { coords = B; }
+    // irlosc_set_episodes wrote start state 0 of B robots into the coordinates on the device, both layouts: they are the slot's coordinates.
+    void restarted(int B) { coords = B; }
     // pack_slot built the block of B robots from records it found eligible (lane_eligible: the tree verdict, so records > 0).
     void block_packed(int B) { packed = B; }
 };
@@ -345,6 +377,9 @@ struct irlosc_ctx {
     DevBuf<int32_t> dlog_robots;
     PinnedBuf log_stage[2];
     Event log_full[2], log_drained[2];
+    // the early exit of a rollout with episodes: two pinned copies of the running array in turn, each behind its event on the rollout's stream
+    PinnedBuf run_stage;
+    Event run_copied[2];
     DevBuf<int32_t> dsym;     // symmetry probe of the throughput paths: {count, first instance}
     // Tree-structured factorisation on dense records (row16 kernel), for slots whose records carry the tree's zeros (Slot::tree)
     int tree_enabled = 1;              // IRLOSC_TREE=0 turns the form off (A/B measurements)
@@ -594,7 +629,10 @@ extern "C" int irlosc_set_gains(irlosc_ctx* c, const double* gains, const double
     HIPCHK(c, hipMemcpyAsync(c->dnullkv, b.data(), b.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->gains_nb = nb;
-    for (Slot& s : c->slot) s.prog.end(Program::LIST);      // their gain copies were made from the gains this call replaced
+    for (Slot& s : c->slot) {      // their gain copies were made from the gains this call replaced (and episodes go with the list they reset)
+        if (s.prog.kind == Program::LIST) s.episodes.end();
+        s.prog.end(Program::LIST);
+    }
     return IRLOSC_OK;
 }
 
@@ -901,9 +939,10 @@ extern "C" int irlosc_set_targets(irlosc_ctx* c, int32_t slot, int32_t B, const 
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (B == 0) { s.targets = -1; s.prog.end(); return IRLOSC_OK; }
+    if (B == 0) { s.targets = -1; s.prog.end(); s.episodes.end(); return IRLOSC_OK; }
     if (!tgt_pose) return fail(c, IRLOSC_ERR_ARG, "tgt_pose is NULL");
     s.prog.end();      // the targets are the caller's from here on: one entry point writes them at a time
+    s.episodes.end();  // (their snapshot of the targets is stale)
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t b = (size_t)B, nd = (size_t)c->cfg.ndev, e = c->esz;
     HIPCHK(c, hipMemcpyAsync(s.tgt, tgt_pose, b * nd * 7 * e, hipMemcpyHostToDevice, c->stream));
@@ -1581,7 +1620,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); s.episodes.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1908,6 +1947,47 @@ static LogArgs log_args(const irlosc_ctx* c, const Slot& s, const irlosc_ctx::Ba
     return a;
 }
 
+// The arguments of the slot's episode kernel over B robots: a tick (the program, walls and rows in force on it travel as uniform arguments)
+// or, with init, the launch of irlosc_set_episodes for description d, which is not in force yet
+static EpisodeArgs episode_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_episodes& d, bool init) {
+    const Episodes& e = s.episodes;
+    const Program& p = s.prog;
+    const size_t Bm = (size_t)c->cfg.max_batch, plane = (size_t)c->cfg.ndev * Bm;
+    EpisodeArgs a;
+    memset(&a, 0, sizeof a);
+    a.count = e.count(Bm); a.age = e.age(Bm); a.start_tick = e.start_tick(Bm); a.ring = e.ring(Bm); a.running = e.running;
+    a.qt = s.qt; a.qpos = s.qpos; a.qvel = s.qvel; a.starts = e.starts; a.tgt = s.tgt; a.snap = e.snap;
+    a.kind = p.kind == Program::LIST ? EP_LIST : p.kind == Program::PATHS ? EP_PATHS : EP_NONE;
+    if (a.kind == EP_LIST) {
+        a.action = p.action(Bm); a.entered = p.entered(Bm); a.grip_left = p.grip_left(Bm); a.finished_tick = p.finished_tick(Bm);
+        a.err = p.err(Bm); a.max_vel0 = p.max_vel0(Bm); a.gripper_force = p.gripper_force(Bm); a.start_xyz = p.start_xyz(Bm);
+        a.al_table = p.al_table; a.variants = e.variants; a.al_gains = p.al_gains; a.gains = c->dgains;
+        a.A = p.al.n_actions; a.active = p.al.active_dev; a.gains_per_robot = c->gains_nb > 1;
+        a.V = d.n_variants; a.vstride = (int64_t)e.vstride; a.list_per_robot = e.list_per_robot;
+    }
+    if (a.kind == EP_PATHS) {
+        a.wp_index = p.index(plane); a.wp_arrivals = (uint32_t*)p.arrivals(plane); a.wp_last_tick = p.last_tick(plane); a.wp_table = p.wp_table;
+        for (int k = 0; k < c->cfg.ndev; ++k) {
+            a.wp_count[k] = p.wp.count[k]; a.wp_loop[k] = p.wp.loop[k];
+            a.wmax = std::max(a.wmax, p.wp.count[k]);
+        }
+        a.wp_per_robot = p.wp.nb > 1;
+    }
+    if (!init && s.walls.robots) {
+        a.walls = 1;
+        a.wall_force = s.walls.force(plane); a.wall_depth = s.walls.max_depth(plane);
+        a.wall_contact = s.walls.contact_ticks(plane); a.wall_first = s.walls.first_tick(plane);
+    }
+    if (!init && s.joints.robots) {
+        a.joints = 1; a.R = s.joints.d.n_rows;
+        a.jt_tau = s.joints.tau(Bm); a.jt_violation = s.joints.max_violation(Bm); a.jt_ctrl = s.joints.ctrl(Bm, a.R); a.jt_active = s.joints.active_ticks(Bm);
+    }
+    a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.S = d.n_starts; a.starts_per_robot = e.starts_per_robot;
+    a.max_ticks = d.max_ticks; a.end_on_finish = d.end_on_finish; a.max_episodes = d.max_episodes; a.records = d.records;
+    a.tick = e.tick; a.init = init ? 1 : 0;
+    return a;
+}
+
 // What the slot has of one part (`robots` of `what`; 0: none) covers B robots.  With `setter` (a download) a slot that has none is refused,
 // by the name of the entry point that sets it; without (a rollout) it passes.
 static int check_covers(irlosc_ctx* c, int slot, int B, int robots, const char* what, const char* covers, const char* setter) {
@@ -1972,10 +2052,10 @@ static int download_state(irlosc_ctx* c, int B, const double* sd, size_t nd, std
 
 // What a tick of a rollout runs next to its fused step, decided once per tick from the slot (the default: no tick, nothing): the program that writes its
 // targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); rows
-// it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on)
-struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; };
+// it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on); episodes it has
+struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; };
 static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
-    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading()};
+    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading(), s0.episodes.robots != 0};
     for (int p = 0; tp.push_sense && p < IRLOSC_MAX_PUSHES; ++p)
         if (((tp.push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) tp.push_sense &= ~(1u << p);
     if (s0.feed > 0 && s0.walls.tick > 0) tp.wall_sense = tp.wall_apply;
@@ -1995,7 +2075,9 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
 //                   coordinates and overwrites the block's M entries (the EE entries it leaves alone; the order does not lean on that)]
 //     tick_behind:  [waypoint cycler: the targets move where an arm arrived]; [pushes APPLY] [walls APPLY] [joint rows], each into the bias
 //                   entries of the block, which only the plant reads from here on; [log BACK (a logged tick with WALL_FORCE or JOINT_TAU):
-//                   the force / tau planes the two launches ahead of it just wrote]; the plant: every robot has its u by then
+//                   the force / tau planes the two launches ahead of it just wrote]; the plant: every robot has its u by then;
+//                   [episodes: LAST, because the plant wrote the coordinates that a reset replaces -- and the cycler, the action kernel,
+//                   the walls and the rows have judged and recorded the tick whose state a reset wipes]
 // The log launches only read, and write nothing but their sample of the ring.
 // What rests on this order alone: "pushes, then walls, then joint rows" on one bias entry of one tick.
 template <typename T>
@@ -2014,13 +2096,14 @@ static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp,
     if (tp.joints) HIPCHK(c, (hipError_t)launch_joints(joint_args(c, s0, B, bk.xside[0]), st));
     if (pl.log && (pl.log->channels & LOG_BACK)) HIPCHK(c, (hipError_t)launch_log<T>(log_args(c, s0, bk, *pl.log, LOG_BACK, nullptr), st));
     HIPCHK(c, (hipError_t)launch_plant<T>(plant_args(c, s0, B, bk, pl.trace), st));
+    if (tp.episodes) HIPCHK(c, (hipError_t)launch_episodes<T>(episode_args(c, s0, B, s0.episodes.d, false), st));
     return IRLOSC_OK;
 }
 // The whole tick is enqueued: the slot's coordinates are the plant's, and what ran is a tick older (a slot without a program ticks none).
 static void tick_done(Slot& s0, int B, const TickPlan& tp) {
     s0.advanced(B);
     if (tp.prog != Program::NONE) s0.prog.ticked();
-    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked();      // (each ticks only where it is in force)
+    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); s0.episodes.ticked();      // (each ticks only where it is in force)
 }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
@@ -2405,7 +2488,21 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     HIPCHK(c, hipMemsetAsync(c->dflags_any, 0, (size_t)B * sizeof(uint32_t), c->stream));
     int filled = 0, sent = 0;      // samples written / copied to the host
     int logged_n = 0;              // samples of the log written
-    for (int t = 0; t < ticks; ++t) {
+    // The early exit of a slot with episodes (include/irlosc.h: its formula): after the ticks P - 1, 2 P - 1, ... the waves' running counts
+    // go to one of two pinned blocks behind an event; before tick m P (m >= 2) the host waits for the copy made after tick (m - 1) P - 1
+    // and stops there if no robot of the call is running.  Waiting makes the ticks run a function of the inputs.  P == 0: none of it.
+    Slot& s0 = c->slot[slot];
+    const int P = s0.episodes.robots ? s0.episodes.d.poll_every : 0, waves = (B + 63) / 64;
+    int32_t* const run_host = (int32_t*)(unsigned char*)c->run_stage;
+    int t = 0;
+    for (; t < ticks; ++t) {
+        if (P && t % P == 0 && t >= 2 * P) {
+            const int h = (t / P - 1) % 2;
+            HIPCHK(c, hipEventSynchronize(c->run_copied[h]));
+            int running = 0;
+            for (int w = 0; w < waves; ++w) running += run_host[(size_t)h * waves + w];
+            if (!running) break;
+        }
         const bool traced = nsamples && t % every == 0;
         const bool logged = lr && t % lr->every == 0;
         const int lh = logged ? (logged_n / lr->hcap) % 2 : 0, lpos = logged ? logged_n % lr->hcap : 0;      // the log's half and place in it
@@ -2427,6 +2524,21 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
                                      hipMemcpyDeviceToHost, c->stream));
             sent = filled;
         }
+        if (P && (t + 1) % P == 0 && t + 1 + P < ticks) {      // (a copy nobody would wait for is not made)
+            const int h = ((t + 1) / P) % 2;
+            HIPCHK(c, hipMemcpyAsync(run_host + (size_t)h * waves, s0.episodes.running, (size_t)waves * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventRecord(c->run_copied[h], c->stream));
+        }
+    }
+    s0.ticks_run = t;
+    if (t < ticks) {      // an early exit: what the ticks run have written and not yet sent leaves now
+        if (lr && logged_n % lr->hcap != 0 && logged_n != lr->nsamples) {
+            const int n = logged_n % lr->hcap, rcl = log_drain(c, *lr, ((logged_n - 1) / lr->hcap) % 2, logged_n - n, n);
+            if (rcl) return rcl;
+        }
+        if (filled > sent)
+            HIPCHK(c, hipMemcpyAsync(trace_host + (size_t)sent * sample, c->dtrace, (size_t)(filled - sent) * sample * sizeof(double),
+                                     hipMemcpyDeviceToHost, c->stream));
     }
     return IRLOSC_OK;
 }
@@ -2523,7 +2635,9 @@ static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, i
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].push.robots, "pushes", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].walls.robots, "walls", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].episodes.robots, "episodes", "cover", nullptr);
     if (rc) return rc;
+    c->slot[slot].ticks_run = B == 0 ? ticks : 0;      // (rollout_ticks says how many were enqueued; an empty batch: all, none of them a launch)
     if (B == 0) return IRLOSC_OK;
     LogRun lr;
     if (log && (rc = log_plan(c, slot, B, ticks, log, robots, log_host, lr))) return rc;
@@ -2533,6 +2647,11 @@ static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, i
                     "is switched off; steps from joint coordinates run through dense records)");
     HIPCHK(c, c->slot[slot].qt.ensure(qt_bytes(c)));
     if (!got(c->dflags_any.ensure((size_t)c->cfg.max_batch * sizeof(uint32_t)))) return fail(c, IRLOSC_ERR_HIP, "out of device memory for flags_any");
+    if (c->slot[slot].episodes.robots && c->slot[slot].episodes.d.poll_every) {      // the early exit's pinned blocks and events
+        if (!got(c->run_stage.reserve(2 * (((size_t)c->cfg.max_batch + 63) / 64) * sizeof(int32_t))))
+            return fail(c, IRLOSC_ERR_HIP, "out of pinned host memory for the early exit");
+        for (int h = 0; h < 2; ++h) HIPCHK(c, c->run_copied[h].ensure(hipEventDisableTiming));
+    }
     // (from here on work may be in flight: every path below joins the streams before it returns)
     if (log) rc = log_buffers(c, robots, lr);
     if (!rc) rc = rollout_ticks(c, slot, B, ticks, trace_every, ee_trace_host, log ? &lr : nullptr);
@@ -2574,7 +2693,7 @@ extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, cons
             return fail(c, IRLOSC_ERR_ARG, "waypoints: count[%d]=%d out of [0,%d]", d, w->count[d], d < nd ? IRLOSC_MAX_WAYPOINTS : 0);
         wmax = std::max(wmax, (int)w->count[d]);
     }
-    if (!w || wmax == 0) { s.prog.end(Program::PATHS); return IRLOSC_OK; }
+    if (!w || wmax == 0) { if (s.prog.kind == Program::PATHS) s.episodes.end(); s.prog.end(Program::PATHS); return IRLOSC_OK; }
     if (B < 1) return fail(c, IRLOSC_ERR_ARG, "waypoints: B=%d must be >= 1", B);
     if (w->nb != 1 && w->nb != B) return fail(c, IRLOSC_ERR_ARG, "waypoints: nb=%d must be 1 or B=%d", w->nb, B);
     if (!xyz) return fail(c, IRLOSC_ERR_ARG, "waypoints: xyz is NULL");
@@ -2599,6 +2718,7 @@ extern "C" int irlosc_set_waypoints(irlosc_ctx* c, int32_t slot, int32_t B, cons
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     Program& p = s.prog;
     p.end();           // (none until the new ones are in their buffers; the paths write the targets from here on: an action list ends)
+    s.episodes.end();  // (set on the program this call replaces)
     const std::vector<double> tab = walk_table(dense.data(), w->nb, E);
     const size_t bytes = tab.size() * sizeof(double), state = p.wp_words((size_t)nd * c->cfg.max_batch) * sizeof(int32_t);
     if (!got(p.wp_table.reserve(bytes)) || !got(p.wp_i.ensure(state)))
@@ -2646,6 +2766,8 @@ extern "C" int irlosc_set_pushes(irlosc_ctx* c, int32_t slot, int32_t B, const i
         if (!std::isfinite(wrench[i]))
             return fail(c, IRLOSC_ERR_ARG, "pushes: wrench of push %zu, robot %zu is not finite", i % E / 6, i / E);
     if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (s.episodes.robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d has episodes: the pushes' windows are the slot's ticks, not a robot's (irlosc_set_episodes with NULL first)", slot);
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     Pushes& ps = s.push;
     ps.end();          // (none until the new ones are in their table)
@@ -2790,7 +2912,7 @@ extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, co
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (!d) { s.prog.end(Program::LIST); return IRLOSC_OK; }
+    if (!d) { if (s.prog.kind == Program::LIST) s.episodes.end(); s.prog.end(Program::LIST); return IRLOSC_OK; }
     const int nd = c->cfg.ndev, A = d->n_actions;
     if (A < 1 || A > IRLOSC_MAX_ACTIONS) return fail(c, IRLOSC_ERR_ARG, "action list: n_actions=%d out of [1,%d]", A, IRLOSC_MAX_ACTIONS);
     if (B < 1) return fail(c, IRLOSC_ERR_ARG, "action list: B=%d must be >= 1", B);
@@ -2848,6 +2970,7 @@ extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, co
                         "a WP sets would be ignored", d->active_dev, b);
     Program& p = s.prog;
     p.end(Program::LIST);      // (none until the new one is in its buffers; paths end when it is in force)
+    s.episodes.end();          // (set on the program this call replaces)
     std::vector<unsigned char> gs((size_t)B * rec), nks((size_t)B * e);
     for (size_t b = 0; b < (size_t)B; ++b) {
         memcpy(gs.data() + b * rec, g.data() + (nbg > 1 ? b : 0) * rec, rec);
@@ -2929,6 +3052,8 @@ extern "C" int irlosc_set_teleop_stream(irlosc_ctx* c, int32_t slot, int32_t B, 
     if (B > std::max(0, s.targets))
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, teleop stream given for %d: irlosc_set_targets first", slot,
                     std::max(0, s.targets), B);
+    if (s.episodes.robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d has episodes: a stream's reading index is the slot's tick, not a robot's (irlosc_set_episodes with NULL first)", slot);
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     Program& p = s.prog;
     p.end();           // (none until the new one is in its buffers; the stream writes the targets from here on: paths or a list end)
@@ -2973,6 +3098,108 @@ extern "C" int irlosc_download_targets(irlosc_ctx* c, int32_t slot, int32_t B, v
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     HIPCHK(c, hipMemcpyAsync(tgt_pose, s.tgt, (size_t)B * c->cfg.ndev * 7 * c->esz, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return IRLOSC_OK;
+}
+
+// ---- episodes of the rollout (osc_episode.hpp) --------------------------------------------------------------------------------------
+extern "C" int irlosc_set_episodes(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_episodes* d, const double* qpos0, const double* qvel0,
+                                   const double* poses) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.episodes.end(); return IRLOSC_OK; }
+    const int n = c->cfg.n, nd = c->cfg.ndev, S = d->n_starts, V = d->n_variants;
+    if (d->max_ticks < 0 || d->max_episodes < 0 || d->poll_every < 0)
+        return fail(c, IRLOSC_ERR_ARG, "episodes: max_ticks=%d, max_episodes=%d, poll_every=%d must be >= 0", d->max_ticks, d->max_episodes, d->poll_every);
+    if ((d->end_on_finish != 0 && d->end_on_finish != 1) || (d->starts_per_robot != 0 && d->starts_per_robot != 1))
+        return fail(c, IRLOSC_ERR_ARG, "episodes: end_on_finish=%d, starts_per_robot=%d must be 0 or 1", d->end_on_finish, d->starts_per_robot);
+    if (S < 1 || S > IRLOSC_MAX_EPISODE_STARTS) return fail(c, IRLOSC_ERR_ARG, "episodes: n_starts=%d out of [1,%d]", S, IRLOSC_MAX_EPISODE_STARTS);
+    if (V < 0 || V > IRLOSC_MAX_EPISODE_STARTS) return fail(c, IRLOSC_ERR_ARG, "episodes: n_variants=%d out of [0,%d]", V, IRLOSC_MAX_EPISODE_STARTS);
+    if (d->records < 1 || d->records > IRLOSC_MAX_EPISODE_RECORDS)
+        return fail(c, IRLOSC_ERR_ARG, "episodes: records=%d out of [1,%d]", d->records, IRLOSC_MAX_EPISODE_RECORDS);
+    if (d->reserved != 0) return fail(c, IRLOSC_ERR_ARG, "episodes: reserved must be 0");
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "episodes: B=%d must be >= 1", B);
+    if (!qpos0 || !qvel0) return fail(c, IRLOSC_ERR_ARG, "episodes: qpos0 and qvel0 are required");
+    if (V > 0 && !poses) return fail(c, IRLOSC_ERR_ARG, "episodes: poses is NULL with n_variants=%d", V);
+    const int nbs = d->starts_per_robot ? B : 1;
+    for (size_t i = 0; i < (size_t)nbs * S * n; ++i)
+        if (!std::isfinite(qpos0[i]) || !std::isfinite(qvel0[i]))
+            return fail(c, IRLOSC_ERR_ARG, "episodes: start state %zu of robot %zu is not finite", i / n % S, i / n / S);
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (n != plant_joints()) return fail(c, IRLOSC_ERR_STATE, "no episodes on this context: the rollout's kernels hold %d joints, n=%d", plant_joints(), n);
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, episodes given for %d: irlosc_set_targets first", slot,
+                    std::max(0, s.targets), B);
+    const Program& p = s.prog;
+    const struct { int robots; const char* what; } parts[] = {{p.robots, "program"}, {s.walls.robots, "walls"}, {s.joints.robots, "joint rows"}};
+    for (const auto& k : parts)
+        if (k.robots && B > k.robots)
+            return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s covers %d robots, episodes given for %d (their resets write its state)", slot, k.what, k.robots, B);
+    if (p.kind == Program::STREAM)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d has a teleoperation stream: its reading index is the slot's tick, not a robot's (no episodes next to it)", slot);
+    if (s.push.robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d has pushes: their windows are the slot's ticks, not a robot's (no episodes next to them)", slot);
+    const int A = p.kind == Program::LIST ? p.al.n_actions : 0;
+    if (V > 0 && p.kind != Program::LIST) return fail(c, IRLOSC_ERR_STATE, "episodes: pose variants need an action list on slot %d (irlosc_set_action_list)", slot);
+    if (V > 0 && p.al.nb == 1 && p.robots > 1)
+        return fail(c, IRLOSC_ERR_STATE, "episodes: pose variants need a pose table per robot, the list of slot %d shares one (nb == 1)", slot);
+    for (size_t i = 0; i < (size_t)V * B * A; ++i)
+        for (int w = 0; w < 7 && p.al.kind[i % A] == IRLOSC_ACTION_WP; ++w)
+            if (!std::isfinite(poses[i * 7 + w]))
+                return fail(c, IRLOSC_ERR_ARG, "episodes: pose of action %zu, robot %zu, variant %zu is not finite", i % A, i / A % B, i / A / B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Episodes& e = s.episodes;
+    e.end();           // (none until the new ones are in their buffers and their state is reset)
+    // the start states, a hinge's pair side by side as the walk's layout has them; the variants, each laid out as the list's own table
+    std::vector<double> dense((size_t)nbs * S * 2 * n);
+    for (size_t i = 0; i < (size_t)nbs * S; ++i)
+        for (int j = 0; j < n; ++j) { dense[(i * n + j) * 2] = qpos0[i * n + j]; dense[(i * n + j) * 2 + 1] = qvel0[i * n + j]; }
+    const int starts_pr = d->starts_per_robot && B > 1, list_pr = V > 0 && p.al.nb > 1;
+    const std::vector<double> st = walk_table(dense.data(), starts_pr ? B : 1, (size_t)S * 2 * n);
+    const size_t E = (size_t)A * 7, vstride = list_pr ? ((size_t)B + 63) / 64 * E * 64 : E;
+    std::vector<double> vt((size_t)V * vstride, 0.0);
+    for (size_t v = 0; v < (size_t)V; ++v)
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t k = 0; k < E; ++k) vt[v * vstride + (list_pr ? ((b / 64) * E + k) * 64 + b % 64 : k)] = poses[(v * B + b) * E + k];
+    const size_t Bm = (size_t)c->cfg.max_batch, i_bytes = e.i_words(Bm) * sizeof(int32_t);
+    if (!got(e.st_i.ensure(i_bytes)) || !got(e.running.ensure((Bm + 63) / 64 * sizeof(int32_t))) || !got(e.snap.ensure(Bm * nd * 7 * c->esz)) ||
+        !got(e.starts.reserve(st.size() * sizeof(double))) || !got(e.variants.reserve(vt.size() * sizeof(double))) || !got(s.qt.ensure(qt_bytes(c))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the episodes of slot %d", slot);
+    e.laid_out(starts_pr, list_pr, vstride);
+    const EpisodeArgs init = episode_args(c, s, B, *d, true);
+    rc = setter_upload(c, {{e.starts, st.data(), st.size() * sizeof(double)}, {e.variants, vt.data(), vt.size() * sizeof(double)},
+                           {e.st_i, nullptr, i_bytes, 0}},      // (the ring = 0; count, age, start_tick: the init launch)
+                       c->cfg.dtype == IRLOSC_F64 ? launch_episodes<double> : launch_episodes<float>, &init);
+    if (rc) return rc;
+    e.set(B, *d);
+    s.restarted(B);
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_episode_state(irlosc_ctx* c, int32_t slot, int32_t B, int32_t* count, int32_t* age, int32_t* start_tick,
+                                             int32_t* running, int32_t* records, int32_t* ticks_run) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Slot& s = c->slot[slot];
+    if (ticks_run) *ticks_run = s.ticks_run;
+    if (B == 0) return IRLOSC_OK;
+    rc = check_covers(c, slot, B, s.episodes.robots, "episodes", "cover", "irlosc_set_episodes");
+    if (rc) return rc;
+    const Episodes& e = s.episodes;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, R = (size_t)e.d.records;      // rows [max_batch] on the device -> [B], [B][R][4] for the caller
+    std::vector<int32_t> cnt((size_t)B);
+    rc = download_state(c, B, nullptr, 0, {}, e.st_i, e.i_words(Bm), {{cnt.data(), e.count(Bm), 1, 1, 0, 1}, {age, e.age(Bm), 1, 1, 0, 1},
+                        {start_tick, e.start_tick(Bm), 1, 1, 0, 1}, {records, e.ring(Bm), 4 * R, 4 * R, 0, 1}});
+    if (rc) return rc;
+    int live = 0;
+    for (int b = 0; b < B; ++b) {
+        if (count) count[b] = cnt[b];
+        live += !(e.d.max_episodes > 0 && cnt[b] >= e.d.max_episodes);
+    }
+    if (running) *running = live;
     return IRLOSC_OK;
 }
 

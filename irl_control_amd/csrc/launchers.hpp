@@ -128,6 +128,12 @@ struct LogArgs;
 template <typename T>
 int launch_log(const LogArgs& a, hipStream_t st);
 
+// tu_episode.hip -- the episodes of a rollout tick whose slot has some (osc_episode.hpp): behind the plant, the last launch of the tick;
+// init mode: the launch of irlosc_set_episodes; T = record type (of the targets and of the gains)
+struct EpisodeArgs;
+template <typename T>
+int launch_episodes(const EpisodeArgs& a, hipStream_t st);
+
 // tu_assemble.hip -- state assembly from raw simulator arrays (osc_assemble.hpp)
 struct RawDesc;
 template <typename T> struct RawPtrs;

@@ -1,0 +1,207 @@
+// The EPISODES of a rollout (irlosc_set_episodes): per tick and robot the judgement whether its running episode has ended -- its list or
+// its non-looping paths are through (FINISHED), or it has been run max_ticks ticks (TIMEOUT) -- and, where it has, the record of the
+// episode and the robot's RESET: everything the setters' init launches would leave, so that the robot's next tick is the first tick of a
+// fresh rollout while its neighbours go on.  It runs last in a tick, behind the plant: the plant wrote the coordinates a reset replaces,
+// the cycler (PATHS) and the action kernel (LIST) have judged the tick, walls and joint rows have written their state.
+//
+// One lane per robot, one block per walk wave (its 64 robots), like the other program kernels.  What is in force travels as uniform
+// launch arguments.  Per-robot state is SoA [field][stride]; the ring of the last `records` ended episodes is [records][4][stride].
+//   a QUIET tick (no lane of the wave ends an episode) loads count, age and, by kind, finished_tick or the listed devices' index, and
+//     stores age (and start_tick on the first tick that runs an episode); no tile store, no coordinate store;
+//   a lane whose episode ENDS writes its record and count, and unless it parks (max_episodes reached) resets: coordinates from start
+//     state count mod S (qt in the walk's layout, row-major qpos and qvel), its target row from the snapshot through the wave's target
+//     tile (osc_common.hpp: its contract; PATHS: waypoint 0 of every listed device on top), the list's state as osc_action_kernel's init
+//     branch leaves it with word 9 of the active device's gain record taken again from the context's gains and, with pose variants,
+//     the robot's lines of the list's pose table rewritten with variant count mod V, the paths' state as the cycler's init, the walls'
+//     and the joint rows' state as their setters' fills;
+//   idle lanes of a ragged last wave neither load nor store.
+// Every wave stores the number of its robots that are not parked into running[walk wave] (a plain store by lane 0): the early exit's input.
+//
+// init = 1 (irlosc_set_episodes): count 0, age 0, start_tick -1, start state 0 into the coordinates, variant 0 into the list's table, and
+// the snapshot of the targets is taken; nothing else is touched.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/irlosc.h"
+#include "osc_common.hpp"
+
+namespace irlosc {
+
+enum : int32_t { EP_NONE = 0, EP_PATHS = 1, EP_LIST = 2 };      // the program in force on the tick (Program::Kind of irlosc.hip, STREAM refused)
+
+struct EpisodeArgs {
+    int32_t* count;           // [stride] each
+    int32_t* age;
+    int32_t* start_tick;
+    int32_t* ring;            // [records][4][stride]: start_tick, length, outcome, start | variant << 16
+    int32_t* running;         // [walk waves]
+    double* qt;               // [walk wave][2 NJ][64]
+    double* qpos;             // [B][NJ] row-major
+    double* qvel;
+    const double* starts;     // starts_per_robot: [walk wave][S][2 NJ][64], else [S][2 NJ]; entry 2 j = q_j, 2 j + 1 = qd_j
+    void* tgt;                // [B][ndev][7] targets of the slot, record type
+    void* snap;               // ... their snapshot
+    // LIST (osc_action.hpp)
+    int32_t* action; int32_t* entered; int32_t* grip_left; int32_t* finished_tick;
+    double* err; double* max_vel0; double* gripper_force; double* start_xyz;
+    double* al_table;         // list_per_robot: [walk wave][A][7][64], else [A][7]
+    const double* variants;   // [V] tables of that layout, vstride doubles apart
+    void* al_gains;           // [B][ndev][IRLOSC_GAIN_WORDS] the slot's gain copy, record type
+    const void* gains;        // the context's gains, record type: [1 | max_batch][ndev][IRLOSC_GAIN_WORDS]
+    // PATHS (osc_waypoint.hpp)
+    int32_t* wp_index; uint32_t* wp_arrivals; int32_t* wp_last_tick;      // [ndev][stride]
+    const double* wp_table;   // wp_per_robot: [walk wave][ndev][wmax][3][64], else [ndev][wmax][3]
+    // walls (osc_wall.hpp): planes [ndev][stride]; joint rows (osc_joint.hpp): rows [stride]
+    double* wall_force; double* wall_depth; int32_t* wall_contact; int32_t* wall_first;
+    double* jt_tau; double* jt_violation; double* jt_ctrl; int32_t* jt_active;
+    int64_t vstride;
+    int32_t wp_count[IRLOSC_MAX_DEV];
+    uint8_t wp_loop[IRLOSC_MAX_DEV];
+    int32_t B, ndev, stride, kind, walls, joints, R, A, S, V, wmax;
+    int32_t starts_per_robot, list_per_robot, wp_per_robot, gains_per_robot, active;
+    int32_t max_ticks, end_on_finish, max_episodes, records, tick, init;
+};
+
+template <class TOPO, typename T>
+__global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
+    constexpr int NJ = TOPO::NJ;
+    __shared__ T s_t[64 * IRLOSC_MAX_DEV * 7];      // the wave's target tile
+    const int lane = threadIdx.x;
+    const int b0 = (int)blockIdx.x * 64;
+    const int nvalid = min(64, a.B - b0);           // robots of this wave
+    const bool valid = lane < nvalid;
+    const size_t so = (size_t)b0 + lane;
+    const int row = a.ndev * 7;
+    T* __restrict__ tg = (T*)a.tgt + (size_t)b0 * row;
+    T* __restrict__ sn = (T*)a.snap + (size_t)b0 * row;
+    int cnt = 0;
+    bool ends = false, reset = false;
+    if (a.init) {                                   // (uniform over the launch)
+        tgt_tile_load(s_t, tg, nvalid, row);
+        for (int t = 0; t < row; ++t) {
+            const int i = t * 64 + lane;
+            if (i < nvalid * row) sn[i] = s_t[i];
+        }
+        if (valid) { a.count[so] = 0; a.age[so] = 0; a.start_tick[so] = -1; }
+    } else if (valid) {                             // idle lanes load nothing
+        cnt = a.count[so];
+        const int age0 = a.age[so];
+        const bool parked = a.max_episodes > 0 && cnt >= a.max_episodes;
+        bool fin = false;
+        if (a.end_on_finish && a.kind == EP_LIST) fin = a.finished_tick[so] >= 0;
+        if (a.end_on_finish && a.kind == EP_PATHS) {
+            bool all = true, some = false;
+            for (int d = 0; d < a.ndev; ++d)
+                if (a.wp_count[d] > 0 && !a.wp_loop[d]) {
+                    some = true;
+                    all = all & (a.wp_index[(size_t)d * a.stride + so] == a.wp_count[d]);
+                }
+            fin = some & all;
+        }
+        const int age = parked ? age0 : age0 + 1;   // a parked robot is never judged again
+        const bool tmo = a.max_ticks > 0 && age == a.max_ticks;
+        ends = !parked && (fin | tmo);
+        const bool first = !parked && age0 == 0;    // the first tick that runs this episode
+        if (first) a.start_tick[so] = a.tick;
+        if (ends) {
+            int32_t* __restrict__ r = a.ring + ((size_t)(cnt % a.records) * 4) * a.stride + so;
+            r[0] = first ? a.tick : a.start_tick[so];
+            r[(size_t)a.stride] = age;
+            r[2 * (size_t)a.stride] = fin ? IRLOSC_EPISODE_FINISHED : IRLOSC_EPISODE_TIMEOUT;
+            r[3 * (size_t)a.stride] = (cnt % a.S) | ((a.V > 0 ? cnt % a.V : 0) << 16);
+            cnt += 1;
+            a.count[so] = cnt;
+            reset = a.max_episodes == 0 || cnt < a.max_episodes;
+            if (reset) a.start_tick[so] = -1;
+        }
+        if (!parked) a.age[so] = reset ? 0 : age;
+    }
+    // the fleet's state for the early exit
+    {
+        const bool still = valid && !(a.max_episodes > 0 && cnt >= a.max_episodes);
+        const unsigned long long m = __ballot(still);
+        if (lane == 0) a.running[blockIdx.x] = __popcll(m);
+    }
+    const bool fresh = reset || (a.init && valid);  // the lanes that get a start state (and a variant)
+    if (fresh) {
+        // ---- coordinates: start state count mod S, in the walk's layout and row-major ----
+        const int s = cnt % a.S;
+        const double* __restrict__ src = a.starts_per_robot ? a.starts + (((size_t)blockIdx.x * a.S + s) * (2 * NJ)) * 64 + lane
+                                                            : a.starts + (size_t)s * (2 * NJ);
+        const int cs = a.starts_per_robot ? 64 : 1;
+        double* __restrict__ qc = a.qt + (size_t)blockIdx.x * (2 * NJ * 64) + lane;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const double q = src[(size_t)(2 * j) * cs], qd = src[(size_t)(2 * j + 1) * cs];
+            qc[(2 * j) * 64] = q;
+            qc[(2 * j + 1) * 64] = qd;
+            a.qpos[so * NJ + j] = q;
+            a.qvel[so * NJ + j] = qd;
+        }
+        // ---- the list's pose table: this robot's lines from variant count mod V ----
+        if (a.kind == EP_LIST && a.V > 0) {
+            const double* __restrict__ vs = a.variants + (size_t)(cnt % a.V) * a.vstride;
+            const int E = a.A * 7;
+            const size_t o = a.list_per_robot ? ((size_t)blockIdx.x * E) * 64 + lane : 0;
+            const int ls = a.list_per_robot ? 64 : 1;
+            for (int e = 0; e < E; ++e) a.al_table[o + (size_t)e * ls] = vs[o + (size_t)e * ls];
+        }
+    }
+    if (reset) {                                    // THE branch around the reset body (state; the targets follow through the tile)
+        if (a.kind == EP_LIST) {                    // as osc_action_kernel's init branch
+            a.action[so] = 0; a.entered[so] = -1; a.grip_left[so] = 0; a.finished_tick[so] = -1;
+            a.err[so] = __builtin_huge_val(); a.max_vel0[so] = 0.0; a.gripper_force[so] = 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = 0.0;
+            const size_t w9 = (size_t)a.active * IRLOSC_GAIN_WORDS + 9;
+            ((T*)a.al_gains)[so * a.ndev * IRLOSC_GAIN_WORDS + w9] = ((const T*)a.gains)[(a.gains_per_robot ? so : 0) * a.ndev * IRLOSC_GAIN_WORDS + w9];
+        }
+        if (a.kind == EP_PATHS) {                   // as the cycler's init: (0, 0, -1) for listed devices
+            for (int d = 0; d < a.ndev; ++d) {
+                if (a.wp_count[d] <= 0) continue;
+                const size_t o = (size_t)d * a.stride + so;
+                a.wp_index[o] = 0; a.wp_arrivals[o] = 0u; a.wp_last_tick[o] = -1;
+            }
+        }
+        if (a.walls) {                              // as irlosc_set_walls' fills
+            const size_t plane = (size_t)a.ndev * a.stride;
+            for (int d = 0; d < a.ndev; ++d) {
+                const size_t o = (size_t)d * a.stride + so;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) a.wall_force[c * plane + o] = 0.0;
+                a.wall_depth[o] = 0.0; a.wall_contact[o] = 0; a.wall_first[o] = -1;
+            }
+        }
+        if (a.joints) {                             // as irlosc_set_joints' fills; ctrl = 0: an ACTION drive lets go
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) a.jt_tau[(size_t)j * a.stride + so] = 0.0;
+            for (int r = 0; r < a.R; ++r) {
+                const size_t o = (size_t)r * a.stride + so;
+                a.jt_violation[o] = 0.0; a.jt_ctrl[o] = 0.0; a.jt_active[o] = 0;
+            }
+        }
+    }
+    // ---- targets: the whole row back from the snapshot, through the wave's tile; only a wave in which a lane reset touches it ----
+    if (!a.init && __any(reset)) {                  // (one wave per block: uniform over the block)
+        tgt_tile_load(s_t, tg, nvalid, row);
+        if (reset) {
+            T* t = s_t + lane * row;
+            const T* __restrict__ p = sn + lane * row;
+            for (int c = 0; c < row; ++c) t[c] = p[c];
+            if (a.kind == EP_PATHS) {               // waypoint 0 of every listed device, as the cycler's init
+                for (int d = 0; d < a.ndev; ++d) {
+                    if (a.wp_count[d] <= 0) continue;
+                    const size_t e = ((size_t)d * a.wmax) * 3;
+                    const double* __restrict__ w = a.wp_per_robot ? a.wp_table + ((size_t)blockIdx.x * a.ndev * a.wmax * 3 + e) * 64 + lane : a.wp_table + e;
+                    const int ws = a.wp_per_robot ? 64 : 1;
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) t[d * 7 + c] = (T)w[c * ws];
+                }
+            }
+        }
+        tgt_tile_store(tg, s_t, nvalid, row, reset);
+    }
+}
+
+}  // namespace irlosc
