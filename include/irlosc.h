@@ -898,6 +898,10 @@ IRLOSC_API int irlosc_rollout_from_q_logged(irlosc_ctx* ctx, int32_t slot, int32
  * first_tick -1 (the SENSE launch of the next tick subtracts +0.0: the feed's wrench keeps its bits); joint rows: tau, max_violation,
  * active_ticks 0 and ctrl 0 (an ACTION drive lets go).  The next tick is the first tick of a fresh rollout for that robot.  Tick-valued
  * state (finished_tick, last_tick, first_tick) keeps counting its owner's ticks: subtract the episode's start_tick.
+ * "The first tick of a fresh rollout" is meant bit for bit WITHIN ONE FORM OF THE EIGEN PASS: which form a step runs follows from how
+ * many robots of the fleet are flagged on that tick (IRLOSC_LANE_EIG_MIN), and in a rollout with episodes that number differs from any
+ * fresh rollout's.  A fleet that stays on one side of the threshold (or a process with the form pinned) repeats its fresh rollouts'
+ * bits; one that crosses it repeats them to the two forms' agreement (1e-9 relative) only.
  * EARLY EXIT.  poll_every = P > 0: after the ticks P - 1, 2 P - 1, ... of a call the number of robots of the call that are not parked
  * goes to pinned host memory behind an event on the rollout's stream; before enqueuing tick m P (m >= 2) the host WAITS for the copy
  * made after tick (m - 1) P - 1 and ends the call there if it is zero.  Waiting, not polling: the ticks a call runs are a function of

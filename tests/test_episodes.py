@@ -14,7 +14,8 @@ import test_joints as tjn
 import test_rollout as tr
 import test_teleop_stream as tts
 import test_walls as twl
-from irl_control_amd import _lib, episodes as ep
+from irl_control_amd import _lib, episodes as ep, synth
+from test_action_list_layouts import quat_mul
 
 pytestmark = pytest.mark.gpu
 F64, F32 = np.float64, np.float32
@@ -34,33 +35,43 @@ FRONT = ("qpos", "qvel", "ee_pose", "targets", "u", "flags")
 _FLEET = {}
 
 
-def fleet(B, kinds=(WP, GRIP, WP)):
+def fleet(B, kinds=(WP, GRIP, WP), cfg="k13", active=None, passive=None, S=S, V=V):
     """-> dict(q, qd [B, S, 25]; tgt [B, ndev, 7]: the EE poses at start 0, the slot's targets; poses [V, B, A, 7]; desc: the list's
-    description with variant 0's poses).  Start 1 is start 0 with the active arm moved by up to 2e-4 rad, the other arm elsewhere and
-    small joint velocities.  A WP's pose is the active EE pose of start 0 moved along x by max_error + delta, delta accumulated over the
+    description with variant 0's poses; cfg, ia, io: the layout and the list's active and passive device (default: k13's, by name); ee:
+    the EE poses at start 0).  Start 1 is start 0 with the active arm moved by up to 2e-4 rad, the other arm elsewhere and small joint
+    velocities.  A WP's pose is the active EE pose of start 0 moved along x by max_error + delta, delta accumulated over the
     list's WPs: < 0 (within max_error at once), log-uniform in [1e-6, 1e-3] m (the arm has to come that much closer: a few ticks to a
     timeout) or FAR (no chance).  The ragged wave's robots: 128 at once everywhere, 129 FAR in variant 0.
     A list that opens with a GRIP writes no target on its first ticks: there the slot's target of the active arm lies 5 cm beside its EE,
-    so that the first OSC steps of an episode run into the velocity limit of the gain record -- word 9, which a reset must take back."""
-    key = (B, tuple(kinds))
+    so that the first OSC steps of an episode run into the velocity limit of the gain record -- word 9, which a reset must take back.
+    Every arm of every layout has k13's gains (kp 200, kv 50, k_x 1: synth.make_batch), so the distances hold off k13; an active device
+    WITHOUT xyz rows (rlbr10's block 3) gets its WP poses turned about x instead of shifted along it, by max_error + 4 delta: left to
+    theta'' = -ko theta - kv theta' the angle shrinks by 1.7e-3 rad in 24 ticks where the limited arm covers 4.2e-4 m
+    (test_action_list_layouts.turned / travel).  Start s >= 1 is start 0 perturbed as described, drawn anew per s; V = 0: no variants
+    (poses is empty and desc holds variant 0's table)."""
+    key = (B, tuple(kinds), cfg, active, passive, S, V)
     if key in _FLEET:
         return _FLEET[key]
     rng = np.random.default_rng(77)
+    ia, io = tal.device_roles(cfg, active, passive)
+    arm = tal.arm_joints(cfg, ia)
+    other = tal.LEFT if arm == tal.RIGHT else tal.RIGHT
     q0, _ = tal.start_state(B, rng)
-    q = np.stack([q0, q0], axis=1)
-    q[:, 1, tal.RIGHT] += rng.uniform(-2e-4, 2e-4, (B, 6))
-    q[:, 1, tal.LEFT] += rng.uniform(-0.1, 0.1, (B, 6))
+    q = np.stack([q0] * S, axis=1)
     qd = np.zeros_like(q)
-    qd[:, 1, tal.RIGHT] = rng.uniform(-0.01, 0.01, (B, 6))
-    ee = tal.ee_start(q[:, 0], qd[:, 0], "k13")
-    ia, io = tal.device_roles("k13")
+    for s in range(1, S):
+        q[:, s, arm] += rng.uniform(-2e-4, 2e-4, (B, 6))
+        q[:, s, other] += rng.uniform(-0.1, 0.1, (B, 6))
+        qd[:, s, arm] = rng.uniform(-0.01, 0.01, (B, 6))
+    ee = tal.ee_start(q[:, 0], qd[:, 0], cfg)
+    has_xyz = bool(np.any(synth.make_layout(cfg).ctrlr_dof[ia][:3]))
     tgt = ee.copy()
     if kinds[0] == GRIP:
         tgt[:, ia, 1] += 0.05
     A = len(kinds)
-    poses = np.zeros((V, B, A, 7))
+    poses = np.zeros((max(V, 1), B, A, 7))
     poses[..., 3] = 1.0
-    for v in range(V):
+    for v in range(max(V, 1)):
         u = rng.uniform(size=(B, A))
         delta = np.where(u < 0.25, -0.01, np.where(u < 0.85, 10.0 ** rng.uniform(-6, -3, (B, A)), FAR))
         if B > 129:
@@ -73,25 +84,53 @@ def fleet(B, kinds=(WP, GRIP, WP)):
                 continue
             acc = acc + np.maximum(delta[:, a], 0.0) if a else np.maximum(delta[:, a], 0.0)
             poses[v, :, a] = ee[:, ia]
-            poses[v, :, a, 0] += MAX_ERROR + np.where(delta[:, a] < 0, delta[:, a], acc)
-    desc = dict(n_actions=A, active_dev=ia, passive_dev=io, passive_hold_orientation=1, passive_quat=np.array([1.0, 0, 0, 0]), pose=poses[0],
+            if has_xyz:
+                poses[v, :, a, 0] += MAX_ERROR + np.where(delta[:, a] < 0, delta[:, a], acc)
+            else:
+                th = MAX_ERROR + np.where(delta[:, a] < 0, delta[:, a], np.where(acc >= FAR, acc, 4.0 * acc))
+                for b in range(B):
+                    poses[v, b, a, 3:] = quat_mul(np.array([np.cos(th[b] / 2), np.sin(th[b] / 2), 0.0, 0.0]), ee[b, ia, 3:])
+    variant0 = poses[0]
+    poses = poses[:V]
+    desc = dict(n_actions=A, active_dev=ia, passive_dev=io, passive_hold_orientation=1, passive_quat=np.array([1.0, 0, 0, 0]), pose=variant0,
                 kind=np.array(kinds, np.int32), xyz_from_start=np.zeros(A, np.int32), grip_ticks=np.full(A, 2, np.int32), kp=np.full(A, tal.KP),
                 max_error=np.full(A, MAX_ERROR), min_speed=np.full(A, tal.SPEED_CLIP[0]), max_speed=np.full(A, tal.SPEED_CLIP[1]),
                 gripper_force=np.where(np.array(kinds) == GRIP, 0.2, 0.0))
-    for a in (q, qd, tgt, poses):
+    for a in (q, qd, tgt, poses, variant0, ee):
         a.setflags(write=False)
-    _FLEET[key] = dict(q=q, qd=qd, tgt=tgt, poses=poses, desc=desc, B=B)
+    _FLEET[key] = dict(q=q, qd=qd, tgt=tgt, poses=poses, desc=desc, B=B, cfg=cfg, ia=ia, io=io, ee=ee)
     return _FLEET[key]
 
 
 def sub(fl, rows):
     """The fleet's robots `rows` as a fleet of their own."""
-    return dict(q=fl["q"][rows], qd=fl["qd"][rows], tgt=fl["tgt"][rows], poses=np.ascontiguousarray(fl["poses"][:, rows]),
+    return dict(fl, q=fl["q"][rows], qd=fl["qd"][rows], tgt=fl["tgt"][rows], ee=fl["ee"][rows], poses=np.ascontiguousarray(fl["poses"][:, rows]),
                 desc=dict(fl["desc"], pose=np.ascontiguousarray(fl["desc"]["pose"][rows])), B=len(fl["q"][rows]))
 
 
-def open_ctx(B, dtype=F64, feed=False, max_batch=BMAX, n_slots=1):
-    return tal.make_ctx(B, dtype, n_slots=n_slots, max_batch=max(max_batch, B), feed=feed)
+def open_ctx(B, dtype=F64, feed=False, max_batch=BMAX, n_slots=1, cfg="k13", gains=None):
+    return tal.make_ctx(B, dtype, n_slots=n_slots, max_batch=max(max_batch, B), feed=feed, cfg=cfg, gains=gains)
+
+
+def open_for(fl, dtype, feed=False, max_batch=BMAX, n_slots=1):
+    """The context of a fleet: its own opener where it brings one (fl["open"](capacity, dtype, feed, n_slots): another layout, with its
+    route asserted; per-robot gains), else open_ctx on its layout."""
+    cap = max(max_batch, fl["B"])
+    if "open" in fl:
+        return fl["open"](cap, dtype, feed, n_slots)
+    return open_ctx(fl["B"], dtype, feed, cap, n_slots, cfg=fl.get("cfg", "k13"))
+
+
+def start_of(fl, s):
+    """(q, qd) [B, n] of start state s: the fleet's own row, or the one the fleet shares ([S, n] start states)."""
+    q, qd = fl["q"], fl["qd"]
+    if q.ndim == 2:
+        return np.broadcast_to(q[s], (fl["B"], q.shape[1])), np.broadcast_to(qd[s], (fl["B"], q.shape[1]))
+    return q[:, s], qd[:, s]
+
+
+def set_slot_targets(osc, fl, slot=0):
+    osc.set_targets(fl["tgt"], fl.get("tgt_vel"), slot=slot)
 
 
 def arm_extras(osc, fl, extras, slot=0):
@@ -100,17 +139,26 @@ def arm_extras(osc, fl, extras, slot=0):
     if "walls" in extras:
         osc.set_sensordata(np.random.default_rng(43).normal(0.0, 5.0, size=(B, tr.NS)), slot=slot)
         # per arm the plane x = the median of the fleet's EE x at start 0 shifted to where the moving arm crosses it within a few ticks
-        osc.set_walls(twl.median_walls(fl["tgt"][:, :, :3], (0, 1), r=0.0005, normals=(twl.N_X,)), slot=slot)
+        # (a fleet off k13 names its walled devices and their normals)
+        osc.set_walls(twl.median_walls(fl.get("wall_x", fl["tgt"])[:, :, :3], fl.get("wall_devs", (0, 1)), r=0.0005,
+                                       normals=fl.get("wall_normals", (twl.N_X,))), slot=slot)
     if "joints" in extras:
         osc.set_joints(tjn.scene(osc.layout), slot=slot)
 
 
 def arm_program(osc, fl, program, variant=0, slot=0):
     if program == "list":
-        osc.set_action_list(dict(fl["desc"], pose=np.ascontiguousarray(fl["poses"][variant])), slot=slot)
+        osc.set_action_list(dict(fl["desc"], pose=np.ascontiguousarray(fl["poses"][variant])) if len(fl["poses"]) else fl["desc"], slot=slot)
     elif program == "paths":
-        ia, _ = tal.device_roles("k13")
-        osc.set_waypoints(paths_of(fl), PATH_THR, [d != ia for d in range(fl["tgt"].shape[1])], slot=slot)
+        paths, loop = paths_and_loops(fl)
+        osc.set_waypoints(paths, PATH_THR, loop, slot=slot)
+
+
+def paths_and_loops(fl):
+    """The fleet's own (paths, loop flags per device) where it brings them, else paths_of's with every device but the active one looping."""
+    if "paths" in fl:
+        return fl["paths"], list(fl["loop"])
+    return paths_of(fl), [d != fl["ia"] for d in range(fl["tgt"].shape[1])]
 
 
 def paths_of(fl):
@@ -118,7 +166,7 @@ def paths_of(fl):
     threshold + need1 away from there, the third need2 beyond the second -- need1 < 0 (it has arrived when it sets out), log-uniform
     in [1e-7, 2e-5] m (from rest the arm covers about 1.5e-5 m in 24 ticks: a few ticks to a timeout) or FAR; need2 log-uniform in
     [1e-7, 5e-6] m --; the other arm loops over two; the stand keeps its target."""
-    ia, io = tal.device_roles("k13")
+    ia, io = fl["ia"], fl["io"]
     B = fl["B"]
     rng = np.random.default_rng(78)
     u = rng.uniform(size=B)
@@ -126,10 +174,11 @@ def paths_of(fl):
     need2 = 10.0 ** rng.uniform(-7, -5.3, B)
     ex = np.array([1.0, 0.0, 0.0])
     xa = fl["tgt"][:, ia, :3]
-    xo = fl["tgt"][:, io, :3]
     out = [None] * fl["tgt"].shape[1]
     out[ia] = np.stack([xa, xa + (PATH_THR + need1)[:, None] * ex, xa + (PATH_THR + need1 + need2)[:, None] * ex], axis=1)
-    out[io] = np.stack([xo, xo + [0.0, 3e-4, 0.0]], axis=1)
+    if io >= 0:      # (a layout of one device has no other arm)
+        xo = fl["tgt"][:, io, :3]
+        out[io] = np.stack([xo, xo + [0.0, 3e-4, 0.0]], axis=1)
     return out
 
 
@@ -141,51 +190,58 @@ def finish_ticks(osc, program, fl):
     """The tick of a fresh rollout that found each robot done (-1: not yet)."""
     if program == "list":
         return osc.action_state()["finished_tick"]
-    if program == "paths":
-        ia, _ = tal.device_roles("k13")
+    if program == "paths":      # every listed device that does not loop is through: the tick of the last of their last arrivals
+        paths, loop = paths_and_loops(fl)
+        judges = [d for d, p in enumerate(paths) if p is not None and not loop[d]]
+        if not judges:
+            return np.full(fl["B"], -1)
         st = osc.waypoint_state()
-        return np.where(st["index"][:, ia] == 3, st["last_tick"][:, ia], -1)
+        done = np.all([st["index"][:, d] == np.shape(paths[d])[-2] for d in judges], axis=0)
+        return np.where(done, np.max([st["last_tick"][:, d] for d in judges], axis=0), -1)
     return np.full(fl["B"], -1)
 
 
 _FRESH = {}
 
 
-def fresh(fl, dtype, program="list", extras=(), ticks=T, max_ticks=MAX_TICKS, key=None, max_batch=BMAX):
+def fresh(fl, dtype, program="list", extras=(), ticks=T, max_ticks=MAX_TICKS, key=None, max_batch=BMAX, end_on_finish=True):
     """The reference: S x V fresh logged rollouts of `ticks` ticks WITHOUT episodes -- start s into the coordinates, the targets, the
     case's extras, the program with variant v -- every channel of the case.  -> dict(log: name -> [S, V, ticks, B, ...], lengths,
     outcomes [S, V, B]).  Computed once per key and never written to."""
-    key = (key or fl["B"], np.dtype(dtype).name, program, tuple(extras), ticks, max_ticks)
+    key = (key or fl["B"], np.dtype(dtype).name, program, tuple(extras), ticks, max_ticks, end_on_finish)
     if key in _FRESH:
         return _FRESH[key]
-    nv = V if program == "list" else 1
+    ns = fl["q"].shape[-2]
+    nv = max(1, len(fl["poses"])) if program == "list" else 1
     ch = channels_of(extras)
-    osc = open_ctx(fl["B"], dtype, feed="walls" in extras, max_batch=max_batch)
+    osc = open_for(fl, dtype, feed="walls" in extras, max_batch=max_batch)
     logs = {n: [] for n in ch}
-    fin = np.zeros((S, nv, fl["B"]), np.int64)
-    for s in range(S):
+    fin = np.zeros((ns, nv, fl["B"]), np.int64)
+    wps = [[None] * nv for _ in range(ns)]      # (PATHS: the cycler's state behind every fresh run)
+    for s in range(ns):
         row = {n: [] for n in ch}
         for v in range(nv):
-            osc.upload_q(fl["q"][:, s], fl["qd"][:, s])
-            osc.set_targets(fl["tgt"])
+            osc.upload_q(*start_of(fl, s))
+            set_slot_targets(osc, fl)
             arm_extras(osc, fl, extras)
             arm_program(osc, fl, program, v)
             r = osc.rollout_logged(ticks, ch)
             assert r["ticks_run"] == ticks
             fin[s, v] = finish_ticks(osc, program, fl)
+            wps[s][v] = osc.waypoint_state() if program == "paths" else None
             for n in ch:
                 row[n].append(r["log"][n])
         for n in ch:
             logs[n].append(np.stack(row[n]))
     osc.close()
     log = {n: np.stack(a) for n, a in logs.items()}
-    lengths, outcomes = ep.lengths_from_finish(fin, max_ticks)
+    lengths, outcomes = ep.lengths_from_finish(fin, max_ticks, end_on_finish)
     print(f"\n[fresh {key}] episode lengths of wave 0: {sorted(set(lengths[:, :, :64].ravel().tolist()))}; FINISHED {int((outcomes == ep.FINISHED).sum())}, "
           f"TIMEOUT {int((outcomes == ep.TIMEOUT).sum())} of {outcomes.size}")
     assert not np.any(log["flags"].astype(np.uint32) & tal_bad()), "a robot froze in a fresh run"
     for a in list(log.values()) + [lengths, outcomes]:
         a.setflags(write=False)
-    _FRESH[key] = dict(log=log, lengths=lengths, outcomes=outcomes, channels=ch)
+    _FRESH[key] = dict(log=log, lengths=lengths, outcomes=outcomes, channels=ch, finish=fin, wp_state=wps)
     return _FRESH[key]
 
 
@@ -201,21 +257,22 @@ def assert_preconditions(ref, sched, B):
     outs = {r[2] for rec in sched["records"] for r in rec}
     assert outs == {ep.FINISHED, ep.TIMEOUT}, outs
     assert sched["count"].max() >= 3
+    assert sched["count"].max() > RECORDS, "no robot's ring of RECORDS entries wrapped"
     if B == B0:
         assert [r[:3] for r in sched["records"][128]] != [r[:3] for r in sched["records"][129]], "the last wave's two robots do not differ"
     assert ln.shape[2] == B
 
 
 def run_with_episodes(fl, dtype, program, extras, ticks=T, pieces=None, max_episodes=0, poll_every=0, max_ticks=MAX_TICKS, logged=True,
-                      end_on_finish=True, max_batch=BMAX):
+                      end_on_finish=True, max_batch=BMAX, records=RECORDS):
     """One context: extras, program (variant 0), episodes, then the rollout(s).  -> (list of the pieces' results, episode_state, osc closed)."""
-    osc = open_ctx(fl["B"], dtype, feed="walls" in extras, max_batch=max_batch)
-    osc.upload_q(fl["q"][:, 1], fl["qd"][:, 1])      # (NOT start 0: set_episodes has to write it)
-    osc.set_targets(fl["tgt"])
+    osc = open_for(fl, dtype, feed="walls" in extras, max_batch=max_batch)
+    osc.upload_q(*start_of(fl, fl["q"].shape[-2] - 1))      # (NOT start 0, where there is another: set_episodes has to write it)
+    set_slot_targets(osc, fl)
     arm_extras(osc, fl, extras)
     arm_program(osc, fl, program, 0)
     osc.set_episodes(fl["q"], fl["qd"], max_ticks=max_ticks, end_on_finish=end_on_finish, max_episodes=max_episodes,
-                     poses=fl["poses"] if program == "list" else None, records=RECORDS, poll_every=poll_every)
+                     poses=fl["poses"] if program == "list" and len(fl["poses"]) else None, records=records, poll_every=poll_every)
     outs = []
     for p in pieces or [ticks]:
         outs.append(osc.rollout_logged(p, channels_of(extras)) if logged else osc.rollout(p))
@@ -237,11 +294,11 @@ def assert_equals_stitched(log, ref, sched, ticks=slice(None), rows=slice(None))
                                  f"age {sched['age'][t, b]}); max |diff| {np.nanmax(np.abs(log[n].astype(F64) - w.astype(F64))):.3e}")
 
 
-def assert_state_is(st, sched, ticks):
+def assert_state_is(st, sched, ticks, records=RECORDS):
     assert np.array_equal(st["count"], sched["count"])
     assert np.array_equal(st["age"], sched["age_end"])
     assert np.array_equal(st["start_tick"], sched["start_tick"])
-    assert np.array_equal(st["records"], ep.ring(sched, RECORDS))
+    assert np.array_equal(st["records"], ep.ring(sched, records))
     assert st["running"] == int((sched["park_tick"] < 0).sum()) and st["ticks_run"] == ticks
 
 
