@@ -120,10 +120,13 @@ def angle_diff(a, b):
     return np.abs(np.arctan2(np.sin(d), np.cos(d)))
 
 
-def fill(osc, B, slot=0, tgt=None):
+def fill(osc, B, slot=0, tgt=None, tgt_vel=None, sens=None):
+    """The start state and the start targets (or `tgt`) of the slot; tgt_vel, sens: its target velocities and its sensor feed's reading."""
     q, qd = start_state(B)
     osc.upload_q(q, qd, slot=slot)
-    osc.set_targets(start_targets(B, osc.layout.ndev) if tgt is None else tgt, slot=slot)
+    osc.set_targets(start_targets(B, osc.layout.ndev) if tgt is None else tgt, tgt_vel, slot=slot)
+    if sens is not None:
+        osc.set_sensordata(sens, slot=slot)
 
 
 def tick_by_tick(osc, ticks, slot=0):
@@ -137,20 +140,44 @@ def tick_by_tick(osc, ticks, slot=0):
     return {k: np.array(v) for k, v in out.items()}
 
 
-def stepped(cfg, B, dtype):
-    """The run the first tests share: per-robot streams (B > 1) of T readings, T x rollout(1), with its mirror."""
+def stepped(cfg, B, dtype, rig=None, name=None, open_ctx=None, **filled):
+    """The run the first tests share: per-robot streams (B > 1) of T readings, T x rollout(1), with its mirror.  rig: the followers
+    (default: the demo's for the layout); open_ctx: what opens the context (default: make_ctx on cfg), under the cache name `name`;
+    filled: what fill() gets beyond the start state and targets."""
     def make():
-        osc = make_ctx(B, dtype, cfg=cfg)
-        fill(osc, B)
+        osc = make_ctx(B, dtype, cfg=cfg) if open_ctx is None else open_ctx()
+        fill(osc, B, **filled)
         rd = fleet_readings(B) if B > 1 else readings_of(SEED)
-        osc.set_teleop_stream(rd, ORIGIN)
+        followers = teleop.space_mouse_rig(synth.make_layout(cfg)) if rig is None else rig
+        osc.set_teleop_stream(rd, ORIGIN, rig=followers)
         first = osc.teleop_state()
         dev = tick_by_tick(osc, T)
         osc.close()
-        rig = teleop.space_mouse_rig(synth.make_layout(cfg))
-        poses, tgts = mirror(ORIGIN, rd, rig, start_targets(B, len(rig)), B)
-        return dict(dev=dev, poses=poses, tgts=tgts, first=first, readings=rd)
-    return cached(("stepped", cfg, B, np.dtype(dtype).name), make)
+        poses, tgts = mirror(ORIGIN, rd, followers, start_targets(B, len(followers)), B)
+        return dict(dev=dev, poses=poses, tgts=tgts, first=first, readings=rd, rig=followers)
+    return cached(("stepped", cfg if name is None else name, B, np.dtype(dtype).name), make)
+
+
+def assert_follows_the_mirror(run, B, dtype, label, ticks=T):
+    """The assertions of test 1 on a run of stepped()'s form -> (max angle diff, max target word diff: float64 absolute, float32 in ulp)."""
+    dev, poses, tgts = run["dev"], run["poses"], run["tgts"]
+    assert run["first"]["tick"] == 0 and same_bits(run["first"]["pose"], np.tile(ORIGIN, (B, 1)))
+    assert list(dev["tick"]) == list(range(1, ticks + 1))
+    assert same_bits(dev["pose"][:, :, :3], poses[:, :, :3])
+    da = angle_diff(dev["pose"][:, :, 3:], poses[:, :, 3:]).max()
+    assert np.abs(dev["pose"][:, :, 3:]).max() <= np.pi
+    assert dev["tgt"].dtype == dtype
+    if dtype == F64:
+        dt = np.abs(dev["tgt"] - tgts).max()
+        print(f"{label} B={B} float64: device vs mirror over {ticks} ticks: max angle diff {da:.3g}, max target word diff {dt:.3g}")
+        assert dt <= BOUND, dt
+    else:
+        want = tgts.astype(F32)
+        dt = (np.abs(dev["tgt"].astype(F64) - want.astype(F64)) / np.spacing(np.abs(want)).astype(F64)).max()
+        print(f"{label} B={B} float32: device vs mirror over {ticks} ticks: max angle diff {da:.3g}, max target word diff {dt:.3g} float32 ulp")
+        assert dt <= 1.0, dt
+    assert da <= BOUND, da
+    return da, dt
 
 
 # ---- 1. device against the mirror, tick by tick -----------------------------------------------------------------------------------
@@ -160,24 +187,7 @@ def test_device_follows_the_mirror_tick_by_tick(cfg, B, dtype):
     mirror's cast; the setter wrote no target and left pose = origin, tick = 0.
     Observed on an MI355X over the 48 ticks: angles within 2.22e-15 (B = 70, k13 and r6, both dtypes) and 1.78e-15 (B = 1); float64
     target words within 1.22e-15 (B = 70) and 1.08e-15 (B = 1); float32 target words equal to the mirror's cast (0 ulp)."""
-    run = stepped(cfg, B, dtype)
-    dev, poses, tgts = run["dev"], run["poses"], run["tgts"]
-    assert run["first"]["tick"] == 0 and same_bits(run["first"]["pose"], np.tile(ORIGIN, (B, 1)))
-    assert list(dev["tick"]) == list(range(1, T + 1))
-    assert same_bits(dev["pose"][:, :, :3], poses[:, :, :3])
-    da = angle_diff(dev["pose"][:, :, 3:], poses[:, :, 3:]).max()
-    assert np.abs(dev["pose"][:, :, 3:]).max() <= np.pi
-    assert dev["tgt"].dtype == dtype
-    if dtype == F64:
-        dt = np.abs(dev["tgt"] - tgts).max()
-        print(f"{cfg} B={B} float64: device vs mirror over {T} ticks: max angle diff {da:.3g}, max target word diff {dt:.3g}")
-        assert dt <= BOUND, dt
-    else:
-        want = tgts.astype(F32)
-        ulps = (np.abs(dev["tgt"].astype(F64) - want.astype(F64)) / np.spacing(np.abs(want)).astype(F64)).max()
-        print(f"{cfg} B={B} float32: device vs mirror over {T} ticks: max angle diff {da:.3g}, max target word diff {ulps:.3g} float32 ulp")
-        assert ulps <= 1.0, ulps
-    assert da <= BOUND, da
+    assert_follows_the_mirror(stepped(cfg, B, dtype), B, dtype, cfg)
 
 
 # ---- 2. the same tick, nothing else changed ------------------------------------------------------------------------------------
@@ -259,14 +269,14 @@ def test_a_shared_stream_equals_its_row_repeated_and_origins_per_robot_give_pose
 
 
 # ---- 5. end and loop -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B", [70, 1])
-def test_a_stream_ends_or_loops_after_its_last_reading(B):
+def assert_ends_or_loops(osc, B, rig, refill):
+    """The body of test 5 on an open context whose slot 0 `refill` puts back to the start: no launch after the last reading while the
+    tick counts on; a looped stream reads reading 0 again; a stream of one reading, looped and played once."""
     rd = readings_of(SEED)
-    rig = teleop.space_mouse_rig(synth.make_layout("k13"))
-    two, tgts2 = mirror(ORIGIN, np.concatenate([rd, rd[:3]]), rig, start_targets(B, 3), B)      # the looped stream, three ticks into its second pass
-    osc = make_ctx(B)
-    fill(osc, B)
-    osc.set_teleop_stream(rd, ORIGIN, loop=False)
+    ndev = len(rig)
+    two, tgts2 = mirror(ORIGIN, np.concatenate([rd, rd[:3]]), rig, start_targets(B, ndev), B)      # the looped stream, three ticks into its second pass
+    refill()
+    osc.set_teleop_stream(rd, ORIGIN, rig=rig, loop=False)
     osc.rollout(T)
     end_pose, end_tgt = osc.teleop_state()["pose"], osc.download_targets()
     for extra in range(1, 7):                            # ticks T .. T + 5: no launch, nothing moves, the tick counts
@@ -274,25 +284,31 @@ def test_a_stream_ends_or_loops_after_its_last_reading(B):
         st = osc.teleop_state()
         assert st["tick"] == T + extra and same_bits(st["pose"], end_pose) and same_bits(osc.download_targets(), end_tgt)
     assert same_bits(end_pose[:, :3], two[T - 1][:, :3])
-    fill(osc, B)
-    osc.set_teleop_stream(rd, ORIGIN, loop=True)
+    refill()
+    osc.set_teleop_stream(rd, ORIGIN, rig=rig, loop=True)
     osc.rollout(T + 3)                                   # tick T reads reading 0 again
     st, tg = osc.teleop_state(), osc.download_targets()
     assert st["tick"] == T + 3
     assert same_bits(st["pose"][:, :3], two[T + 2][:, :3]) and angle_diff(st["pose"][:, 3:], two[T + 2][:, 3:]).max() <= BOUND
     assert np.abs(tg - tgts2[T + 2]).max() <= BOUND
     # T = 1: one reading, looped three times and played once
-    one, tg1 = mirror(ORIGIN, np.tile(rd[:1], (3, 1)), rig, start_targets(B, 3), B)
-    fill(osc, B)
-    osc.set_teleop_stream(rd[:1], ORIGIN, loop=True)
+    one, tg1 = mirror(ORIGIN, np.tile(rd[:1], (3, 1)), rig, start_targets(B, ndev), B)
+    refill()
+    osc.set_teleop_stream(rd[:1], ORIGIN, rig=rig, loop=True)
     osc.rollout(3)
     st = osc.teleop_state()
     assert st["tick"] == 3 and same_bits(st["pose"][:, :3], one[2][:, :3]) and np.abs(osc.download_targets() - tg1[2]).max() <= BOUND
-    fill(osc, B)
-    osc.set_teleop_stream(rd[:1], ORIGIN, loop=False)
+    refill()
+    osc.set_teleop_stream(rd[:1], ORIGIN, rig=rig, loop=False)
     osc.rollout(3)
     st = osc.teleop_state()
     assert st["tick"] == 3 and same_bits(st["pose"][:, :3], one[0][:, :3]) and np.abs(osc.download_targets() - tg1[0]).max() <= BOUND
+
+
+@pytest.mark.parametrize("B", [70, 1])
+def test_a_stream_ends_or_loops_after_its_last_reading(B):
+    osc = make_ctx(B)
+    assert_ends_or_loops(osc, B, teleop.space_mouse_rig(synth.make_layout("k13")), lambda: fill(osc, B))
     osc.close()
 
 
