@@ -520,7 +520,16 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *                                                                                      slot with a stream or with pushes: the reading index and
  *                                                                                      the windows are the slot's ticks, not a robot's
  *     everything else (uploads of coordinates, feeds, gains without a list, walls, joint rows, other steps)  leaves them alone
- * Only irlosc_rollout_from_q and irlosc_rollout_from_q_logged run them and advance their tick. */
+ * Only irlosc_rollout_from_q and irlosc_rollout_from_q_logged run them and advance their tick.
+ * ACTION OBJECTS (irlosc_set_objects, "action objects" below) write no targets and act on nothing: they coexist with every program,
+ * pushes, walls, joint rows and episodes, and none ends another.  A list's REFS (irlosc_set_action_refs) name the objects in force:
+ *     irlosc_set_objects with desc == NULL, irlosc_set_model (all slots)               objects end, and the list's refs with them
+ *     irlosc_set_objects that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE               nothing changes: objects and refs in force stay, whole
+ *     irlosc_set_objects that succeeds                                                 its objects replace those in force; state and tick reset; refs end
+ *     irlosc_set_objects that answers IRLOSC_ERR_HIP                                   no objects, no refs
+ *     whatever ends or replaces the slot's list                                        refs end, objects stay
+ *     everything else (uploads, targets, gains, feeds, pushes, walls, joint rows, episodes, other steps)  leaves them, their state and their tick alone
+ * Only the two rollout entry points run them and advance their tick; episodes reset a robot's objects with the rest of it. */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -844,6 +853,9 @@ IRLOSC_API int irlosc_download_joint_state(irlosc_ctx* ctx, int32_t slot, int32_
 #define IRLOSC_LOG_FLAGS      64u   /* [R][1]        the step's flag word of the tick as a double (not what the plant adds)      */
 #define IRLOSC_LOG_WALL_FORCE 128u  /* [R][ndev][3]  F_d(t) the walls applied on this tick                                       */
 #define IRLOSC_LOG_JOINT_TAU  256u  /* [R][n]        tau the joint rows applied on this tick                                     */
+#define IRLOSC_LOG_OBJECT_POSE 512u /* [R][nobj][8]  FRONT: the action objects as this tick's object kernel left them: x y z qw qx qy qz
+                                       and the holder (-1 = free, else the gripper) as a double.  Only on a slot with action objects
+                                       (irlosc_set_objects); elsewhere the bit is unknown: irlosc_log_layout_objects, below          */
 typedef struct irlosc_log {
     uint32_t channels;      /* OR of the above, not 0, no other bit */
     int32_t  every;         /* >= 1: ticks 0, every, 2 every, ... of THIS call are logged (as trace_every counts) */
@@ -857,6 +869,10 @@ typedef struct irlosc_log {
  * *sample_words = the sample's size.  IRLOSC_ERR_ARG: channels 0 or with an unknown bit, R < 1, n outside [1, IRLOSC_MAX_N], ndev
  * outside [1, IRLOSC_MAX_DEV], offset or sample_words NULL. */
 IRLOSC_API int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int32_t R, int64_t offset[9], int64_t* sample_words);
+/* The same for a slot with nobj action objects (nobj in [0, IRLOSC_MAX_OBJECTS]): ten offsets, the tenth IRLOSC_LOG_OBJECT_POSE's plane
+ * [R][nobj][8].  With nobj == 0 that bit is unknown, as it is to irlosc_log_layout, and the first nine offsets are irlosc_log_layout's. */
+IRLOSC_API int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, uint32_t channels, int32_t R, int64_t offset[10],
+                                         int64_t* sample_words);
 /* irlosc_rollout_from_q with a log in place of the EE trace: log_host[ceil(ticks / every)][sample_words] (double), one sample per logged
  * tick of the R robots of `robots` (strictly ascending, in [0, B); NULL: all B).  log == NULL is
  * irlosc_rollout_from_q(ctx, slot, B, ticks, 0, NULL, u_host, flags_any_host); robots and log_host are not read then.
@@ -867,7 +883,8 @@ IRLOSC_API int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int
  * when it needs the block again, and at the end.  Ticks keep running while a half is on the link; the rollout waits only where a half
  * would be refilled before it has left.
  * Every argument is checked before anything is enqueued, sizes in 64 bits; after a refusal the slot is exactly as it was: no tick ran.
- *   IRLOSC_ERR_ARG    what irlosc_log_layout refuses; every < 1; reserved != 0; robots == NULL with n_robots not 0 or B; robots given with
+ *   IRLOSC_ERR_ARG    what irlosc_log_layout_objects refuses for the slot's action objects (none: what irlosc_log_layout refuses, so
+ *                     IRLOSC_LOG_OBJECT_POSE on a slot without objects is an unknown bit); every < 1; reserved != 0; robots == NULL with n_robots not 0 or B; robots given with
  *                     n_robots outside [1, B], not strictly ascending or outside [0, B); log_host NULL; a buffer_bytes != 0 that
  *                     holds fewer than two samples
  *   IRLOSC_ERR_STATE  what irlosc_rollout_from_q refuses; IRLOSC_LOG_WRENCH on a slot without a sensor feed; IRLOSC_LOG_WALL_FORCE on a
@@ -912,6 +929,8 @@ IRLOSC_API int irlosc_rollout_from_q_logged(irlosc_ctx* ctx, int32_t slot, int32
  * a rollout enqueues exactly what it enqueued before. */
 #define IRLOSC_EPISODE_FINISHED 1
 #define IRLOSC_EPISODE_TIMEOUT  2
+#define IRLOSC_EPISODE_INSERTED 4             /* OR-ed into the outcome on a slot with mates ("action objects", below): every mate of the
+                                                 slot has mated_tick >= 0 on the tick the episode ends -- 5 or 6 in place of 1 or 2 */
 #define IRLOSC_MAX_EPISODE_RECORDS 16
 #define IRLOSC_MAX_EPISODE_STARTS  4096       /* start states and pose variants, each */
 typedef struct irlosc_episodes {
@@ -945,6 +964,86 @@ IRLOSC_API int irlosc_set_episodes(irlosc_ctx* ctx, int32_t slot, int32_t B, con
  * Synchronous. */
 IRLOSC_API int irlosc_download_episode_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* count, int32_t* age, int32_t* start_tick,
                                              int32_t* running, int32_t* records, int32_t* ticks_run);
+
+/* ---- action objects: kinematic bodies the gripper carries, and an insertion outcome (csrc/osc_object.hpp) --------------------------
+ * The insertion demo grips the male part, carries it to the female part and releases it there; in the reference a WP reads an object's
+ * pose from the simulator when it is entered (insertion_task.py:226-262).  OBJECTS give a slot's rollouts that much of it, and no more:
+ * an object rides rigidly on an EE once that arm's fingers have closed near it, stays where it is let go, a WP of the slot's action
+ * list can aim at its live pose, and a plug released inside its socket's tolerances is recorded.  What this is NOT: the object has no
+ * mass -- nothing acts on the plant or the F/T feed; no collision, no gravity, no slipping; a released object hangs where it was let go.
+ * One more small kernel per tick, behind the walk (and the feed's SENSE launches) and directly in front of the action kernel, so a WP
+ * entered on tick t sees the objects of tick t.  Float64 whatever the context's dtype, only + - x, comparisons and the one correctly
+ * rounded division of quat2mat (2 / |q|^2), every operation rounded on its own: irl_control_amd/objects.py::object_step repeats the bits.
+ * Per robot the device keeps, per object: pose[7] (x y z qw qx qy qz), holder (-1 = free, else the gripper), rel[7] (its pose in the
+ * holder's EE frame), grasp_tick, release_tick (the objects' ticks, -1: never); per gripper was_closed; per mate mated_tick (-1: not yet).
+ *   GRIPPER g: device dev[g] (targets order), knuckle hinge joint[g], sign[g] in {+1, -1}, q_close[g], q_open[g] with
+ *              sign q_open < sign q_close, grip_xyz[g] a point in the EE frame.  With q the knuckle coordinate at the start of the tick:
+ *              closed = sign q >= sign q_close, open = sign q <= sign q_open, a NaN is neither.
+ *   OBJECT o:  radius[o] >= 0.
+ *   MATE m:    plug[m] != socket[m], seat_xyz[m] / seat_quat[m] in the socket's frame, tol_xyz[m] > 0, min_abs_dot[m] in [0, 1].
+ * Per tick t and covered robot, T_ee = (p_ee, q_ee) the EE pose of a gripper's device, R() = quat2mat:
+ *   0. an EE pose word of a gripper's device that is not finite: objects, grippers and mates of the robot stay as they are
+ *   1. held objects, ascending o:  holder open -> holder = -1, release_tick = t, the pose stays;
+ *                                  else xyz = p_ee + R(q_ee) rel_xyz, quat = q_ee (x) rel_quat
+ *   2. free objects not released on this tick, ascending o, grippers ascending g: g closed, was_closed[g] == 0 (the rising edge: a hand
+ *      that travels closed picks nothing up), g holds nothing, |p_ee + R(q_ee) grip_xyz - p_obj|^2 <= radius^2
+ *      -> holder = g, rel_xyz = R(q_ee)^T (p_obj - p_ee), rel_quat = conj(q_ee) (x) q_obj, grasp_tick = t
+ *   3. was_closed[g] = closed(g)
+ *   4. mates, ascending m, with mated_tick < 0 and the plug free: target xyz = p_sock + R(q_sock) seat_xyz, quat = q_sock (x) seat_quat;
+ *      |p_plug - target|^2 <= tol_xyz^2 and |q_plug . q_target| >= min_abs_dot -> mated_tick = t
+ * Episodes (above) reset a robot's objects with the rest of it: free, pose = start poses count mod V, ticks -1, was_closed 0; and on a
+ * slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED.  Order of calls: program, objects, refs, then episodes.
+ * A slot without objects launches exactly the kernels it launched before. */
+#define IRLOSC_MAX_OBJECTS  4
+#define IRLOSC_MAX_GRIPPERS 2
+#define IRLOSC_MAX_MATES    2
+typedef struct irlosc_objects {
+    int32_t n_objects;                               /* in [1, IRLOSC_MAX_OBJECTS] */
+    int32_t n_grippers;                              /* in [1, IRLOSC_MAX_GRIPPERS] */
+    int32_t n_mates;                                 /* in [0, IRLOSC_MAX_MATES] */
+    int32_t n_variants;                              /* V in [1, IRLOSC_MAX_EPISODE_STARTS]: sets of start poses (episodes cycle them) */
+    int32_t dev[IRLOSC_MAX_GRIPPERS];                /* device in [0, ndev) */
+    int32_t joint[IRLOSC_MAX_GRIPPERS];              /* knuckle hinge in [0, n) */
+    int32_t sign[IRLOSC_MAX_GRIPPERS];               /* +1 / -1 */
+    int32_t plug[IRLOSC_MAX_MATES];                  /* object in [0, n_objects) */
+    int32_t socket[IRLOSC_MAX_MATES];                /* ... another one */
+    double q_close[IRLOSC_MAX_GRIPPERS];
+    double q_open[IRLOSC_MAX_GRIPPERS];
+    double grip_xyz[IRLOSC_MAX_GRIPPERS][3];
+    double radius[IRLOSC_MAX_OBJECTS];
+    double seat_xyz[IRLOSC_MAX_MATES][3];
+    double seat_quat[IRLOSC_MAX_MATES][4];
+    double tol_xyz[IRLOSC_MAX_MATES];
+    double min_abs_dot[IRLOSC_MAX_MATES];
+} irlosc_objects;
+/* Gives slot `slot`'s B robots their action objects: pose0 [V][B][n_objects][7] double.  Every argument is checked before anything is
+ * touched (IRLOSC_ERR_ARG: a count outside its range above, B < 1, a device, hinge or object index out of range, plug == socket, sign
+ * not +-1, pose0 NULL, a value that is not finite, sign q_open >= sign q_close, radius < 0, tol_xyz <= 0, min_abs_dot outside [0, 1];
+ * the objects in force stay, whole).  IRLOSC_ERR_STATE: before irlosc_set_model, or before the slot has coordinates for B robots
+ * (irlosc_upload_q).  desc == NULL clears.  On success the state is that of variant 0: every object free at its start pose, ticks -1,
+ * was_closed 0, the objects' tick base 0; the list's refs (below) end.  A rollout over more robots than the objects cover answers
+ * IRLOSC_ERR_STATE, and so does irlosc_set_episodes for more robots than they cover.  The model's change ends them.  Buffers are
+ * allocated by the first use; IRLOSC_ERR_HIP leaves the slot without objects.  Synchronous. */
+IRLOSC_API int irlosc_set_objects(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_objects* desc, const double* pose0);
+/* The objects' per-robot state of the slot's first B robots: pose[B][n_objects][7], rel[B][n_objects][7] (double), holder, grasp_tick,
+ * release_tick [B][n_objects], mated_tick[B][n_mates] (int32); any may be NULL.  IRLOSC_ERR_STATE: the slot has no objects, or they
+ * cover fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_object_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* pose, int32_t* holder, double* rel,
+                                            int32_t* grasp_tick, int32_t* release_tick, int32_t* mated_tick);
+/* The slot's action list aims at its objects.  For a WP action a with xyz_obj[a] >= 0 the xyz words of the list's pose a are an OFFSET:
+ * on entry, target xyz = the object's xyz + offset, one add per word (the reference's obj_pos + offset); xyz_from_start wins.  With
+ * quat_obj[a] >= 0 the quaternion words are the grip rotation: target quat = q_obj (x) q_grip, the Hamilton product with its terms left
+ * to right, no normalisation, no sign change (the reference reaches the same rotation through mat2euler -> set_abg: equal up to the
+ * quaternion's sign, which calc_error does not see).  Targets are read at ENTRY only: a held object does not drag a target along.
+ * Entries of GRIP actions and beyond n_actions are not read.  IRLOSC_ERR_ARG: an entry of a WP that is neither -1 nor an object index.
+ * IRLOSC_ERR_STATE: the slot has no action list, no objects, or objects that cover fewer robots than the list; the refs in force stay.
+ * refs == NULL clears.  irlosc_set_action_list and irlosc_set_objects end the refs (set them last).  Pose variants of episodes
+ * rewrite offsets and grip rotations like any other pose word.  Without refs the list's kernel computes what it computed before. */
+typedef struct irlosc_action_refs {
+    int32_t xyz_obj[IRLOSC_MAX_ACTIONS];
+    int32_t quat_obj[IRLOSC_MAX_ACTIONS];
+} irlosc_action_refs;
+IRLOSC_API int irlosc_set_action_refs(irlosc_ctx* ctx, int32_t slot, const irlosc_action_refs* refs);
 
 /* ---- multi-GPU: the final throughput reduction -----------------------------------------------
  * Instances are independent (osc.py:120-210 touches one robot), so a node runs one process per GPU on its own shard

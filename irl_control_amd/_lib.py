@@ -39,9 +39,12 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_set_waypoints", "irlosc_download_waypoint_state", "irlosc_set_action_list", "irlosc_download_action_state",
            "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state", "irlosc_set_joints",
            "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets",
-           "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state"]
+           "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state",
+           "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
-EPISODE_FINISHED, EPISODE_TIMEOUT = 1, 2
+LOG_OBJECT_POSE = 512                                    # only on a slot with action objects
+EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED = 1, 2, 4
+MAX_OBJECTS, MAX_GRIPPERS, MAX_MATES = 4, 2, 2
 MAX_EPISODE_RECORDS, MAX_EPISODE_STARTS = 16, 4096
 ABI_VERSION = 3
 CLASS_GENERIC, CLASS_ROW16, CLASS_ROW16_PADDED = 0, 1, 2
@@ -136,6 +139,21 @@ class Episodes(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class Objects(C.Structure):
+    """struct irlosc_objects (include/irlosc.h): the action objects of irlosc_set_objects."""
+    _fields_ = [("n_objects", C.c_int32), ("n_grippers", C.c_int32), ("n_mates", C.c_int32), ("n_variants", C.c_int32),
+                ("dev", C.c_int32 * MAX_GRIPPERS), ("joint", C.c_int32 * MAX_GRIPPERS), ("sign", C.c_int32 * MAX_GRIPPERS),
+                ("plug", C.c_int32 * MAX_MATES), ("socket", C.c_int32 * MAX_MATES),
+                ("q_close", C.c_double * MAX_GRIPPERS), ("q_open", C.c_double * MAX_GRIPPERS), ("grip_xyz", (C.c_double * 3) * MAX_GRIPPERS),
+                ("radius", C.c_double * MAX_OBJECTS), ("seat_xyz", (C.c_double * 3) * MAX_MATES), ("seat_quat", (C.c_double * 4) * MAX_MATES),
+                ("tol_xyz", C.c_double * MAX_MATES), ("min_abs_dot", C.c_double * MAX_MATES)]
+
+
+class ActionRefs(C.Structure):
+    """struct irlosc_action_refs (include/irlosc.h): the objects a list's WP actions aim at, irlosc_set_action_refs."""
+    _fields_ = [("xyz_obj", C.c_int32 * MAX_ACTIONS), ("quat_obj", C.c_int32 * MAX_ACTIONS)]
+
+
 class Cfg(C.Structure):
     _fields_ = [("hip_device", C.c_int32), ("dtype", C.c_int32), ("max_batch", C.c_int32),
                 ("n_slots", C.c_int32), ("n", C.c_int32), ("ndev", C.c_int32),
@@ -225,6 +243,10 @@ def load():
     lib.irlosc_download_joint_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.irlosc_set_episodes.argtypes = [vp, i32, i32, C.POINTER(Episodes), vp, vp, vp]
     lib.irlosc_download_episode_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.irlosc_set_objects.argtypes = [vp, i32, i32, C.POINTER(Objects), vp]
+    lib.irlosc_download_object_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.irlosc_set_action_refs.argtypes = [vp, i32, C.POINTER(ActionRefs)]
+    lib.irlosc_log_layout_objects.argtypes = [i32, i32, i32, C.c_uint32, i32, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

@@ -333,6 +333,48 @@ def compile_action_list(sequence: List[Dict], objects: List[Dict], active_dev: i
     return d
 
 
+OBJECT_INDEX = {"male_object": 0, "female_object": 1}            # the action objects of the `nist` and `grommet` sets, as object indices
+
+
+def grip_quat(obj: Dict):
+    """The grip rotation of an action object: the quaternion of euler2mat(DEFAULT_EE_ROT + [0, 0, grip_yaw]) (insertion_task.py:252)."""
+    return euler2quat(*(DEFAULT_EE_ROT + [0, 0, np.deg2rad(obj["grip_yaw"])]))
+
+
+def compile_action_list_refs(sequence: List[Dict], objects: List[Dict], active_dev: int, passive_dev: int = -1, tick_seconds: float = 0.001,
+                             passive_hold_orientation: bool = False, passive_quat=None):
+    """compile_action_list for a slot with ACTION OBJECTS (BatchedOSC.set_objects): a WP that names an object aims at the object's pose
+    AT THE MOMENT THE WP IS ENTERED, as set_waypoint_targets reads it from the simulator (insertion_task.py:226-262), not at the pose it
+    had when the list was compiled.  -> (desc, refs, pose0):
+      desc   compile_action_list's dict, but for a WP whose target_xyz names an object the xyz words of `pose` are the OFFSET (the
+             named one of the object, or the list given), and for a WP whose target_abg names an object the quaternion words are the
+             object's grip rotation (grip_quat)
+      refs   dict(xyz_obj, quat_obj: int32 [A]): per action the object index (OBJECT_INDEX) or -1 -- BatchedOSC.set_action_refs
+      pose0  [B, 2, 7] the objects' start poses (x y z qw qx qy qz) from each robot's {"pos", "quat"} -- BatchedOSC.set_objects
+    With the objects at rest the targets the GPU composes -- object xyz + offset, q_obj (x) q_grip -- are compile_action_list's static
+    table: the xyz words bit for bit, the quaternion to rounding and up to its sign (objects.ref_target; tests/test_objects_host.py)."""
+    d = compile_action_list(sequence, objects, active_dev, passive_dev, tick_seconds, passive_hold_orientation, passive_quat)
+    A, B = d["n_actions"], len(objects)
+    refs = dict(xyz_obj=np.full(A, -1, np.int32), quat_obj=np.full(A, -1, np.int32))
+    for a, p in enumerate(sequence):
+        if p["action"] != "WP":
+            continue
+        txyz, tabg = p["target_xyz"], p.get("target_abg")
+        if isinstance(txyz, str) and txyz != "start_pos":
+            refs["xyz_obj"][a] = OBJECT_INDEX[txyz]
+            offset = p.get("offset", [0.0, 0.0, 0.0])
+            for b in range(B):
+                d["pose"][b, a, :3] = np.asarray(objects[b][txyz][offset] if isinstance(offset, str) else offset, dtype=np.float64)
+        if isinstance(tabg, str):
+            refs["quat_obj"][a] = OBJECT_INDEX[tabg]
+            for b in range(B):
+                d["pose"][b, a, 3:] = grip_quat(objects[b][tabg])
+    names = sorted(OBJECT_INDEX, key=OBJECT_INDEX.get)
+    pose0 = np.array([[np.concatenate([np.asarray(o[nm]["pos"], dtype=np.float64), np.asarray(o[nm]["quat"], dtype=np.float64)]) for nm in names]
+                      for o in objects])
+    return d, refs, pose0
+
+
 def action_list_state(B: int) -> Dict:
     """The per-robot state of an action list as irlosc_set_action_list resets it."""
     return dict(action=np.zeros(B, np.int32), entered=np.full(B, -1, np.int32), grip_left=np.zeros(B, np.int32),

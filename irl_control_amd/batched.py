@@ -34,6 +34,7 @@ class BatchedOSC:
         self._B = [0] * self.n_slots
         self._joint_rows = [0] * self.n_slots      # rows of each slot's set_joints (the width of joint_state's arrays)
         self._episode_records = [1] * self.n_slots      # ring length of each slot's set_episodes (the width of episode_state's records)
+        self._objects = [(0, 0)] * self.n_slots      # (objects, mates) of each slot's set_objects (the widths of object_state's arrays)
         if kernel == _lib.KERNEL_AUTO and self.max_batch >= 1024 and self.kernel_class == _lib.CLASS_GENERIC:
             import warnings
             warnings.warn(f"layout (n={layout.n}, k={layout.k}, ndev={layout.ndev}) has no throughput kernel: "
@@ -211,6 +212,7 @@ class BatchedOSC:
         self._chk(self.lib.irlosc_set_model(self._h, C.byref(st)))
         self._model = model
         self._joint_rows = [0] * self.n_slots      # (irlosc_set_model ends every slot's joint rows)
+        self._objects = [(0, 0)] * self.n_slots    # (... and action objects)
 
     def upload_q(self, qpos, qvel, slot: int = 0):
         B = int(np.shape(qpos)[0])
@@ -375,15 +377,16 @@ class BatchedOSC:
             lg = _lib.Log(m & 0xFFFFFFFF, every, 0 if idx is None else R, 0, int(buffer_bytes))
             S = -(-ticks // every) if every > 0 and ticks > 0 else 0
             words = 0
-            if S and R >= 1 and m and not m & ~rollout_log.ALL:
-                words = rollout_log.layout(L.n, L.ndev, m, R)[1]
+            nobj = self._objects[slot][0]
+            if S and R >= 1 and m and not m & ~(rollout_log.ALL | (rollout_log.OBJECT_POSE_BIT if nobj else 0)):
+                words = rollout_log.layout(L.n, L.ndev, m, R, nobj)[1]
             buf = np.empty((S, words), dtype=np.float64)
         self._chk(self.lib.irlosc_rollout_from_q_logged(self._h, slot, B, ticks, C.byref(lg) if lg is not None else None, _lib.ptr(idx),
                                                         _lib.ptr(buf), _lib.ptr(u), _lib.ptr(fl)))
         run = self._ticks_run(slot)
         if buf is not None:
             log_ticks = np.arange(0, min(ticks, run) if B else ticks, every, dtype=np.int64)      # (an early exit: the rows of the ticks run)
-            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype) if B else {}
+            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype, nobj=nobj) if B else {}
         qpos, qvel = self.download_q(slot)
         return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=None, log=log, log_ticks=log_ticks, ticks_run=run)
 
@@ -530,6 +533,54 @@ class BatchedOSC:
             desc.min_speed[a], desc.max_speed[a] = float(d["min_speed"][a]), float(d["max_speed"][a])
             desc.gripper_force[a] = float(d["gripper_force"][a])
         self._chk(self.lib.irlosc_set_action_list(self._h, slot, B, C.byref(desc), _lib.ptr(pose)))
+
+    # -- action objects of the rollout (irlosc_set_objects / irlosc_set_action_refs / irlosc_download_object_state) ---------------------
+    def set_objects(self, objs, pose0=None, slot: int = 0):
+        """Kinematic action objects for the slot's robots (objects.ObjectSet): inside `rollout` an object rides rigidly on the EE of a
+        gripper whose fingers close near it (the rising edge of `closed`, inside the object's radius), stays where it is let go, and a
+        plug that is free inside its socket's tolerances is recorded as mated.  No mass, no contact, no gravity, no slipping.
+        `pose0`: [B, nobj, 7] start poses (x y z qw qx qy qz), or [V, B, nobj, 7]: variants that episodes cycle (a reset takes
+        variant count mod V).  After set_model and upload_q; resets the objects' state and ends the list's refs.  objs=None clears."""
+        B = self._B[slot]
+        if objs is None:
+            self._chk(self.lib.irlosc_set_objects(self._h, slot, B, None, None))
+            self._objects[slot] = (0, 0)
+            return
+        objs.check()
+        NO = objs.n_objects
+        p0 = np.ascontiguousarray(pose0, dtype=np.float64)
+        if p0.ndim == 3:
+            p0 = p0[None]
+        if p0.ndim != 4 or p0.shape[0] < 1 or p0.shape[1:] != (B, NO, 7):
+            raise ValueError(f"pose0: expected shape ({B}, {NO}, 7) or (V, {B}, {NO}, 7) with V >= 1, got {p0.shape}")
+        d = objs.to_struct(p0.shape[0])
+        self._chk(self.lib.irlosc_set_objects(self._h, slot, B, C.byref(d), _lib.ptr(p0)))
+        self._objects[slot] = (NO, len(objs.mates))
+
+    def set_action_refs(self, xyz_obj, quat_obj=None, slot: int = 0):
+        """The slot's action list aims at its objects: per action the object (index, or -1) whose live xyz a WP's pose words are an
+        OFFSET to, and the object whose live quaternion they are a grip rotation on (target = q_obj (x) q_grip), both read when the
+        WP is entered.  After set_action_list and set_objects, which both end the refs.  xyz_obj=None clears them."""
+        if xyz_obj is None:
+            self._chk(self.lib.irlosc_set_action_refs(self._h, slot, None))
+            return
+        r = _lib.ActionRefs()
+        quat_obj = [-1] * len(xyz_obj) if quat_obj is None else quat_obj
+        for i in range(_lib.MAX_ACTIONS):
+            r.xyz_obj[i] = int(xyz_obj[i]) if i < len(xyz_obj) else -1
+            r.quat_obj[i] = int(quat_obj[i]) if i < len(quat_obj) else -1
+        self._chk(self.lib.irlosc_set_action_refs(self._h, slot, C.byref(r)))
+
+    def object_state(self, slot: int = 0):
+        """-> dict(pose [B, nobj, 7], rel [B, nobj, 7], holder, grasp_tick, release_tick [B, nobj], mated_tick [B, nmates]): the slot's
+        action objects as the last tick's object kernel left them (or a reset behind it).  (irlosc_download_object_state)"""
+        B = self._B[slot]
+        NO, NM = self._objects[slot]
+        out = dict(pose=np.empty((B, NO, 7)), holder=np.empty((B, NO), np.int32), rel=np.empty((B, NO, 7)), grasp_tick=np.empty((B, NO), np.int32),
+                   release_tick=np.empty((B, NO), np.int32), mated_tick=np.empty((B, NM), np.int32))
+        self._chk(self.lib.irlosc_download_object_state(self._h, slot, B, *[_lib.ptr(out[k]) if out[k].size else None for k in
+                                                                             ("pose", "holder", "rel", "grasp_tick", "release_tick", "mated_tick")]))
+        return out
 
     def action_state(self, slot: int = 0):
         """-> dict(action, grip_left, err, max_vel0, gripper_force, finished_tick), each [B]: where every robot stands in the slot's

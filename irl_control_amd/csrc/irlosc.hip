@@ -28,6 +28,7 @@
 #include "osc_waypoint.hpp"
 #include "osc_action.hpp"
 #include "osc_teleop.hpp"
+#include "osc_object.hpp"
 #include "osc_push.hpp"
 #include "osc_wall.hpp"
 #include "osc_joint.hpp"
@@ -54,6 +55,8 @@ struct Program {
     irlosc_action_list al{};
     irlosc_teleop_stream ts{};
     std::vector<double> ts_shared;      // a shared stream's readings [T][6]: they travel as kernel arguments, tick by tick
+    int refs = 0;              // 1: the list aims at the slot's action objects as `rf` says (irlosc_set_action_refs)
+    irlosc_action_refs rf{};
     // Device buffers, allocated by the first use and kept across programs: per-robot state SoA over max_batch robots (wp_i, al_i, al_d), the
     // table (walk_table), and a list's own gains [robots][ndev][12] and null_kv [robots] in the context's dtype (its rollout reads these per instance)
     // A stream: the pose SoA [6][max_batch] (ts_pose), per-robot readings (ts_table) and per-robot origins (ts_origin), both walk_table.
@@ -74,14 +77,17 @@ struct Program {
     // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
     void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
     // A list of B robots is in force, its state reset by the kernel's init launch and its gain copy made: it writes the targets from here on.
-    void list(int B, const irlosc_action_list& d) { kind = LIST; robots = B; tick = 0; al = d; }
+    void list(int B, const irlosc_action_list& d) { kind = LIST; robots = B; tick = 0; al = d; refs = 0; }
+    // The list in force aims at the slot's objects / at its own table alone again (its refs were cleared, or the objects they name changed)
+    void aims(const irlosc_action_refs& r) { refs = 1; rf = r; }
+    void aimless() { refs = 0; }
     // A stream over B robots is in force, their poses at the origins by the kernel's init launch (which wrote no target: the first tick
     // does); `shared`: the readings of a stream for the whole fleet.
     void stream(int B, const irlosc_teleop_stream& d, std::vector<double>&& shared) { kind = STREAM; robots = B; tick = 0; ts = d; ts_shared = std::move(shared); }
     // The reading a stream takes on the tick to come: tick mod T of one that loops, none (-1) once one that does not has ended
     int reading() const { return kind != STREAM ? -1 : ts.loop ? tick % ts.ticks : tick < ts.ticks ? tick : -1; }
     // The program ends: irlosc_set_targets wrote the targets, another program takes them over, the model changed, or its buffers failed.
-    void end() { kind = NONE; robots = 0; tick = 0; }
+    void end() { kind = NONE; robots = 0; tick = 0; refs = 0; }
     // The program ends if it is of this kind (its own setter cleared it; a list: the gains its copy was made from were replaced): one of the other kind stays whole
     void end(Kind k) { if (kind == k) end(); }
     // A tick of a rollout ran the program's kernel.  (Marked once the whole tick is enqueued: if a launch behind the kernel fails, the
@@ -151,6 +157,24 @@ struct Joints : PlantForce {
     void set(int B, const irlosc_joint_rows& desc) { in_force(B); d = desc; }
 };
 
+// The action objects (irlosc_set_objects, osc_object.hpp): kinematic bodies a gripper carries.  They act on nothing -- no force on the
+// plant, none in the feed -- but live here with the parts that have a table (the start poses), per-robot state and a tick of their own.
+struct Objects : PlantForce {
+    irlosc_objects d{};        // the description in force
+    size_t vstride = 0;        // doubles between two variants' start poses in `table` ([V][walk wave][nobj 7][64])
+    DevBuf<double> st_d;       // per-robot state, allocated by the first use for max_batch robots: pose, rel
+    DevBuf<int32_t> st_i;      // ... holder, grasp_tick, release_tick, was_closed, mated_tick
+    // THE LAYOUT of the state (osc_object.hpp): rows of Bm = max_batch words
+    double* pose(size_t) const { return st_d; }  double* rel(size_t Bm) const { return st_d + (size_t)OBJ_POSE_ROWS * Bm; }
+    int32_t* holder(size_t) const { return st_i; }  int32_t* grasp_tick(size_t Bm) const { return st_i + (size_t)IRLOSC_MAX_OBJECTS * Bm; }
+    int32_t* release_tick(size_t Bm) const { return st_i + 2 * (size_t)IRLOSC_MAX_OBJECTS * Bm; }
+    int32_t* was_closed(size_t Bm) const { return st_i + 3 * (size_t)IRLOSC_MAX_OBJECTS * Bm; }
+    int32_t* mated_tick(size_t Bm) const { return st_i + (3 * (size_t)IRLOSC_MAX_OBJECTS + IRLOSC_MAX_GRIPPERS) * Bm; }
+    static size_t d_words(size_t Bm) { return (size_t)OBJ_D_ROWS * Bm; }  static size_t i_words(size_t Bm) { return (size_t)OBJ_I_ROWS * Bm; }
+    void set(int B, const irlosc_objects& desc, size_t vs) { in_force(B); d = desc; vstride = vs; }
+    int count() const { return robots ? d.n_objects : 0; }      // objects of the slot (0: it has none)
+};
+
 // The episodes (irlosc_set_episodes, osc_episode.hpp): per robot the judgement whether its running episode has ended, its record and its
 // reset on the device, and per wave the robots still running for the early exit.  They write no targets but a reset robot's snapshot row,
 // so they are no Program: they live next to one.  Written by laid_out(), set(), end() and ticked(), and by nothing else.
@@ -211,6 +235,7 @@ struct Slot {
     Pushes push;               // what pushes the plant inside a rollout
     Walls walls;               // what the EE bodies run into inside a rollout
     Joints joints;             // what acts on single hinges inside a rollout: stops, couplings, drives
+    Objects objects;           // what the grippers carry inside a rollout
     Episodes episodes;         // what ends and restarts single robots inside a rollout
     int ticks_run = 0;         // ticks the last rollout call on the slot ran (fewer than asked: an early exit of its episodes)
 
@@ -1620,7 +1645,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); s.episodes.end(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); s.objects.end(); s.episodes.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1789,7 +1814,7 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 // tick, is the slot's to say (Slot::prog).  log: the episode log's sample of this tick (irlosc_rollout_from_q_logged), or nullptr.
 // A logged tick: the ring's sample it fills, the event its first log launch waits for on the tick's stream (the half it starts was still
 // draining: the copy that empties it; else null), and what stays the same over the call -- channels, robots (device, or nullptr: all), layout
-struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };
+struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };      // (off[9]: OBJECT_POSE, of a slot with objects)
 struct PlantCall { double* trace; const LogCall* log; };
 
 // The exchange entry of each device's EE pose (its x; y z qw qx qy qz follow): what the rollout's kernels find an EE body by
@@ -1805,6 +1830,10 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
     a.action = p.action(Bm); a.entered = p.entered(Bm); a.grip_left = p.grip_left(Bm); a.finished_tick = p.finished_tick(Bm);
     a.err = p.err(Bm); a.max_vel0 = p.max_vel0(Bm); a.gripper_force = p.gripper_force(Bm); a.start_xyz = p.start_xyz(Bm);
     a.table = p.al_table;
+    if (xside && p.refs && s.objects.robots) {      // (refs live only next to the objects they name: irlosc_set_objects ends them)
+        a.obj_pose = s.objects.pose(Bm);
+        for (int i = 0; i < d.n_actions; ++i) { a.xyz_obj[i] = (int8_t)p.rf.xyz_obj[i]; a.quat_obj[i] = (int8_t)p.rf.quat_obj[i]; }
+    }
     for (int i = 0; i < d.n_actions; ++i) {
         a.kp[i] = d.kp[i]; a.max_error[i] = d.max_error[i]; a.min_speed[i] = d.min_speed[i]; a.max_speed[i] = d.max_speed[i];
         a.force[i] = d.gripper_force[i]; a.grip_ticks[i] = d.grip_ticks[i];
@@ -1818,6 +1847,32 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
     a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.A = d.n_actions; a.per_robot = d.nb > 1;
     a.n_entries = (int32_t)c->model.fe_xentries; a.tick = tick; a.init = xside ? 0 : 1;
     a.active = d.active_dev; a.passive = d.passive_dev; a.hold = d.passive_hold_orientation;
+    return a;
+}
+
+// The arguments of the slot's object kernel over B robots for description d (init: the launch of irlosc_set_objects, d not in force yet;
+// else a tick on exchange block xside)
+static ObjectArgs object_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_objects& d, const double* xside) {
+    const Objects& o = s.objects;
+    ObjectArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    a.xside = xside; a.qt = s.qt; a.pose0 = o.table;
+    a.pose = o.pose(Bm); a.rel = o.rel(Bm); a.holder = o.holder(Bm); a.grasp_tick = o.grasp_tick(Bm); a.release_tick = o.release_tick(Bm);
+    a.was_closed = o.was_closed(Bm); a.mated_tick = o.mated_tick(Bm);
+    for (int g = 0; g < d.n_grippers; ++g) {
+        a.sign[g] = (double)d.sign[g]; a.q_close[g] = d.q_close[g]; a.q_open[g] = d.q_open[g]; a.joint[g] = d.joint[g];
+        for (int i = 0; i < 3; ++i) a.grip_xyz[g][i] = d.grip_xyz[g][i];
+        for (int i = 0; i < 7 && xside; ++i) a.ee[g][i] = c->model.tables.eetab[d.dev[g]][i];
+    }
+    for (int i = 0; i < d.n_objects; ++i) a.radius[i] = d.radius[i];
+    for (int m = 0; m < d.n_mates; ++m) {
+        a.plug[m] = d.plug[m]; a.socket[m] = d.socket[m]; a.tol_xyz[m] = d.tol_xyz[m]; a.min_abs_dot[m] = d.min_abs_dot[m];
+        for (int i = 0; i < 3; ++i) a.seat_xyz[m][i] = d.seat_xyz[m][i];
+        for (int i = 0; i < 4; ++i) a.seat_quat[m][i] = d.seat_quat[m][i];
+    }
+    a.B = B; a.n = c->cfg.n; a.stride = (int32_t)Bm; a.nobj = d.n_objects; a.ng = d.n_grippers; a.nm = d.n_mates;
+    a.n_entries = (int32_t)c->model.fe_xentries; a.tick = o.tick; a.init = xside ? 0 : 1;
     return a;
 }
 
@@ -1942,6 +1997,7 @@ static LogArgs log_args(const irlosc_ctx* c, const Slot& s, const irlosc_ctx::Ba
     for (int i = 0; i < LOG_CHANNELS; ++i) a.off[i] = lg.off[i];
     a.qpos = s.qpos; a.qvel = s.qvel; a.xside = bk.xside[0]; a.tgt = s.tgt; a.wrench = wrench; a.u = bk.u[0]; a.flags = bk.flags[0];
     a.wall_force = s.walls.force((size_t)c->cfg.ndev * Bm); a.joint_tau = s.joints.tau(Bm);
+    a.obj_pose = s.objects.pose(Bm); a.obj_holder = s.objects.holder(Bm); a.nobj = s.objects.count();
     a.R = lg.R; a.n = c->cfg.n; a.ndev = c->cfg.ndev; a.n_entries = (int32_t)c->model.fe_xentries; a.stride = (int32_t)Bm;
     fill_ee0(c, a.ee0);
     return a;
@@ -1981,6 +2037,12 @@ static EpisodeArgs episode_args(const irlosc_ctx* c, const Slot& s, int B, const
     if (!init && s.joints.robots) {
         a.joints = 1; a.R = s.joints.d.n_rows;
         a.jt_tau = s.joints.tau(Bm); a.jt_violation = s.joints.max_violation(Bm); a.jt_ctrl = s.joints.ctrl(Bm, a.R); a.jt_active = s.joints.active_ticks(Bm);
+    }
+    if (!init && s.objects.robots) {
+        const Objects& o = s.objects;
+        a.objects = 1; a.nobj = o.d.n_objects; a.ng = o.d.n_grippers; a.nm = o.d.n_mates; a.OV = o.d.n_variants;
+        a.ob_pose = o.pose(Bm); a.ob_rel = o.rel(Bm); a.ob_holder = o.holder(Bm); a.ob_grasp = o.grasp_tick(Bm); a.ob_release = o.release_tick(Bm);
+        a.ob_closed = o.was_closed(Bm); a.ob_mated = o.mated_tick(Bm); a.ob_pose0 = o.table; a.ob_vstride = (int64_t)o.vstride;
     }
     a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.S = d.n_starts; a.starts_per_robot = e.starts_per_robot;
     a.max_ticks = d.max_ticks; a.end_on_finish = d.end_on_finish; a.max_episodes = d.max_episodes; a.records = d.records;
@@ -2053,9 +2115,9 @@ static int download_state(irlosc_ctx* c, int B, const double* sd, size_t nd, std
 // What a tick of a rollout runs next to its fused step, decided once per tick from the slot (the default: no tick, nothing): the program that writes its
 // targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); rows
 // it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on); episodes it has
-struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; };
+struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; bool objects = false; };
 static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
-    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading(), s0.episodes.robots != 0};
+    TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading(), s0.episodes.robots != 0, s0.objects.robots != 0};
     for (int p = 0; tp.push_sense && p < IRLOSC_MAX_PUSHES; ++p)
         if (((tp.push_sense >> p) & 1u) && c->ft_f0[s0.push.d.dev[p]] < 0) tp.push_sense &= ~(1u << p);
     if (s0.feed > 0 && s0.walls.tick > 0) tp.wall_sense = tp.wall_apply;
@@ -2067,7 +2129,8 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
 // THE ORDER OF A TICK'S LAUNCHES on the stream of bank 0 ([..]: where the plan has it; the unnamed lines are fused_train's own):
 //     the walk, the feed's wrench (ft_launch)
 //     tick_front:   [pushes SENSE: their reaction goes into the wrench ahead of every kernel that reads it] [walls SENSE: their force of the
-//                   tick before, behind it] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel
+//                   tick before, behind it] [action objects: on this tick's EE poses and knuckle coordinates, in front of the action kernel,
+//                   whose refs read their poses] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel
 //                   | stream kernel: its targets are this tick's too]
 //     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
 //     [log FRONT (a logged tick): coordinates, EE poses, targets, wrench, u and flags as the step used and left them -- behind the give-up
@@ -2084,6 +2147,7 @@ template <typename T>
 static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, const irlosc_ctx::Bank& bk, void* wrench, hipStream_t st) {
     if (tp.push_sense) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_sense, nullptr, wrench), st));
     if (tp.wall_sense) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_sense, nullptr, wrench), st));
+    if (tp.objects) HIPCHK(c, (hipError_t)launch_objects(object_args(c, s0, B, s0.objects.d, bk.xside[0]), st));
     if (tp.prog == Program::LIST) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (tp.reading >= 0) HIPCHK(c, (hipError_t)launch_teleop<T>(teleop_args(c, s0, B, s0.prog.ts, s0.prog.ts_shared.data(), tp.reading), st));
     return IRLOSC_OK;
@@ -2103,7 +2167,7 @@ static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp,
 static void tick_done(Slot& s0, int B, const TickPlan& tp) {
     s0.advanced(B);
     if (tp.prog != Program::NONE) s0.prog.ticked();
-    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); s0.episodes.ticked();      // (each ticks only where it is in force)
+    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); s0.objects.ticked(); s0.episodes.ticked();      // (each ticks only where it is in force)
 }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
@@ -2543,19 +2607,28 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     return IRLOSC_OK;
 }
 
-extern "C" int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int32_t R, int64_t offset[9], int64_t* sample_words) {
+extern "C" int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, uint32_t channels, int32_t R, int64_t offset[10], int64_t* sample_words) {
     if (!offset || !sample_words) return fail(nullptr, IRLOSC_ERR_ARG, "log: offset and sample_words are required");
-    if (channels == 0 || (channels & ~(LOG_FRONT | LOG_BACK))) return fail(nullptr, IRLOSC_ERR_ARG, "log: channels=0x%x must be a non-empty OR of the IRLOSC_LOG_* bits", channels);
+    if (nobj < 0 || nobj > IRLOSC_MAX_OBJECTS) return fail(nullptr, IRLOSC_ERR_ARG, "log: nobj=%d out of [0,%d]", nobj, IRLOSC_MAX_OBJECTS);
+    const uint32_t known = (LOG_FRONT | LOG_BACK) & ~(nobj ? 0u : (uint32_t)IRLOSC_LOG_OBJECT_POSE);      // (no objects: no such channel)
+    if (channels == 0 || (channels & ~known)) return fail(nullptr, IRLOSC_ERR_ARG, "log: channels=0x%x must be a non-empty OR of the IRLOSC_LOG_* bits", channels);
     if (R < 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: R=%d must be >= 1", R);
     if (n < 1 || n > IRLOSC_MAX_N) return fail(nullptr, IRLOSC_ERR_ARG, "log: n=%d out of [1,%d]", n, IRLOSC_MAX_N);
     if (ndev < 1 || ndev > IRLOSC_MAX_DEV) return fail(nullptr, IRLOSC_ERR_ARG, "log: ndev=%d out of [1,%d]", ndev, IRLOSC_MAX_DEV);
     int64_t words = 0;
     for (int i = 0; i < LOG_CHANNELS; ++i) {
         offset[i] = (channels >> i) & 1u ? words : -1;
-        if ((channels >> i) & 1u) words += (int64_t)R * log_width(i, n, ndev);
+        if ((channels >> i) & 1u) words += (int64_t)R * log_width(i, n, ndev, nobj);
     }
     *sample_words = words;
     return IRLOSC_OK;
+}
+
+extern "C" int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int32_t R, int64_t offset[9], int64_t* sample_words) {
+    int64_t off[LOG_CHANNELS];
+    const int rc = irlosc_log_layout_objects(n, ndev, 0, channels, R, offset ? off : nullptr, sample_words);
+    for (int i = 0; !rc && i < 9; ++i) offset[i] = off[i];
+    return rc;
 }
 
 // The log of a call, checked against the slot (every refusal ahead of the first allocation or launch) and planned into lr; B >= 1
@@ -2571,7 +2644,7 @@ static int log_plan(irlosc_ctx* c, int slot, int B, int ticks, const irlosc_log*
         if (robots[i] < 0 || robots[i] >= B || (i && robots[i] <= robots[i - 1]))
             return fail(c, IRLOSC_ERR_ARG, "log: robots[%d]=%d: the list must be strictly ascending in [0,%d)", i, robots[i], B);
     int64_t words = 0;
-    if (irlosc_log_layout(c->cfg.n, c->cfg.ndev, log->channels, R, lr.call.off, &words)) return fail(c, IRLOSC_ERR_ARG, "%s", irlosc_last_error(nullptr));
+    if (irlosc_log_layout_objects(c->cfg.n, c->cfg.ndev, c->slot[slot].objects.count(), log->channels, R, lr.call.off, &words)) return fail(c, IRLOSC_ERR_ARG, "%s", irlosc_last_error(nullptr));
     const uint64_t sb = (uint64_t)words * sizeof(double);      // (R <= max_batch, 170 words a robot at most: far from 2^63)
     if (log->buffer_bytes && log->buffer_bytes / 2 < sb)
         return fail(c, IRLOSC_ERR_ARG, "log: buffer_bytes=%llu holds fewer than two samples of %llu bytes", (unsigned long long)log->buffer_bytes, (unsigned long long)sb);
@@ -2635,6 +2708,7 @@ static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, i
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].push.robots, "pushes", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].walls.robots, "walls", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].objects.robots, "action objects", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].episodes.robots, "episodes", "cover", nullptr);
     if (rc) return rc;
     c->slot[slot].ticks_run = B == 0 ? ticks : 0;      // (rollout_ticks says how many were enqueued; an empty batch: all, none of them a launch)
@@ -2906,6 +2980,110 @@ extern "C" int irlosc_download_joint_state(irlosc_ctx* c, int32_t slot, int32_t 
                           {ctrl, js.ctrl(Bm, R), R, R, 0, 1}}, js.st_i, js.i_words(Bm, R), {{active_ticks, js.active_ticks(Bm), R, R, 0, 1}});
 }
 
+// ---- action objects of the rollout (osc_object.hpp) ---------------------------------------------------------------------------------
+extern "C" int irlosc_set_objects(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_objects* d, const double* pose0) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.objects.end(); s.prog.aimless(); return IRLOSC_OK; }
+    const int n = c->cfg.n, nd = c->cfg.ndev, NO = d->n_objects, NG = d->n_grippers, NM = d->n_mates, V = d->n_variants;
+    if (NO < 1 || NO > IRLOSC_MAX_OBJECTS) return fail(c, IRLOSC_ERR_ARG, "objects: n_objects=%d out of [1,%d]", NO, IRLOSC_MAX_OBJECTS);
+    if (NG < 1 || NG > IRLOSC_MAX_GRIPPERS) return fail(c, IRLOSC_ERR_ARG, "objects: n_grippers=%d out of [1,%d]", NG, IRLOSC_MAX_GRIPPERS);
+    if (NM < 0 || NM > IRLOSC_MAX_MATES) return fail(c, IRLOSC_ERR_ARG, "objects: n_mates=%d out of [0,%d]", NM, IRLOSC_MAX_MATES);
+    if (V < 1 || V > IRLOSC_MAX_EPISODE_STARTS) return fail(c, IRLOSC_ERR_ARG, "objects: n_variants=%d out of [1,%d]", V, IRLOSC_MAX_EPISODE_STARTS);
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "objects: B=%d must be >= 1", B);
+    for (int g = 0; g < NG; ++g) {
+        if (d->dev[g] < 0 || d->dev[g] >= nd) return fail(c, IRLOSC_ERR_ARG, "objects: dev[%d]=%d out of [0,%d)", g, d->dev[g], nd);
+        if (d->joint[g] < 0 || d->joint[g] >= n) return fail(c, IRLOSC_ERR_ARG, "objects: joint[%d]=%d out of [0,%d)", g, d->joint[g], n);
+        if (d->sign[g] != 1 && d->sign[g] != -1) return fail(c, IRLOSC_ERR_ARG, "objects: sign[%d]=%d must be +1 or -1", g, d->sign[g]);
+        bool fin = std::isfinite(d->q_close[g]) && std::isfinite(d->q_open[g]);
+        for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(d->grip_xyz[g][i]);
+        if (!fin) return fail(c, IRLOSC_ERR_ARG, "objects: q_close / q_open / grip_xyz of gripper %d must be finite", g);
+        if (!(d->sign[g] * d->q_open[g] < d->sign[g] * d->q_close[g]))
+            return fail(c, IRLOSC_ERR_ARG, "objects: gripper %d opens at %g and closes at %g: sign q_open must lie below sign q_close", g, d->q_open[g], d->q_close[g]);
+    }
+    for (int o = 0; o < NO; ++o)
+        if (!(std::isfinite(d->radius[o]) && d->radius[o] >= 0.0)) return fail(c, IRLOSC_ERR_ARG, "objects: radius[%d]=%g must be finite and >= 0", o, d->radius[o]);
+    for (int m = 0; m < NM; ++m) {
+        if (d->plug[m] < 0 || d->plug[m] >= NO || d->socket[m] < 0 || d->socket[m] >= NO)
+            return fail(c, IRLOSC_ERR_ARG, "objects: plug[%d]=%d, socket[%d]=%d out of [0,%d)", m, d->plug[m], m, d->socket[m], NO);
+        if (d->plug[m] == d->socket[m]) return fail(c, IRLOSC_ERR_ARG, "objects: mate %d plugs object %d into itself", m, d->plug[m]);
+        bool fin = true;
+        for (int i = 0; i < 3; ++i) fin = fin && std::isfinite(d->seat_xyz[m][i]);
+        for (int i = 0; i < 4; ++i) fin = fin && std::isfinite(d->seat_quat[m][i]);
+        if (!fin) return fail(c, IRLOSC_ERR_ARG, "objects: seat_xyz / seat_quat of mate %d must be finite", m);
+        if (!(std::isfinite(d->tol_xyz[m]) && d->tol_xyz[m] > 0.0)) return fail(c, IRLOSC_ERR_ARG, "objects: tol_xyz[%d]=%g must be finite and > 0", m, d->tol_xyz[m]);
+        if (!(d->min_abs_dot[m] >= 0.0 && d->min_abs_dot[m] <= 1.0)) return fail(c, IRLOSC_ERR_ARG, "objects: min_abs_dot[%d]=%g out of [0,1]", m, d->min_abs_dot[m]);
+    }
+    if (!pose0) return fail(c, IRLOSC_ERR_ARG, "objects: pose0 is NULL");
+    const size_t E = (size_t)NO * 7;
+    for (size_t i = 0; i < (size_t)V * B * E; ++i)
+        if (!std::isfinite(pose0[i]))
+            return fail(c, IRLOSC_ERR_ARG, "objects: start pose of object %zu, robot %zu, variant %zu is not finite", i % E / 7, i / E % B, i / E / B);
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (B > std::max(0, s.coords))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds joint coordinates of %d instances, objects given for %d: irlosc_upload_q first", slot, std::max(0, s.coords), B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Objects& os = s.objects;
+    os.end();          // (none until the new ones are in their table and their state is reset; the refs named the old ones)
+    s.prog.aimless();
+    // the start poses, every variant in the walk's layout even for a lone robot: [V][walk wave][NO 7][64]
+    const size_t vstride = ((size_t)B + 63) / 64 * E * 64;
+    std::vector<double> tab((size_t)V * vstride, 0.0);
+    for (size_t v = 0; v < (size_t)V; ++v)
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t k = 0; k < E; ++k) tab[v * vstride + ((b / 64) * E + k) * 64 + b % 64] = pose0[(v * B + b) * E + k];
+    const size_t bytes = tab.size() * sizeof(double), Bm = (size_t)c->cfg.max_batch;
+    const size_t d_bytes = os.d_words(Bm) * sizeof(double), i_bytes = os.i_words(Bm) * sizeof(int32_t);
+    if (!got(os.table.reserve(bytes)) || !got(os.st_d.ensure(d_bytes)) || !got(os.st_i.ensure(i_bytes)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the action objects of slot %d (%zu bytes)", slot, bytes + d_bytes + i_bytes);
+    const ObjectArgs init = object_args(c, s, B, *d, nullptr);
+    rc = setter_upload(c, {{os.table, tab.data(), bytes}, {os.st_d, nullptr, d_bytes, 0}, {os.st_i, nullptr, i_bytes, 0}}, launch_objects, &init);
+    if (!rc) os.set(B, *d, vstride);
+    return rc;
+}
+
+extern "C" int irlosc_download_object_state(irlosc_ctx* c, int32_t slot, int32_t B, double* pose, int32_t* holder, double* rel,
+                                            int32_t* grasp_tick, int32_t* release_tick, int32_t* mated_tick) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].objects.robots, "action objects", "cover", "irlosc_set_objects");
+    if (rc) return rc;
+    const Objects& os = c->slot[slot].objects;
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t NO = (size_t)os.d.n_objects, NM = (size_t)os.d.n_mates, Bm = (size_t)c->cfg.max_batch;      // rows [max_batch] -> [B][NO][7], [B][NO], [B][NM]
+    return download_state(c, B, os.st_d, os.d_words(Bm), {{pose, os.pose(Bm), NO * 7, NO * 7, 0, 1}, {rel, os.rel(Bm), NO * 7, NO * 7, 0, 1}},
+                          os.st_i, os.i_words(Bm), {{holder, os.holder(Bm), NO, NO, 0, 1}, {grasp_tick, os.grasp_tick(Bm), NO, NO, 0, 1},
+                          {release_tick, os.release_tick(Bm), NO, NO, 0, 1}, {mated_tick, os.mated_tick(Bm), NM, NM, 0, 1}});
+}
+
+extern "C" int irlosc_set_action_refs(irlosc_ctx* c, int32_t slot, const irlosc_action_refs* r) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, 0);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!r) { s.prog.aimless(); return IRLOSC_OK; }
+    const int NO = s.objects.count();
+    for (int i = 0; s.prog.kind == Program::LIST && NO && i < s.prog.al.n_actions; ++i) {
+        if (s.prog.al.kind[i] != IRLOSC_ACTION_WP) continue;
+        if (r->xyz_obj[i] < -1 || r->xyz_obj[i] >= NO || r->quat_obj[i] < -1 || r->quat_obj[i] >= NO)
+            return fail(c, IRLOSC_ERR_ARG, "action refs: xyz_obj[%d]=%d, quat_obj[%d]=%d must be -1 or an object in [0,%d)", i, r->xyz_obj[i], i, r->quat_obj[i], NO);
+    }
+    if (s.prog.kind != Program::LIST) return fail(c, IRLOSC_ERR_STATE, "slot %d has no action list (irlosc_set_action_list)", slot);
+    if (!NO) return fail(c, IRLOSC_ERR_STATE, "slot %d has no action objects (irlosc_set_objects)", slot);
+    if (s.objects.robots < s.prog.robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its action objects cover %d robots, its action list %d", slot, s.objects.robots, s.prog.robots);
+    irlosc_action_refs clean;
+    for (int i = 0; i < IRLOSC_MAX_ACTIONS; ++i) {
+        const bool wp = i < s.prog.al.n_actions && s.prog.al.kind[i] == IRLOSC_ACTION_WP;
+        clean.xyz_obj[i] = wp ? r->xyz_obj[i] : -1; clean.quat_obj[i] = wp ? r->quat_obj[i] : -1;
+    }
+    s.prog.aims(clean);
+    return IRLOSC_OK;
+}
+
 // ---- the WP / GRIP action list of the rollout (osc_action.hpp) ---------------------------------------------------------------
 extern "C" int irlosc_set_action_list(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_action_list* d, const double* pose) {
     if (!c) return IRLOSC_ERR_ARG;
@@ -3132,7 +3310,8 @@ extern "C" int irlosc_set_episodes(irlosc_ctx* c, int32_t slot, int32_t B, const
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, episodes given for %d: irlosc_set_targets first", slot,
                     std::max(0, s.targets), B);
     const Program& p = s.prog;
-    const struct { int robots; const char* what; } parts[] = {{p.robots, "program"}, {s.walls.robots, "walls"}, {s.joints.robots, "joint rows"}};
+    const struct { int robots; const char* what; } parts[] = {{p.robots, "program"}, {s.walls.robots, "walls"}, {s.joints.robots, "joint rows"},
+                                                              {s.objects.robots, "action objects"}};
     for (const auto& k : parts)
         if (k.robots && B > k.robots)
             return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s covers %d robots, episodes given for %d (their resets write its state)", slot, k.what, k.robots, B);

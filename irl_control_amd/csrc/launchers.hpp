@@ -99,6 +99,11 @@ struct ActionArgs;
 template <typename T>
 int launch_actions(const ActionArgs& a, hipStream_t st);
 
+// tu_object.hip -- the action objects of a rollout tick whose slot has some (osc_object.hpp): behind the walk and the SENSE launches,
+// directly in front of the action kernel; init mode: the launch of irlosc_set_objects
+struct ObjectArgs;
+int launch_objects(const ObjectArgs& a, hipStream_t st);
+
 // tu_teleop.hip -- the teleoperation stream where the action list's kernel goes, on a rollout tick whose slot has one and a reading
 // for the tick (osc_teleop.hpp); T = record type (of the targets)
 struct TeleopArgs;

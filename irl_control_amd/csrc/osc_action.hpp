@@ -22,6 +22,11 @@
 //                        GRIP: grip_left = grip_ticks[a], targets stay
 //   4. a < A and WP:     max_vel0 = max(min_speed[a], min(max_speed[a], kp[a] * err)) -> word 9 of the active device's gain record
 // A robot that has finished holds its last targets and gains.
+// REFS (irlosc_set_action_refs, on a slot with action objects: osc_object.hpp, whose kernel has run on this tick already).  A WP with
+// xyz_obj[a] >= 0: the xyz words of pose a are an OFFSET, target xyz = the object's xyz + offset, one add per word (the reference's
+// obj_pos + offset); xyz_from_start wins.  With quat_obj[a] >= 0 the quaternion words are the grip rotation, target quat = q_obj (x)
+// q_grip (quat_mul_rn: no normalisation, no sign change) -- the reference reaches the same rotation through mat2euler -> set_abg, equal
+// up to the quaternion's sign, which calc_error does not see.  Read at ENTRY only: a held object does not drag a target along.
 //
 // init = 1 (irlosc_set_action_list): action 0, entered -1, grip_left 0, err +inf, max_vel0 0, gripper_force 0, finished_tick -1,
 // start_xyz 0; neither the exchange block nor the targets are read.
@@ -47,11 +52,13 @@ struct ActionArgs {
     double* gripper_force;
     double* start_xyz;        // [3][stride]
     const double* table;      // per_robot: [walk wave][A][7][64], else [A][7]
+    const double* obj_pose;   // REFS in force: the action objects' poses of this tick [IRLOSC_MAX_OBJECTS 7][stride] (osc_object.hpp); else nullptr
     double kp[IRLOSC_MAX_ACTIONS], max_error[IRLOSC_MAX_ACTIONS], min_speed[IRLOSC_MAX_ACTIONS], max_speed[IRLOSC_MAX_ACTIONS];
     double force[IRLOSC_MAX_ACTIONS];
     double passive_quat[4];
     int32_t grip_ticks[IRLOSC_MAX_ACTIONS];
     uint8_t kind[IRLOSC_MAX_ACTIONS], xyz_from_start[IRLOSC_MAX_ACTIONS];
+    int8_t xyz_obj[IRLOSC_MAX_ACTIONS], quat_obj[IRLOSC_MAX_ACTIONS];      // refs: the object a WP's xyz / quaternion aims at, or -1
     int32_t ee_act[7], ee_pas[7];       // exchange entries of the active / passive device's x y z qw qx qy qz
     int32_t B, ndev, stride, A, per_robot, n_entries, tick, init;
     int32_t active, passive, hold;      // device indices (passive -1: none); hold: the passive arm keeps its EE orientation
@@ -135,8 +142,28 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) sx[c] = a.start_xyz[(size_t)c * a.stride + so];
                 }
+                const int xo = a.obj_pose ? a.xyz_obj[act] : -1, qo = a.obj_pose ? a.quat_obj[act] : -1;
+                if (xo < 0 && qo < 0) {
 #pragma unroll
-                for (int c = 0; c < 7; ++c) ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)p[c * cs];
+                    for (int c = 0; c < 7; ++c) ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)p[c * cs];
+                } else {                            // the table's words are an offset / the grip rotation on the object's pose of this tick
+                    double w[7];
+#pragma unroll
+                    for (int c = 0; c < 7; ++c) w[c] = p[c * cs];
+                    if (xo >= 0) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) w[c] = __dadd_rn(a.obj_pose[(size_t)(xo * 7 + c) * a.stride + so], w[c]);
+                    }
+                    if (qo >= 0) {
+                        double q[4];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) q[c] = a.obj_pose[(size_t)(qo * 7 + 3 + c) * a.stride + so];
+                        const double g[4] = {w[3], w[4], w[5], w[6]};
+                        quat_mul_rn(q, g, w + 3);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 7; ++c) ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)w[c];
+                }
                 err = __builtin_huge_val();
                 a.err[so] = err;
                 moved = true;

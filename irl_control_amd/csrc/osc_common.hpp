@@ -230,6 +230,39 @@ __device__ __forceinline__ void tgt_tile_store(T* tg, const T* s_t, int nvalid, 
     }
 }
 
+// Quaternion helpers of the rollout's float64 program kernels (osc_teleop.hpp, osc_object.hpp, osc_action.hpp): every product and sum
+// rounded on its own and in the order written, so that the host can repeat the bits with plain NumPy expressions.
+//   r = a (x) b, the Hamilton product (w x y z), terms left to right; no normalisation, no sign change
+__device__ __forceinline__ void quat_mul_rn(const double a[4], const double b[4], double r[4]) {
+    r[0] = __dsub_rn(__dsub_rn(__dsub_rn(__dmul_rn(a[0], b[0]), __dmul_rn(a[1], b[1])), __dmul_rn(a[2], b[2])), __dmul_rn(a[3], b[3]));
+    r[1] = __dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(a[0], b[1]), __dmul_rn(a[1], b[0])), __dmul_rn(a[2], b[3])), __dmul_rn(a[3], b[2]));
+    r[2] = __dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(a[0], b[2]), __dmul_rn(a[2], b[0])), __dmul_rn(a[3], b[1])), __dmul_rn(a[1], b[3]));
+    r[3] = __dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(a[0], b[3]), __dmul_rn(a[3], b[0])), __dmul_rn(a[1], b[2])), __dmul_rn(a[2], b[1]));
+}
+//   R(q): transforms.quat2mat without its Nq < eps branch (the callers' quaternions are of unit length to rounding); the one division,
+//   2 / Nq, is correctly rounded like the products
+__device__ __forceinline__ void quat2mat_rn(const double q[4], double R[3][3]) {
+    const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+    const double Nq = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(qw, qw), __dmul_rn(qx, qx)), __dmul_rn(qy, qy)), __dmul_rn(qz, qz));
+    const double s = __ddiv_rn(2.0, Nq);
+    const double X = __dmul_rn(qx, s), Y = __dmul_rn(qy, s), Z = __dmul_rn(qz, s);
+    const double wX = __dmul_rn(qw, X), wY = __dmul_rn(qw, Y), wZ = __dmul_rn(qw, Z);
+    const double xX = __dmul_rn(qx, X), xY = __dmul_rn(qx, Y), xZ = __dmul_rn(qx, Z);
+    const double yY = __dmul_rn(qy, Y), yZ = __dmul_rn(qy, Z), zZ = __dmul_rn(qz, Z);
+    R[0][0] = __dsub_rn(1.0, __dadd_rn(yY, zZ)); R[0][1] = __dsub_rn(xY, wZ); R[0][2] = __dadd_rn(xZ, wY);
+    R[1][0] = __dadd_rn(xY, wZ); R[1][1] = __dsub_rn(1.0, __dadd_rn(xX, zZ)); R[1][2] = __dsub_rn(yZ, wX);
+    R[2][0] = __dsub_rn(xZ, wY); R[2][1] = __dadd_rn(yZ, wX); R[2][2] = __dsub_rn(1.0, __dadd_rn(xX, yY));
+}
+//   R v and R^T v, each row's three products summed left to right
+__device__ __forceinline__ void mat_vec_rn(const double R[3][3], const double v[3], double r[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = __dadd_rn(__dadd_rn(__dmul_rn(R[c][0], v[0]), __dmul_rn(R[c][1], v[1])), __dmul_rn(R[c][2], v[2]));
+}
+__device__ __forceinline__ void mat_t_vec_rn(const double R[3][3], const double v[3], double r[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = __dadd_rn(__dadd_rn(__dmul_rn(R[0][c], v[0]), __dmul_rn(R[1][c], v[1])), __dmul_rn(R[2][c], v[2]));
+}
+
 // zero pattern asked of dense records (osc_structure_kernel): bit c of mrow[j]: M[j][c] may be non-zero; bit c of jcols: column c of J
 struct StructureMasks { uint32_t mrow[32]; uint32_t jcols; };
 

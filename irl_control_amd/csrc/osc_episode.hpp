@@ -13,7 +13,8 @@
 //     tile (osc_common.hpp: its contract; PATHS: waypoint 0 of every listed device on top), the list's state as osc_action_kernel's init
 //     branch leaves it with word 9 of the active device's gain record taken again from the context's gains and, with pose variants,
 //     the robot's lines of the list's pose table rewritten with variant count mod V, the paths' state as the cycler's init, the walls'
-//     and the joint rows' state as their setters' fills;
+//     and the joint rows' state as their setters' fills, the action objects' state as osc_object_kernel's init leaves it, on their
+//     start poses count mod OV; on a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
 //   idle lanes of a ragged last wave neither load nor store.
 // Every wave stores the number of its robots that are not parked into running[walk wave] (a plain store by lane 0): the early exit's input.
 //
@@ -55,6 +56,12 @@ struct EpisodeArgs {
     // walls (osc_wall.hpp): planes [ndev][stride]; joint rows (osc_joint.hpp): rows [stride]
     double* wall_force; double* wall_depth; int32_t* wall_contact; int32_t* wall_first;
     double* jt_tau; double* jt_violation; double* jt_ctrl; int32_t* jt_active;
+    // action objects (osc_object.hpp: its layout): state [row][stride]; start poses [OV][walk wave][nobj 7][64], ob_vstride doubles apart
+    double* ob_pose; double* ob_rel;
+    int32_t* ob_holder; int32_t* ob_grasp; int32_t* ob_release; int32_t* ob_closed; int32_t* ob_mated;
+    const double* ob_pose0;
+    int64_t ob_vstride;
+    int32_t objects, nobj, ng, nm, OV;
     int64_t vstride;
     int32_t wp_count[IRLOSC_MAX_DEV];
     uint8_t wp_loop[IRLOSC_MAX_DEV];
@@ -108,7 +115,13 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
             int32_t* __restrict__ r = a.ring + ((size_t)(cnt % a.records) * 4) * a.stride + so;
             r[0] = first ? a.tick : a.start_tick[so];
             r[(size_t)a.stride] = age;
-            r[2 * (size_t)a.stride] = fin ? IRLOSC_EPISODE_FINISHED : IRLOSC_EPISODE_TIMEOUT;
+            int outcome = fin ? IRLOSC_EPISODE_FINISHED : IRLOSC_EPISODE_TIMEOUT;
+            if (a.nm > 0) {                         // a slot with mates: every one of them mated by this tick's object kernel
+                bool all = true;
+                for (int m = 0; m < a.nm; ++m) all = all & (a.ob_mated[(size_t)m * a.stride + so] >= 0);
+                if (all) outcome |= IRLOSC_EPISODE_INSERTED;
+            }
+            r[2 * (size_t)a.stride] = outcome;
             r[3 * (size_t)a.stride] = (cnt % a.S) | ((a.V > 0 ? cnt % a.V : 0) << 16);
             cnt += 1;
             a.count[so] = cnt;
@@ -172,6 +185,20 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
                 for (int c = 0; c < 3; ++c) a.wall_force[c * plane + o] = 0.0;
                 a.wall_depth[o] = 0.0; a.wall_contact[o] = 0; a.wall_first[o] = -1;
             }
+        }
+        if (a.objects) {                            // as osc_object_kernel's init branch, on start poses count mod OV
+            const double* __restrict__ p0 = a.ob_pose0 + (size_t)(cnt % a.OV) * a.ob_vstride + (size_t)blockIdx.x * a.nobj * 7 * 64 + lane;
+            for (int o = 0; o < a.nobj; ++o) {
+#pragma unroll
+                for (int c = 0; c < 7; ++c) {
+                    a.ob_pose[(size_t)(o * 7 + c) * a.stride + so] = p0[(size_t)(o * 7 + c) * 64];
+                    a.ob_rel[(size_t)(o * 7 + c) * a.stride + so] = 0.0;
+                }
+                const size_t i = (size_t)o * a.stride + so;
+                a.ob_holder[i] = -1; a.ob_grasp[i] = -1; a.ob_release[i] = -1;
+            }
+            for (int g = 0; g < a.ng; ++g) a.ob_closed[(size_t)g * a.stride + so] = 0;
+            for (int m = 0; m < a.nm; ++m) a.ob_mated[(size_t)m * a.stride + so] = -1;
         }
         if (a.joints) {                             // as irlosc_set_joints' fills; ctrl = 0: an ACTION drive lets go
 #pragma unroll

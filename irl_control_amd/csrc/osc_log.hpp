@@ -6,7 +6,8 @@
 //   FRONT, directly behind the give-up pass and in front of the waypoint cycler: QPOS, QVEL (the slot's row-major coordinates, which the
 //       plant has not advanced yet: what the tick's walk read), EE_POSE (the walk's poses in the tick's exchange block), TARGETS and WRENCH
 //       (as the OSC step read them: a list's or a stream's targets of the tick are in, the cycler's move is not), U (the give-up pass has
-//       run: every robot has its torques), FLAGS (the step's word; what the plant adds behind it is not in).
+//       run: every robot has its torques), FLAGS (the step's word; what the plant adds behind it is not in), OBJECT_POSE (the action
+//       objects as this tick's object kernel left them: seven pose words and the holder as a double, per object).
 //   BACK, behind the joint rows and directly in front of the plant: WALL_FORCE and JOINT_TAU, the `force` and `tau` planes of the walls'
 //       and rows' per-robot state as this tick's APPLY launches left them.  Launched only where one of the two is asked for.
 //
@@ -32,14 +33,14 @@
 
 namespace irlosc {
 
-constexpr int LOG_CHANNELS = 9;
+constexpr int LOG_CHANNELS = 10;
 constexpr uint32_t LOG_FRONT = IRLOSC_LOG_QPOS | IRLOSC_LOG_QVEL | IRLOSC_LOG_EE_POSE | IRLOSC_LOG_TARGETS | IRLOSC_LOG_WRENCH |
-                               IRLOSC_LOG_U | IRLOSC_LOG_FLAGS;
+                               IRLOSC_LOG_U | IRLOSC_LOG_FLAGS | IRLOSC_LOG_OBJECT_POSE;
 constexpr uint32_t LOG_BACK = IRLOSC_LOG_WALL_FORCE | IRLOSC_LOG_JOINT_TAU;
 
-// Words per robot of channel bit i
-__host__ __device__ inline int log_width(int i, int n, int ndev) {
-    return i == 0 || i == 1 || i == 5 || i == 8 ? n : i == 2 || i == 3 ? ndev * 7 : i == 4 ? ndev * 6 : i == 6 ? 1 : ndev * 3;
+// Words per robot of channel bit i (nobj: the action objects of the slot; 0: it has none, and no OBJECT_POSE channel)
+__host__ __device__ inline int log_width(int i, int n, int ndev, int nobj = 0) {
+    return i == 9 ? nobj * 8 : i == 0 || i == 1 || i == 5 || i == 8 ? n : i == 2 || i == 3 ? ndev * 7 : i == 4 ? ndev * 6 : i == 6 ? 1 : ndev * 3;
 }
 
 struct LogArgs {
@@ -55,8 +56,10 @@ struct LogArgs {
     const uint32_t* flags;            // [B]
     const double* wall_force;         // [3][ndev][stride]
     const double* joint_tau;          // [n][stride]
+    const double* obj_pose;           // [IRLOSC_MAX_OBJECTS 7][stride] the action objects' poses (osc_object.hpp) ...
+    const int32_t* obj_holder;        // [IRLOSC_MAX_OBJECTS][stride] ... and their holders
     uint32_t mask;                    // the channels of THIS launch
-    int32_t R, n, ndev, n_entries, stride;
+    int32_t R, n, ndev, n_entries, stride, nobj;
     int32_t ee0[IRLOSC_MAX_DEV];      // exchange entry of each device's EE pose (x y z qw qx qy qz follow each other)
 };
 
@@ -126,6 +129,16 @@ __global__ __launch_bounds__(64) void osc_log_kernel(const LogArgs a) {
             for (int j = 0; j < w; ++j) s_t[lane * w + j] = a.joint_tau[(size_t)j * a.stride + rb];
         }
         store_tile(8, w);
+    }
+    if (a.mask & IRLOSC_LOG_OBJECT_POSE) {
+        const int w = a.nobj * 8;
+        if (valid)
+            for (int o = 0; o < a.nobj; ++o) {
+#pragma unroll
+                for (int c = 0; c < 7; ++c) s_t[lane * w + o * 8 + c] = a.obj_pose[(size_t)(o * 7 + c) * a.stride + rb];
+                s_t[lane * w + o * 8 + 7] = (double)a.obj_holder[(size_t)o * a.stride + rb];
+            }
+        store_tile(9, w);
     }
 }
 

@@ -83,27 +83,19 @@ __global__ __launch_bounds__(64) void osc_teleop_kernel(const TeleopArgs a) {
         const double qw = __dsub_rn(__dmul_rn(cx, cc), __dmul_rn(sx, ss)), qx = __dadd_rn(__dmul_rn(cx, ss), __dmul_rn(sx, cc));
         const double qy = __dsub_rn(__dmul_rn(cx, sc), __dmul_rn(sx, cs)), qz = __dadd_rn(__dmul_rn(cx, cs), __dmul_rn(sx, sc));
         // R(q_p): transforms.quat2mat (|q_p| is 1 to rounding, far from its Nq < eps branch)
-        const double Nq = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(qw, qw), __dmul_rn(qx, qx)), __dmul_rn(qy, qy)), __dmul_rn(qz, qz));
-        const double s = __ddiv_rn(2.0, Nq);
-        const double X = __dmul_rn(qx, s), Y = __dmul_rn(qy, s), Z = __dmul_rn(qz, s);
-        const double wX = __dmul_rn(qw, X), wY = __dmul_rn(qw, Y), wZ = __dmul_rn(qw, Z);
-        const double xX = __dmul_rn(qx, X), xY = __dmul_rn(qx, Y), xZ = __dmul_rn(qx, Z);
-        const double yY = __dmul_rn(qy, Y), yZ = __dmul_rn(qy, Z), zZ = __dmul_rn(qz, Z);
-        const double R[3][3] = {{__dsub_rn(1.0, __dadd_rn(yY, zZ)), __dsub_rn(xY, wZ), __dadd_rn(xZ, wY)},
-                                {__dadd_rn(xY, wZ), __dsub_rn(1.0, __dadd_rn(xX, zZ)), __dsub_rn(yZ, wX)},
-                                {__dsub_rn(xZ, wY), __dadd_rn(yZ, wX), __dsub_rn(1.0, __dadd_rn(xX, yY))}};
+        const double qp[4] = {qw, qx, qy, qz};
+        double R[3][3];
+        quat2mat_rn(qp, R);
         for (int d = 0; d < a.ndev; ++d) {
             T* t = s_t + lane * row + d * 7;
             if (a.kind[d] == IRLOSC_TELEOP_RIGID) {
-                const double* o = a.off_xyz[d];
-                const double* q = a.off_quat[d];
+                double ro[3], qt[4];
+                mat_vec_rn(R, a.off_xyz[d], ro);
+                quat_mul_rn(qp, a.off_quat[d], qt);
 #pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    t[c] = (T)__dadd_rn(p[c], __dadd_rn(__dadd_rn(__dmul_rn(R[c][0], o[0]), __dmul_rn(R[c][1], o[1])), __dmul_rn(R[c][2], o[2])));
-                t[3] = (T)__dsub_rn(__dsub_rn(__dsub_rn(__dmul_rn(qw, q[0]), __dmul_rn(qx, q[1])), __dmul_rn(qy, q[2])), __dmul_rn(qz, q[3]));
-                t[4] = (T)__dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(qw, q[1]), __dmul_rn(qx, q[0])), __dmul_rn(qy, q[3])), __dmul_rn(qz, q[2]));
-                t[5] = (T)__dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(qw, q[2]), __dmul_rn(qy, q[0])), __dmul_rn(qz, q[1])), __dmul_rn(qx, q[3]));
-                t[6] = (T)__dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(qw, q[3]), __dmul_rn(qz, q[0])), __dmul_rn(qx, q[2])), __dmul_rn(qy, q[1]));
+                for (int c = 0; c < 3; ++c) t[c] = (T)__dadd_rn(p[c], ro[c]);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) t[3 + c] = (T)qt[c];
             } else if (a.kind[d] == IRLOSC_TELEOP_HEADING) {
                 const double h = __dmul_rn(__dadd_rn(atan2(p[1], p[0]), a.heading[d]), 0.5);
                 t[3] = (T)cos(h); t[4] = (T)0.0; t[5] = (T)0.0; t[6] = (T)sin(h);

@@ -6,7 +6,15 @@ import numpy as np
 CHANNELS = ("qpos", "qvel", "ee_pose", "targets", "wrench", "u", "flags", "wall_force", "joint_tau")
 BITS = {name: 1 << i for i, name in enumerate(CHANNELS)}
 ALL = (1 << len(CHANNELS)) - 1
-MAX_N, MAX_DEV = 32, 4
+# ... and bit 9, IRLOSC_LOG_OBJECT_POSE, which only a slot with action objects knows (nobj > 0 below): [R, nobj, 8], the seven pose words
+# and the holder as a double.  It is no part of CHANNELS / ALL: those are the channels every slot can log.
+OBJECT_POSE = "object_pose"
+OBJECT_POSE_BIT = 1 << len(CHANNELS)
+MAX_N, MAX_DEV, MAX_OBJECTS = 32, 4, 4
+
+
+def _channels(nobj: int) -> tuple:
+    return CHANNELS + (OBJECT_POSE,) if nobj else CHANNELS
 
 
 def mask(channels) -> int:
@@ -17,8 +25,11 @@ def mask(channels) -> int:
         channels = [channels]
     m = 0
     for name in channels:
+        if name == OBJECT_POSE:
+            m |= OBJECT_POSE_BIT
+            continue
         if name not in BITS:
-            raise ValueError(f"unknown log channel {name!r}: one of {CHANNELS}")
+            raise ValueError(f"unknown log channel {name!r}: one of {CHANNELS + (OBJECT_POSE,)}")
         m |= BITS[name]
     return m
 
@@ -26,42 +37,48 @@ def mask(channels) -> int:
 def names(channels) -> tuple:
     """The names of the channels of a mask, in bit order."""
     m = mask(channels)
-    return tuple(name for i, name in enumerate(CHANNELS) if (m >> i) & 1)
+    return tuple(name for i, name in enumerate(CHANNELS + (OBJECT_POSE,)) if (m >> i) & 1)
 
 
-def shape(name: str, n: int, ndev: int) -> tuple:
+def shape(name: str, n: int, ndev: int, nobj: int = 0) -> tuple:
     """The per-robot shape of a channel: its plane is [R, *shape]."""
+    if name == OBJECT_POSE:
+        return (nobj, 8)
     return {"qpos": (n,), "qvel": (n,), "ee_pose": (ndev, 7), "targets": (ndev, 7), "wrench": (ndev, 6), "u": (n,), "flags": (),
             "wall_force": (ndev, 3), "joint_tau": (n,)}[name]
 
 
-def layout(n: int, ndev: int, channels, R: int):
+def layout(n: int, ndev: int, channels, R: int, nobj: int = 0):
     """-> (offset[9] int64, sample_words) as irlosc_log_layout gives them: where each channel's plane [R][w] starts inside a sample, in
-    doubles (-1: not asked for), and the sample's size.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
+    doubles (-1: not asked for), and the sample's size.  With nobj > 0 (a slot with action objects): offset[10] as
+    irlosc_log_layout_objects gives them, the tenth OBJECT_POSE's.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
     m = mask(channels)
-    if m == 0 or m & ~ALL:
+    if not 0 <= nobj <= MAX_OBJECTS:
+        raise ValueError(f"nobj={nobj} out of range")
+    chans = _channels(nobj)
+    if m == 0 or m & ~((1 << len(chans)) - 1):
         raise ValueError(f"channels=0x{m:x} must be a non-empty OR of the IRLOSC_LOG_* bits")
     if R < 1 or not 1 <= n <= MAX_N or not 1 <= ndev <= MAX_DEV:
         raise ValueError(f"R={R}, n={n}, ndev={ndev} out of range")
-    off = np.full(len(CHANNELS), -1, dtype=np.int64)
+    off = np.full(len(chans), -1, dtype=np.int64)
     words = 0
-    for i, name in enumerate(CHANNELS):
+    for i, name in enumerate(chans):
         if (m >> i) & 1:
             off[i] = words
-            words += R * int(np.prod(shape(name, n, ndev), dtype=np.int64))
+            words += R * int(np.prod(shape(name, n, ndev, nobj), dtype=np.int64))
     return off, words
 
 
-def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64) -> dict:
+def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64, nobj: int = 0) -> dict:
     """The raw log buffer [S, sample_words] (float64) as named arrays [S, R, ...].  u, targets and wrench come back in `dtype` (the
     context's: the cast undoes the exact widening), flags as uint32, everything else float64."""
-    off, words = layout(n, ndev, channels, R)
+    off, words = layout(n, ndev, channels, R, nobj)
     buf = np.asarray(buf, dtype=np.float64).reshape(-1, words)
     out = {}
-    for i, name in enumerate(CHANNELS):
+    for i, name in enumerate(_channels(nobj)):
         if off[i] < 0:
             continue
-        shp = shape(name, n, ndev)
+        shp = shape(name, n, ndev, nobj)
         w = int(np.prod(shp, dtype=np.int64))
         a = buf[:, off[i]:off[i] + R * w].reshape((buf.shape[0], R) + shp)
         if name in ("u", "targets", "wrench"):
