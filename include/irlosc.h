@@ -529,7 +529,16 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *     irlosc_set_objects that answers IRLOSC_ERR_HIP                                   no objects, no refs
  *     whatever ends or replaces the slot's list                                        refs end, objects stay
  *     everything else (uploads, targets, gains, feeds, pushes, walls, joint rows, episodes, other steps)  leaves them, their state and their tick alone
- * Only the two rollout entry points run them and advance their tick; episodes reset a robot's objects with the rest of it. */
+ * Only the two rollout entry points run them and advance their tick; episodes reset a robot's objects with the rest of it.
+ * A list's MOTION (irlosc_set_action_motion, "the motion of the list in force" below) is a side description of the list, like its refs:
+ * it writes the targets only through the list's own kernel, so the list stays the one writer.
+ *     irlosc_set_action_motion with motion == NULL                                     the motion ends, the list stays (and jumps again)
+ *     irlosc_set_action_motion that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE         nothing changes: the motion in force stays, whole
+ *     irlosc_set_action_motion that succeeds                                           its motion replaces the one in force; its state reset
+ *     irlosc_set_action_motion that answers IRLOSC_ERR_HIP                             no motion, the list stays
+ *     whatever ends or replaces the slot's list (irlosc_set_action_list included)      the motion ends
+ *     everything else (refs, objects, episodes, uploads, feeds, pushes, walls, rows)   leaves it and its state alone; a reset of
+ *                                                                                      episodes keeps a robot's draws */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -626,6 +635,56 @@ IRLOSC_API int irlosc_set_action_list(irlosc_ctx* ctx, int32_t slot, int32_t B, 
  * IRLOSC_ERR_STATE on a slot without a list, or with a list for fewer than B robots.  Synchronous. */
 IRLOSC_API int irlosc_download_action_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* action, int32_t* grip_left, double* err,
                                             double* max_vel0, double* gripper_force, int32_t* finished_tick);
+
+/* ---- the MOTION of the list in force: INTERP moves and seeded target noise (csrc/osc_action.hpp, csrc/osc_rng.hpp) ------------------
+ * A side description of the list in force, like its refs: irlosc_action_list and its validation are untouched and there is no new
+ * kind.  An INTERP action of the reference's action_sequence_configs/iros2022_task.yaml is a WP with steps[a] = N >= 1: its target
+ * travels from where the arm is to the goal over N control ticks instead of jumping.  `noise: [mean, std]` on a WP or an INTERP is
+ * Gaussian scatter on the goal's position, so that no two demonstrations are alike.  (The reference ships no runner for that file:
+ * these semantics are this library's.)  A slot with a motion runs the action kernel's MOTION form; the list's four steps hold, with:
+ *   3'. entry of a WP:   the goal is composed as in step 3 (table, start_xyz, refs) and KEPT IN FLOAT64.  An action with noise
+ *                        (noise_std[a] > 0 or noise_mean[a] != 0): goal_c += noise_mean[a] + noise_std[a] * z_c for c in x, y, z, every
+ *                        product and sum rounded on its own; then draws += 1.  goal is stored, origin = active_dev's EE pose of this
+ *                        tick, step = 0.  The entry of a GRIP writes none of the motion's state.
+ *       the draw:        (z_0, z_1, z_2) are Box-Muller normals of ONE Philox4x32-10 block: key (seed's low 32 bits, its high 32 bits),
+ *                        counter (robot's index in the slot, draws before the increment, a, 0).  The index is the slot's, not a lane's:
+ *                        a rollout over fewer robots changes nobody's draws.  u = (2 w0 + 1) / 2^33, r = sqrt(-2 ln u), z_0 = r cos(2 pi
+ *                        w1 / 2^32), z_1 = r sin(same); z_2 the cosine branch of (w2, w3).  ln, sin and cos are written out in add,
+ *                        multiply, divide and square root (csrc/osc_rng.hpp), so the host repeats every bit
+ *                        (irl_control_amd/action_motion.py: normal3).
+ *       steps[a] == 0:   tgt[b][active_dev] = goal in the context's dtype, on the entry tick only -- a WP as before.
+ *       steps[a] = N:    on the entry tick and on every later tick in this action while step < N:  step += 1, w = step / N.
+ *                        step < N:   xyz_c = origin_c + w * (goal_c - origin_c);  the quaternion is an nlerp on the short arc: both ends
+ *                                    divided by their norms, the goal's sign flipped where their dot product is negative, the blend
+ *                                    qa_c + w * (qb_c - qa_c) divided by its norm.
+ *                        step == N:  the seven goal words as composed -- no flip, no renormalisation -- so steps = 1 without noise is
+ *                                    a WP bit for bit.
+ *   1'. judgement:       err stays the error against the target AS STORED, which is now the moving one, and feeds the limit of step 4
+ *                        unchanged.  An INTERP advances only when step == N and err <= max_error[a].
+ * All arithmetic above is add, multiply, divide, square root and integer operations, each rounded on its own, in float64 whatever the
+ * context's dtype; the targets are rounded to the dtype when they are written.
+ * EPISODES: a reset leaves the list as irlosc_set_action_list does -- nothing entered -- so the robot's next tick enters action 0 again,
+ * which rewrites goal, origin and step.  draws is deliberately NOT reset: every episode of a robot draws fresh noise. */
+typedef struct irlosc_action_motion {
+    int32_t  steps[IRLOSC_MAX_ACTIONS];      /* 0: the WP jumps; N in [1, 1 << 20]: INTERP over N ticks.  WP actions only */
+    double   noise_mean[IRLOSC_MAX_ACTIONS]; /* finite; metres; WP actions only */
+    double   noise_std[IRLOSC_MAX_ACTIONS];  /* finite, >= 0; WP actions only */
+    uint64_t seed;
+} irlosc_action_motion;
+/* Gives the list in force on slot `slot` its motion.  Call it after irlosc_set_action_list, and after irlosc_set_action_refs where refs
+ * are used.  draw0: uint32 [B of the list], every robot's draws to start from, or NULL: zeros (continue a robot's sequence of draws in a
+ * fresh rollout by passing the draws it has used).  Every argument is checked before anything is touched -- IRLOSC_ERR_ARG: steps < 0
+ * or > 1 << 20, a mean that is not finite, a std that is negative or not finite, or steps / mean / std other than 0 on a GRIP action;
+ * IRLOSC_ERR_STATE: the slot has no list.  In both cases the motion in force stays, whole.  Entries beyond n_actions are not read.  On
+ * success: step 0, draws = draw0, origin and goal 0 for every robot; the list's own state and its tick are left alone (set the motion
+ * before the first rollout).  motion == NULL clears it: the list jumps from pose to pose again.  irlosc_set_action_list, and whatever
+ * else ends the list, ends the motion ("one writer of the targets" above).  Buffers are allocated by the first use; IRLOSC_ERR_HIP
+ * leaves the list in force WITHOUT a motion.  Synchronous. */
+IRLOSC_API int irlosc_set_action_motion(irlosc_ctx* ctx, int32_t slot, const irlosc_action_motion* motion, const uint32_t* draw0);
+/* step: int32 [B]; draws: uint32 [B]; origin, goal: double [B][7] (x y z qw qx qy qz); any may be NULL.  As of the last tick run.
+ * IRLOSC_ERR_STATE on a slot without a list, with a list for fewer than B robots, or whose list has no motion.  Synchronous. */
+IRLOSC_API int irlosc_download_action_motion_state(irlosc_ctx* ctx, int32_t slot, int32_t B, int32_t* step, uint32_t* draws,
+                                                   double* origin, double* goal);
 
 /* ---- the space-mouse teleoperation stream on the GPU: a recorded session inside a rollout (csrc/osc_teleop.hpp) ------------------
  * What examples/teleop_loops.py::space_mouse_loop does on the host per tick -- SpaceMouse.update_state() integrates the device's rate

@@ -40,7 +40,8 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_set_pushes", "irlosc_set_walls", "irlosc_download_wall_state", "irlosc_set_joints",
            "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets",
            "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state",
-           "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects"]
+           "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects",
+           "irlosc_set_action_motion", "irlosc_download_action_motion_state"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
 LOG_OBJECT_POSE = 512                                    # only on a slot with action objects
 EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED = 1, 2, 4
@@ -154,6 +155,12 @@ class ActionRefs(C.Structure):
     _fields_ = [("xyz_obj", C.c_int32 * MAX_ACTIONS), ("quat_obj", C.c_int32 * MAX_ACTIONS)]
 
 
+class ActionMotion(C.Structure):
+    """struct irlosc_action_motion (include/irlosc.h): INTERP steps and target noise of the list in force, irlosc_set_action_motion."""
+    _fields_ = [("steps", C.c_int32 * MAX_ACTIONS), ("noise_mean", C.c_double * MAX_ACTIONS), ("noise_std", C.c_double * MAX_ACTIONS),
+                ("seed", C.c_uint64)]
+
+
 class Cfg(C.Structure):
     _fields_ = [("hip_device", C.c_int32), ("dtype", C.c_int32), ("max_batch", C.c_int32),
                 ("n_slots", C.c_int32), ("n", C.c_int32), ("ndev", C.c_int32),
@@ -247,6 +254,8 @@ def load():
     lib.irlosc_download_object_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.irlosc_set_action_refs.argtypes = [vp, i32, C.POINTER(ActionRefs)]
     lib.irlosc_log_layout_objects.argtypes = [i32, i32, i32, C.c_uint32, i32, vp, vp]
+    lib.irlosc_set_action_motion.argtypes = [vp, i32, C.POINTER(ActionMotion), vp]
+    lib.irlosc_download_action_motion_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.irlosc_slot_structure.argtypes = [vp, C.c_int32]
     lib.irlosc_slot_structure.restype = C.c_int
     lib.irlosc_slot_route.argtypes = [vp, C.c_int32, C.c_int32]

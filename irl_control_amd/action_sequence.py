@@ -197,6 +197,8 @@ def waypoint_target(obj, params, start_xyz):
             quat = euler2quat(*mat2euler(R))
         else:
             quat = euler2quat(*np.deg2rad(tabg))
+    elif "target_quat" in params:                                    # the iros2022 dialect (action_motion.compile_iros2022): taken as given
+        quat = np.asarray(params["target_quat"], dtype=np.float64)
     else:
         quat = DEFAULT_EE_QUAT
     return np.concatenate([xyz, quat])

@@ -534,6 +534,48 @@ class BatchedOSC:
             desc.gripper_force[a] = float(d["gripper_force"][a])
         self._chk(self.lib.irlosc_set_action_list(self._h, slot, B, C.byref(desc), _lib.ptr(pose)))
 
+    # -- the motion of the list in force (irlosc_set_action_motion / irlosc_download_action_motion_state) ------------------------------
+    def set_action_motion(self, steps, noise_mean=None, noise_std=None, seed: int = 0, draw0=None, slot: int = 0):
+        """INTERP moves and seeded target noise for the slot's action list (action_motion.py; "the motion of the list in force" in
+        include/irlosc.h): per action `steps` (0: the WP jumps; N >= 1: its target travels from where the arm is to the goal over N
+        ticks) and `noise_mean`, `noise_std` (Gaussian scatter on the goal's xyz, drawn on the GPU from `seed`, the robot's index, its
+        count of draws and the action -- repeatable, and the same whatever else runs); `steps` may be the motion dict of
+        action_motion.compile_action_motion / make_motion (its seed counts unless `seed` is given non-zero).  `draw0`: [B] draws to
+        start from (default zeros).  After set_action_list, and after set_action_refs where refs are used; set_action_list ends it.
+        steps=None clears the motion and nothing else."""
+        if steps is None:
+            self._chk(self.lib.irlosc_set_action_motion(self._h, slot, None, None))
+            return
+        if isinstance(steps, dict):
+            noise_mean, noise_std, seed, steps = steps["noise_mean"], steps["noise_std"], seed or steps.get("seed", 0), steps["steps"]
+        m = _lib.ActionMotion()
+        n = len(steps)
+        if n > _lib.MAX_ACTIONS:
+            raise ValueError(f"an action list holds up to {_lib.MAX_ACTIONS} actions, got {n} steps")
+        for name, v in (("noise_mean", noise_mean), ("noise_std", noise_std)):
+            if v is not None and len(v) != n:
+                raise ValueError(f"{name}: expected {n} entries like steps, got {len(v)}")
+        for a in range(n):
+            m.steps[a] = int(steps[a])
+            m.noise_mean[a] = 0.0 if noise_mean is None else float(noise_mean[a])
+            m.noise_std[a] = 0.0 if noise_std is None else float(noise_std[a])
+        m.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        d0 = None
+        if draw0 is not None:
+            d0 = np.ascontiguousarray(draw0, dtype=np.uint32)
+            if d0.shape != (self._B[slot],):
+                raise ValueError(f"draw0: expected shape ({self._B[slot]},), got {d0.shape}")
+        self._chk(self.lib.irlosc_set_action_motion(self._h, slot, C.byref(m), _lib.ptr(d0)))
+
+    def action_motion_state(self, slot: int = 0):
+        """-> dict(step [B] int32, draws [B] uint32, origin [B, 7], goal [B, 7]): the motion's state as of the last tick run -- where
+        every robot's INTERP stands, the noise draws it has used, and the float64 goal (noise included) and origin of the WP it entered
+        last.  (irlosc_download_action_motion_state)"""
+        B = self._B[slot]
+        out = dict(step=np.empty(B, np.int32), draws=np.empty(B, np.uint32), origin=np.empty((B, 7)), goal=np.empty((B, 7)))
+        self._chk(self.lib.irlosc_download_action_motion_state(self._h, slot, B, *[_lib.ptr(out[k]) for k in ("step", "draws", "origin", "goal")]))
+        return out
+
     # -- action objects of the rollout (irlosc_set_objects / irlosc_set_action_refs / irlosc_download_object_state) ---------------------
     def set_objects(self, objs, pose0=None, slot: int = 0):
         """Kinematic action objects for the slot's robots (objects.ObjectSet): inside `rollout` an object rides rigidly on the EE of a

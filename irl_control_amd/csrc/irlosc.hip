@@ -57,6 +57,13 @@ struct Program {
     std::vector<double> ts_shared;      // a shared stream's readings [T][6]: they travel as kernel arguments, tick by tick
     int refs = 0;              // 1: the list aims at the slot's action objects as `rf` says (irlosc_set_action_refs)
     irlosc_action_refs rf{};
+    int motion = 0;            // 1: the list's WPs travel and scatter as `am` says (irlosc_set_action_motion): its ticks launch the MOTION kernel
+    irlosc_action_motion am{};
+    DevBuf<int32_t> am_i;      // the motion's per-robot state, allocated by its first use for max_batch robots: step, draws (uint32) ...
+    DevBuf<double> am_d;       // ... origin[7], goal[7]
+    int32_t* m_step(size_t) const { return am_i; }  uint32_t* m_draws(size_t Bm) const { return (uint32_t*)(am_i + Bm); }
+    double* m_origin(size_t) const { return am_d; }  double* m_goal(size_t Bm) const { return am_d + 7 * Bm; }
+    static size_t am_i_words(size_t Bm) { return 2 * Bm; }  static size_t am_d_words(size_t Bm) { return 14 * Bm; }
     // Device buffers, allocated by the first use and kept across programs: per-robot state SoA over max_batch robots (wp_i, al_i, al_d), the
     // table (walk_table), and a list's own gains [robots][ndev][12] and null_kv [robots] in the context's dtype (its rollout reads these per instance)
     // A stream: the pose SoA [6][max_batch] (ts_pose), per-robot readings (ts_table) and per-robot origins (ts_origin), both walk_table.
@@ -77,7 +84,10 @@ struct Program {
     // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
     void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
     // A list of B robots is in force, its state reset by the kernel's init launch and its gain copy made: it writes the targets from here on.
-    void list(int B, const irlosc_action_list& d) { kind = LIST; robots = B; tick = 0; al = d; refs = 0; }
+    void list(int B, const irlosc_action_list& d) { kind = LIST; robots = B; tick = 0; al = d; refs = 0; motion = 0; }
+    // The list in force has a motion, its state on the device / jumps from pose to pose again (its motion was cleared)
+    void moves(const irlosc_action_motion& m) { motion = 1; am = m; }
+    void still() { motion = 0; }
     // The list in force aims at the slot's objects / at its own table alone again (its refs were cleared, or the objects they name changed)
     void aims(const irlosc_action_refs& r) { refs = 1; rf = r; }
     void aimless() { refs = 0; }
@@ -87,7 +97,7 @@ struct Program {
     // The reading a stream takes on the tick to come: tick mod T of one that loops, none (-1) once one that does not has ended
     int reading() const { return kind != STREAM ? -1 : ts.loop ? tick % ts.ticks : tick < ts.ticks ? tick : -1; }
     // The program ends: irlosc_set_targets wrote the targets, another program takes them over, the model changed, or its buffers failed.
-    void end() { kind = NONE; robots = 0; tick = 0; refs = 0; }
+    void end() { kind = NONE; robots = 0; tick = 0; refs = 0; motion = 0; }
     // The program ends if it is of this kind (its own setter cleared it; a list: the gains its copy was made from were replaced): one of the other kind stays whole
     void end(Kind k) { if (kind == k) end(); }
     // A tick of a rollout ran the program's kernel.  (Marked once the whole tick is enqueued: if a launch behind the kernel fails, the
@@ -1850,6 +1860,19 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
     return a;
 }
 
+// ... of a tick of a slot whose list has a motion: the list's, and the motion in force with its state
+static ActionMotionArgs action_motion_args(const irlosc_ctx* c, const Slot& s, int B, const double* xside, int tick) {
+    const Program& p = s.prog;
+    ActionMotionArgs a;
+    memset(&a, 0, sizeof a);
+    static_cast<ActionArgs&>(a) = action_args(c, s, B, p.al, xside, tick);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    a.m_step = p.m_step(Bm); a.m_draws = p.m_draws(Bm); a.m_origin = p.m_origin(Bm); a.m_goal = p.m_goal(Bm);
+    for (int i = 0; i < p.al.n_actions; ++i) { a.steps[i] = p.am.steps[i]; a.noise_mean[i] = p.am.noise_mean[i]; a.noise_std[i] = p.am.noise_std[i]; }
+    a.seed = p.am.seed;
+    return a;
+}
+
 // The arguments of the slot's object kernel over B robots for description d (init: the launch of irlosc_set_objects, d not in force yet;
 // else a tick on exchange block xside)
 static ObjectArgs object_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_objects& d, const double* xside) {
@@ -2148,7 +2171,8 @@ static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, 
     if (tp.push_sense) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_sense, nullptr, wrench), st));
     if (tp.wall_sense) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_sense, nullptr, wrench), st));
     if (tp.objects) HIPCHK(c, (hipError_t)launch_objects(object_args(c, s0, B, s0.objects.d, bk.xside[0]), st));
-    if (tp.prog == Program::LIST) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
+    if (tp.prog == Program::LIST && !s0.prog.motion) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
+    if (tp.prog == Program::LIST && s0.prog.motion) HIPCHK(c, (hipError_t)launch_actions_motion<T>(action_motion_args(c, s0, B, bk.xside[0], s0.prog.tick), st));
     if (tp.reading >= 0) HIPCHK(c, (hipError_t)launch_teleop<T>(teleop_args(c, s0, B, s0.prog.ts, s0.prog.ts_shared.data(), tp.reading), st));
     return IRLOSC_OK;
 }
@@ -3184,6 +3208,56 @@ extern "C" int irlosc_download_action_state(irlosc_ctx* c, int32_t slot, int32_t
         if (dd[i]) HIPCHK(c, hipMemcpyAsync(dd[i], sd[i], (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return IRLOSC_OK;
+}
+
+// ---- the motion of the list in force: INTERP moves and seeded target noise (osc_action.hpp: MOTION; osc_rng.hpp) -----------------------
+extern "C" int irlosc_set_action_motion(irlosc_ctx* c, int32_t slot, const irlosc_action_motion* m, const uint32_t* draw0) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, 0);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    Program& p = s.prog;
+    if (!m) { p.still(); return IRLOSC_OK; }
+    for (int i = 0; p.kind == Program::LIST && i < p.al.n_actions; ++i) {
+        const int32_t st = m->steps[i];
+        const double mean = m->noise_mean[i], sd = m->noise_std[i];
+        if (p.al.kind[i] != IRLOSC_ACTION_WP) {
+            if (st != 0 || mean != 0.0 || sd != 0.0)      // (a NaN is not 0)
+                return fail(c, IRLOSC_ERR_ARG, "action motion: action %d is a GRIP: steps=%d, noise_mean=%g, noise_std=%g must be 0", i, st, mean, sd);
+            continue;
+        }
+        if (st < 0 || st > (1 << 20)) return fail(c, IRLOSC_ERR_ARG, "action motion: steps[%d]=%d out of [0,%d]", i, st, 1 << 20);
+        if (!std::isfinite(mean)) return fail(c, IRLOSC_ERR_ARG, "action motion: noise_mean[%d] is not finite", i);
+        if (!std::isfinite(sd) || sd < 0.0) return fail(c, IRLOSC_ERR_ARG, "action motion: noise_std[%d]=%g must be finite and >= 0", i, sd);
+    }
+    if (p.kind != Program::LIST) return fail(c, IRLOSC_ERR_STATE, "slot %d has no action list (irlosc_set_action_list)", slot);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, B = (size_t)p.robots;
+    irlosc_action_motion clean;
+    memset(&clean, 0, sizeof clean);
+    for (int i = 0; i < p.al.n_actions; ++i) { clean.steps[i] = m->steps[i]; clean.noise_mean[i] = m->noise_mean[i]; clean.noise_std[i] = m->noise_std[i]; }
+    clean.seed = m->seed;
+    p.still();                 // (none until the new one's state is in its buffers)
+    if (!got(p.am_i.ensure(p.am_i_words(Bm) * sizeof(int32_t))) || !got(p.am_d.ensure(p.am_d_words(Bm) * sizeof(double))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the action motion of slot %d", slot);
+    rc = setter_upload(c, {{p.am_i.get(), nullptr, p.am_i_words(Bm) * sizeof(int32_t), 0}, {p.am_d.get(), nullptr, p.am_d_words(Bm) * sizeof(double), 0},
+                           {p.m_draws(Bm), draw0, draw0 ? B * sizeof(uint32_t) : 0, 0}});
+    if (!rc) p.moves(clean);
+    return rc;
+}
+
+extern "C" int irlosc_download_action_motion_state(irlosc_ctx* c, int32_t slot, int32_t B, int32_t* step, uint32_t* draws, double* origin, double* goal) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B, Program::LIST);
+    if (rc) return rc;
+    const Program& p = c->slot[slot].prog;
+    if (!p.motion) return fail(c, IRLOSC_ERR_STATE, "slot %d: its action list has no motion (irlosc_set_action_motion)", slot);
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch;      // rows [max_batch] -> [B], [B], [B][7], [B][7]
+    return download_state(c, B, p.am_d, p.am_d_words(Bm), {{origin, p.m_origin(Bm), 7, 7, 0, 1}, {goal, p.m_goal(Bm), 7, 7, 0, 1}},
+                          p.am_i, p.am_i_words(Bm), {{step, p.m_step(Bm), 1, 1, 0, 1}, {(int32_t*)draws, (const int32_t*)p.m_draws(Bm), 1, 1, 0, 1}});
 }
 
 // ---- the teleoperation stream of the rollout (osc_teleop.hpp) -------------------------------------------------------------------

@@ -98,6 +98,10 @@ int launch_waypoints(const WaypointArgs& a, hipStream_t st);
 struct ActionArgs;
 template <typename T>
 int launch_actions(const ActionArgs& a, hipStream_t st);
+// ... the same tick of a slot whose list has a motion (irlosc_set_action_motion): the kernel's MOTION instantiation
+struct ActionMotionArgs;
+template <typename T>
+int launch_actions_motion(const ActionMotionArgs& a, hipStream_t st);
 
 // tu_object.hip -- the action objects of a rollout tick whose slot has some (osc_object.hpp): behind the walk and the SENSE launches,
 // directly in front of the action kernel; init mode: the launch of irlosc_set_objects

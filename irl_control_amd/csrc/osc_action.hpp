@@ -28,6 +28,23 @@
 // q_grip (quat_mul_rn: no normalisation, no sign change) -- the reference reaches the same rotation through mat2euler -> set_abg, equal
 // up to the quaternion's sign, which calc_error does not see.  Read at ENTRY only: a held object does not drag a target along.
 //
+// MOTION (irlosc_set_action_motion; the MOTION = true instantiation, launched only for a slot that has one -- the MOTION = false
+// instantiation is the kernel above and nothing else).  Per action steps[a] (0: the WP jumps; N >= 1: INTERP, the target travels to the
+// goal over N ticks) and noise_mean[a], noise_std[a]; per robot step, draws, origin[7], goal[7], SoA like the rest.
+//   3'. entry of a WP:   the goal is composed as in 3. and KEPT IN FLOAT64; an action with noise (noise_std[a] > 0 or noise_mean[a] != 0):
+//                        goal_c += noise_mean[a] + noise_std[a] * z_c for c in x, y, z, each product and sum rounded on its own, (z_0, z_1,
+//                        z_2) = normal3(seed, robot's index in the slot, draws, a) (osc_rng.hpp), then draws += 1;  goal is stored,
+//                        origin = the active device's EE pose of this tick, step = 0.  (A GRIP's entry writes none of them.)
+//       steps[a] == 0:   target = goal in the record type, on the entry tick only
+//       steps[a] = N:    on the entry tick and every later tick in this action with step < N:  step += 1, w = step / N;
+//                        step < N:  xyz_c = origin_c + w * (goal_c - origin_c);  quaternion: both ends divided by their norms, the goal's
+//                        sign flipped where their dot product is negative, the blend qa_c + w * (qb_c - qa_c) divided by its norm;
+//                        step == N: the seven goal words as composed (no flip, no renormalisation: steps = 1 without noise is a WP)
+//   1'. an INTERP action advances only when step == N and err <= max_error[a]; err is the error against the target as stored -- the
+//       moving one -- and feeds the limit of 4. unchanged.
+// A reset of episodes leaves entered = -1, which re-enters action 0 and with it rewrites goal, origin and step; draws is NOT reset, so
+// that every episode of a robot draws fresh noise.
+//
 // init = 1 (irlosc_set_action_list): action 0, entered -1, grip_left 0, err +inf, max_vel0 0, gripper_force 0, finished_tick -1,
 // start_xyz 0; neither the exchange block nor the targets are read.
 #pragma once
@@ -36,6 +53,7 @@
 
 #include "../../include/irlosc.h"
 #include "osc_common.hpp"
+#include "osc_rng.hpp"
 
 namespace irlosc {
 
@@ -64,8 +82,41 @@ struct ActionArgs {
     int32_t active, passive, hold;      // device indices (passive -1: none); hold: the passive arm keeps its EE orientation
 };
 
-template <typename T>
-__global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
+// The arguments of the MOTION = true instantiation: the list's, and the motion in force (irlosc_set_action_motion)
+struct ActionMotionArgs : ActionArgs {
+    int32_t* m_step;          // [stride]
+    uint32_t* m_draws;        // [stride]
+    double* m_origin;         // [7][stride]
+    double* m_goal;           // [7][stride]
+    double noise_mean[IRLOSC_MAX_ACTIONS], noise_std[IRLOSC_MAX_ACTIONS];
+    int32_t steps[IRLOSC_MAX_ACTIONS];
+    uint64_t seed;
+};
+static_assert(sizeof(ActionMotionArgs) <= 4096, "kernel arguments travel in a 4 KB segment");
+template <bool MOTION> struct action_args_of { typedef ActionArgs type; };
+template <> struct action_args_of<true> { typedef ActionMotionArgs type; };
+
+// qa + w (qb - qa) between the normalised ends on the short arc, normalised (nlerp); every operation rounded on its own
+__device__ __forceinline__ void quat_nlerp_rn(const double* o, const double* g, double w, double r[4]) {
+    const double no = __dsqrt_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(o[0], o[0]), __dmul_rn(o[1], o[1])), __dmul_rn(o[2], o[2])), __dmul_rn(o[3], o[3])));
+    const double ng = __dsqrt_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(g[0], g[0]), __dmul_rn(g[1], g[1])), __dmul_rn(g[2], g[2])), __dmul_rn(g[3], g[3])));
+    double qa[4], qb[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { qa[c] = __ddiv_rn(o[c], no); qb[c] = __ddiv_rn(g[c], ng); }
+    const double dot = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(qa[0], qb[0]), __dmul_rn(qa[1], qb[1])), __dmul_rn(qa[2], qb[2])), __dmul_rn(qa[3], qb[3]));
+    if (dot < 0.0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) qb[c] = -qb[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = __dadd_rn(qa[c], __dmul_rn(w, __dsub_rn(qb[c], qa[c])));
+    const double nr = __dsqrt_rn(__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(r[0], r[0]), __dmul_rn(r[1], r[1])), __dmul_rn(r[2], r[2])), __dmul_rn(r[3], r[3])));
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = __ddiv_rn(r[c], nr);
+}
+
+template <typename T, bool MOTION = false>
+__global__ __launch_bounds__(64) void osc_action_kernel(const typename action_args_of<MOTION>::type a) {
     __shared__ T s_t[64 * IRLOSC_MAX_DEV * 7];      // the wave's target tile
     const int lane = threadIdx.x;
     const int b0 = (int)blockIdx.x * 64;
@@ -96,6 +147,10 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
         double ea[7];
 #pragma unroll
         for (int c = 0; c < 7; ++c) ea[c] = xs[(size_t)a.ee_act[c] * 64];
+        int stp = 0;                                // MOTION: the robot's step, its goal and origin where this tick enters a WP
+        bool wp_entered = false;
+        double g[7], og[7];
+        if constexpr (MOTION) stp = a.m_step[so];
         if (!first && act < A) {                    // after_step of the previous tick, on the state its plant step produced
             double t7[7], e[6];
 #pragma unroll
@@ -107,8 +162,10 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
             err = __dsqrt_rn(s2);
             a.err[so] = err;
             bool next;
-            if (a.kind[act] == 0) next = err <= a.max_error[act];      // NaN: stays
-            else {
+            if (a.kind[act] == 0) {
+                next = err <= a.max_error[act];     // NaN: stays
+                if constexpr (MOTION) next = next && (a.steps[act] == 0 || stp == a.steps[act]);      // an INTERP has arrived first
+            } else {
                 const int gl = a.grip_left[so] - 1;
                 a.grip_left[so] = gl;
                 next = gl <= 0;
@@ -145,7 +202,10 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
                 const int xo = a.obj_pose ? a.xyz_obj[act] : -1, qo = a.obj_pose ? a.quat_obj[act] : -1;
                 if (xo < 0 && qo < 0) {
 #pragma unroll
-                    for (int c = 0; c < 7; ++c) ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)p[c * cs];
+                    for (int c = 0; c < 7; ++c) {
+                        if constexpr (MOTION) g[c] = (c < 3 && from_start) ? sx[c < 3 ? c : 0] : p[c * cs];
+                        else ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)p[c * cs];
+                    }
                 } else {                            // the table's words are an offset / the grip rotation on the object's pose of this tick
                     double w[7];
 #pragma unroll
@@ -162,13 +222,69 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const ActionArgs a) {
                         quat_mul_rn(q, g, w + 3);
                     }
 #pragma unroll
-                    for (int c = 0; c < 7; ++c) ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)w[c];
+                    for (int c = 0; c < 7; ++c) {
+                        if constexpr (MOTION) g[c] = (c < 3 && from_start) ? sx[c < 3 ? c : 0] : w[c];
+                        else ta[c] = (c < 3 && from_start) ? (T)sx[c < 3 ? c : 0] : (T)w[c];
+                    }
                 }
                 err = __builtin_huge_val();
                 a.err[so] = err;
-                moved = true;
+                if constexpr (MOTION) {
+                    const double mean = a.noise_mean[act], sd = a.noise_std[act];
+                    if (sd > 0.0 || mean != 0.0) {
+                        const uint32_t dr = a.m_draws[so];
+                        double z[3];
+                        normal3(a.seed, (uint32_t)so, dr, (uint32_t)act, z);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) g[c] = __dadd_rn(g[c], __dadd_rn(mean, __dmul_rn(sd, z[c])));
+                        a.m_draws[so] = dr + 1u;
+                    }
+#pragma unroll
+                    for (int c = 0; c < 7; ++c) {
+                        og[c] = ea[c];
+                        a.m_goal[(size_t)c * a.stride + so] = g[c];
+                        a.m_origin[(size_t)c * a.stride + so] = og[c];
+                    }
+                    stp = 0;
+                    wp_entered = true;
+                    if (a.steps[act] == 0) {        // the WP jumps (an INTERP's step and target: below)
+                        a.m_step[so] = 0;
+#pragma unroll
+                        for (int c = 0; c < 7; ++c) ta[c] = (T)g[c];
+                        moved = true;
+                    }
+                } else {
+                    moved = true;
+                }
             } else {
                 a.grip_left[so] = a.grip_ticks[act];
+            }
+        }
+        if constexpr (MOTION) {                     // an INTERP on its way: the entry tick and every later one until step == N
+            const int N = (act < A && a.kind[act] == 0) ? a.steps[act] : 0;
+            if (N >= 1 && stp < N) {
+                if (!wp_entered) {
+#pragma unroll
+                    for (int c = 0; c < 7; ++c) {
+                        g[c] = a.m_goal[(size_t)c * a.stride + so];
+                        og[c] = a.m_origin[(size_t)c * a.stride + so];
+                    }
+                }
+                stp += 1;
+                a.m_step[so] = stp;
+                if (stp < N) {
+                    const double w = __ddiv_rn((double)stp, (double)N);
+                    double q[4];
+                    quat_nlerp_rn(og + 3, g + 3, w, q);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) ta[c] = (T)__dadd_rn(og[c], __dmul_rn(w, __dsub_rn(g[c], og[c])));
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) ta[3 + c] = (T)q[c];
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 7; ++c) ta[c] = (T)g[c];
+                }
+                moved = true;
             }
         }
         if (act < A && a.kind[act] == 0) {          // the error-adaptive velocity limit of the active arm (insertion_task.py:293-295)
