@@ -5,8 +5,11 @@ tick), the scene's joint rows drive the hand (set_joints), and episodes restart 
 (set_episodes).  An object rides rigidly on the EE once the fingers have closed near it, stays where it is let go, and a plug that is
 let go inside its socket's tolerances gives the episode the outcome bit INSERTED.
 
-What this is NOT: contact.  The object has no mass -- nothing acts on the plant or the F/T feed -- nothing collides, falls or slips; a
-released object hangs where it was let go.
+With --mass M the plug weighs M kg (BatchedOSC.set_object_loads: csrc/osc_object_load.hpp): the hand that holds it feels m g on its
+EE body, on the plant and -- a tick later -- in the F/T feed.
+
+What this is NOT: contact.  The weight is quasi-static (no inertial force), nothing collides, falls or slips, the fingers' forces are not
+in the feed; a released object hangs where it was let go.
 
 Two lists:
   the demo's (default)   the twelve actions of action_sequence_configs/insertion_task.yaml on the `nist` parts, each placed where the
@@ -14,8 +17,8 @@ Two lists:
   --carry                CARRY: WP hover -> GRIP close -> WP lift -> WP over the socket -> GRIP open, on poses a few centimetres from
                          the start -- about 1150 ticks an episode; the scenario of tests/test_objects.py.
 
-    python examples/insertion_carry_resident_headless.py [--robots 32] [--episodes 2] [--variants 2] [--carry] [--ticks N]
-    python examples/insertion_carry_resident_headless.py --cpu-loop [--robots 2] [--ticks 1300]      # no GPU: CARRY in NumPy
+    python examples/insertion_carry_resident_headless.py [--robots 32] [--episodes 2] [--variants 2] [--carry] [--ticks N] [--mass M]
+    python examples/insertion_carry_resident_headless.py --cpu-loop [--robots 2] [--ticks 1300] [--mass M]      # no GPU: CARRY in NumPy
 
 Prints the share of episodes with INSERTED."""
 import argparse
@@ -28,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from irl_control_amd import joints, objects as ob, synth             # noqa: E402
+from irl_control_amd import joints, object_loads as ol, objects as ob, synth      # noqa: E402
 from irl_control_amd.rigid_body import DUAL_UR5_EE, RigidBodyModel   # noqa: E402
 import gripper_fleet_resident_headless as grip                       # noqa: E402
 
@@ -50,6 +53,7 @@ OVER_MAX_ERROR = 0.04                       # of the WP over the socket: |xyz er
 KP = 20.0                                   # of the error-adaptive velocity limit: clip(KP err, 0.05, 1) m/s
 DAMPING = 0.0                               # N m s / rad, the plant's joint damping
 SPREAD = 0.03                               # rad per arm joint around the start configuration: see carry_states
+MASS = 0.2                                  # kg of the plug (--mass): chosen on the CPU, see cpu_loop
 OVER_ELBOW = 0.2                            # rad of the elbow between the start and the pose over the socket: 9 cm at the EE
 
 
@@ -131,11 +135,22 @@ def live_table(desc, refs, obj_pose):
     return table
 
 
-def cpu_loop(robots=2, ticks=1300, dt=1e-3, damping=DAMPING, seed=0, verbose=True, far=(), **kw):
+def carry_loads(mass=MASS):
+    """CARRY's loads: the plug weighs `mass` kg at its frame origin, the socket nothing (nobody takes it)"""
+    return ol.ObjectLoads(mass=[float(mass), 0.0])
+
+
+def cpu_loop(robots=2, ticks=1300, dt=1e-3, damping=DAMPING, seed=0, verbose=True, far=(), mass=0.0, **kw):
     """CARRY in NumPy, no GPU -- the loop its thresholds, gears and GRIP lengths were chosen with: gripper_fleet_resident_headless.cpu_loop's
     tick (the rigid-body oracle's records, the list's host restatement, the OSC oracle's u, joints.joint_torque, semi-implicit Euler) with
     objects.object_step in front of the list and the list's table composed on the live objects.
-    -> dict(knuckle [T, B], action [T, B], state: the objects' state at the end, obj_log [T, B, 2, 7])
+    With `mass` > 0 the plug weighs that much (object_loads.load_wrench behind object_step; J^T W of the holder's EE body goes to the
+    plant with the joint rows' torques, as csrc/osc_object_load.hpp takes it off the bias).  MASS = 0.2 kg was chosen with this loop
+    (2 robots, 1300 ticks): grasp on tick 141 / 144 as without a mass, the arm 0.40 mm lower mid-carry (tick 600), release and mate on tick
+    1022 / 1031 (without: 1019 / 1028), the list through on 1131 / 1138 -- CARRY still grasps, carries and mates, inside the band of
+    profiles/object_rates.md (grasped by tick 155, let go from tick 994 on).  0.5 kg does too: 1.0 mm, release on 1028 / 1037.
+    -> dict(knuckle [T, B], action [T, B], state: the objects' state at the end, obj_log [T, B, 2, 7], ee_log [T, B, 3]: the active
+            arm's EE xyz, holder_log [T, B], load_log [T, B, 6])
     Run with the constants above (2 robots, 1300 ticks) it printed: the driven knuckle crosses Q_CLOSE = 0.3 rad 140 ticks into the GRIP
     of 330 ticks and is at its upper stop (0.83 rad) when the arm sets off -- with a GRIP of 170 ticks the hand was still closing then,
     and on the GPU the arm's start pulled the knuckle of 2 robots in 130 back under Q_OPEN: a premature release -- and crosses Q_OPEN =
@@ -166,6 +181,9 @@ def cpu_loop(robots=2, ticks=1300, dt=1e-3, damping=DAMPING, seed=0, verbose=Tru
     state, ost = aseq.action_list_state(robots), ob.object_state(sc["pose0"])
     ctrl = np.zeros((robots, table.shape[1]))
     knuckle, act, olog = np.zeros((ticks, robots)), np.zeros((ticks, robots), np.int32), np.zeros((ticks, robots, 2, 7))
+    eelog, hlog, wlog = np.zeros((ticks, robots, 3)), np.zeros((ticks, robots), np.int32), np.zeros((ticks, robots, 6))
+    loads = carry_loads(mass) if mass else None
+    ee_body = om.body_id(DUAL_UR5_EE[ARM])
     keys = ("M", "J", "dq", "bias", "ee_pose")
     for t in range(ticks):
         recs = [rb.records(om, ld, DUAL_UR5_EE, q[b], qd[b]) for b in range(robots)]
@@ -175,6 +193,11 @@ def cpu_loop(robots=2, ticks=1300, dt=1e-3, damping=DAMPING, seed=0, verbose=Tru
         u = osc_oracle.generate_batch(ld, dict(gains, max_vel=grec[:, :, 9:11].copy()), r["M"], r["J"], r["dq"], r["bias"], r["ee_pose"], tgt)
         tau, ctrl, _ = joints.joint_torque(q, qd, jd, table, ctrl, state["gripper_force"], ia)
         knuckle[t], act[t], olog[t] = q[:, kn], state["action"], ost["pose"]
+        eelog[t], hlog[t] = r["ee_pose"][:, ia, :3], ost["holder"][:, 0]
+        if loads is not None:                             # the weight of what the hand holds after this tick's object step, on the plant
+            W = ol.load_wrench(loads, objs, r["ee_pose"], ost["pose"], ost["holder"])[:, 0]
+            wlog[t] = W
+            tau = tau + np.array([np.vstack(rb.body_jacobian(om, recs[b]["kin"], ee_body)).T @ W[b] for b in range(robots)])
         qacc = np.linalg.solve(r["M"], (u - r["bias"] - damping * qd + tau)[:, :, None])[:, :, 0]
         qd = qd + dt * qacc
         q = q + dt * qd
@@ -185,7 +208,7 @@ def cpu_loop(robots=2, ticks=1300, dt=1e-3, damping=DAMPING, seed=0, verbose=Tru
             print(f"robot {b}: actions entered on ticks {ent}, through on {int(state['finished_tick'][b])}; knuckle crosses q_close {cross(Q_CLOSE, ent[1], True)} "
                   f"ticks into the closing GRIP, q_open {cross(Q_OPEN, ent[4], False)} into the opening one (max {knuckle[:, b].max():.3f} rad); grasp "
                   f"{ost['grasp_tick'][b, 0]}, release {ost['release_tick'][b, 0]}, mated {ost['mated_tick'][b, 0]}")
-    return dict(knuckle=knuckle, action=act, state=ost, obj_log=olog, finished=state["finished_tick"].copy())
+    return dict(knuckle=knuckle, action=act, state=ost, obj_log=olog, finished=state["finished_tick"].copy(), ee_log=eelog, holder_log=hlog, load_log=wlog)
 
 
 def make_ctx(robots, dtype=np.float64, n_slots=1, dt=1e-3, damping=DAMPING):
@@ -220,9 +243,9 @@ def summary(st, verbose=True):
     return dict(episodes=len(rec), inserted=ins, finished=fin, share=share)
 
 
-def run_carry(robots=32, ticks=3200, episodes=2, variants=2, limit=1500, seed=0, verbose=True):
+def run_carry(robots=32, ticks=3200, episodes=2, variants=2, limit=1500, seed=0, verbose=True, mass=0.0):
     """CARRY with episodes: every robot's episode e starts from start state e mod V on its objects' start poses e mod V (the list's
-    table of offsets and grip rotations likewise)"""
+    table of offsets and grip rotations likewise).  mass > 0: the plug weighs that much (set_object_loads, behind set_objects)."""
     osc = make_ctx(robots)
     lay = osc.layout
     q, near, over = carry_states(robots, seed, variants)
@@ -236,6 +259,8 @@ def run_carry(robots=32, ticks=3200, episodes=2, variants=2, limit=1500, seed=0,
     osc.set_action_list(scs[0]["desc"])
     osc.set_joints(grip.scene_rows())
     osc.set_objects(scs[0]["objs"], np.stack([s["pose0"] for s in scs]))
+    if mass:
+        osc.set_object_loads(carry_loads(mass))
     osc.set_action_refs(scs[0]["refs"]["xyz_obj"], scs[0]["refs"]["quat_obj"])
     osc.set_episodes(np.swapaxes(q, 0, 1), None, max_ticks=limit, max_episodes=episodes, poses=np.stack([s["desc"]["pose"] for s in scs]),
                      records=16, poll_every=64 if episodes else 0)
@@ -243,7 +268,7 @@ def run_carry(robots=32, ticks=3200, episodes=2, variants=2, limit=1500, seed=0,
     st = osc.episode_state()
     osc.close()
     if verbose:
-        print(f"CARRY: {robots} robots, {out['ticks_run']} ticks in one call, {int(st['count'].sum())} episodes ended")
+        print(f"CARRY: {robots} robots, {out['ticks_run']} ticks in one call, {int(st['count'].sum())} episodes ended" + (f", the plug weighing {mass} kg" if mass else ""))
     return dict(summary(st, verbose), ticks_run=out["ticks_run"], count=st["count"], records=st["records"])
 
 
@@ -333,12 +358,13 @@ if __name__ == "__main__":
     ap.add_argument("--grip-ticks", type=int, default=150)
     ap.add_argument("--carry", action="store_true")
     ap.add_argument("--cpu-loop", action="store_true")
+    ap.add_argument("--mass", type=float, default=0.0, help=f"kg of the plug (CARRY and --cpu-loop; 0: no loads; chosen on the CPU: {MASS})")
     a = ap.parse_args()
     if a.cpu_loop:
-        cpu_loop(a.robots or 2, a.ticks or 1300)
+        cpu_loop(a.robots or 2, a.ticks or 1300, mass=a.mass)
         sys.exit(0)
     if a.carry:
-        r = run_carry(a.robots or 32, a.ticks or 3200, a.episodes, a.variants, a.limit or 1500)
+        r = run_carry(a.robots or 32, a.ticks or 3200, a.episodes, a.variants, a.limit or 1500, mass=a.mass)
     else:
         r = run(a.robots or 32, a.ticks or 70000, a.episodes, a.variants, a.limit or 30000, a.grip_ticks)
     sys.exit(0 if r["inserted"] > 0 else 1)

@@ -521,8 +521,14 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *                                                                                      the windows are the slot's ticks, not a robot's
  *     everything else (uploads of coordinates, feeds, gains without a list, walls, joint rows, other steps)  leaves them alone
  * Only irlosc_rollout_from_q and irlosc_rollout_from_q_logged run them and advance their tick.
- * ACTION OBJECTS (irlosc_set_objects, "action objects" below) write no targets and act on nothing: they coexist with every program,
- * pushes, walls, joint rows and episodes, and none ends another.  A list's REFS (irlosc_set_action_refs) name the objects in force:
+ * ACTION OBJECTS (irlosc_set_objects, "action objects" below) write no targets and, without loads, act on nothing: they coexist with every
+ * program, pushes, walls, joint rows and episodes, and none ends another.  Their LOADS (irlosc_set_object_loads) are a side description of
+ * the objects in force -- a carried object's weight on the plant and in the feed -- and end with them:
+ *     irlosc_set_object_loads with desc == NULL                                        the loads end; the objects and their state stay
+ *     irlosc_set_object_loads that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE          nothing changes: the loads in force stay, whole
+ *     irlosc_set_object_loads that succeeds                                            its loads replace those in force; their state and tick reset
+ *     irlosc_set_object_loads that answers IRLOSC_ERR_HIP                              no loads, the objects stay
+ *     irlosc_set_objects (set or clear, unless refused), irlosc_set_model              the loads end  A list's REFS (irlosc_set_action_refs) name the objects in force:
  *     irlosc_set_objects with desc == NULL, irlosc_set_model (all slots)               objects end, and the list's refs with them
  *     irlosc_set_objects that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE               nothing changes: objects and refs in force stay, whole
  *     irlosc_set_objects that succeeds                                                 its objects replace those in force; state and tick reset; refs end
@@ -901,7 +907,7 @@ IRLOSC_API int irlosc_download_joint_state(irlosc_ctx* ctx, int32_t slot, int32_
  *   BACK channels (WALL_FORCE, JOINT_TAU), gathered behind the joint rows and directly in front of the plant: the `force` and `tau` that
  *     irlosc_download_wall_state / irlosc_download_joint_state would read behind this tick.
  * The log only reads: coordinates, torques, flags, programs, pushes, walls and rows of a logged rollout are bit for bit those of the
- * unlogged one, all tick counts continue as there, and the order of a tick's launches (pushes, then walls, then joint rows on one bias
+ * unlogged one, all tick counts continue as there, and the order of a tick's launches (pushes, then walls, then loads, then joint rows on one bias
  * entry) is unchanged.  A rollout without a log launches exactly the kernels it launched before. */
 #define IRLOSC_LOG_QPOS        1u   /* [R][n]        coordinates at the START of the tick: what the tick's walk read            */
 #define IRLOSC_LOG_QVEL        2u   /* [R][n]                                                                                    */
@@ -1028,8 +1034,10 @@ IRLOSC_API int irlosc_download_episode_state(irlosc_ctx* ctx, int32_t slot, int3
  * The insertion demo grips the male part, carries it to the female part and releases it there; in the reference a WP reads an object's
  * pose from the simulator when it is entered (insertion_task.py:226-262).  OBJECTS give a slot's rollouts that much of it, and no more:
  * an object rides rigidly on an EE once that arm's fingers have closed near it, stays where it is let go, a WP of the slot's action
- * list can aim at its live pose, and a plug released inside its socket's tolerances is recorded.  What this is NOT: the object has no
- * mass -- nothing acts on the plant or the F/T feed; no collision, no gravity, no slipping; a released object hangs where it was let go.
+ * list can aim at its live pose, and a plug released inside its socket's tolerances is recorded.  With LOADS (irlosc_set_object_loads,
+ * below) a held object also has a weight, which the plant and the F/T feed see.  What this is NOT: no inertial force (the weight is
+ * quasi-static: m g, never m a), no fall (a released object hangs where it was let go, and a free one weighs on nothing), no collision, no
+ * slipping, and the fingers' forces are not in the feed.
  * One more small kernel per tick, behind the walk (and the feed's SENSE launches) and directly in front of the action kernel, so a WP
  * entered on tick t sees the objects of tick t.  Float64 whatever the context's dtype, only + - x, comparisons and the one correctly
  * rounded division of quat2mat (2 / |q|^2), every operation rounded on its own: irl_control_amd/objects.py::object_step repeats the bits.
@@ -1051,7 +1059,7 @@ IRLOSC_API int irlosc_download_episode_state(irlosc_ctx* ctx, int32_t slot, int3
  *   4. mates, ascending m, with mated_tick < 0 and the plug free: target xyz = p_sock + R(q_sock) seat_xyz, quat = q_sock (x) seat_quat;
  *      |p_plug - target|^2 <= tol_xyz^2 and |q_plug . q_target| >= min_abs_dot -> mated_tick = t
  * Episodes (above) reset a robot's objects with the rest of it: free, pose = start poses count mod V, ticks -1, was_closed 0; and on a
- * slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED.  Order of calls: program, objects, refs, then episodes.
+ * slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED.  Order of calls: program, objects, loads, refs, then episodes.
  * A slot without objects launches exactly the kernels it launched before. */
 #define IRLOSC_MAX_OBJECTS  4
 #define IRLOSC_MAX_GRIPPERS 2
@@ -1089,6 +1097,38 @@ IRLOSC_API int irlosc_set_objects(irlosc_ctx* ctx, int32_t slot, int32_t B, cons
  * cover fewer than B robots.  Synchronous. */
 IRLOSC_API int irlosc_download_object_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* pose, int32_t* holder, double* rel,
                                             int32_t* grasp_tick, int32_t* release_tick, int32_t* mated_tick);
+/* The slot's objects get a WEIGHT (csrc/osc_object_load.hpp): per object a mass and a centre of mass in the object's frame, and a gravity
+ * vector.  A gripper that holds an object feels the weight as a wrench on its device's EE body, at the body's frame origin, the way a wall's
+ * force is felt (irlosc_set_walls): computed on the device per robot and tick, added to the bias in front of the plant -- behind the pushes
+ * and the walls, in front of the joint rows -- remembered for one tick and taken off the feed's wrench on the next (slots with a feed,
+ * devices with a sensor), all six words.  Per tick and gripper g, ascending, with o the lowest object whose holder is g after this tick's
+ * object kernel:
+ *     no such object, or mass[o] == 0:   W_g = 0
+ *     else   c = R(q_obj) com,  p_c = p_obj + c,  r = p_c - p_ee,  F = mass gravity,  T = r x F,  W_g = (F, T)
+ *     a word of W_g that is not finite:  W_g = 0 on this tick, and the tick is not counted
+ *     unless W_g is all zero:            bias_i = fma(-J[5][i], W5, ... fma(-J[0][i], W0, bias_i)) on every hinge above the EE body -- the
+ *                                        pushes' chain -- and carry_ticks[g] += 1
+ * Float64 whatever the context's dtype, every operation rounded on its own: irl_control_amd/object_loads.py::load_wrench repeats the bits.
+ * QUASI-STATIC: the object's inertial force m a is not modelled; nothing falls, collides or slips, and the fingers' forces are not in the
+ * feed.  The existing wrench channel of the log carries the sensed weight; there is no channel of its own.
+ * table: [n_objects][4] (per_robot == 0: shared by the fleet) or [B][n_objects][4]; row of object o: mass (>= 0), com_x com_y com_z in the
+ * object's frame.  Every argument is checked before anything is touched (IRLOSC_ERR_ARG: B < 1, table NULL, a value that is not finite,
+ * mass < 0, per_robot outside {0, 1}, reserved != 0; the loads in force stay, whole).  IRLOSC_ERR_STATE: the slot has no objects, or they
+ * cover fewer than B robots.  desc == NULL clears the loads and leaves the objects' state untouched.  irlosc_set_objects, set or clear,
+ * ends the loads, and so does the model's change.  On success the per-robot state is zero -- load 0, carry_ticks 0 -- and the loads' tick
+ * base is 0.  A rollout over more robots than the loads cover answers IRLOSC_ERR_STATE.  Episodes reset a robot's load words and
+ * carry_ticks to zero.  Buffers are allocated by the first use; IRLOSC_ERR_HIP leaves the slot without loads.  A slot without loads
+ * launches exactly the kernels it launched before.  Synchronous. */
+typedef struct irlosc_object_loads {
+    int32_t per_robot;                               /* 0: table [n_objects][4] shared by the fleet; 1: [B][n_objects][4] */
+    int32_t reserved;                                /* 0 */
+    double gravity[3];                               /* world frame, e.g. 0 0 -9.81 */
+} irlosc_object_loads;
+IRLOSC_API int irlosc_set_object_loads(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_object_loads* desc, const double* table);
+/* The loads' per-robot state of the slot's first B robots: load[B][n_grippers][6] (double: the wrench the last tick applied per gripper,
+ * fx fy fz tx ty tz, world frame), carry_ticks[B][n_grippers] (int32: ticks on which a weight was applied); either may be NULL.
+ * IRLOSC_ERR_STATE: the slot has no loads, or they cover fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_object_load_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* load, int32_t* carry_ticks);
 /* The slot's action list aims at its objects.  For a WP action a with xyz_obj[a] >= 0 the xyz words of the list's pose a are an OFFSET:
  * on entry, target xyz = the object's xyz + offset, one add per word (the reference's obj_pos + offset); xyz_from_start wins.  With
  * quat_obj[a] >= 0 the quaternion words are the grip rotation: target quat = q_obj (x) q_grip, the Hamilton product with its terms left

@@ -41,7 +41,8 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_download_joint_state", "irlosc_set_teleop_stream", "irlosc_download_teleop_state", "irlosc_download_targets",
            "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state",
            "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects",
-           "irlosc_set_action_motion", "irlosc_download_action_motion_state"]
+           "irlosc_set_action_motion", "irlosc_download_action_motion_state", "irlosc_set_object_loads",
+           "irlosc_download_object_load_state"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
 LOG_OBJECT_POSE = 512                                    # only on a slot with action objects
 EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED = 1, 2, 4
@@ -150,6 +151,11 @@ class Objects(C.Structure):
                 ("tol_xyz", C.c_double * MAX_MATES), ("min_abs_dot", C.c_double * MAX_MATES)]
 
 
+class ObjectLoads(C.Structure):
+    """struct irlosc_object_loads (include/irlosc.h): the weight of the slot's action objects, irlosc_set_object_loads."""
+    _fields_ = [("per_robot", C.c_int32), ("reserved", C.c_int32), ("gravity", C.c_double * 3)]
+
+
 class ActionRefs(C.Structure):
     """struct irlosc_action_refs (include/irlosc.h): the objects a list's WP actions aim at, irlosc_set_action_refs."""
     _fields_ = [("xyz_obj", C.c_int32 * MAX_ACTIONS), ("quat_obj", C.c_int32 * MAX_ACTIONS)]
@@ -252,6 +258,8 @@ def load():
     lib.irlosc_download_episode_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.irlosc_set_objects.argtypes = [vp, i32, i32, C.POINTER(Objects), vp]
     lib.irlosc_download_object_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.irlosc_set_object_loads.argtypes = [vp, i32, i32, C.POINTER(ObjectLoads), vp]
+    lib.irlosc_download_object_load_state.argtypes = [vp, i32, i32, vp, vp]
     lib.irlosc_set_action_refs.argtypes = [vp, i32, C.POINTER(ActionRefs)]
     lib.irlosc_log_layout_objects.argtypes = [i32, i32, i32, C.c_uint32, i32, vp, vp]
     lib.irlosc_set_action_motion.argtypes = [vp, i32, C.POINTER(ActionMotion), vp]

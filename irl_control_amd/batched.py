@@ -35,6 +35,7 @@ class BatchedOSC:
         self._joint_rows = [0] * self.n_slots      # rows of each slot's set_joints (the width of joint_state's arrays)
         self._episode_records = [1] * self.n_slots      # ring length of each slot's set_episodes (the width of episode_state's records)
         self._objects = [(0, 0)] * self.n_slots      # (objects, mates) of each slot's set_objects (the widths of object_state's arrays)
+        self._grippers = [0] * self.n_slots          # ... and its grippers (the width of object_load_state's)
         if kernel == _lib.KERNEL_AUTO and self.max_batch >= 1024 and self.kernel_class == _lib.CLASS_GENERIC:
             import warnings
             warnings.warn(f"layout (n={layout.n}, k={layout.k}, ndev={layout.ndev}) has no throughput kernel: "
@@ -213,6 +214,7 @@ class BatchedOSC:
         self._model = model
         self._joint_rows = [0] * self.n_slots      # (irlosc_set_model ends every slot's joint rows)
         self._objects = [(0, 0)] * self.n_slots    # (... and action objects)
+        self._grippers = [0] * self.n_slots
 
     def upload_q(self, qpos, qvel, slot: int = 0):
         B = int(np.shape(qpos)[0])
@@ -580,13 +582,15 @@ class BatchedOSC:
     def set_objects(self, objs, pose0=None, slot: int = 0):
         """Kinematic action objects for the slot's robots (objects.ObjectSet): inside `rollout` an object rides rigidly on the EE of a
         gripper whose fingers close near it (the rising edge of `closed`, inside the object's radius), stays where it is let go, and a
-        plug that is free inside its socket's tolerances is recorded as mated.  No mass, no contact, no gravity, no slipping.
+        plug that is free inside its socket's tolerances is recorded as mated.  No contact, no fall, no slipping; a weight only with
+        set_object_loads.
         `pose0`: [B, nobj, 7] start poses (x y z qw qx qy qz), or [V, B, nobj, 7]: variants that episodes cycle (a reset takes
         variant count mod V).  After set_model and upload_q; resets the objects' state and ends the list's refs.  objs=None clears."""
         B = self._B[slot]
         if objs is None:
             self._chk(self.lib.irlosc_set_objects(self._h, slot, B, None, None))
             self._objects[slot] = (0, 0)
+            self._grippers[slot] = 0
             return
         objs.check()
         NO = objs.n_objects
@@ -598,6 +602,35 @@ class BatchedOSC:
         d = objs.to_struct(p0.shape[0])
         self._chk(self.lib.irlosc_set_objects(self._h, slot, B, C.byref(d), _lib.ptr(p0)))
         self._objects[slot] = (NO, len(objs.mates))
+        self._grippers[slot] = len(objs.grippers)
+
+    # -- the weight of the action objects (irlosc_set_object_loads / irlosc_download_object_load_state) ---------------------------------
+    def set_object_loads(self, loads, slot: int = 0):
+        """A weight for the slot's action objects (object_loads.ObjectLoads: per object a mass and a centre of mass, and gravity): inside
+        `rollout` a gripper that holds an object feels m g at the object's centre of mass as a wrench on its EE body -- on the plant on
+        that tick, behind the pushes and the walls, and in the F/T wrench of the next tick (slots with a sensor feed).  Quasi-static: no
+        inertial force, no fall, no collision, no slipping, and the fingers' forces are not in the feed.  After set_objects (which ends the
+        loads, as set_model does), in front of set_action_refs and set_episodes; resets the loads' state and tick.  loads=None clears them
+        and leaves the objects' state alone."""
+        B = self._B[slot]
+        if loads is None:
+            self._chk(self.lib.irlosc_set_object_loads(self._h, slot, B, None, None))
+            return
+        NO = self._objects[slot][0]
+        if not NO:
+            raise _lib.IrloscError("set_objects must precede set_object_loads")
+        table = np.ascontiguousarray(loads.table(B, NO))
+        d = loads.to_struct(table.shape[0] > 1)      # (a lone robot's table is the shared form)
+        self._chk(self.lib.irlosc_set_object_loads(self._h, slot, B, C.byref(d), _lib.ptr(table)))
+
+    def object_load_state(self, slot: int = 0):
+        """-> dict(load [B, n_grippers, 6]: the wrench the last tick applied per gripper (fx fy fz tx ty tz, world frame; zeros where it
+        holds nothing), carry_ticks [B, n_grippers]: the ticks on which a weight was applied since set_object_loads or the robot's last
+        reset).  (irlosc_download_object_load_state)"""
+        B, NG = self._B[slot], self._grippers[slot]
+        out = dict(load=np.empty((B, NG, 6)), carry_ticks=np.empty((B, NG), np.int32))
+        self._chk(self.lib.irlosc_download_object_load_state(self._h, slot, B, _lib.ptr(out["load"]) if NG else None, _lib.ptr(out["carry_ticks"]) if NG else None))
+        return out
 
     def set_action_refs(self, xyz_obj, quat_obj=None, slot: int = 0):
         """The slot's action list aims at its objects: per action the object (index, or -1) whose live xyz a WP's pose words are an

@@ -31,6 +31,7 @@
 #include "osc_object.hpp"
 #include "osc_push.hpp"
 #include "osc_wall.hpp"
+#include "osc_object_load.hpp"
 #include "osc_joint.hpp"
 #include "osc_log.hpp"
 #include "osc_episode.hpp"
@@ -167,8 +168,8 @@ struct Joints : PlantForce {
     void set(int B, const irlosc_joint_rows& desc) { in_force(B); d = desc; }
 };
 
-// The action objects (irlosc_set_objects, osc_object.hpp): kinematic bodies a gripper carries.  They act on nothing -- no force on the
-// plant, none in the feed -- but live here with the parts that have a table (the start poses), per-robot state and a tick of their own.
+// The action objects (irlosc_set_objects, osc_object.hpp): kinematic bodies a gripper carries.  By themselves they act on nothing -- no force on the
+// plant, none in the feed: that is their Loads', below -- but live here with the parts that have a table (the start poses), per-robot state and a tick of their own.
 struct Objects : PlantForce {
     irlosc_objects d{};        // the description in force
     size_t vstride = 0;        // doubles between two variants' start poses in `table` ([V][walk wave][nobj 7][64])
@@ -183,6 +184,19 @@ struct Objects : PlantForce {
     static size_t d_words(size_t Bm) { return (size_t)OBJ_D_ROWS * Bm; }  static size_t i_words(size_t Bm) { return (size_t)OBJ_I_ROWS * Bm; }
     void set(int B, const irlosc_objects& desc, size_t vs) { in_force(B); d = desc; vstride = vs; }
     int count() const { return robots ? d.n_objects : 0; }      // objects of the slot (0: it has none)
+};
+
+// The carried objects' weight (irlosc_set_object_loads, osc_object_load.hpp): a side description of the slot's objects -- per object a
+// mass and a centre of mass, and gravity -- whose wrench on the holder's EE body is computed on the device per robot and tick, applied to
+// the plant and taken off the sensor feed's wrench a tick later.  They live and end with the objects they describe.
+struct Loads : PlantForce {
+    irlosc_object_loads d{};   // the description in force (per_robot: how `table` is laid out -- a lone robot's is the shared form)
+    DevBuf<double> st_d;       // per-robot state, allocated by the first use for max_batch robots: load[MAX_GRIPPERS 6]
+    DevBuf<int32_t> st_i;      // ... carry_ticks[MAX_GRIPPERS]
+    // THE LAYOUT of the state (osc_object_load.hpp): rows of Bm = max_batch words
+    double* load(size_t) const { return st_d; }  int32_t* carry_ticks(size_t) const { return st_i; }
+    static size_t d_words(size_t Bm) { return (size_t)IRLOSC_MAX_GRIPPERS * 6 * Bm; }  static size_t i_words(size_t Bm) { return (size_t)IRLOSC_MAX_GRIPPERS * Bm; }
+    void set(int B, const irlosc_object_loads& desc) { in_force(B); d = desc; }
 };
 
 // The episodes (irlosc_set_episodes, osc_episode.hpp): per robot the judgement whether its running episode has ended, its record and its
@@ -246,6 +260,7 @@ struct Slot {
     Walls walls;               // what the EE bodies run into inside a rollout
     Joints joints;             // what acts on single hinges inside a rollout: stops, couplings, drives
     Objects objects;           // what the grippers carry inside a rollout
+    Loads loads;               // what the carried objects weigh (only next to the objects they describe)
     Episodes episodes;         // what ends and restarts single robots inside a rollout
     int ticks_run = 0;         // ticks the last rollout call on the slot ran (fewer than asked: an early exit of its episodes)
 
@@ -1655,7 +1670,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); s.objects.end(); s.episodes.end(); }
+    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); s.objects.end(); s.loads.end(); s.episodes.end(); }
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1970,6 +1985,24 @@ static WallArgs wall_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t de
     return a;
 }
 
+// The arguments of the slot's load kernel over B robots: the grippers of `grippers`, their weight applied to exchange block xside or
+// (xside == nullptr) their stored load taken off the feed's wrench
+static ObjectLoadArgs load_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t grippers, double* xside, void* wrench) {
+    const Loads& l = s.loads;
+    const Objects& o = s.objects;
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    ObjectLoadArgs a;
+    memset(&a, 0, sizeof a);
+    a.xside = xside; a.wrench = wrench; a.table = l.table;
+    a.obj_pose = o.pose(Bm); a.obj_holder = o.holder(Bm); a.load = l.load(Bm); a.carry_ticks = l.carry_ticks(Bm);
+    for (int i = 0; i < 3; ++i) a.gravity[i] = l.d.gravity[i];
+    a.B = B; a.ndev = c->cfg.ndev; a.nobj = o.d.n_objects; a.ng = o.d.n_grippers; a.per_robot = l.d.per_robot; a.stride = (int32_t)Bm;
+    a.apply = xside ? 1 : 0; a.grippers = grippers;
+    for (int g = 0; g < o.d.n_grippers; ++g) a.dev[g] = o.d.dev[g];
+    fill_ee0(c, a.ee0);
+    return a;
+}
+
 // The arguments of the slot's joint-row kernel over B robots on exchange block xside: per hinge the rows that name it, in ascending row
 // (the accumulation order of osc_joint.hpp), and the ACTION drives that the list in force arms on this tick
 static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* xside) {
@@ -2067,6 +2100,7 @@ static EpisodeArgs episode_args(const irlosc_ctx* c, const Slot& s, int B, const
         a.ob_pose = o.pose(Bm); a.ob_rel = o.rel(Bm); a.ob_holder = o.holder(Bm); a.ob_grasp = o.grasp_tick(Bm); a.ob_release = o.release_tick(Bm);
         a.ob_closed = o.was_closed(Bm); a.ob_mated = o.mated_tick(Bm); a.ob_pose0 = o.table; a.ob_vstride = (int64_t)o.vstride;
     }
+    if (!init && s.loads.robots) { a.loads = 1; a.ld_load = s.loads.load(Bm); a.ld_carry = s.loads.carry_ticks(Bm); }
     a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.S = d.n_starts; a.starts_per_robot = e.starts_per_robot;
     a.max_ticks = d.max_ticks; a.end_on_finish = d.end_on_finish; a.max_episodes = d.max_episodes; a.records = d.records;
     a.tick = e.tick; a.init = init ? 1 : 0;
@@ -2136,9 +2170,10 @@ static int download_state(irlosc_ctx* c, int B, const double* sd, size_t nd, std
 }
 
 // What a tick of a rollout runs next to its fused step, decided once per tick from the slot (the default: no tick, nothing): the program that writes its
-// targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); rows
+// targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); the
+// grippers whose carried object weighs on the plant, and those whose device's sensor reads the weight of the tick before; rows
 // it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on); episodes it has
-struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; bool objects = false; };
+struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; bool objects = false; uint32_t load_apply = 0, load_sense = 0; };
 static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
     TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading(), s0.episodes.robots != 0, s0.objects.robots != 0};
     for (int p = 0; tp.push_sense && p < IRLOSC_MAX_PUSHES; ++p)
@@ -2146,30 +2181,35 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
     if (s0.feed > 0 && s0.walls.tick > 0) tp.wall_sense = tp.wall_apply;
     for (int d = 0; tp.wall_sense && d < c->cfg.ndev; ++d)
         if (c->ft_f0[d] < 0) tp.wall_sense &= ~(1u << d);
+    for (int g = 0; s0.loads.robots && g < s0.objects.d.n_grippers; ++g) {      // the grippers: bit g
+        tp.load_apply |= 1u << g;
+        if (s0.feed > 0 && s0.loads.tick > 0 && c->ft_f0[s0.objects.d.dev[g]] >= 0) tp.load_sense |= 1u << g;
+    }
     return tp;
 }
 
 // THE ORDER OF A TICK'S LAUNCHES on the stream of bank 0 ([..]: where the plan has it; the unnamed lines are fused_train's own):
 //     the walk, the feed's wrench (ft_launch)
 //     tick_front:   [pushes SENSE: their reaction goes into the wrench ahead of every kernel that reads it] [walls SENSE: their force of the
-//                   tick before, behind it] [action objects: on this tick's EE poses and knuckle coordinates, in front of the action kernel,
+//                   tick before, behind it] [loads SENSE: the carried objects' weight of the tick before, behind that] [action objects: on this tick's EE poses and knuckle coordinates, in front of the action kernel,
 //                   whose refs read their poses] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel
 //                   | stream kernel: its targets are this tick's too]
 //     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
 //     [log FRONT (a logged tick): coordinates, EE poses, targets, wrench, u and flags as the step used and left them -- behind the give-up
 //                   pass, which completes u; in front of the cycler, which moves the targets, and of the plant, which moves the
 //                   coordinates and overwrites the block's M entries (the EE entries it leaves alone; the order does not lean on that)]
-//     tick_behind:  [waypoint cycler: the targets move where an arm arrived]; [pushes APPLY] [walls APPLY] [joint rows], each into the bias
+//     tick_behind:  [waypoint cycler: the targets move where an arm arrived]; [pushes APPLY] [walls APPLY] [loads APPLY: on the holders this tick's object kernel left] [joint rows], each into the bias
 //                   entries of the block, which only the plant reads from here on; [log BACK (a logged tick with WALL_FORCE or JOINT_TAU):
 //                   the force / tau planes the two launches ahead of it just wrote]; the plant: every robot has its u by then;
 //                   [episodes: LAST, because the plant wrote the coordinates that a reset replaces -- and the cycler, the action kernel,
 //                   the walls and the rows have judged and recorded the tick whose state a reset wipes]
 // The log launches only read, and write nothing but their sample of the ring.
-// What rests on this order alone: "pushes, then walls, then joint rows" on one bias entry of one tick.
+// What rests on this order alone: "pushes, then walls, then loads, then joint rows" on one bias entry of one tick.
 template <typename T>
 static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, const irlosc_ctx::Bank& bk, void* wrench, hipStream_t st) {
     if (tp.push_sense) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_sense, nullptr, wrench), st));
     if (tp.wall_sense) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_sense, nullptr, wrench), st));
+    if (tp.load_sense) HIPCHK(c, (hipError_t)launch_object_loads<T>(load_args(c, s0, B, tp.load_sense, nullptr, wrench), st));
     if (tp.objects) HIPCHK(c, (hipError_t)launch_objects(object_args(c, s0, B, s0.objects.d, bk.xside[0]), st));
     if (tp.prog == Program::LIST && !s0.prog.motion) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (tp.prog == Program::LIST && s0.prog.motion) HIPCHK(c, (hipError_t)launch_actions_motion<T>(action_motion_args(c, s0, B, bk.xside[0], s0.prog.tick), st));
@@ -2181,6 +2221,7 @@ static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp,
     if (tp.prog == Program::PATHS) HIPCHK(c, (hipError_t)launch_waypoints<T>(waypoint_args(c, s0, B, s0.prog.wp, bk.xside[0], s0.prog.tick), st));
     if (tp.push_apply) HIPCHK(c, (hipError_t)launch_pushes<T>(push_args(c, s0, B, tp.push_apply, bk.xside[0], nullptr), st));
     if (tp.wall_apply) HIPCHK(c, (hipError_t)launch_walls<T>(wall_args(c, s0, B, tp.wall_apply, bk.xside[0], nullptr), st));
+    if (tp.load_apply) HIPCHK(c, (hipError_t)launch_object_loads<T>(load_args(c, s0, B, tp.load_apply, bk.xside[0], nullptr), st));
     if (tp.joints) HIPCHK(c, (hipError_t)launch_joints(joint_args(c, s0, B, bk.xside[0]), st));
     if (pl.log && (pl.log->channels & LOG_BACK)) HIPCHK(c, (hipError_t)launch_log<T>(log_args(c, s0, bk, *pl.log, LOG_BACK, nullptr), st));
     HIPCHK(c, (hipError_t)launch_plant<T>(plant_args(c, s0, B, bk, pl.trace), st));
@@ -2191,7 +2232,7 @@ static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp,
 static void tick_done(Slot& s0, int B, const TickPlan& tp) {
     s0.advanced(B);
     if (tp.prog != Program::NONE) s0.prog.ticked();
-    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); s0.objects.ticked(); s0.episodes.ticked();      // (each ticks only where it is in force)
+    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); s0.objects.ticked(); s0.loads.ticked(); s0.episodes.ticked();      // (each ticks only where it is in force)
 }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
@@ -2733,6 +2774,7 @@ static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, i
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].walls.robots, "walls", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].objects.robots, "action objects", "cover", nullptr);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].loads.robots, "object loads", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].episodes.robots, "episodes", "cover", nullptr);
     if (rc) return rc;
     c->slot[slot].ticks_run = B == 0 ? ticks : 0;      // (rollout_ticks says how many were enqueued; an empty batch: all, none of them a launch)
@@ -3010,7 +3052,7 @@ extern "C" int irlosc_set_objects(irlosc_ctx* c, int32_t slot, int32_t B, const 
     int rc = check_slot(c, slot, B);
     if (rc) return rc;
     Slot& s = c->slot[slot];
-    if (!d) { s.objects.end(); s.prog.aimless(); return IRLOSC_OK; }
+    if (!d) { s.objects.end(); s.loads.end(); s.prog.aimless(); return IRLOSC_OK; }
     const int n = c->cfg.n, nd = c->cfg.ndev, NO = d->n_objects, NG = d->n_grippers, NM = d->n_mates, V = d->n_variants;
     if (NO < 1 || NO > IRLOSC_MAX_OBJECTS) return fail(c, IRLOSC_ERR_ARG, "objects: n_objects=%d out of [1,%d]", NO, IRLOSC_MAX_OBJECTS);
     if (NG < 1 || NG > IRLOSC_MAX_GRIPPERS) return fail(c, IRLOSC_ERR_ARG, "objects: n_grippers=%d out of [1,%d]", NG, IRLOSC_MAX_GRIPPERS);
@@ -3051,6 +3093,7 @@ extern "C" int irlosc_set_objects(irlosc_ctx* c, int32_t slot, int32_t B, const 
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     Objects& os = s.objects;
     os.end();          // (none until the new ones are in their table and their state is reset; the refs named the old ones)
+    s.loads.end();     // (... and the loads described them)
     s.prog.aimless();
     // the start poses, every variant in the walk's layout even for a lone robot: [V][walk wave][NO 7][64]
     const size_t vstride = ((size_t)B + 63) / 64 * E * 64;
@@ -3081,6 +3124,59 @@ extern "C" int irlosc_download_object_state(irlosc_ctx* c, int32_t slot, int32_t
     return download_state(c, B, os.st_d, os.d_words(Bm), {{pose, os.pose(Bm), NO * 7, NO * 7, 0, 1}, {rel, os.rel(Bm), NO * 7, NO * 7, 0, 1}},
                           os.st_i, os.i_words(Bm), {{holder, os.holder(Bm), NO, NO, 0, 1}, {grasp_tick, os.grasp_tick(Bm), NO, NO, 0, 1},
                           {release_tick, os.release_tick(Bm), NO, NO, 0, 1}, {mated_tick, os.mated_tick(Bm), NM, NM, 0, 1}});
+}
+
+// ---- the carried objects' weight (osc_object_load.hpp) ---------------------------------------------------------------------------------
+extern "C" int irlosc_set_object_loads(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_object_loads* d, const double* table) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.loads.end(); return IRLOSC_OK; }      // (the objects and their state are not touched)
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "object loads: B=%d must be >= 1", B);
+    if (d->per_robot != 0 && d->per_robot != 1) return fail(c, IRLOSC_ERR_ARG, "object loads: per_robot=%d must be 0 or 1", d->per_robot);
+    if (d->reserved != 0) return fail(c, IRLOSC_ERR_ARG, "object loads: reserved must be 0");
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(d->gravity[i])) return fail(c, IRLOSC_ERR_ARG, "object loads: gravity[%d] is not finite", i);
+    if (!table) return fail(c, IRLOSC_ERR_ARG, "object loads: table is NULL");
+    const int NO = s.objects.count();      // (the table's width is the objects': without them there is nothing to read it by)
+    if (!NO) return fail(c, IRLOSC_ERR_STATE, "slot %d has no action objects (irlosc_set_objects)", slot);
+    const int nb = d->per_robot ? B : 1;
+    const size_t E = (size_t)NO * 4;
+    for (size_t i = 0; i < (size_t)nb * E; ++i) {
+        if (!std::isfinite(table[i]))
+            return fail(c, IRLOSC_ERR_ARG, "object loads: word %zu of object %zu, robot %zu is not finite", i % 4, i % E / 4, i / E);
+        if (i % 4 == 0 && table[i] < 0.0)
+            return fail(c, IRLOSC_ERR_ARG, "object loads: mass %g of object %zu, robot %zu must be >= 0", table[i], i % E / 4, i / E);
+    }
+    if (B > s.objects.robots)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its action objects cover %d robots, loads given for %d", slot, s.objects.robots, B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Loads& ls = s.loads;
+    ls.end();          // (none until the new ones are in their table and their state is reset)
+    const std::vector<double> tab = walk_table(table, nb, E);
+    const size_t bytes = tab.size() * sizeof(double), Bm = (size_t)c->cfg.max_batch;
+    const size_t d_bytes = ls.d_words(Bm) * sizeof(double), i_bytes = ls.i_words(Bm) * sizeof(int32_t);
+    if (!got(ls.table.reserve(bytes)) || !got(ls.st_d.ensure(d_bytes)) || !got(ls.st_i.ensure(i_bytes)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the object loads of slot %d (%zu bytes)", slot, bytes + d_bytes + i_bytes);
+    rc = setter_upload(c, {{ls.table, tab.data(), bytes}, {ls.st_d, nullptr, d_bytes, 0}, {ls.st_i, nullptr, i_bytes, 0}});      // load, carry_ticks = 0
+    irlosc_object_loads in_force = *d;
+    in_force.per_robot = nb > 1;      // (walk_table lays a lone robot's table out as the shared one)
+    if (!rc) ls.set(B, in_force);
+    return rc;
+}
+
+extern "C" int irlosc_download_object_load_state(irlosc_ctx* c, int32_t slot, int32_t B, double* load, int32_t* carry_ticks) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].loads.robots, "object loads", "cover", "irlosc_set_object_loads");
+    if (rc) return rc;
+    const Loads& ls = c->slot[slot].loads;
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t NG = (size_t)c->slot[slot].objects.d.n_grippers, Bm = (size_t)c->cfg.max_batch;      // rows [max_batch] -> [B][NG][6], [B][NG]
+    return download_state(c, B, ls.st_d, ls.d_words(Bm), {{load, ls.load(Bm), NG * 6, NG * 6, 0, 1}}, ls.st_i, ls.i_words(Bm),
+                          {{carry_ticks, ls.carry_ticks(Bm), NG, NG, 0, 1}});
 }
 
 extern "C" int irlosc_set_action_refs(irlosc_ctx* c, int32_t slot, const irlosc_action_refs* r) {
@@ -3385,7 +3481,7 @@ extern "C" int irlosc_set_episodes(irlosc_ctx* c, int32_t slot, int32_t B, const
                     std::max(0, s.targets), B);
     const Program& p = s.prog;
     const struct { int robots; const char* what; } parts[] = {{p.robots, "program"}, {s.walls.robots, "walls"}, {s.joints.robots, "joint rows"},
-                                                              {s.objects.robots, "action objects"}};
+                                                              {s.objects.robots, "action objects"}, {s.loads.robots, "object loads"}};
     for (const auto& k : parts)
         if (k.robots && B > k.robots)
             return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s covers %d robots, episodes given for %d (their resets write its state)", slot, k.what, k.robots, B);

@@ -126,6 +126,13 @@ struct WallArgs;
 template <typename T>
 int launch_walls(const WallArgs& a, hipStream_t st);
 
+// tu_object_load.hip -- the weight of the objects a slot's grippers carry, on a rollout tick whose slot has loads
+// (osc_object_load.hpp): sense mode behind the walls' sense launch, in front of the object kernel; apply mode behind the walls' apply
+// launch, in front of the joint rows; T = record type (of the wrench)
+struct ObjectLoadArgs;
+template <typename T>
+int launch_object_loads(const ObjectLoadArgs& a, hipStream_t st);
+
 // tu_joint.hip -- the joint rows of a rollout tick whose slot has some (osc_joint.hpp): range stops, finger couplings and gripper
 // drives as one torque per hinge, taken off the bias behind the walls' apply launch, directly in front of the plant
 struct JointArgs;

@@ -14,7 +14,7 @@
 //     branch leaves it with word 9 of the active device's gain record taken again from the context's gains and, with pose variants,
 //     the robot's lines of the list's pose table rewritten with variant count mod V, the paths' state as the cycler's init, the walls'
 //     and the joint rows' state as their setters' fills, the action objects' state as osc_object_kernel's init leaves it, on their
-//     start poses count mod OV; on a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
+//     start poses count mod OV, the carried objects' load words and carry_ticks zero; on a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
 //   idle lanes of a ragged last wave neither load nor store.
 // Every wave stores the number of its robots that are not parked into running[walk wave] (a plain store by lane 0): the early exit's input.
 //
@@ -62,6 +62,9 @@ struct EpisodeArgs {
     const double* ob_pose0;
     int64_t ob_vstride;
     int32_t objects, nobj, ng, nm, OV;
+    // the carried objects' weight (osc_object_load.hpp): state [MAX_GRIPPERS 6][stride], [MAX_GRIPPERS][stride]
+    double* ld_load; int32_t* ld_carry;
+    int32_t loads, ld_pad;
     int64_t vstride;
     int32_t wp_count[IRLOSC_MAX_DEV];
     uint8_t wp_loop[IRLOSC_MAX_DEV];
@@ -199,6 +202,13 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
             }
             for (int g = 0; g < a.ng; ++g) a.ob_closed[(size_t)g * a.stride + so] = 0;
             for (int m = 0; m < a.nm; ++m) a.ob_mated[(size_t)m * a.stride + so] = -1;
+        }
+        if (a.loads) {                              // as irlosc_set_object_loads' fills
+            for (int g = 0; g < a.ng; ++g) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) a.ld_load[(size_t)(g * 6 + c) * a.stride + so] = 0.0;
+                a.ld_carry[(size_t)g * a.stride + so] = 0;
+            }
         }
         if (a.joints) {                             // as irlosc_set_joints' fills; ctrl = 0: an ACTION drive lets go
 #pragma unroll

@@ -1,7 +1,8 @@
 // The ACTION OBJECTS of a rollout (irlosc_set_objects): kinematic bodies that a gripper carries -- per tick and robot, a held object
 // rides rigidly on the EE that holds it, a free one is taken by a hand that closes near it, one that is let go stays where it is, and a
-// plug that is free inside its socket's tolerances is recorded as mated.  NO contact model: the object has no mass, nothing acts on the
-// plant or the F/T feed, nothing collides, falls or slips.  It runs behind the walk (and the feed's SENSE launches) and in front of the
+// plug that is free inside its socket's tolerances is recorded as mated.  NO contact model: this kernel moves poses and nothing else --
+// a held object's weight on the plant and in the F/T feed is osc_object_load.hpp's, on a slot with loads -- and nothing collides, falls or
+// slips.  It runs behind the walk (and the feed's SENSE launches) and in front of the
 // action kernel: a WP entered on tick t (osc_action.hpp, refs) reads the objects of tick t.
 //
 // One lane per robot, one block per walk wave (its 64 robots), like the action kernel.  The EE pose of a gripper's device is seven

@@ -1,0 +1,123 @@
+// THE WEIGHT OF A CARRIED OBJECT in a rollout (irlosc_set_object_loads): an action object (osc_object.hpp) with a mass and a centre of
+// mass pulls on the EE body of the gripper that holds it -- a wrench at the EE body's frame origin, computed on the device per robot
+// and tick from the object's pose as this tick's object kernel left it, added to the bias entries in front of the plant, remembered for
+// one tick and taken off the feed's wrench on the next.  The precedent is the compliant walls (osc_wall.hpp).  QUASI-STATIC: the
+// object's inertial force m a is not modelled; a free object neither falls nor weighs on anything.  Two launches of one kernel per tick:
+//
+//   APPLY, behind the pushes' and the walls' APPLY, in front of the joint rows and the plant: per gripper g in ascending g
+//       1. o = the lowest object with holder[o] == g (the object kernel's "g holds nothing" rule leaves at most one); none, or
+//          mass[o] == 0:  W_g = 0
+//       2. else   c = R(q_obj) com;   p_c = p_obj + c;   r = p_c - p_ee   (p_ee: the EE xyz of dev[g] in this tick's exchange block)
+//                 F = mass gravity (three products);   T = (r1 F2 - r2 F1, r2 F0 - r0 F2, r0 F1 - r1 F0);   W_g = (F, T)
+//       3. a word of W_g that is not finite: W_g = 0 on this tick, and the tick is not counted
+//       4. unless W_g is all zero: the chain of osc_push.hpp (wrench_off_bias) on every hinge above the EE body of dev[g]
+//       5. W_g goes into the per-robot state, zeros included; carry_ticks[g] += 1 when W_g was applied
+//     Float64 whatever the record type, every product, sum and difference rounded on its own, in the order written: the host repeats
+//     the bits (irl_control_amd/object_loads.py::load_wrench).  Two grippers on one device update its bias one after the other.
+//   SENSE, behind the walls' SENSE and in front of the object kernel, on every tick after the loads' first: per gripper g whose device
+//       has a sensor,   wrench[b][dev[g]][c] = (T)((double)wrench[b][dev[g]][c] - W_g(t - 1)[c]), c = 0..5: the pushes' SENSE arithmetic.
+//
+// One lane per robot, one block per walk wave (its 64 robots), like the wall kernel.  A per-robot table is [walk wave][nobj 4][64] (every
+// operand one coalesced 512-byte line), a shared one [nobj][4] (its address is uniform: scalar loads); object o's row is mass, com xyz.
+// The state is SoA [row][stride]: load word c of gripper g in row g 6 + c.  The entry indices of J and the bias are compile-time constants
+// of FeTopo<TOPO> per EE-candidate body; the runtime device finds its body by a uniform branch over the candidates.  No LDS, no barrier.
+// Idle lanes of a ragged last wave neither load nor store.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/irlosc.h"
+#include "osc_frontend_lane.hpp"
+#include "osc_push.hpp"
+
+namespace irlosc {
+
+struct ObjectLoadArgs {
+    double* xside;            // apply: the tick's exchange block [walk wave][n_compact][64], bias entries in place
+    void* wrench;             // sense: the feed's wrench of the tick [B][ndev][6], record type, in place
+    const double* table;      // per_robot: [walk wave][nobj 4][64], else [nobj][4]
+    const double* obj_pose;   // apply: the objects' poses [MAX_OBJECTS 7][stride] (osc_object.hpp: its layout)
+    const int32_t* obj_holder;      // apply: [MAX_OBJECTS][stride]
+    double* load;             // state [MAX_GRIPPERS 6][stride]: what the last tick applied
+    int32_t* carry_ticks;     // state [MAX_GRIPPERS][stride]: ticks on which a weight was applied
+    double gravity[3];
+    int32_t B, ndev, nobj, ng, per_robot, stride;
+    int32_t apply;            // 1: apply mode, 0: sense mode (uniform over the launch)
+    uint32_t grippers;        // bit g: gripper g is part of this launch (sense: its device has a sensor)
+    int32_t dev[IRLOSC_MAX_GRIPPERS];     // device of gripper g
+    int32_t ee0[IRLOSC_MAX_DEV];          // exchange entry of each device's EE pose: names its EE body
+};
+
+template <class TOPO, typename T>
+__global__ __launch_bounds__(64) void osc_object_load_kernel(const ObjectLoadArgs a) {
+    using TI = FeTopo<TOPO>;
+    constexpr int n_compact = TI::n_compact();
+    const int lane = threadIdx.x;
+    const int b = (int)blockIdx.x * 64 + lane;
+    if (b >= a.B) return;                           // (no barrier below)
+    const size_t S = (size_t)a.stride;
+    if (!a.apply) {
+        for (int g = 0; g < a.ng; ++g) {            // (uniform: kernel arguments)
+            if (!((a.grippers >> g) & 1u)) continue;
+            T* w = (T*)a.wrench + ((size_t)b * a.ndev + a.dev[g]) * 6;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) w[c] = (T)__dsub_rn((double)w[c], a.load[(size_t)(g * 6 + c) * S + b]);
+        }
+        return;
+    }
+    const double* __restrict__ tab = a.per_robot ? a.table + (size_t)blockIdx.x * a.nobj * 4 * 64 + lane : a.table;
+    const int cs = a.per_robot ? 64 : 1;
+    double* col = a.xside + (size_t)blockIdx.x * n_compact * 64 + lane;
+    const double* __restrict__ pose = a.obj_pose + b;
+    const int32_t* __restrict__ holder = a.obj_holder + b;
+    for (int g = 0; g < a.ng; ++g) {
+        if (!((a.grippers >> g) & 1u)) continue;
+        const int e0d = a.ee0[a.dev[g]];
+        double W[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        bool found = false;
+        for (int o = 0; o < a.nobj; ++o) {          // 1. the lowest object that g holds
+            if (found || holder[o * S] != g) continue;
+            found = true;
+            const double* __restrict__ row = tab + (size_t)o * 4 * cs;      // (o is uniform: a shared table's row is a scalar load)
+            const double mass = row[0];
+            if (mass == 0.0) continue;
+            const double com[3] = {row[cs], row[2 * cs], row[3 * cs]};
+            double po[3], qo[4], R[3][3], c3[3], r[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) po[c] = pose[(size_t)(o * 7 + c) * S];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) qo[c] = pose[(size_t)(o * 7 + 3 + c) * S];
+            quat2mat_rn(qo, R);                     // 2.
+            mat_vec_rn(R, com, c3);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = __dsub_rn(__dadd_rn(po[c], c3[c]), col[(size_t)(e0d + c) * 64]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) W[c] = __dmul_rn(mass, a.gravity[c]);
+            W[3] = __dsub_rn(__dmul_rn(r[1], W[2]), __dmul_rn(r[2], W[1]));
+            W[4] = __dsub_rn(__dmul_rn(r[2], W[0]), __dmul_rn(r[0], W[2]));
+            W[5] = __dsub_rn(__dmul_rn(r[0], W[1]), __dmul_rn(r[1], W[0]));
+        }
+        bool fin = true, any = false;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { fin = fin && t_finite(W[c]); any = any || W[c] != 0.0; }
+        if (!fin) {                                 // 3. (a NaN robot adds no force of its own)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) W[c] = 0.0;
+        }
+        const bool on = fin && any;
+        static_for<0, TOPO::NB>([&](auto bc) {      // 4.
+            constexpr int body = decltype(bc)::value;
+            if constexpr (TOPO::ee_cand[body] != 0) {
+                constexpr int e0 = TI::ee_index(body);
+                if (e0d == e0) {
+                    if (on) wrench_off_bias<TOPO, body>(col, W);
+                }
+            }
+        });
+#pragma unroll
+        for (int c = 0; c < 6; ++c) a.load[(size_t)(g * 6 + c) * S + b] = W[c];      // 5.
+        if (on) a.carry_ticks[(size_t)g * S + b] += 1;
+    }
+}
+
+}  // namespace irlosc

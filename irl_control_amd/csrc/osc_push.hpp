@@ -41,6 +41,27 @@ struct PushArgs {
     int32_t ee0[IRLOSC_MAX_DEV];          // exchange entry of each device's EE pose: names its EE body
 };
 
+// THE CHAIN that takes a wrench W at the frame origin of EE-candidate `body` off the bias, for every hinge i above the body in ascending i:
+//     bias_i = fma(-J[5][i], W5, ... fma(-J[0][i], W0, bias_i))
+// on the lane's column `col` of the tick's exchange block.  Stated once: the pushes (below) and the carried objects' weight
+// (osc_object_load.hpp) both go through it, so a load and a push of the same wrench leave the same bits.
+template <class TOPO, int body>
+__device__ __forceinline__ void wrench_off_bias(double* __restrict__ col, const double W[6]) {
+    using TI = FeTopo<TOPO>;
+    constexpr int e0 = TI::ee_index(body);      // (indices through constexpr VARIABLES: evaluated at compile time)
+    static_for<0, TOPO::NJ>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        if constexpr (TI::moves(i, body)) {
+            constexpr int ej = e0 + 7 + 6 * TI::anc_rank(i, body);
+            constexpr int eb = TI::bias_index(i);
+            double acc = col[(size_t)eb * 64];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) acc = fma(-col[(size_t)(ej + c) * 64], W[c], acc);
+            col[(size_t)eb * 64] = acc;
+        }
+    });
+}
+
 template <class TOPO, typename T>
 __global__ __launch_bounds__(64) void osc_push_kernel(const PushArgs a) {
     using TI = FeTopo<TOPO>;
@@ -74,20 +95,8 @@ __global__ __launch_bounds__(64) void osc_push_kernel(const PushArgs a) {
         static_for<0, TOPO::NB>([&](auto bc) {
             constexpr int body = decltype(bc)::value;
             if constexpr (TOPO::ee_cand[body] != 0) {
-                constexpr int e0 = TI::ee_index(body);      // (indices through constexpr VARIABLES: evaluated at compile time)
-                if (e0d == e0) {
-                    static_for<0, TOPO::NJ>([&](auto ic) {
-                        constexpr int i = decltype(ic)::value;
-                        if constexpr (TI::moves(i, body)) {
-                            constexpr int ej = e0 + 7 + 6 * TI::anc_rank(i, body);
-                            constexpr int eb = TI::bias_index(i);
-                            double acc = col[(size_t)eb * 64];
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) acc = fma(-col[(size_t)(ej + c) * 64], W[c], acc);
-                            col[(size_t)eb * 64] = acc;
-                        }
-                    });
-                }
+                constexpr int e0 = TI::ee_index(body);
+                if (e0d == e0) wrench_off_bias<TOPO, body>(col, W);
             }
         });
     }

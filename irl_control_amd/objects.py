@@ -4,7 +4,8 @@ and sum is one NumPy operation on float64 arrays, so each is rounded on its own 
 repeats the kernel's bits.  ref_target is the same for the composition an action list's refs make at a WP's entry (csrc/osc_action.hpp).
 
 What an object is: a pose that rides rigidly on an EE once that arm's fingers have closed near it, stays where it is let go, and can be
-recorded as mated with a socket.  What it is not: it has no mass, acts on nothing, collides with nothing and does not fall or slip."""
+recorded as mated with a socket.  By itself it acts on nothing; with loads (object_loads.py) a held object has a weight that the plant
+and the F/T feed see.  What it is not: it has no inertial force, collides with nothing and does not fall or slip."""
 from dataclasses import dataclass, field
 from typing import Dict, List, Sequence
 
