@@ -473,13 +473,14 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
 
 /* ---- ONE WRITER OF THE TARGETS: the program of a slot's rollouts -------------------------------------------------------------
  * Inside a rollout the slot's targets are written by at most one PROGRAM: waypoint paths (irlosc_set_waypoints), a WP / GRIP action
- * list (irlosc_set_action_list) or a teleoperation stream (irlosc_set_teleop_stream), never two of them; outside one by
+ * list (irlosc_set_action_list), a teleoperation stream (irlosc_set_teleop_stream) or a policy (irlosc_set_policy), never two of them; outside one by
  * irlosc_set_targets.  Targets are written by one entry point at a time:
  *     irlosc_set_targets on the slot (B == 0 too), irlosc_set_model (all slots)        any program ends
  *     irlosc_set_gains (all slots)                                                     a list ends (its gain copy is stale), paths and a stream stay
  *     irlosc_set_waypoints with desc == NULL or all counts 0                           paths end, a list or a stream stays
  *     irlosc_set_action_list with desc == NULL                                         a list ends, paths or a stream stay
  *     irlosc_set_teleop_stream with desc == NULL                                       a stream ends, paths or a list stay
+ *     irlosc_set_policy with desc == NULL                                              a policy ends (and episodes set on it), every other program stays
  *     a setter that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE                         nothing changes: the program in force stays, whole
  *     a setter that succeeds                                                           its program replaces whatever was in force
  *     a setter that answers IRLOSC_ERR_HIP (allocation, copy or init launch)           no program of its kind; irlosc_set_waypoints and
@@ -512,7 +513,7 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *     irlosc_set_episodes with desc == NULL, irlosc_set_model (all slots)              episodes end
  *     irlosc_set_targets on the slot (B == 0 too)                                      episodes end: the snapshot is stale
  *     a setter of the slot's program that succeeds, or that ends the program in force
- *     (irlosc_set_waypoints, irlosc_set_action_list; irlosc_set_gains where it ends a list)   episodes end
+ *     (irlosc_set_waypoints, irlosc_set_action_list, irlosc_set_policy; irlosc_set_gains where it ends a list)   episodes end
  *     irlosc_set_episodes that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE              nothing changes: the episodes in force stay, whole
  *     irlosc_set_episodes that succeeds                                                its episodes replace those in force; state and tick reset
  *     irlosc_set_episodes that answers IRLOSC_ERR_HIP                                  no episodes
@@ -752,6 +753,84 @@ IRLOSC_API int irlosc_download_teleop_state(irlosc_ctx* ctx, int32_t slot, int32
  * program of the slot's rollouts.  Works with or without a program.  IRLOSC_ERR_ARG: tgt_pose NULL; IRLOSC_ERR_STATE on a slot that
  * holds targets for fewer than B robots.  Synchronous. */
 IRLOSC_API int irlosc_download_targets(irlosc_ctx* ctx, int32_t slot, int32_t B, void* tgt_pose);
+
+/* ---- a learned policy steers the teleoperation targets: live input inside a rollout (csrc/osc_policy.hpp) -------------------------
+ * A POLICY is the fourth kind of program: where a stream replays recorded space-mouse readings, a policy COMPUTES the tick's reading
+ * from the tick's observations -- one small ReLU network for the whole fleet, evaluated per robot and tick on the device -- and hands
+ * it to the stream's own integration and follower arithmetic (above: "robot b on tick t"), unchanged.  Its kernel runs where the
+ * stream's runs: behind the walk, the feed's wrench with every SENSE launch and the object kernel, in front of the first OSC kernel, so
+ * THIS tick's OSC step aims at the targets of THIS tick's output.
+ * THE OBSERVATION of a robot is the concatenation, in ascending bit order, of the channels `obs` names; every word is cast to float
+ * (round to nearest, a double beyond float's range becomes an infinity):
+ *     IRLOSC_OBS_QPOS         n        the coordinates this tick's walk read
+ *     IRLOSC_OBS_QVEL         n
+ *     IRLOSC_OBS_EE_POSE      ndev 7   the walk's EE poses, device-major (x y z qw qx qy qz)
+ *     IRLOSC_OBS_TARGETS      ndev 7   the slot's targets as they stand in front of this tick's write (what the tick before aimed at)
+ *     IRLOSC_OBS_WRENCH       ndev 6   the feed's wrench behind every SENSE launch of the tick; zeros on a slot without a sensor feed
+ *     IRLOSC_OBS_PLATE        6        the plate pose (x y z roll pitch yaw) before this tick's integration
+ *     IRLOSC_OBS_OBJECT_POSE  nobj 7   the action objects' poses as this tick's object kernel left them
+ * n_in = the sum of the selected widths, 1 <= n_in <= IRLOSC_POLICY_MAX_IN.
+ * THE NETWORK: n_layers in [1, IRLOSC_POLICY_MAX_LAYERS] affine layers, ReLU between them, none behind the last; layer l maps
+ * in_l -> out_l with in_0 = n_in, out_l = width[l] for l < n_layers - 1 (each in [1, IRLOSC_POLICY_MAX_WIDTH]) and n_out (6 or 7) for
+ * the last.  `weights` holds, layer after layer, W[out_l][in_l] row-major (torch.nn.Linear.weight's layout) and then b[out_l].
+ * THE ARITHMETIC is float32 and the host can repeat it bit for bit (irl_control_amd/policy.py::mlp).  With in_l padded by zeros to a
+ * multiple of 4 and out_l to a multiple of 16 (padding changes no value: fmaf(0, 0, acc) == acc for every acc the chain meets but -0):
+ *     acc = b[j];  for i ascending over the padded inputs:  acc = fmaf(W[j][i], x[i], acc)          -- one rounding per step
+ *     hidden layer:  x'[j] = acc > 0 ? acc : 0          last layer:  out[j] = acc
+ * (the device runs the chains on v_mfma_f32_16x16x4_f32, whose result is this chain).  Then, per robot:
+ *     reading r[c] = (double) clamp(out[c]),  c < 6;  clamp(v) = clip > 0 ? (v < -clip ? -clip : v > clip ? clip : v) : v  (in float)
+ *     pose and followers' targets from r exactly as a stream's tick takes them from its reading
+ *     n_out == 7:  grip = out[6] > 0 ? grip_close : grip_open, stored per robot; the ACTION drive rows (irlosc_set_joints) of device
+ *                  grip_dev read it on the same tick exactly where they read an action list's gripper_force
+ * A robot whose observation or output holds a word that is not finite KEEPS pose, targets, out and grip on that tick and gets
+ * IRLOSC_FLAG_NONFINITE in flags_any; the robots of its wave are not affected.  A robot that a rollout over fewer robots leaves out keeps
+ * all of its state.  A policy is never "finished": next to episodes (irlosc_set_episodes accepts it, unlike a stream -- nothing of a
+ * policy follows the slot's tick) an episode ends by max_ticks alone, and a reset puts the plate back to the robot's origin and zeroes out and grip. */
+#define IRLOSC_POLICY_MAX_IN     192
+#define IRLOSC_POLICY_MAX_WIDTH  128
+#define IRLOSC_POLICY_MAX_LAYERS 4
+#define IRLOSC_OBS_QPOS         1u
+#define IRLOSC_OBS_QVEL         2u
+#define IRLOSC_OBS_EE_POSE      4u
+#define IRLOSC_OBS_TARGETS      8u
+#define IRLOSC_OBS_WRENCH      16u
+#define IRLOSC_OBS_PLATE       32u
+#define IRLOSC_OBS_OBJECT_POSE 64u
+typedef struct irlosc_policy {
+    uint32_t obs;                          /* OR of IRLOSC_OBS_*: at least one; OBJECT_POSE only on a slot with action objects */
+    int32_t n_layers;                      /* [1, IRLOSC_POLICY_MAX_LAYERS] */
+    int32_t width[IRLOSC_POLICY_MAX_LAYERS];   /* width[l], l < n_layers - 1: outputs of hidden layer l, [1, IRLOSC_POLICY_MAX_WIDTH]; the others: 0 */
+    int32_t n_out;                         /* 6: the reading; 7: and the grip */
+    int32_t keep_obs;                      /* 1: the kernel also stores the observation it used ([B][n_in] float: 4 n_in bytes per robot and tick) */
+    int32_t grip_dev;                      /* n_out == 7: the device whose ACTION drive rows take the grip, in [0, ndev); else 0 */
+    int32_t nb_origin;                     /* origin: 1 or B */
+    float clip;                            /* > 0: the six readings are clamped to [-clip, clip]; 0: no clamp; finite, >= 0 */
+    int32_t reserved;                      /* 0 */
+    double grip_close, grip_open;          /* n_out == 7: finite and not 0; else not read */
+    double increment;                      /* the rig, as irlosc_teleop_stream's: finite */
+    int32_t kind[IRLOSC_MAX_DEV];          /* IRLOSC_TELEOP_*; devices >= ndev: NONE; at least one device not NONE */
+    double off_xyz[IRLOSC_MAX_DEV][3];     /* RIGID: finite */
+    double off_quat[IRLOSC_MAX_DEV][4];    /* RIGID: w x y z, | |q|^2 - 1 | <= 1e-12 */
+    double heading_offset[IRLOSC_MAX_DEV]; /* HEADING: finite */
+} irlosc_policy;
+/* Gives slot `slot`'s B robots the policy: weights as above (float), origin[nb_origin][6] double (the plate pose before tick 0).  Every
+ * argument is checked before anything is touched (IRLOSC_ERR_ARG: what irlosc_set_teleop_stream refuses of the rig and the origin; obs
+ * 0 or with an unknown bit; n_in outside [1, 192]; n_layers, a width or n_out out of range; a width behind the hidden layers that is
+ * not 0; keep_obs not 0 / 1; clip negative or not finite; reserved != 0; n_out == 7 with grip_dev outside [0, ndev) or a force that is
+ * 0 or not finite; a weight that is not finite; weights or origin NULL; B < 1).  After irlosc_set_model and irlosc_set_targets for at
+ * least B robots (IRLOSC_ERR_STATE otherwise, as is IRLOSC_OBS_OBJECT_POSE on a slot without action objects for B robots -- a rollout
+ * checks that again: objects come and go).  On ERR_ARG / ERR_STATE the program in force stays, whole.  On success the policy replaces
+ * whatever program was in force (and, like every program's setter, ends the slot's episodes), pose = origin, out = 0, grip = 0, the
+ * tick base is 0; NO targets are written: the first tick does that.  The setter packs the weights once into the order the kernel's
+ * matrix operands are loaded in.  desc == NULL clears a policy and nothing else.  IRLOSC_ERR_HIP leaves the slot WITHOUT a program.
+ * Synchronous. */
+IRLOSC_API int irlosc_set_policy(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_policy* desc, const float* weights, const double* origin);
+/* pose: [B][6] double; out: [B][n_out] float, the network's output BEFORE the clamp, as the last tick that ran the robot left it (0
+ * before the first); grip: [B] double; obs: [B][n_in] float, the observation of the last tick that ran the robot (IRLOSC_ERR_STATE if
+ * asked for without keep_obs); tick: one int32.  Any may be NULL.  IRLOSC_ERR_STATE on a slot without a policy, or with one for fewer
+ * than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_policy_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* pose, float* out, double* grip, float* obs,
+                                            int32_t* tick);
 
 /* ---- external pushes on the plant, sensed by the F/T feed: admit_test / force_test inside a rollout (csrc/osc_push.hpp) ------------
  * What examples/headless_loops.py::admit_test_loop does on the host -- xfrc_applied on a gripper body during a window of ticks, the

@@ -19,6 +19,8 @@ JOINT_SRC_CONST, JOINT_SRC_ACTION = 0, 1
 ACTION_WP, ACTION_GRIP = 0, 1
 MAX_STREAM_TICKS = 16384
 TELEOP_NONE, TELEOP_RIGID, TELEOP_HEADING = 0, 1, 2
+POLICY_MAX_IN, POLICY_MAX_WIDTH, POLICY_MAX_LAYERS = 192, 128, 4
+OBS_QPOS, OBS_QVEL, OBS_EE_POSE, OBS_TARGETS, OBS_WRENCH, OBS_PLATE, OBS_OBJECT_POSE = (1 << i for i in range(7))
 F32, F64 = 0, 1
 USE_G, ADMITTANCE, NULLSPACE = 1, 2, 4
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_ROW16 = 0, 1, 3      # (2: the fp32-arithmetic kernel removed in ABI version 3)
@@ -42,7 +44,7 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state",
            "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects",
            "irlosc_set_action_motion", "irlosc_download_action_motion_state", "irlosc_set_object_loads",
-           "irlosc_download_object_load_state"]
+           "irlosc_download_object_load_state", "irlosc_set_policy", "irlosc_download_policy_state"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
 LOG_OBJECT_POSE = 512                                    # only on a slot with action objects
 EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED = 1, 2, 4
@@ -106,6 +108,15 @@ class ActionList(C.Structure):
 class TeleopStream(C.Structure):
     """struct irlosc_teleop_stream (include/irlosc.h): the teleoperation stream of irlosc_set_teleop_stream."""
     _fields_ = [("ticks", C.c_int32), ("nb", C.c_int32), ("nb_origin", C.c_int32), ("loop", C.c_int32), ("increment", C.c_double),
+                ("kind", C.c_int32 * MAX_DEV), ("off_xyz", (C.c_double * 3) * MAX_DEV), ("off_quat", (C.c_double * 4) * MAX_DEV),
+                ("heading_offset", C.c_double * MAX_DEV)]
+
+
+class Policy(C.Structure):
+    """struct irlosc_policy (include/irlosc.h): the policy of irlosc_set_policy."""
+    _fields_ = [("obs", C.c_uint32), ("n_layers", C.c_int32), ("width", C.c_int32 * POLICY_MAX_LAYERS), ("n_out", C.c_int32),
+                ("keep_obs", C.c_int32), ("grip_dev", C.c_int32), ("nb_origin", C.c_int32), ("clip", C.c_float), ("reserved", C.c_int32),
+                ("grip_close", C.c_double), ("grip_open", C.c_double), ("increment", C.c_double),
                 ("kind", C.c_int32 * MAX_DEV), ("off_xyz", (C.c_double * 3) * MAX_DEV), ("off_quat", (C.c_double * 4) * MAX_DEV),
                 ("heading_offset", C.c_double * MAX_DEV)]
 
@@ -249,6 +260,8 @@ def load():
     lib.irlosc_set_teleop_stream.argtypes = [vp, i32, i32, C.POINTER(TeleopStream), vp, vp]
     lib.irlosc_download_teleop_state.argtypes = [vp, i32, i32, vp, vp]
     lib.irlosc_download_targets.argtypes = [vp, i32, i32, vp]
+    lib.irlosc_set_policy.argtypes = [vp, i32, i32, C.POINTER(Policy), vp, vp]
+    lib.irlosc_download_policy_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     lib.irlosc_set_pushes.argtypes = [vp, i32, i32, C.POINTER(Pushes), vp]
     lib.irlosc_set_walls.argtypes = [vp, i32, i32, C.POINTER(Walls), vp]
     lib.irlosc_download_wall_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]

@@ -35,6 +35,7 @@ class BatchedOSC:
         self._joint_rows = [0] * self.n_slots      # rows of each slot's set_joints (the width of joint_state's arrays)
         self._episode_records = [1] * self.n_slots      # ring length of each slot's set_episodes (the width of episode_state's records)
         self._objects = [(0, 0)] * self.n_slots      # (objects, mates) of each slot's set_objects (the widths of object_state's arrays)
+        self._policy = [None] * self.n_slots      # (n_in, n_out, keep_obs) of each slot's set_policy (the widths of policy_state's arrays)
         self._grippers = [0] * self.n_slots          # ... and its grippers (the width of object_load_state's)
         if kernel == _lib.KERNEL_AUTO and self.max_batch >= 1024 and self.kernel_class == _lib.CLASS_GENERIC:
             import warnings
@@ -712,6 +713,63 @@ class BatchedOSC:
         tick = C.c_int32(0)
         self._chk(self.lib.irlosc_download_teleop_state(self._h, slot, B, _lib.ptr(pose), C.byref(tick)))
         return dict(pose=pose, tick=int(tick.value))
+
+    # -- the policy of the rollout (irlosc_set_policy / irlosc_download_policy_state) ---------------------------------------------------
+    def set_policy(self, layers, obs, origin, rig=None, increment: float = 0.0015, clip: float = 0.0, keep_obs: bool = False,
+                   grip_dev=0, grip_close: float = 0.0, grip_open: float = 0.0, slot: int = 0):
+        """A policy for the slot's robots, evaluated on the GPU by `rollout`: per tick and robot the network `layers` ([(W [out, in],
+        b [out]), ...] float32, ReLU between the layers; policy.from_torch reads them off a torch Sequential) maps the observation --
+        the channels of `obs` (names of policy.OBS_BITS or an OR of _lib.OBS_*) in bit order, cast to float32 -- to the tick's
+        space-mouse reading (outputs 0 .. 5, clamped to [-clip, clip] where clip > 0), which moves the plate and the followers' targets
+        exactly as a stream's reading does (set_teleop_stream: `origin` [6] or [B, 6], `rig`, `increment`), in front of the same tick's
+        OSC step.  A seventh output drives the gripper: the ACTION drive rows (set_joints) of device `grip_dev` take `grip_close` where
+        it is > 0 and `grip_open` elsewhere.  The arithmetic is policy.mlp's, bit for bit.  `keep_obs`: policy_state also returns the
+        observation of the last tick.  After set_model and set_targets (and set_objects, if it observes object_pose); replaces the
+        slot's program; layers=None (or clear_policy) clears the policy and nothing else."""
+        from . import policy as _p, teleop as _t
+        B = self._B[slot]
+        if layers is None:
+            self._chk(self.lib.irlosc_set_policy(self._h, slot, B, None, None, None))
+            self._policy[slot] = None
+            return
+        layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in layers]
+        mask = _p.obs_mask(obs)
+        n_in = _p.obs_width(mask, self.layout.n, self.layout.ndev, self._objects[slot][0])
+        dims = [n_in] + [W.shape[0] for W, _ in layers]
+        for l, (W, b) in enumerate(layers):
+            if W.shape != (dims[l + 1], dims[l]) or b.shape != (dims[l + 1],):
+                raise ValueError(f"layer {l}: expected W {(dims[l + 1], dims[l])} and b {(dims[l + 1],)}, got {W.shape} and {b.shape}")
+        og = np.ascontiguousarray(origin, dtype=np.float64)
+        if og.ndim == 1:
+            og = og[None]
+        if og.ndim != 2 or og.shape[1] != 6 or og.shape[0] not in (1, B):
+            raise ValueError(f"origin: expected shape (6,) or ({B}, 6), got {np.shape(origin)}")
+        rig = _t.space_mouse_rig(self.layout) if rig is None else list(rig)
+        if len(rig) != self.layout.ndev:
+            raise ValueError(f"rig: expected one follower per device ({self.layout.ndev}), got {len(rig)}")
+        if isinstance(grip_dev, str):
+            grip_dev = self.layout.dev_names.index(grip_dev)
+        desc = _p.to_struct(layers, mask, rig, og.shape[0], increment, clip, keep_obs, grip_dev, grip_close, grip_open)
+        self._chk(self.lib.irlosc_set_policy(self._h, slot, B, C.byref(desc), _lib.ptr(_p.weights(layers)), _lib.ptr(og)))
+        self._policy[slot] = (n_in, dims[-1], bool(keep_obs))
+
+    def clear_policy(self, slot: int = 0):
+        """Ends the slot's policy (irlosc_set_policy with desc == NULL); targets and any other program are left alone."""
+        self.set_policy(None, None, None, slot=slot)
+
+    def policy_state(self, slot: int = 0):
+        """-> dict(pose [B, 6]: every robot's plate as the last tick that ran it left it (the origin before the first); out [B, n_out]
+        float32: the network's output of that tick, before the clamp; grip [B]; obs [B, n_in] float32 (with keep_obs, else None); tick:
+        the slot's rollout ticks since set_policy).  (irlosc_download_policy_state)"""
+        B = self._B[slot]
+        if self._policy[slot] is None:      # (the library says why)
+            self._chk(self.lib.irlosc_download_policy_state(self._h, slot, B, None, None, None, None, None))
+        n_in, n_out, keep = self._policy[slot]
+        pose, out, grip = np.empty((B, 6), dtype=np.float64), np.empty((B, n_out), dtype=np.float32), np.empty(B, dtype=np.float64)
+        obs = np.empty((B, n_in), dtype=np.float32) if keep else None
+        tick = C.c_int32(0)
+        self._chk(self.lib.irlosc_download_policy_state(self._h, slot, B, _lib.ptr(pose), _lib.ptr(out), _lib.ptr(grip), _lib.ptr(obs), C.byref(tick)))
+        return dict(pose=pose, out=out, grip=grip, obs=obs, tick=int(tick.value))
 
     def download_targets(self, slot: int = 0):
         """-> the slot's targets [B, ndev, 7] in the context's dtype as they sit in HBM: given by set_targets, or written by the

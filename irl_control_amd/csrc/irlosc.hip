@@ -28,6 +28,7 @@
 #include "osc_waypoint.hpp"
 #include "osc_action.hpp"
 #include "osc_teleop.hpp"
+#include "osc_policy.hpp"
 #include "osc_object.hpp"
 #include "osc_push.hpp"
 #include "osc_wall.hpp"
@@ -45,16 +46,17 @@ static_assert(FT_TRAIN == R16_TRAIN, "the sensor-feed wrench kernel covers a who
 static thread_local std::string g_create_error;
 
 // The program that writes a slot's targets inside a rollout, if any: waypoint paths (irlosc_set_waypoints, osc_waypoint.hpp), the
-// WP / GRIP action list (irlosc_set_action_list, osc_action.hpp) or a teleoperation stream (irlosc_set_teleop_stream, osc_teleop.hpp).
-// One entry point writes the targets at a time, so a slot has one program at most -- `kind` says which: paths, a list and a stream
-// exclude each other.  Written by the transitions below and by nothing else.
+// WP / GRIP action list (irlosc_set_action_list, osc_action.hpp), a teleoperation stream (irlosc_set_teleop_stream, osc_teleop.hpp) or a
+// policy (irlosc_set_policy, osc_policy.hpp).  One entry point writes the targets at a time, so a slot has one program at most -- `kind`
+// says which: paths, a list, a stream and a policy exclude each other.  Written by the transitions below and by nothing else.
 struct Program {
-    enum Kind { NONE, PATHS, LIST, STREAM };
+    enum Kind { NONE, PATHS, LIST, STREAM, POLICY };
     Kind kind = NONE;          // (NONE: a rollout tick launches none of the kernels and reads the context's gains)
     int robots = 0, tick = 0;  // robots the program covers; rollout ticks since it came in force
     irlosc_waypoints wp{};     // the description in force: of paths; of a list; of a stream
     irlosc_action_list al{};
-    irlosc_teleop_stream ts{};
+    irlosc_teleop_stream ts{};  // (a policy: its rig in a stream's form, which is what the shared body reads)
+    irlosc_policy po{};
     std::vector<double> ts_shared;      // a shared stream's readings [T][6]: they travel as kernel arguments, tick by tick
     int refs = 0;              // 1: the list aims at the slot's action objects as `rf` says (irlosc_set_action_refs)
     irlosc_action_refs rf{};
@@ -71,6 +73,14 @@ struct Program {
     DevBuf<int32_t> wp_i, al_i;
     DevBuf<double> wp_table, al_d, al_table, ts_pose, ts_table, ts_origin;
     DevBuf<void> al_gains, al_nullkv;
+    // A policy: the network as the kernel walks it (po_net) over the packed weights (po_w); per-robot state out [n_out][max_batch] (po_out) and grip
+    // [max_batch] (po_grip), the kept observation [robots][n_in] (po_obs); the pose and per-robot origins are the stream's ts_pose and ts_origin;
+    // a fleet-wide origin (po_origin0) and the objects the observation was sized for (po_nobj; -1: it does not look at them) stay on the host
+    PolicyNet po_net{};
+    double po_origin0[6] = {};
+    int po_nobj = -1;
+    DevBuf<float> po_w, po_out, po_obs;
+    DevBuf<double> po_grip;
     // THE LAYOUT of the state -- the kernels' arguments, the setters' sizes and the downloads all ask here: wp_i in planes of `plane` =
     // ndev x max_batch words; al_i and al_d in rows of Bm = max_batch words (start_xyz: three rows); and their sizes
     int32_t* index(size_t) const { return wp_i; }  int32_t* arrivals(size_t plane) const { return wp_i + plane; }  int32_t* last_tick(size_t plane) const { return wp_i + 2 * plane; }
@@ -95,6 +105,11 @@ struct Program {
     // A stream over B robots is in force, their poses at the origins by the kernel's init launch (which wrote no target: the first tick
     // does); `shared`: the readings of a stream for the whole fleet.
     void stream(int B, const irlosc_teleop_stream& d, std::vector<double>&& shared) { kind = STREAM; robots = B; tick = 0; ts = d; ts_shared = std::move(shared); }
+    // A policy over B robots is in force, their poses at the origins by the stream kernel's init launch, out and grip zero (no target written: the first tick does)
+    void policy(int B, const irlosc_policy& d, const irlosc_teleop_stream& rig, const PolicyNet& net, int nobj, const double* origin0) {
+        kind = POLICY; robots = B; tick = 0; po = d; ts = rig; po_net = net; po_nobj = nobj;
+        for (int i = 0; i < 6; ++i) po_origin0[i] = origin0[i];
+    }
     // The reading a stream takes on the tick to come: tick mod T of one that loops, none (-1) once one that does not has ended
     int reading() const { return kind != STREAM ? -1 : ts.loop ? tick % ts.ticks : tick < ts.ticks ? tick : -1; }
     // The program ends: irlosc_set_targets wrote the targets, another program takes them over, the model changed, or its buffers failed.
@@ -1935,6 +1950,21 @@ static TeleopArgs teleop_args(const irlosc_ctx* c, const Slot& s, int B, const i
     return a;
 }
 
+// The arguments of the slot's policy kernel over B robots: a tick on exchange block xside, wrench: the feed's wrench of the tick (or nullptr)
+static PolicyArgs policy_args(const irlosc_ctx* c, const Slot& s, int B, const double* xside, const void* wrench) {
+    const Program& p = s.prog;
+    PolicyArgs a;
+    memset(&a, 0, sizeof a);
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    a.t = teleop_args(c, s, B, p.ts, p.po_origin0, 0);      // (the rig, the targets, the pose; no reading: the kernel computes it)
+    a.net = p.po_net; a.w = p.po_w; a.qt = s.qt; a.xside = xside; a.wrench = wrench; a.obj_pose = s.objects.pose(Bm);
+    a.out = p.po_out; a.grip = p.po_grip; a.obs = p.po.keep_obs ? p.po_obs.get() : nullptr; a.flags_any = c->dflags_any;
+    a.grip_close = p.po.grip_close; a.grip_open = p.po.grip_open; a.clip = p.po.clip; a.obs_mask = p.po.obs;
+    a.n = c->cfg.n; a.n_entries = (int32_t)c->model.fe_xentries; a.nobj = std::max(0, p.po_nobj);
+    fill_ee0(c, a.ee0);
+    return a;
+}
+
 // The arguments of the slot's waypoint cycler over B robots (init: the launch of irlosc_set_waypoints; else a tick on exchange block xside)
 static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_waypoints& w, const double* xside, int tick) {
     WaypointArgs a;
@@ -2014,8 +2044,8 @@ static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* x
     a.xside = xside; a.qt = s.qt; a.table = j.table;
     a.tau = j.tau(Bm); a.max_violation = j.max_violation(Bm); a.ctrl = j.ctrl(Bm, d.n_rows); a.active_ticks = j.active_ticks(Bm);
     a.B = B; a.R = d.n_rows; a.per_robot = d.per_robot; a.stride = (int32_t)Bm;
-    const bool list = s.prog.kind == Program::LIST;
-    a.gripper_force = list ? s.prog.gripper_force(Bm) : nullptr;      // (the list's own state: what its ACTION drives read)
+    const bool list = s.prog.kind == Program::LIST, grips = s.prog.kind == Program::POLICY && s.prog.po.n_out == 7;
+    a.gripper_force = list ? s.prog.gripper_force(Bm) : grips ? s.prog.po_grip.get() : nullptr;      // (the list's own state, or the policy's grip: what its ACTION drives read)
     int items = 0;
     for (int h = 0; h < (int)n; ++h) {
         a.first[h] = (uint8_t)items;
@@ -2027,7 +2057,7 @@ static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* x
     for (int h = (int)n; h <= IRLOSC_MAX_N; ++h) a.first[h] = (uint8_t)items;
     for (int r = 0; r < d.n_rows; ++r) {
         a.kind[r] = (uint8_t)d.kind[r]; a.ja[r] = (uint8_t)d.joint_a[r]; a.jb[r] = (uint8_t)d.joint_b[r]; a.source[r] = (uint8_t)d.source[r];
-        if (list && d.kind[r] == IRLOSC_JOINT_DRIVE && d.source[r] == IRLOSC_JOINT_SRC_ACTION && d.dev[r] == s.prog.al.active_dev)
+        if ((list || grips) && d.kind[r] == IRLOSC_JOINT_DRIVE && d.source[r] == IRLOSC_JOINT_SRC_ACTION && d.dev[r] == (list ? s.prog.al.active_dev : s.prog.po.grip_dev))
             a.armed |= (uint64_t)1 << r;
     }
     return a;
@@ -2069,7 +2099,11 @@ static EpisodeArgs episode_args(const irlosc_ctx* c, const Slot& s, int B, const
     memset(&a, 0, sizeof a);
     a.count = e.count(Bm); a.age = e.age(Bm); a.start_tick = e.start_tick(Bm); a.ring = e.ring(Bm); a.running = e.running;
     a.qt = s.qt; a.qpos = s.qpos; a.qvel = s.qvel; a.starts = e.starts; a.tgt = s.tgt; a.snap = e.snap;
-    a.kind = p.kind == Program::LIST ? EP_LIST : p.kind == Program::PATHS ? EP_PATHS : EP_NONE;
+    a.kind = p.kind == Program::LIST ? EP_LIST : p.kind == Program::PATHS ? EP_PATHS : p.kind == Program::POLICY ? EP_POLICY : EP_NONE;
+    if (a.kind == EP_POLICY) {
+        a.pl_pose = p.pose(Bm); a.pl_origin = p.po.nb_origin > 1 ? p.ts_origin.get() : nullptr; a.pl_out = p.po_out; a.pl_grip = p.po_grip; a.pl_n_out = p.po.n_out;
+        for (int i = 0; i < 6; ++i) a.pl_origin0[i] = p.po_origin0[i];
+    }
     if (a.kind == EP_LIST) {
         a.action = p.action(Bm); a.entered = p.entered(Bm); a.grip_left = p.grip_left(Bm); a.finished_tick = p.finished_tick(Bm);
         a.err = p.err(Bm); a.max_vel0 = p.max_vel0(Bm); a.gripper_force = p.gripper_force(Bm); a.start_xyz = p.start_xyz(Bm);
@@ -2118,12 +2152,22 @@ static int check_covers(irlosc_ctx* c, int slot, int B, int robots, const char* 
 
 // The slot's program covers B robots and, with `need` (a download), is of that kind; without (a rollout) a slot that has none passes
 static int check_program(irlosc_ctx* c, int slot, int B, Program::Kind need = Program::NONE) {
-    static const char* const what[] = {"", "waypoint paths", "action list", "teleoperation stream"};      // by Program::Kind
-    static const char* const covers[] = {"", "cover", "covers", "covers"};
-    static const char* const setter[] = {"", "irlosc_set_waypoints", "irlosc_set_action_list", "irlosc_set_teleop_stream"};
+    static const char* const what[] = {"", "waypoint paths", "action list", "teleoperation stream", "policy"};      // by Program::Kind
+    static const char* const covers[] = {"", "cover", "covers", "covers", "covers"};
+    static const char* const setter[] = {"", "irlosc_set_waypoints", "irlosc_set_action_list", "irlosc_set_teleop_stream", "irlosc_set_policy"};
     const Program& p = c->slot[slot].prog;
     const Program::Kind k = need ? need : p.kind;
     return check_covers(c, slot, B, !need || p.kind == need ? p.robots : 0, what[k], covers[k], need ? setter[k] : nullptr);
+}
+
+// A policy that observes the action objects finds those it was sized for, for B robots (objects come and go behind a policy's back)
+static int check_policy_objects(irlosc_ctx* c, int slot, int B) {
+    const Slot& s = c->slot[slot];
+    if (s.prog.kind != Program::POLICY || s.prog.po_nobj < 0) return IRLOSC_OK;
+    if (s.objects.count() != s.prog.po_nobj || s.objects.robots < B)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its policy observes %d action objects of %d robots, the slot has %d of %d (irlosc_set_policy again)", slot,
+                    s.prog.po_nobj, B, s.objects.count(), s.objects.robots);
+    return IRLOSC_OK;
 }
 
 // A program's table [nb][E] in the layout its kernel walks: per robot [walk wave][E][64] (idle lanes zero), shared (nb == 1) as given
@@ -2193,7 +2237,8 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
 //     tick_front:   [pushes SENSE: their reaction goes into the wrench ahead of every kernel that reads it] [walls SENSE: their force of the
 //                   tick before, behind it] [loads SENSE: the carried objects' weight of the tick before, behind that] [action objects: on this tick's EE poses and knuckle coordinates, in front of the action kernel,
 //                   whose refs read their poses] [action kernel: its targets and velocity limit are this tick's, so in front of every OSC kernel
-//                   | stream kernel: its targets are this tick's too]
+//                   | stream kernel: its targets are this tick's too | policy kernel: likewise, and it reads what the launches above left: the wrench behind
+//                   every SENSE, the objects' poses of this tick]
 //     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
 //     [log FRONT (a logged tick): coordinates, EE poses, targets, wrench, u and flags as the step used and left them -- behind the give-up
 //                   pass, which completes u; in front of the cycler, which moves the targets, and of the plant, which moves the
@@ -2214,6 +2259,7 @@ static int tick_front(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp, 
     if (tp.prog == Program::LIST && !s0.prog.motion) HIPCHK(c, (hipError_t)launch_actions<T>(action_args(c, s0, B, s0.prog.al, bk.xside[0], s0.prog.tick), st));
     if (tp.prog == Program::LIST && s0.prog.motion) HIPCHK(c, (hipError_t)launch_actions_motion<T>(action_motion_args(c, s0, B, bk.xside[0], s0.prog.tick), st));
     if (tp.reading >= 0) HIPCHK(c, (hipError_t)launch_teleop<T>(teleop_args(c, s0, B, s0.prog.ts, s0.prog.ts_shared.data(), tp.reading), st));
+    if (tp.prog == Program::POLICY) HIPCHK(c, (hipError_t)launch_policy<T>(policy_args(c, s0, B, bk.xside[0], wrench), st));
     return IRLOSC_OK;
 }
 template <typename T>
@@ -2770,6 +2816,7 @@ static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, i
     rc = check_slot_q(c, slot, B);
     if (!rc) rc = check_slot_feed(c, slot, B);
     if (!rc) rc = check_program(c, slot, B);
+    if (!rc) rc = check_policy_objects(c, slot, B);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].push.robots, "pushes", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].walls.robots, "walls", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
@@ -3356,6 +3403,32 @@ extern "C" int irlosc_download_action_motion_state(irlosc_ctx* c, int32_t slot, 
                           p.am_i, p.am_i_words(Bm), {{step, p.m_step(Bm), 1, 1, 0, 1}, {(int32_t*)draws, (const int32_t*)p.m_draws(Bm), 1, 1, 0, 1}});
 }
 
+// The rig of a stream or of a policy (the same fields, the same rules): IRLOSC_ERR_ARG with `what` in front of the reason
+template <class D>
+static int check_rig(irlosc_ctx* c, const char* what, int nd, const D* d) {
+    if (!std::isfinite(d->increment)) return fail(c, IRLOSC_ERR_ARG, "%s: increment is not finite", what);
+    bool any = false;
+    for (int k = 0; k < IRLOSC_MAX_DEV; ++k) {
+        const int kind = d->kind[k];
+        if (kind != IRLOSC_TELEOP_NONE && kind != IRLOSC_TELEOP_RIGID && kind != IRLOSC_TELEOP_HEADING)
+            return fail(c, IRLOSC_ERR_ARG, "%s: kind[%d]=%d is none of NONE, RIGID, HEADING", what, k, kind);
+        if (kind != IRLOSC_TELEOP_NONE && k >= nd) return fail(c, IRLOSC_ERR_ARG, "%s: kind[%d]=%d on a device >= ndev=%d", what, k, kind, nd);
+        any = any || kind != IRLOSC_TELEOP_NONE;
+        if (kind == IRLOSC_TELEOP_RIGID) {
+            double n2 = 0.0;
+            for (int i = 0; i < 3; ++i)
+                if (!std::isfinite(d->off_xyz[k][i])) return fail(c, IRLOSC_ERR_ARG, "%s: off_xyz[%d][%d] is not finite", what, k, i);
+            for (int i = 0; i < 4; ++i) n2 += d->off_quat[k][i] * d->off_quat[k][i];
+            if (!(std::fabs(n2 - 1.0) <= 1e-12))      // (a NaN or an infinity fails here too)
+                return fail(c, IRLOSC_ERR_ARG, "%s: off_quat[%d] is not of unit length (|q|^2 = %.17g)", what, k, n2);
+        }
+        if (kind == IRLOSC_TELEOP_HEADING && !std::isfinite(d->heading_offset[k]))
+            return fail(c, IRLOSC_ERR_ARG, "%s: heading_offset[%d] is not finite", what, k);
+    }
+    if (!any) return fail(c, IRLOSC_ERR_ARG, "%s: every device has kind NONE", what);
+    return IRLOSC_OK;
+}
+
 // ---- the teleoperation stream of the rollout (osc_teleop.hpp) -------------------------------------------------------------------
 extern "C" int irlosc_set_teleop_stream(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_teleop_stream* d, const double* readings,
                                         const double* origin) {
@@ -3370,26 +3443,7 @@ extern "C" int irlosc_set_teleop_stream(irlosc_ctx* c, int32_t slot, int32_t B, 
     if (d->nb != 1 && d->nb != B) return fail(c, IRLOSC_ERR_ARG, "teleop stream: nb=%d must be 1 or B=%d", d->nb, B);
     if (d->nb_origin != 1 && d->nb_origin != B) return fail(c, IRLOSC_ERR_ARG, "teleop stream: nb_origin=%d must be 1 or B=%d", d->nb_origin, B);
     if (d->loop != 0 && d->loop != 1) return fail(c, IRLOSC_ERR_ARG, "teleop stream: loop=%d must be 0 or 1", d->loop);
-    if (!std::isfinite(d->increment)) return fail(c, IRLOSC_ERR_ARG, "teleop stream: increment is not finite");
-    bool any = false;
-    for (int k = 0; k < IRLOSC_MAX_DEV; ++k) {
-        const int kind = d->kind[k];
-        if (kind != IRLOSC_TELEOP_NONE && kind != IRLOSC_TELEOP_RIGID && kind != IRLOSC_TELEOP_HEADING)
-            return fail(c, IRLOSC_ERR_ARG, "teleop stream: kind[%d]=%d is none of NONE, RIGID, HEADING", k, kind);
-        if (kind != IRLOSC_TELEOP_NONE && k >= nd) return fail(c, IRLOSC_ERR_ARG, "teleop stream: kind[%d]=%d on a device >= ndev=%d", k, kind, nd);
-        any = any || kind != IRLOSC_TELEOP_NONE;
-        if (kind == IRLOSC_TELEOP_RIGID) {
-            double n2 = 0.0;
-            for (int i = 0; i < 3; ++i)
-                if (!std::isfinite(d->off_xyz[k][i])) return fail(c, IRLOSC_ERR_ARG, "teleop stream: off_xyz[%d][%d] is not finite", k, i);
-            for (int i = 0; i < 4; ++i) n2 += d->off_quat[k][i] * d->off_quat[k][i];
-            if (!(std::fabs(n2 - 1.0) <= 1e-12))      // (a NaN or an infinity fails here too)
-                return fail(c, IRLOSC_ERR_ARG, "teleop stream: off_quat[%d] is not of unit length (|q|^2 = %.17g)", k, n2);
-        }
-        if (kind == IRLOSC_TELEOP_HEADING && !std::isfinite(d->heading_offset[k]))
-            return fail(c, IRLOSC_ERR_ARG, "teleop stream: heading_offset[%d] is not finite", k);
-    }
-    if (!any) return fail(c, IRLOSC_ERR_ARG, "teleop stream: every device has kind NONE");
+    if ((rc = check_rig(c, "teleop stream", nd, d))) return rc;
     if (!readings || !origin) return fail(c, IRLOSC_ERR_ARG, "teleop stream: %s is NULL", !readings ? "readings" : "origin");
     const size_t E = (size_t)T * 6;
     for (size_t i = 0; i < (size_t)d->nb * E; ++i)
@@ -3432,6 +3486,125 @@ extern "C" int irlosc_download_teleop_state(irlosc_ctx* c, int32_t slot, int32_t
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     const size_t Bm = (size_t)c->cfg.max_batch;      // rows [max_batch] on the device -> [B][6] for the caller
     return download_state(c, B, p.ts_pose, p.ts_words(Bm), {{pose, p.pose(Bm), 6, 6, 0, 1}}, nullptr, 0, {});
+}
+
+// ---- the policy of the rollout (osc_policy.hpp) -----------------------------------------------------------------------------------------
+// The network of description d over n_in inputs as the kernel walks it, and (with `weights`) the packed copy `out`: per layer the
+// fragments [output tile][k-step][64] -- lane l: W[16 ot + (l & 15)][4 ks + (l >> 4)], zero beyond the matrix -- then the bias padded to 16 ot
+static PolicyNet policy_net(const irlosc_policy& d, int n_in, const float* weights = nullptr, std::vector<float>* out = nullptr) {
+    PolicyNet net;
+    memset(&net, 0, sizeof net);
+    net.L = d.n_layers; net.n_in = n_in; net.n_out = d.n_out;
+    size_t off = 0, src = 0;
+    int in = n_in;
+    for (int l = 0; l < d.n_layers; ++l) {
+        const int o = l + 1 < d.n_layers ? d.width[l] : d.n_out, ks = (in + 3) / 4, ot = (o + 15) / 16;
+        net.ksteps[l] = ks; net.otiles[l] = ot;
+        net.woff[l] = (int32_t)off; net.boff[l] = (int32_t)(off + (size_t)ot * ks * 64);
+        net.rows[l & 1] = std::max(net.rows[l & 1], 4 * ks);
+        net.rows[(l & 1) ^ 1] = std::max(net.rows[(l & 1) ^ 1], 16 * ot);
+        if (out) {
+            out->resize(net.boff[l] + (size_t)ot * 16, 0.0f);
+            for (int t = 0; t < ot; ++t)
+                for (int k = 0; k < ks; ++k)
+                    for (int ln = 0; ln < 64; ++ln) {
+                        const int j = 16 * t + (ln & 15), i = 4 * k + (ln >> 4);
+                        if (j < o && i < in) (*out)[off + ((size_t)t * ks + k) * 64 + ln] = weights[src + (size_t)j * in + i];
+                    }
+            for (int j = 0; j < o; ++j) (*out)[net.boff[l] + j] = weights[src + (size_t)o * in + j];
+        }
+        off = net.boff[l] + (size_t)ot * 16;
+        src += (size_t)o * in + o;
+        in = o;
+    }
+    return net;
+}
+
+extern "C" int irlosc_set_policy(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_policy* d, const float* weights, const double* origin) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { if (s.prog.kind == Program::POLICY) s.episodes.end(); s.prog.end(Program::POLICY); return IRLOSC_OK; }
+    const int nd = c->cfg.ndev, n = c->cfg.n, L = d->n_layers;
+    constexpr uint32_t ALL = IRLOSC_OBS_QPOS | IRLOSC_OBS_QVEL | IRLOSC_OBS_EE_POSE | IRLOSC_OBS_TARGETS | IRLOSC_OBS_WRENCH | IRLOSC_OBS_PLATE | IRLOSC_OBS_OBJECT_POSE;
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "policy: B=%d must be >= 1", B);
+    if (d->obs == 0 || (d->obs & ~ALL)) return fail(c, IRLOSC_ERR_ARG, "policy: obs=0x%x must name at least one of the IRLOSC_OBS_* channels and no other bit", d->obs);
+    if (L < 1 || L > IRLOSC_POLICY_MAX_LAYERS) return fail(c, IRLOSC_ERR_ARG, "policy: n_layers=%d out of [1,%d]", L, IRLOSC_POLICY_MAX_LAYERS);
+    for (int l = 0; l < IRLOSC_POLICY_MAX_LAYERS; ++l) {
+        if (l < L - 1 && (d->width[l] < 1 || d->width[l] > IRLOSC_POLICY_MAX_WIDTH))
+            return fail(c, IRLOSC_ERR_ARG, "policy: width[%d]=%d out of [1,%d]", l, d->width[l], IRLOSC_POLICY_MAX_WIDTH);
+        if (l >= L - 1 && d->width[l] != 0) return fail(c, IRLOSC_ERR_ARG, "policy: width[%d]=%d behind the %d hidden layers must be 0", l, d->width[l], L - 1);
+    }
+    if (d->n_out != 6 && d->n_out != 7) return fail(c, IRLOSC_ERR_ARG, "policy: n_out=%d must be 6 or 7", d->n_out);
+    if ((d->keep_obs != 0 && d->keep_obs != 1) || d->reserved != 0) return fail(c, IRLOSC_ERR_ARG, "policy: keep_obs=%d must be 0 or 1, reserved=%d must be 0", d->keep_obs, d->reserved);
+    if (!(d->clip >= 0.0f) || !std::isfinite(d->clip)) return fail(c, IRLOSC_ERR_ARG, "policy: clip=%g must be finite and >= 0", (double)d->clip);
+    if (d->nb_origin != 1 && d->nb_origin != B) return fail(c, IRLOSC_ERR_ARG, "policy: nb_origin=%d must be 1 or B=%d", d->nb_origin, B);
+    if (d->n_out == 7) {
+        if (d->grip_dev < 0 || d->grip_dev >= nd) return fail(c, IRLOSC_ERR_ARG, "policy: grip_dev=%d out of [0,%d)", d->grip_dev, nd);
+        if (!std::isfinite(d->grip_close) || !std::isfinite(d->grip_open) || d->grip_close == 0.0 || d->grip_open == 0.0)
+            return fail(c, IRLOSC_ERR_ARG, "policy: grip_close=%g and grip_open=%g must be finite and not 0", d->grip_close, d->grip_open);
+    }
+    if ((rc = check_rig(c, "policy", nd, d))) return rc;
+    if (!weights || !origin) return fail(c, IRLOSC_ERR_ARG, "policy: %s is NULL", !weights ? "weights" : "origin");
+    for (size_t i = 0; i < (size_t)d->nb_origin * 6; ++i)
+        if (!std::isfinite(origin[i])) return fail(c, IRLOSC_ERR_ARG, "policy: origin of robot %zu is not finite", i / 6);
+    const bool looks = (d->obs & IRLOSC_OBS_OBJECT_POSE) != 0;
+    if (looks && (!s.objects.count() || s.objects.robots < B))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d has no action objects for %d robots, the policy observes them (irlosc_set_objects first)", slot, B);
+    const int nobj = looks ? s.objects.count() : -1;
+    const int widths[7] = {n, n, nd * 7, nd * 7, nd * 6, 6, std::max(0, nobj) * 7};
+    int n_in = 0;
+    for (int i = 0; i < 7; ++i) n_in += ((d->obs >> i) & 1u) ? widths[i] : 0;
+    if (n_in < 1 || n_in > IRLOSC_POLICY_MAX_IN) return fail(c, IRLOSC_ERR_ARG, "policy: n_in=%d of obs=0x%x out of [1,%d]", n_in, d->obs, IRLOSC_POLICY_MAX_IN);
+    size_t nw = 0;
+    for (int l = 0, in = n_in; l < L; ++l) { const int o = l < L - 1 ? d->width[l] : d->n_out; nw += (size_t)o * in + o; in = o; }
+    for (size_t i = 0; i < nw; ++i)
+        if (!std::isfinite(weights[i])) return fail(c, IRLOSC_ERR_ARG, "policy: weight %zu is not finite", i);
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, policy given for %d: irlosc_set_targets first", slot, std::max(0, s.targets), B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Program& p = s.prog;
+    p.end();           // (none until the new one is in its buffers; the policy writes the targets from here on: paths, a list or a stream end)
+    s.episodes.end();  // (set on the program this call replaces)
+    std::vector<float> packed;
+    const PolicyNet net = policy_net(*d, n_in, weights, &packed);
+    irlosc_teleop_stream rig{};      // the rig in a stream's form: what teleop_args and the shared body read
+    rig.ticks = 1; rig.nb = 1; rig.nb_origin = d->nb_origin; rig.increment = d->increment;
+    memcpy(rig.kind, d->kind, sizeof rig.kind); memcpy(rig.off_xyz, d->off_xyz, sizeof rig.off_xyz);
+    memcpy(rig.off_quat, d->off_quat, sizeof rig.off_quat); memcpy(rig.heading_offset, d->heading_offset, sizeof rig.heading_offset);
+    std::vector<double> org;
+    if (d->nb_origin > 1) org = walk_table(origin, d->nb_origin, 6);
+    const size_t Bm = (size_t)c->cfg.max_batch, out_bytes = 7 * Bm * sizeof(float), obs_bytes = d->keep_obs ? (size_t)B * n_in * sizeof(float) : 0;
+    if (!got(p.ts_pose.ensure(p.ts_words(Bm) * sizeof(double))) || !got(p.ts_origin.reserve(org.size() * sizeof(double))) ||
+        !got(p.po_w.reserve(packed.size() * sizeof(float))) || !got(p.po_out.ensure(out_bytes)) || !got(p.po_grip.ensure(Bm * sizeof(double))) ||
+        !got(p.po_obs.reserve(obs_bytes)))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the policy of slot %d", slot);
+    const TeleopArgs init = teleop_args(c, s, B, rig, origin, -1);
+    const auto launch = c->cfg.dtype == IRLOSC_F64 ? launch_teleop<double> : launch_teleop<float>;
+    rc = setter_upload(c, {{p.ts_origin, org.data(), org.size() * sizeof(double)}, {p.po_w, packed.data(), packed.size() * sizeof(float)},
+                           {p.po_out, nullptr, out_bytes, 0}, {p.po_grip, nullptr, Bm * sizeof(double), 0}, {p.po_obs, nullptr, obs_bytes, 0}}, launch, &init);
+    if (!rc) p.policy(B, *d, rig, net, nobj, origin);
+    return rc;
+}
+
+extern "C" int irlosc_download_policy_state(irlosc_ctx* c, int32_t slot, int32_t B, double* pose, float* out, double* grip, float* obs, int32_t* tick) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B, Program::POLICY);
+    if (rc) return rc;
+    const Program& p = c->slot[slot].prog;
+    if (obs && !p.po.keep_obs) return fail(c, IRLOSC_ERR_STATE, "slot %d: its policy keeps no observation (keep_obs == 0)", slot);
+    if (tick) *tick = p.tick;
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, no = (size_t)p.po.n_out;      // rows [max_batch] on the device -> [B][6], [B][n_out], [B] for the caller
+    if (obs) HIPCHK(c, hipMemcpyAsync(obs, p.po_obs, (size_t)B * p.po_net.n_in * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (pose || out) rc = download_state(c, B, pose ? p.ts_pose.get() : nullptr, pose ? p.ts_words(Bm) : 0, {{pose, p.pose(Bm), 6, 6, 0, 1}},      // (out: float words moved as int32 words)
+                                         out ? (const int32_t*)p.po_out.get() : nullptr, out ? no * Bm : 0, {{(int32_t*)out, (const int32_t*)p.po_out.get(), no, no, 0, 1}});
+    if (!rc) rc = download_state(c, B, grip ? p.po_grip.get() : nullptr, grip ? Bm : 0, {{grip, p.po_grip.get(), 1, 1, 0, 1}}, nullptr, 0, {});      // (synchronises: obs is in)
+    return rc;
 }
 
 extern "C" int irlosc_download_targets(irlosc_ctx* c, int32_t slot, int32_t B, void* tgt_pose) {

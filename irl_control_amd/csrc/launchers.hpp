@@ -114,6 +114,12 @@ struct TeleopArgs;
 template <typename T>
 int launch_teleop(const TeleopArgs& a, hipStream_t st);
 
+// tu_policy.hip -- the policy where the stream's kernel goes, on a rollout tick whose slot has one (osc_policy.hpp): the observation
+// gathered, the network on the f32-input MFMA, the stream's body on its output; T = record type (of the targets and the wrench)
+struct PolicyArgs;
+template <typename T>
+int launch_policy(const PolicyArgs& a, hipStream_t st);
+
 // tu_push.hip -- the external pushes of a rollout tick whose slot has some active (osc_push.hpp): sense mode between the sensor feed's
 // wrench kernel and the first kernel that reads the wrench, apply mode in front of the plant; T = record type (of the wrench)
 struct PushArgs;

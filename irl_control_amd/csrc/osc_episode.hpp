@@ -13,7 +13,7 @@
 //     tile (osc_common.hpp: its contract; PATHS: waypoint 0 of every listed device on top), the list's state as osc_action_kernel's init
 //     branch leaves it with word 9 of the active device's gain record taken again from the context's gains and, with pose variants,
 //     the robot's lines of the list's pose table rewritten with variant count mod V, the paths' state as the cycler's init, the walls'
-//     and the joint rows' state as their setters' fills, the action objects' state as osc_object_kernel's init leaves it, on their
+//     and the joint rows' state as their setters' fills, a policy's plate on the robot's origin with out and grip zero, the action objects' state as osc_object_kernel's init leaves it, on their
 //     start poses count mod OV, the carried objects' load words and carry_ticks zero; on a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
 //   idle lanes of a ragged last wave neither load nor store.
 // Every wave stores the number of its robots that are not parked into running[walk wave] (a plain store by lane 0): the early exit's input.
@@ -29,7 +29,7 @@
 
 namespace irlosc {
 
-enum : int32_t { EP_NONE = 0, EP_PATHS = 1, EP_LIST = 2 };      // the program in force on the tick (Program::Kind of irlosc.hip, STREAM refused)
+enum : int32_t { EP_NONE = 0, EP_PATHS = 1, EP_LIST = 2, EP_POLICY = 3 };      // the program in force on the tick (Program::Kind of irlosc.hip, STREAM refused)
 
 struct EpisodeArgs {
     int32_t* count;           // [stride] each
@@ -53,6 +53,13 @@ struct EpisodeArgs {
     // PATHS (osc_waypoint.hpp)
     int32_t* wp_index; uint32_t* wp_arrivals; int32_t* wp_last_tick;      // [ndev][stride]
     const double* wp_table;   // wp_per_robot: [walk wave][ndev][wmax][3][64], else [ndev][wmax][3]
+    // POLICY (osc_policy.hpp): never finished -- its episodes end by max_ticks alone; a reset puts the plate back to the robot's origin
+    double* pl_pose;          // [6][stride]
+    const double* pl_origin;  // per robot: [walk wave][6][64]; nullptr: pl_origin0 for the fleet
+    double pl_origin0[6];
+    float* pl_out;            // [pl_n_out][stride]
+    double* pl_grip;          // [stride]
+    int32_t pl_n_out, pl_pad;
     // walls (osc_wall.hpp): planes [ndev][stride]; joint rows (osc_joint.hpp): rows [stride]
     double* wall_force; double* wall_depth; int32_t* wall_contact; int32_t* wall_first;
     double* jt_tau; double* jt_violation; double* jt_ctrl; int32_t* jt_active;
@@ -179,6 +186,13 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
                 const size_t o = (size_t)d * a.stride + so;
                 a.wp_index[o] = 0; a.wp_arrivals[o] = 0u; a.wp_last_tick[o] = -1;
             }
+        }
+        if (a.kind == EP_POLICY) {                  // as irlosc_set_policy leaves it: the plate at the origin, out and grip zero
+#pragma unroll
+            for (int c = 0; c < 6; ++c)
+                a.pl_pose[(size_t)c * a.stride + so] = a.pl_origin ? a.pl_origin[((size_t)blockIdx.x * 6 + c) * 64 + lane] : a.pl_origin0[c];
+            for (int c = 0; c < a.pl_n_out; ++c) a.pl_out[(size_t)c * a.stride + so] = 0.0f;
+            a.pl_grip[so] = 0.0;
         }
         if (a.walls) {                              // as irlosc_set_walls' fills
             const size_t plane = (size_t)a.ndev * a.stride;

@@ -17,6 +17,9 @@
 //   RIGID d:    tgt xyz = p + R(q_p) off_xyz[d];  tgt quat = q_p (x) off_quat[d]
 //   HEADING d:  h = atan2(y, x) + heading_offset[d];  tgt quat = (cos(h / 2), 0, 0, sin(h / 2));  xyz stays
 //
+// The per-robot body -- reading -> pose -> followers' targets -- is teleop_follow: the policy kernel (osc_policy.hpp) calls it on the reading its
+// network computed, and its setter uses this kernel's init launch.
+//
 // init = 1 (irlosc_set_teleop_stream): pose = origin (per robot: [walk wave][6][64] at `readings`; shared: `r`); no target is touched.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +42,47 @@ struct TeleopArgs {
 };
 
 __device__ __forceinline__ double teleop_wrap(double a) { return atan2(sin(a), cos(a)); }
+
+// One robot's tick on reading r: the pose integrated and stored, the followers' targets written into the robot's row of the wave's
+// target tile s_t (`row` words per robot).  The body of the stream's tick; osc_policy.hpp calls it with the reading its network computed.
+template <typename T>
+__device__ __forceinline__ void teleop_follow(const TeleopArgs& a, T* s_t, int lane, size_t so, int row, const double r[6]) {
+    double p[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) p[c] = a.pose[(size_t)c * a.stride + so];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = __dadd_rn(p[c], __dmul_rn(a.inc, r[c]));
+    p[5] = teleop_wrap(__dsub_rn(p[5], __dmul_rn(a.inc, r[5])));
+    p[4] = teleop_wrap(__dsub_rn(p[4], __dmul_rn(a.inc, r[4])));
+    p[3] = teleop_wrap(__dadd_rn(p[3], __dmul_rn(a.inc, r[3])));
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a.pose[(size_t)c * a.stride + so] = p[c];
+    // q_p = qx(pitch) (x) qy(roll) (x) qz(yaw)
+    const double hx = __dmul_rn(p[4], 0.5), hy = __dmul_rn(p[3], 0.5), hz = __dmul_rn(p[5], 0.5);
+    const double cx = cos(hx), sx = sin(hx), cy = cos(hy), sy = sin(hy), cz = cos(hz), sz = sin(hz);
+    const double cc = __dmul_rn(cy, cz), ss = __dmul_rn(sy, sz), sc = __dmul_rn(sy, cz), cs = __dmul_rn(cy, sz);
+    const double qw = __dsub_rn(__dmul_rn(cx, cc), __dmul_rn(sx, ss)), qx = __dadd_rn(__dmul_rn(cx, ss), __dmul_rn(sx, cc));
+    const double qy = __dsub_rn(__dmul_rn(cx, sc), __dmul_rn(sx, cs)), qz = __dadd_rn(__dmul_rn(cx, cs), __dmul_rn(sx, sc));
+    // R(q_p): transforms.quat2mat (|q_p| is 1 to rounding, far from its Nq < eps branch)
+    const double qp[4] = {qw, qx, qy, qz};
+    double R[3][3];
+    quat2mat_rn(qp, R);
+    for (int d = 0; d < a.ndev; ++d) {
+        T* t = s_t + lane * row + d * 7;
+        if (a.kind[d] == IRLOSC_TELEOP_RIGID) {
+            double ro[3], qt[4];
+            mat_vec_rn(R, a.off_xyz[d], ro);
+            quat_mul_rn(qp, a.off_quat[d], qt);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) t[c] = (T)__dadd_rn(p[c], ro[c]);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[3 + c] = (T)qt[c];
+        } else if (a.kind[d] == IRLOSC_TELEOP_HEADING) {
+            const double h = __dmul_rn(__dadd_rn(atan2(p[1], p[0]), a.heading[d]), 0.5);
+            t[3] = (T)cos(h); t[4] = (T)0.0; t[5] = (T)0.0; t[6] = (T)sin(h);
+        }
+    }
+}
 
 template <typename T>
 __global__ __launch_bounds__(64) void osc_teleop_kernel(const TeleopArgs a) {
@@ -65,43 +109,7 @@ __global__ __launch_bounds__(64) void osc_teleop_kernel(const TeleopArgs a) {
     const int row = a.ndev * 7;
     T* __restrict__ tg = (T*)a.tgt + (size_t)b0 * row;
     tgt_tile_load(s_t, tg, nvalid, row);
-    if (valid) {
-        double p[6];
-#pragma unroll
-        for (int c = 0; c < 6; ++c) p[c] = a.pose[(size_t)c * a.stride + so];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p[c] = __dadd_rn(p[c], __dmul_rn(a.inc, r[c]));
-        p[5] = teleop_wrap(__dsub_rn(p[5], __dmul_rn(a.inc, r[5])));
-        p[4] = teleop_wrap(__dsub_rn(p[4], __dmul_rn(a.inc, r[4])));
-        p[3] = teleop_wrap(__dadd_rn(p[3], __dmul_rn(a.inc, r[3])));
-#pragma unroll
-        for (int c = 0; c < 6; ++c) a.pose[(size_t)c * a.stride + so] = p[c];
-        // q_p = qx(pitch) (x) qy(roll) (x) qz(yaw)
-        const double hx = __dmul_rn(p[4], 0.5), hy = __dmul_rn(p[3], 0.5), hz = __dmul_rn(p[5], 0.5);
-        const double cx = cos(hx), sx = sin(hx), cy = cos(hy), sy = sin(hy), cz = cos(hz), sz = sin(hz);
-        const double cc = __dmul_rn(cy, cz), ss = __dmul_rn(sy, sz), sc = __dmul_rn(sy, cz), cs = __dmul_rn(cy, sz);
-        const double qw = __dsub_rn(__dmul_rn(cx, cc), __dmul_rn(sx, ss)), qx = __dadd_rn(__dmul_rn(cx, ss), __dmul_rn(sx, cc));
-        const double qy = __dsub_rn(__dmul_rn(cx, sc), __dmul_rn(sx, cs)), qz = __dadd_rn(__dmul_rn(cx, cs), __dmul_rn(sx, sc));
-        // R(q_p): transforms.quat2mat (|q_p| is 1 to rounding, far from its Nq < eps branch)
-        const double qp[4] = {qw, qx, qy, qz};
-        double R[3][3];
-        quat2mat_rn(qp, R);
-        for (int d = 0; d < a.ndev; ++d) {
-            T* t = s_t + lane * row + d * 7;
-            if (a.kind[d] == IRLOSC_TELEOP_RIGID) {
-                double ro[3], qt[4];
-                mat_vec_rn(R, a.off_xyz[d], ro);
-                quat_mul_rn(qp, a.off_quat[d], qt);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) t[c] = (T)__dadd_rn(p[c], ro[c]);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) t[3 + c] = (T)qt[c];
-            } else if (a.kind[d] == IRLOSC_TELEOP_HEADING) {
-                const double h = __dmul_rn(__dadd_rn(atan2(p[1], p[0]), a.heading[d]), 0.5);
-                t[3] = (T)cos(h); t[4] = (T)0.0; t[5] = (T)0.0; t[6] = (T)sin(h);
-            }
-        }
-    }
+    if (valid) teleop_follow(a, s_t, lane, so, row, r);
     tgt_tile_store(tg, s_t, nvalid, row, valid);
 }
 
