@@ -11,6 +11,7 @@
 #include <new>
 #include <string>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <type_traits>
 #include <vector>
@@ -91,6 +92,10 @@ struct Program {
     double* pose(size_t) const { return ts_pose; }      // (x y z roll pitch yaw: six rows of Bm words)
     static size_t wp_words(size_t plane) { return 3 * plane; }  static size_t al_i_words(size_t Bm) { return 4 * Bm; }  static size_t al_d_words(size_t Bm) { return 6 * Bm; }
     static size_t ts_words(size_t Bm) { return 6 * Bm; }
+    // ... and each kind's state as its kernels and a reset of episodes take it (the structs of osc_action.hpp, osc_waypoint.hpp, osc_teleop.hpp, osc_policy.hpp)
+    ListState list_state(size_t Bm) const { return {action(Bm), entered(Bm), grip_left(Bm), finished_tick(Bm), err(Bm), max_vel0(Bm), gripper_force(Bm), start_xyz(Bm)}; }
+    MotionState motion_state(size_t Bm) const { return {m_step(Bm), m_draws(Bm), m_origin(Bm), m_goal(Bm)}; }  PlateState plate_state(size_t Bm) const { return {pose(Bm)}; }
+    PathState path_state(size_t plane) const { return {index(plane), (uint32_t*)arrivals(plane), last_tick(plane)}; }  PolicyState policy_state() const { return {po_out, po_grip}; }
 
     // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
     void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
@@ -161,6 +166,7 @@ struct Walls : PlantForce {
     double* force(size_t plane, size_t axis = 0) const { return st_d + axis * plane; }  double* max_depth(size_t plane) const { return st_d + 3 * plane; }
     int32_t* contact_ticks(size_t) const { return st_i; }  int32_t* first_tick(size_t plane) const { return st_i + plane; }
     static size_t d_words(size_t plane) { return 4 * plane; }  static size_t i_words(size_t plane) { return 2 * plane; }
+    WallState state(size_t plane) const { return {force(plane), max_depth(plane), contact_ticks(plane), first_tick(plane)}; }
     void set(int B, const irlosc_walls& desc) { in_force(B); d = desc; }
     // The devices that have a wall: bit d
     uint32_t devices() const {
@@ -180,6 +186,7 @@ struct Joints : PlantForce {
     double* tau(size_t) const { return st_d; }  double* max_violation(size_t Bm) const { return st_d + (size_t)IRLOSC_MAX_N * Bm; }
     double* ctrl(size_t Bm, size_t R) const { return st_d + ((size_t)IRLOSC_MAX_N + R) * Bm; }  int32_t* active_ticks(size_t) const { return st_i; }
     static size_t d_words(size_t Bm, size_t R) { return ((size_t)IRLOSC_MAX_N + 2 * R) * Bm; }  static size_t i_words(size_t Bm, size_t R) { return R * Bm; }
+    JointState state(size_t Bm) const { return {tau(Bm), max_violation(Bm), ctrl(Bm, d.n_rows), active_ticks(Bm)}; }      // (of the rows in force)
     void set(int B, const irlosc_joint_rows& desc) { in_force(B); d = desc; }
 };
 
@@ -197,6 +204,7 @@ struct Objects : PlantForce {
     int32_t* was_closed(size_t Bm) const { return st_i + 3 * (size_t)IRLOSC_MAX_OBJECTS * Bm; }
     int32_t* mated_tick(size_t Bm) const { return st_i + (3 * (size_t)IRLOSC_MAX_OBJECTS + IRLOSC_MAX_GRIPPERS) * Bm; }
     static size_t d_words(size_t Bm) { return (size_t)OBJ_D_ROWS * Bm; }  static size_t i_words(size_t Bm) { return (size_t)OBJ_I_ROWS * Bm; }
+    ObjectState state(size_t Bm) const { return {pose(Bm), rel(Bm), holder(Bm), grasp_tick(Bm), release_tick(Bm), was_closed(Bm), mated_tick(Bm)}; }
     void set(int B, const irlosc_objects& desc, size_t vs) { in_force(B); d = desc; vstride = vs; }
     int count() const { return robots ? d.n_objects : 0; }      // objects of the slot (0: it has none)
 };
@@ -211,6 +219,7 @@ struct Loads : PlantForce {
     // THE LAYOUT of the state (osc_object_load.hpp): rows of Bm = max_batch words
     double* load(size_t) const { return st_d; }  int32_t* carry_ticks(size_t) const { return st_i; }
     static size_t d_words(size_t Bm) { return (size_t)IRLOSC_MAX_GRIPPERS * 6 * Bm; }  static size_t i_words(size_t Bm) { return (size_t)IRLOSC_MAX_GRIPPERS * Bm; }
+    LoadState state(size_t Bm) const { return {load(Bm), carry_ticks(Bm)}; }
     void set(int B, const irlosc_object_loads& desc) { in_force(B); d = desc; }
 };
 
@@ -278,6 +287,14 @@ struct Slot {
     Loads loads;               // what the carried objects weigh (only next to the objects they describe)
     Episodes episodes;         // what ends and restarts single robots inside a rollout
     int ticks_run = 0;         // ticks the last rollout call on the slot ran (fewer than asked: an early exit of its episodes)
+    // THE SLOT'S ROLLOUT PARTS, listed three times and nowhere else: a new part goes into all three (adding a part).
+    // The model changed: what was laid out for the old one ends -- the compact block and the feed, and every part.
+    void model_changed() { drop_block(true); prog.end(); push.end(); walls.end(); joints.end(); objects.end(); loads.end(); episodes.end(); }
+    // A whole rollout tick is enqueued (prog_ran: with the program's kernel): every part in force is a tick older.
+    void parts_ticked(bool prog_ran) { if (prog_ran) prog.ticked(); push.ticked(); walls.ticked(); joints.ticked(); objects.ticked(); loads.ticked(); episodes.ticked(); }
+    // The parts whose state a reset of episodes writes, with the robots each covers: episodes cover no more (irlosc_set_episodes)
+    struct Cover { int robots; const char* what; };
+    std::array<Cover, 5> reset_covers() const { return {{{prog.robots, "program"}, {walls.robots, "walls"}, {joints.robots, "joint rows"}, {objects.robots, "action objects"}, {loads.robots, "object loads"}}}; }
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -1685,7 +1702,7 @@ int Model::commit(irlosc_ctx* c, const ModelPlan& p) {
     // what was laid out for the old model: bank buffers, every slot's compact block (built again by its next upload / front end) and
     // sensor feed, the F/T description (site bodies, R_rel)
     if (resize) for (irlosc_ctx::Bank& bk : c->bank) free_bank(bk, NEED_X | NEED_LANE);
-    for (Slot& s : c->slot) { s.drop_block(true); s.prog.end(); s.push.end(); s.walls.end(); s.joints.end(); s.objects.end(); s.loads.end(); s.episodes.end(); }
+    for (Slot& s : c->slot) s.model_changed();
     c->ft_set = 0;
     c->plant_set = 0;      // (its joint mask was checked against another model's hinges)
     if (fused) {      // coordinates uploaded while the fused path was off: laid out for the walk here, not by a train on another stream
@@ -1866,12 +1883,9 @@ static ActionArgs action_args(const irlosc_ctx* c, const Slot& s, int B, const i
     ActionArgs a;
     memset(&a, 0, sizeof a);
     const size_t Bm = (size_t)c->cfg.max_batch;
-    a.xside = xside; a.tgt = s.tgt; a.gains = p.al_gains;
-    a.action = p.action(Bm); a.entered = p.entered(Bm); a.grip_left = p.grip_left(Bm); a.finished_tick = p.finished_tick(Bm);
-    a.err = p.err(Bm); a.max_vel0 = p.max_vel0(Bm); a.gripper_force = p.gripper_force(Bm); a.start_xyz = p.start_xyz(Bm);
-    a.table = p.al_table;
+    a.xside = xside; a.tgt = s.tgt; a.gains = p.al_gains; a.st = p.list_state(Bm); a.table = p.al_table;
     if (xside && p.refs && s.objects.robots) {      // (refs live only next to the objects they name: irlosc_set_objects ends them)
-        a.obj_pose = s.objects.pose(Bm);
+        a.obj_pose = s.objects.state(Bm).pose;
         for (int i = 0; i < d.n_actions; ++i) { a.xyz_obj[i] = (int8_t)p.rf.xyz_obj[i]; a.quat_obj[i] = (int8_t)p.rf.quat_obj[i]; }
     }
     for (int i = 0; i < d.n_actions; ++i) {
@@ -1896,8 +1910,7 @@ static ActionMotionArgs action_motion_args(const irlosc_ctx* c, const Slot& s, i
     ActionMotionArgs a;
     memset(&a, 0, sizeof a);
     static_cast<ActionArgs&>(a) = action_args(c, s, B, p.al, xside, tick);
-    const size_t Bm = (size_t)c->cfg.max_batch;
-    a.m_step = p.m_step(Bm); a.m_draws = p.m_draws(Bm); a.m_origin = p.m_origin(Bm); a.m_goal = p.m_goal(Bm);
+    a.mo = p.motion_state((size_t)c->cfg.max_batch);
     for (int i = 0; i < p.al.n_actions; ++i) { a.steps[i] = p.am.steps[i]; a.noise_mean[i] = p.am.noise_mean[i]; a.noise_std[i] = p.am.noise_std[i]; }
     a.seed = p.am.seed;
     return a;
@@ -1910,9 +1923,7 @@ static ObjectArgs object_args(const irlosc_ctx* c, const Slot& s, int B, const i
     ObjectArgs a;
     memset(&a, 0, sizeof a);
     const size_t Bm = (size_t)c->cfg.max_batch;
-    a.xside = xside; a.qt = s.qt; a.pose0 = o.table;
-    a.pose = o.pose(Bm); a.rel = o.rel(Bm); a.holder = o.holder(Bm); a.grasp_tick = o.grasp_tick(Bm); a.release_tick = o.release_tick(Bm);
-    a.was_closed = o.was_closed(Bm); a.mated_tick = o.mated_tick(Bm);
+    a.xside = xside; a.qt = s.qt; a.pose0 = o.table; a.st = o.state(Bm);
     for (int g = 0; g < d.n_grippers; ++g) {
         a.sign[g] = (double)d.sign[g]; a.q_close[g] = d.q_close[g]; a.q_open[g] = d.q_open[g]; a.joint[g] = d.joint[g];
         for (int i = 0; i < 3; ++i) a.grip_xyz[g][i] = d.grip_xyz[g][i];
@@ -1938,7 +1949,7 @@ static TeleopArgs teleop_args(const irlosc_ctx* c, const Slot& s, int B, const i
     const size_t Bm = (size_t)c->cfg.max_batch;
     a.init = index < 0;
     a.per_robot = (a.init ? d.nb_origin : d.nb) > 1;
-    a.tgt = s.tgt; a.pose = p.pose(Bm); a.readings = a.init ? p.ts_origin : p.ts_table;
+    a.tgt = s.tgt; a.st = p.plate_state(Bm); a.readings = a.init ? p.ts_origin : p.ts_table;
     for (int i = 0; i < 6 && !a.per_robot; ++i) a.r[i] = shared[(a.init ? 0 : (size_t)index * 6) + i];
     a.inc = d.increment;
     for (int k = 0; k < c->cfg.ndev; ++k) {
@@ -1957,8 +1968,8 @@ static PolicyArgs policy_args(const irlosc_ctx* c, const Slot& s, int B, const d
     memset(&a, 0, sizeof a);
     const size_t Bm = (size_t)c->cfg.max_batch;
     a.t = teleop_args(c, s, B, p.ts, p.po_origin0, 0);      // (the rig, the targets, the pose; no reading: the kernel computes it)
-    a.net = p.po_net; a.w = p.po_w; a.qt = s.qt; a.xside = xside; a.wrench = wrench; a.obj_pose = s.objects.pose(Bm);
-    a.out = p.po_out; a.grip = p.po_grip; a.obs = p.po.keep_obs ? p.po_obs.get() : nullptr; a.flags_any = c->dflags_any;
+    a.net = p.po_net; a.w = p.po_w; a.qt = s.qt; a.xside = xside; a.wrench = wrench; a.obj_pose = s.objects.state(Bm).pose;
+    a.st = p.policy_state(); a.obs = p.po.keep_obs ? p.po_obs.get() : nullptr; a.flags_any = c->dflags_any;
     a.grip_close = p.po.grip_close; a.grip_open = p.po.grip_open; a.clip = p.po.clip; a.obs_mask = p.po.obs;
     a.n = c->cfg.n; a.n_entries = (int32_t)c->model.fe_xentries; a.nobj = std::max(0, p.po_nobj);
     fill_ee0(c, a.ee0);
@@ -1971,8 +1982,7 @@ static WaypointArgs waypoint_args(const irlosc_ctx* c, const Slot& s, int B, con
     memset(&a, 0, sizeof a);
     const Program& p = s.prog;
     const size_t plane = (size_t)c->cfg.ndev * c->cfg.max_batch;
-    a.xside = xside; a.tgt = s.tgt; a.table = p.wp_table;
-    a.index = p.index(plane); a.arrivals = (uint32_t*)p.arrivals(plane); a.last_tick = p.last_tick(plane);
+    a.xside = xside; a.tgt = s.tgt; a.table = p.wp_table; a.st = p.path_state(plane);
     for (int d = 0; d < c->cfg.ndev; ++d) {
         a.thr2[d] = w.threshold[d] * w.threshold[d];
         a.count[d] = w.count[d];
@@ -2006,8 +2016,7 @@ static WallArgs wall_args(const irlosc_ctx* c, const Slot& s, int B, uint32_t de
     const size_t plane = (size_t)c->cfg.ndev * c->cfg.max_batch;
     WallArgs a;
     memset(&a, 0, sizeof a);
-    a.xside = xside; a.qt = s.qt; a.wrench = wrench; a.table = w.table;
-    a.force = w.force(plane); a.max_depth = w.max_depth(plane); a.contact_ticks = w.contact_ticks(plane); a.first_tick = w.first_tick(plane);
+    a.xside = xside; a.qt = s.qt; a.wrench = wrench; a.table = w.table; a.st = w.state(plane);
     a.B = B; a.ndev = c->cfg.ndev; a.W = w.d.n_walls; a.per_robot = w.d.nb > 1; a.stride = c->cfg.max_batch;
     a.apply = xside ? 1 : 0; a.tick = w.tick; a.devs = devs;
     for (int i = 0; i < w.d.n_walls; ++i) a.dev[i] = w.d.dev[i];
@@ -2024,7 +2033,7 @@ static ObjectLoadArgs load_args(const irlosc_ctx* c, const Slot& s, int B, uint3
     ObjectLoadArgs a;
     memset(&a, 0, sizeof a);
     a.xside = xside; a.wrench = wrench; a.table = l.table;
-    a.obj_pose = o.pose(Bm); a.obj_holder = o.holder(Bm); a.load = l.load(Bm); a.carry_ticks = l.carry_ticks(Bm);
+    a.obj_pose = o.state(Bm).pose; a.obj_holder = o.state(Bm).holder; a.st = l.state(Bm);
     for (int i = 0; i < 3; ++i) a.gravity[i] = l.d.gravity[i];
     a.B = B; a.ndev = c->cfg.ndev; a.nobj = o.d.n_objects; a.ng = o.d.n_grippers; a.per_robot = l.d.per_robot; a.stride = (int32_t)Bm;
     a.apply = xside ? 1 : 0; a.grippers = grippers;
@@ -2041,11 +2050,10 @@ static JointArgs joint_args(const irlosc_ctx* c, const Slot& s, int B, double* x
     const size_t Bm = (size_t)c->cfg.max_batch, n = (size_t)c->cfg.n;
     JointArgs a;
     memset(&a, 0, sizeof a);
-    a.xside = xside; a.qt = s.qt; a.table = j.table;
-    a.tau = j.tau(Bm); a.max_violation = j.max_violation(Bm); a.ctrl = j.ctrl(Bm, d.n_rows); a.active_ticks = j.active_ticks(Bm);
+    a.xside = xside; a.qt = s.qt; a.table = j.table; a.st = j.state(Bm);
     a.B = B; a.R = d.n_rows; a.per_robot = d.per_robot; a.stride = (int32_t)Bm;
     const bool list = s.prog.kind == Program::LIST, grips = s.prog.kind == Program::POLICY && s.prog.po.n_out == 7;
-    a.gripper_force = list ? s.prog.gripper_force(Bm) : grips ? s.prog.po_grip.get() : nullptr;      // (the list's own state, or the policy's grip: what its ACTION drives read)
+    a.gripper_force = list ? s.prog.list_state(Bm).gripper_force : grips ? s.prog.policy_state().grip : nullptr;      // (the list's own state, or the policy's grip: what its ACTION drives read)
     int items = 0;
     for (int h = 0; h < (int)n; ++h) {
         a.first[h] = (uint8_t)items;
@@ -2082,8 +2090,8 @@ static LogArgs log_args(const irlosc_ctx* c, const Slot& s, const irlosc_ctx::Ba
     a.sample = lg.sample; a.robots = lg.robots; a.mask = lg.channels & mask;
     for (int i = 0; i < LOG_CHANNELS; ++i) a.off[i] = lg.off[i];
     a.qpos = s.qpos; a.qvel = s.qvel; a.xside = bk.xside[0]; a.tgt = s.tgt; a.wrench = wrench; a.u = bk.u[0]; a.flags = bk.flags[0];
-    a.wall_force = s.walls.force((size_t)c->cfg.ndev * Bm); a.joint_tau = s.joints.tau(Bm);
-    a.obj_pose = s.objects.pose(Bm); a.obj_holder = s.objects.holder(Bm); a.nobj = s.objects.count();
+    a.wall_force = s.walls.state((size_t)c->cfg.ndev * Bm).force; a.joint_tau = s.joints.state(Bm).tau;
+    a.obj_pose = s.objects.state(Bm).pose; a.obj_holder = s.objects.state(Bm).holder; a.nobj = s.objects.count();
     a.R = lg.R; a.n = c->cfg.n; a.ndev = c->cfg.ndev; a.n_entries = (int32_t)c->model.fe_xentries; a.stride = (int32_t)Bm;
     fill_ee0(c, a.ee0);
     return a;
@@ -2101,40 +2109,30 @@ static EpisodeArgs episode_args(const irlosc_ctx* c, const Slot& s, int B, const
     a.qt = s.qt; a.qpos = s.qpos; a.qvel = s.qvel; a.starts = e.starts; a.tgt = s.tgt; a.snap = e.snap;
     a.kind = p.kind == Program::LIST ? EP_LIST : p.kind == Program::PATHS ? EP_PATHS : p.kind == Program::POLICY ? EP_POLICY : EP_NONE;
     if (a.kind == EP_POLICY) {
-        a.pl_pose = p.pose(Bm); a.pl_origin = p.po.nb_origin > 1 ? p.ts_origin.get() : nullptr; a.pl_out = p.po_out; a.pl_grip = p.po_grip; a.pl_n_out = p.po.n_out;
+        a.pl = p.plate_state(Bm); a.pl_origin = p.po.nb_origin > 1 ? p.ts_origin.get() : nullptr; a.po = p.policy_state(); a.pl_n_out = p.po.n_out;
         for (int i = 0; i < 6; ++i) a.pl_origin0[i] = p.po_origin0[i];
     }
     if (a.kind == EP_LIST) {
-        a.action = p.action(Bm); a.entered = p.entered(Bm); a.grip_left = p.grip_left(Bm); a.finished_tick = p.finished_tick(Bm);
-        a.err = p.err(Bm); a.max_vel0 = p.max_vel0(Bm); a.gripper_force = p.gripper_force(Bm); a.start_xyz = p.start_xyz(Bm);
-        a.al_table = p.al_table; a.variants = e.variants; a.al_gains = p.al_gains; a.gains = c->dgains;
+        a.ls = p.list_state(Bm); a.al_table = p.al_table; a.variants = e.variants; a.al_gains = p.al_gains; a.gains = c->dgains;
         a.A = p.al.n_actions; a.active = p.al.active_dev; a.gains_per_robot = c->gains_nb > 1;
         a.V = d.n_variants; a.vstride = (int64_t)e.vstride; a.list_per_robot = e.list_per_robot;
     }
     if (a.kind == EP_PATHS) {
-        a.wp_index = p.index(plane); a.wp_arrivals = (uint32_t*)p.arrivals(plane); a.wp_last_tick = p.last_tick(plane); a.wp_table = p.wp_table;
+        a.wp = p.path_state(plane); a.wp_table = p.wp_table;
         for (int k = 0; k < c->cfg.ndev; ++k) {
             a.wp_count[k] = p.wp.count[k]; a.wp_loop[k] = p.wp.loop[k];
             a.wmax = std::max(a.wmax, p.wp.count[k]);
         }
         a.wp_per_robot = p.wp.nb > 1;
     }
-    if (!init && s.walls.robots) {
-        a.walls = 1;
-        a.wall_force = s.walls.force(plane); a.wall_depth = s.walls.max_depth(plane);
-        a.wall_contact = s.walls.contact_ticks(plane); a.wall_first = s.walls.first_tick(plane);
-    }
-    if (!init && s.joints.robots) {
-        a.joints = 1; a.R = s.joints.d.n_rows;
-        a.jt_tau = s.joints.tau(Bm); a.jt_violation = s.joints.max_violation(Bm); a.jt_ctrl = s.joints.ctrl(Bm, a.R); a.jt_active = s.joints.active_ticks(Bm);
-    }
+    if (!init && s.walls.robots) { a.walls = 1; a.wl = s.walls.state(plane); }
+    if (!init && s.joints.robots) { a.joints = 1; a.R = s.joints.d.n_rows; a.jt = s.joints.state(Bm); }
     if (!init && s.objects.robots) {
         const Objects& o = s.objects;
         a.objects = 1; a.nobj = o.d.n_objects; a.ng = o.d.n_grippers; a.nm = o.d.n_mates; a.OV = o.d.n_variants;
-        a.ob_pose = o.pose(Bm); a.ob_rel = o.rel(Bm); a.ob_holder = o.holder(Bm); a.ob_grasp = o.grasp_tick(Bm); a.ob_release = o.release_tick(Bm);
-        a.ob_closed = o.was_closed(Bm); a.ob_mated = o.mated_tick(Bm); a.ob_pose0 = o.table; a.ob_vstride = (int64_t)o.vstride;
+        a.ob = o.state(Bm); a.ob_pose0 = o.table; a.ob_vstride = (int64_t)o.vstride;
     }
-    if (!init && s.loads.robots) { a.loads = 1; a.ld_load = s.loads.load(Bm); a.ld_carry = s.loads.carry_ticks(Bm); }
+    if (!init && s.loads.robots) { a.loads = 1; a.ld = s.loads.state(Bm); }
     a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.S = d.n_starts; a.starts_per_robot = e.starts_per_robot;
     a.max_ticks = d.max_ticks; a.end_on_finish = d.end_on_finish; a.max_episodes = d.max_episodes; a.records = d.records;
     a.tick = e.tick; a.init = init ? 1 : 0;
@@ -2275,11 +2273,7 @@ static int tick_behind(irlosc_ctx* c, const Slot& s0, int B, const TickPlan& tp,
     return IRLOSC_OK;
 }
 // The whole tick is enqueued: the slot's coordinates are the plant's, and what ran is a tick older (a slot without a program ticks none).
-static void tick_done(Slot& s0, int B, const TickPlan& tp) {
-    s0.advanced(B);
-    if (tp.prog != Program::NONE) s0.prog.ticked();
-    s0.push.ticked(); s0.walls.ticked(); s0.joints.ticked(); s0.objects.ticked(); s0.loads.ticked(); s0.episodes.ticked();      // (each ticks only where it is in force)
-}
+static void tick_done(Slot& s0, int B, const TickPlan& tp) { s0.advanced(B); s0.parts_ticked(tp.prog != Program::NONE); }
 
 // irlosc_step_from_q_device: the caller's device arrays and stream in place of the slot's inputs and the bank's outputs (one step)
 struct DevCall {
@@ -3653,9 +3647,7 @@ extern "C" int irlosc_set_episodes(irlosc_ctx* c, int32_t slot, int32_t B, const
         return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, episodes given for %d: irlosc_set_targets first", slot,
                     std::max(0, s.targets), B);
     const Program& p = s.prog;
-    const struct { int robots; const char* what; } parts[] = {{p.robots, "program"}, {s.walls.robots, "walls"}, {s.joints.robots, "joint rows"},
-                                                              {s.objects.robots, "action objects"}, {s.loads.robots, "object loads"}};
-    for (const auto& k : parts)
+    for (const Slot::Cover& k : s.reset_covers())
         if (k.robots && B > k.robots)
             return fail(c, IRLOSC_ERR_STATE, "slot %d: its %s covers %d robots, episodes given for %d (their resets write its state)", slot, k.what, k.robots, B);
     if (p.kind == Program::STREAM)

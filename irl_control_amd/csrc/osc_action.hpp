@@ -45,8 +45,7 @@
 // A reset of episodes leaves entered = -1, which re-enters action 0 and with it rewrites goal, origin and step; draws is NOT reset, so
 // that every episode of a robot draws fresh noise.
 //
-// init = 1 (irlosc_set_action_list): action 0, entered -1, grip_left 0, err +inf, max_vel0 0, gripper_force 0, finished_tick -1,
-// start_xyz 0; neither the exchange block nor the targets are read.
+// init = 1 (irlosc_set_action_list): every robot's state fresh (list_fresh); neither the exchange block nor the targets are read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,18 +56,25 @@
 
 namespace irlosc {
 
+struct ListState {            // the list's per-robot state: [stride] each, start_xyz [3][stride]
+    int32_t* action; int32_t* entered; int32_t* grip_left; int32_t* finished_tick;
+    double* err; double* max_vel0; double* gripper_force; double* start_xyz;
+};
+// One robot's fresh list state (so: its column): what the init launch of irlosc_set_action_list leaves, and a reset of episodes
+__device__ __forceinline__ void list_fresh(ListState st, int stride, size_t so) {
+    st.action[so] = 0; st.entered[so] = -1; st.grip_left[so] = 0; st.finished_tick[so] = -1;
+    st.err[so] = __builtin_huge_val(); st.max_vel0[so] = 0.0; st.gripper_force[so] = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) st.start_xyz[(size_t)c * stride + so] = 0.0;
+}
+// The motion's per-robot state: step and draws [stride], origin and goal [7][stride].  No fresh function: a reset leaves it alone (above)
+struct MotionState { int32_t* m_step; uint32_t* m_draws; double* m_origin; double* m_goal; };
+
 struct ActionArgs {
     const double* xside;      // the tick's exchange block [walk wave][n_entries][64] (init: not read)
     void* tgt;                // [B][ndev][7] targets of the slot, record type
     void* gains;              // [B][ndev][IRLOSC_GAIN_WORDS] the slot's gain copy, record type: word 9 of the active device in place
-    int32_t* action;          // [stride] each
-    int32_t* entered;
-    int32_t* grip_left;
-    int32_t* finished_tick;
-    double* err;
-    double* max_vel0;
-    double* gripper_force;
-    double* start_xyz;        // [3][stride]
+    ListState st;
     const double* table;      // per_robot: [walk wave][A][7][64], else [A][7]
     const double* obj_pose;   // REFS in force: the action objects' poses of this tick [IRLOSC_MAX_OBJECTS 7][stride] (osc_object.hpp); else nullptr
     double kp[IRLOSC_MAX_ACTIONS], max_error[IRLOSC_MAX_ACTIONS], min_speed[IRLOSC_MAX_ACTIONS], max_speed[IRLOSC_MAX_ACTIONS];
@@ -84,10 +90,7 @@ struct ActionArgs {
 
 // The arguments of the MOTION = true instantiation: the list's, and the motion in force (irlosc_set_action_motion)
 struct ActionMotionArgs : ActionArgs {
-    int32_t* m_step;          // [stride]
-    uint32_t* m_draws;        // [stride]
-    double* m_origin;         // [7][stride]
-    double* m_goal;           // [7][stride]
+    MotionState mo;
     double noise_mean[IRLOSC_MAX_ACTIONS], noise_std[IRLOSC_MAX_ACTIONS];
     int32_t steps[IRLOSC_MAX_ACTIONS];
     uint64_t seed;
@@ -124,12 +127,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
     const bool valid = lane < nvalid;
     const size_t so = (size_t)b0 + lane;
     if (a.init) {
-        if (valid) {
-            a.action[so] = 0; a.entered[so] = -1; a.grip_left[so] = 0; a.finished_tick[so] = -1;
-            a.err[so] = __builtin_huge_val(); a.max_vel0[so] = 0.0; a.gripper_force[so] = 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = 0.0;
-        }
+        if (valid) list_fresh(a.st, a.stride, so);
         return;
     }
     const int row = a.ndev * 7;
@@ -140,17 +138,17 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
         const int A = a.A;
         const double* __restrict__ xs = a.xside + (size_t)blockIdx.x * a.n_entries * 64 + lane;
         T* ta = s_t + lane * row + a.active * 7;
-        int act = a.action[so];
-        const int ent = a.entered[so];
+        int act = a.st.action[so];
+        const int ent = a.st.entered[so];
         const bool first = ent < 0;                 // the first tick that runs this robot: tick 0, or later behind narrower rollouts
-        double err = a.err[so];
+        double err = a.st.err[so];
         double ea[7];
 #pragma unroll
         for (int c = 0; c < 7; ++c) ea[c] = xs[(size_t)a.ee_act[c] * 64];
         int stp = 0;                                // MOTION: the robot's step, its goal and origin where this tick enters a WP
         bool wp_entered = false;
         double g[7], og[7];
-        if constexpr (MOTION) stp = a.m_step[so];
+        if constexpr (MOTION) stp = a.mo.m_step[so];
         if (!first && act < A) {                    // after_step of the previous tick, on the state its plant step produced
             double t7[7], e[6];
 #pragma unroll
@@ -160,30 +158,30 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
 #pragma unroll
             for (int c = 1; c < 6; ++c) s2 = __dadd_rn(s2, __dmul_rn(e[c], e[c]));
             err = __dsqrt_rn(s2);
-            a.err[so] = err;
+            a.st.err[so] = err;
             bool next;
             if (a.kind[act] == 0) {
                 next = err <= a.max_error[act];     // NaN: stays
                 if constexpr (MOTION) next = next && (a.steps[act] == 0 || stp == a.steps[act]);      // an INTERP has arrived first
             } else {
-                const int gl = a.grip_left[so] - 1;
-                a.grip_left[so] = gl;
+                const int gl = a.st.grip_left[so] - 1;
+                a.st.grip_left[so] = gl;
                 next = gl <= 0;
             }
             if (next) {
                 act += 1;
-                a.action[so] = act;
-                if (act == A) a.finished_tick[so] = a.tick;
+                a.st.action[so] = act;
+                if (act == A) a.st.finished_tick[so] = a.tick;
             }
         }
         double sx[3];
         if (first) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = sx[c] = ea[c];
+            for (int c = 0; c < 3; ++c) a.st.start_xyz[(size_t)c * a.stride + so] = sx[c] = ea[c];
         }
         if (act < A && ent != act) {
-            a.entered[so] = act;
-            a.gripper_force[so] = a.force[act];
+            a.st.entered[so] = act;
+            a.st.gripper_force[so] = a.force[act];
             if (a.kind[act] == 0) {
                 if (a.passive >= 0) {
                     T* tp = s_t + lane * row + a.passive * 7;
@@ -197,7 +195,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
                 const bool from_start = a.xyz_from_start[act] != 0;
                 if (from_start && !first) {
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) sx[c] = a.start_xyz[(size_t)c * a.stride + so];
+                    for (int c = 0; c < 3; ++c) sx[c] = a.st.start_xyz[(size_t)c * a.stride + so];
                 }
                 const int xo = a.obj_pose ? a.xyz_obj[act] : -1, qo = a.obj_pose ? a.quat_obj[act] : -1;
                 if (xo < 0 && qo < 0) {
@@ -228,27 +226,27 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
                     }
                 }
                 err = __builtin_huge_val();
-                a.err[so] = err;
+                a.st.err[so] = err;
                 if constexpr (MOTION) {
                     const double mean = a.noise_mean[act], sd = a.noise_std[act];
                     if (sd > 0.0 || mean != 0.0) {
-                        const uint32_t dr = a.m_draws[so];
+                        const uint32_t dr = a.mo.m_draws[so];
                         double z[3];
                         normal3(a.seed, (uint32_t)so, dr, (uint32_t)act, z);
 #pragma unroll
                         for (int c = 0; c < 3; ++c) g[c] = __dadd_rn(g[c], __dadd_rn(mean, __dmul_rn(sd, z[c])));
-                        a.m_draws[so] = dr + 1u;
+                        a.mo.m_draws[so] = dr + 1u;
                     }
 #pragma unroll
                     for (int c = 0; c < 7; ++c) {
                         og[c] = ea[c];
-                        a.m_goal[(size_t)c * a.stride + so] = g[c];
-                        a.m_origin[(size_t)c * a.stride + so] = og[c];
+                        a.mo.m_goal[(size_t)c * a.stride + so] = g[c];
+                        a.mo.m_origin[(size_t)c * a.stride + so] = og[c];
                     }
                     stp = 0;
                     wp_entered = true;
                     if (a.steps[act] == 0) {        // the WP jumps (an INTERP's step and target: below)
-                        a.m_step[so] = 0;
+                        a.mo.m_step[so] = 0;
 #pragma unroll
                         for (int c = 0; c < 7; ++c) ta[c] = (T)g[c];
                         moved = true;
@@ -257,7 +255,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
                     moved = true;
                 }
             } else {
-                a.grip_left[so] = a.grip_ticks[act];
+                a.st.grip_left[so] = a.grip_ticks[act];
             }
         }
         if constexpr (MOTION) {                     // an INTERP on its way: the entry tick and every later one until step == N
@@ -266,12 +264,12 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
                 if (!wp_entered) {
 #pragma unroll
                     for (int c = 0; c < 7; ++c) {
-                        g[c] = a.m_goal[(size_t)c * a.stride + so];
-                        og[c] = a.m_origin[(size_t)c * a.stride + so];
+                        g[c] = a.mo.m_goal[(size_t)c * a.stride + so];
+                        og[c] = a.mo.m_origin[(size_t)c * a.stride + so];
                     }
                 }
                 stp += 1;
-                a.m_step[so] = stp;
+                a.mo.m_step[so] = stp;
                 if (stp < N) {
                     const double w = __ddiv_rn((double)stp, (double)N);
                     double q[4];
@@ -291,7 +289,7 @@ __global__ __launch_bounds__(64) void osc_action_kernel(const typename action_ar
             const double v = __dmul_rn(a.kp[act], err);
             double m = v < a.max_speed[act] ? v : a.max_speed[act];          // min(max_speed, v) as the host evaluates it
             m = m > a.min_speed[act] ? m : a.min_speed[act];                 // max(min_speed, m)
-            a.max_vel0[so] = m;
+            a.st.max_vel0[so] = m;
             ((T*)a.gains)[(so * a.ndev + a.active) * IRLOSC_GAIN_WORDS + 9] = (T)m;
         }
     }

@@ -10,11 +10,11 @@
 //     stores age (and start_tick on the first tick that runs an episode); no tile store, no coordinate store;
 //   a lane whose episode ENDS writes its record and count, and unless it parks (max_episodes reached) resets: coordinates from start
 //     state count mod S (qt in the walk's layout, row-major qpos and qvel), its target row from the snapshot through the wave's target
-//     tile (osc_common.hpp: its contract; PATHS: waypoint 0 of every listed device on top), the list's state as osc_action_kernel's init
-//     branch leaves it with word 9 of the active device's gain record taken again from the context's gains and, with pose variants,
-//     the robot's lines of the list's pose table rewritten with variant count mod V, the paths' state as the cycler's init, the walls'
-//     and the joint rows' state as their setters' fills, a policy's plate on the robot's origin with out and grip zero, the action objects' state as osc_object_kernel's init leaves it, on their
-//     start poses count mod OV, the carried objects' load words and carry_ticks zero; on a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
+//     tile (osc_common.hpp: its contract; PATHS: waypoint 0 of every listed device on top), word 9 of the active device's gain record taken
+//     again from the context's gains and, with pose variants, the robot's lines of the list's pose table rewritten with variant count mod V,
+//     and the FRESH STATE OF EVERY PART IN FORCE -- list, paths of the listed devices, a policy's plate (on the robot's origin), out and grip,
+//     walls, action objects (on their start poses count mod OV), their loads, joint rows -- each by the fresh function of the part's own header,
+//     which owns the state and its fresh values.  On a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
 //   idle lanes of a ragged last wave neither load nor store.
 // Every wave stores the number of its robots that are not parked into running[walk wave] (a plain store by lane 0): the early exit's input.
 //
@@ -26,6 +26,13 @@
 
 #include "../../include/irlosc.h"
 #include "osc_common.hpp"
+#include "osc_action.hpp"
+#include "osc_waypoint.hpp"
+#include "osc_policy.hpp"
+#include "osc_wall.hpp"
+#include "osc_joint.hpp"
+#include "osc_object.hpp"
+#include "osc_object_load.hpp"
 
 namespace irlosc {
 
@@ -43,34 +50,26 @@ struct EpisodeArgs {
     const double* starts;     // starts_per_robot: [walk wave][S][2 NJ][64], else [S][2 NJ]; entry 2 j = q_j, 2 j + 1 = qd_j
     void* tgt;                // [B][ndev][7] targets of the slot, record type
     void* snap;               // ... their snapshot
-    // LIST (osc_action.hpp)
-    int32_t* action; int32_t* entered; int32_t* grip_left; int32_t* finished_tick;
-    double* err; double* max_vel0; double* gripper_force; double* start_xyz;
+    ListState ls;             // LIST (osc_action.hpp)
     double* al_table;         // list_per_robot: [walk wave][A][7][64], else [A][7]
     const double* variants;   // [V] tables of that layout, vstride doubles apart
     void* al_gains;           // [B][ndev][IRLOSC_GAIN_WORDS] the slot's gain copy, record type
     const void* gains;        // the context's gains, record type: [1 | max_batch][ndev][IRLOSC_GAIN_WORDS]
-    // PATHS (osc_waypoint.hpp)
-    int32_t* wp_index; uint32_t* wp_arrivals; int32_t* wp_last_tick;      // [ndev][stride]
+    PathState wp;             // PATHS (osc_waypoint.hpp)
     const double* wp_table;   // wp_per_robot: [walk wave][ndev][wmax][3][64], else [ndev][wmax][3]
     // POLICY (osc_policy.hpp): never finished -- its episodes end by max_ticks alone; a reset puts the plate back to the robot's origin
-    double* pl_pose;          // [6][stride]
+    PlateState pl;
     const double* pl_origin;  // per robot: [walk wave][6][64]; nullptr: pl_origin0 for the fleet
     double pl_origin0[6];
-    float* pl_out;            // [pl_n_out][stride]
-    double* pl_grip;          // [stride]
+    PolicyState po;
     int32_t pl_n_out, pl_pad;
-    // walls (osc_wall.hpp): planes [ndev][stride]; joint rows (osc_joint.hpp): rows [stride]
-    double* wall_force; double* wall_depth; int32_t* wall_contact; int32_t* wall_first;
-    double* jt_tau; double* jt_violation; double* jt_ctrl; int32_t* jt_active;
-    // action objects (osc_object.hpp: its layout): state [row][stride]; start poses [OV][walk wave][nobj 7][64], ob_vstride doubles apart
-    double* ob_pose; double* ob_rel;
-    int32_t* ob_holder; int32_t* ob_grasp; int32_t* ob_release; int32_t* ob_closed; int32_t* ob_mated;
-    const double* ob_pose0;
+    WallState wl;             // walls (osc_wall.hpp)
+    JointState jt;            // joint rows (osc_joint.hpp)
+    ObjectState ob;           // action objects (osc_object.hpp) ...
+    const double* ob_pose0;   // ... their start poses [OV][walk wave][nobj 7][64], ob_vstride doubles apart
     int64_t ob_vstride;
     int32_t objects, nobj, ng, nm, OV;
-    // the carried objects' weight (osc_object_load.hpp): state [MAX_GRIPPERS 6][stride], [MAX_GRIPPERS][stride]
-    double* ld_load; int32_t* ld_carry;
+    LoadState ld;             // the carried objects' weight (osc_object_load.hpp)
     int32_t loads, ld_pad;
     int64_t vstride;
     int32_t wp_count[IRLOSC_MAX_DEV];
@@ -106,13 +105,13 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
         const int age0 = a.age[so];
         const bool parked = a.max_episodes > 0 && cnt >= a.max_episodes;
         bool fin = false;
-        if (a.end_on_finish && a.kind == EP_LIST) fin = a.finished_tick[so] >= 0;
+        if (a.end_on_finish && a.kind == EP_LIST) fin = a.ls.finished_tick[so] >= 0;
         if (a.end_on_finish && a.kind == EP_PATHS) {
             bool all = true, some = false;
             for (int d = 0; d < a.ndev; ++d)
                 if (a.wp_count[d] > 0 && !a.wp_loop[d]) {
                     some = true;
-                    all = all & (a.wp_index[(size_t)d * a.stride + so] == a.wp_count[d]);
+                    all = all & (a.wp.index[(size_t)d * a.stride + so] == a.wp_count[d]);
                 }
             fin = some & all;
         }
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
             int outcome = fin ? IRLOSC_EPISODE_FINISHED : IRLOSC_EPISODE_TIMEOUT;
             if (a.nm > 0) {                         // a slot with mates: every one of them mated by this tick's object kernel
                 bool all = true;
-                for (int m = 0; m < a.nm; ++m) all = all & (a.ob_mated[(size_t)m * a.stride + so] >= 0);
+                for (int m = 0; m < a.nm; ++m) all = all & (a.ob.mated_tick[(size_t)m * a.stride + so] >= 0);
                 if (all) outcome |= IRLOSC_EPISODE_INSERTED;
             }
             r[2 * (size_t)a.stride] = outcome;
@@ -172,66 +171,27 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
         }
     }
     if (reset) {                                    // THE branch around the reset body (state; the targets follow through the tile)
-        if (a.kind == EP_LIST) {                    // as osc_action_kernel's init branch
-            a.action[so] = 0; a.entered[so] = -1; a.grip_left[so] = 0; a.finished_tick[so] = -1;
-            a.err[so] = __builtin_huge_val(); a.max_vel0[so] = 0.0; a.gripper_force[so] = 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) a.start_xyz[(size_t)c * a.stride + so] = 0.0;
+        if (a.kind == EP_LIST) {                    // ... and word 9 of the active device's gain record taken again
+            list_fresh(a.ls, a.stride, so);
             const size_t w9 = (size_t)a.active * IRLOSC_GAIN_WORDS + 9;
             ((T*)a.al_gains)[so * a.ndev * IRLOSC_GAIN_WORDS + w9] = ((const T*)a.gains)[(a.gains_per_robot ? so : 0) * a.ndev * IRLOSC_GAIN_WORDS + w9];
         }
-        if (a.kind == EP_PATHS) {                   // as the cycler's init: (0, 0, -1) for listed devices
-            for (int d = 0; d < a.ndev; ++d) {
-                if (a.wp_count[d] <= 0) continue;
-                const size_t o = (size_t)d * a.stride + so;
-                a.wp_index[o] = 0; a.wp_arrivals[o] = 0u; a.wp_last_tick[o] = -1;
-            }
+        for (int d = 0; a.kind == EP_PATHS && d < a.ndev; ++d) {      // the listed devices
+            if (a.wp_count[d] <= 0) continue;
+            path_fresh(a.wp, (size_t)d * a.stride + so, a.wp_count[d]);
         }
-        if (a.kind == EP_POLICY) {                  // as irlosc_set_policy leaves it: the plate at the origin, out and grip zero
+        if (a.kind == EP_POLICY) {                  // the plate on the robot's origin
+            double origin[6];
 #pragma unroll
-            for (int c = 0; c < 6; ++c)
-                a.pl_pose[(size_t)c * a.stride + so] = a.pl_origin ? a.pl_origin[((size_t)blockIdx.x * 6 + c) * 64 + lane] : a.pl_origin0[c];
-            for (int c = 0; c < a.pl_n_out; ++c) a.pl_out[(size_t)c * a.stride + so] = 0.0f;
-            a.pl_grip[so] = 0.0;
+            for (int c = 0; c < 6; ++c) origin[c] = a.pl_origin ? a.pl_origin[((size_t)blockIdx.x * 6 + c) * 64 + lane] : a.pl_origin0[c];
+            plate_fresh(a.pl, a.stride, so, origin);
+            policy_fresh(a.po, a.pl_n_out, a.stride, so);
         }
-        if (a.walls) {                              // as irlosc_set_walls' fills
-            const size_t plane = (size_t)a.ndev * a.stride;
-            for (int d = 0; d < a.ndev; ++d) {
-                const size_t o = (size_t)d * a.stride + so;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) a.wall_force[c * plane + o] = 0.0;
-                a.wall_depth[o] = 0.0; a.wall_contact[o] = 0; a.wall_first[o] = -1;
-            }
-        }
-        if (a.objects) {                            // as osc_object_kernel's init branch, on start poses count mod OV
-            const double* __restrict__ p0 = a.ob_pose0 + (size_t)(cnt % a.OV) * a.ob_vstride + (size_t)blockIdx.x * a.nobj * 7 * 64 + lane;
-            for (int o = 0; o < a.nobj; ++o) {
-#pragma unroll
-                for (int c = 0; c < 7; ++c) {
-                    a.ob_pose[(size_t)(o * 7 + c) * a.stride + so] = p0[(size_t)(o * 7 + c) * 64];
-                    a.ob_rel[(size_t)(o * 7 + c) * a.stride + so] = 0.0;
-                }
-                const size_t i = (size_t)o * a.stride + so;
-                a.ob_holder[i] = -1; a.ob_grasp[i] = -1; a.ob_release[i] = -1;
-            }
-            for (int g = 0; g < a.ng; ++g) a.ob_closed[(size_t)g * a.stride + so] = 0;
-            for (int m = 0; m < a.nm; ++m) a.ob_mated[(size_t)m * a.stride + so] = -1;
-        }
-        if (a.loads) {                              // as irlosc_set_object_loads' fills
-            for (int g = 0; g < a.ng; ++g) {
-#pragma unroll
-                for (int c = 0; c < 6; ++c) a.ld_load[(size_t)(g * 6 + c) * a.stride + so] = 0.0;
-                a.ld_carry[(size_t)g * a.stride + so] = 0;
-            }
-        }
-        if (a.joints) {                             // as irlosc_set_joints' fills; ctrl = 0: an ACTION drive lets go
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) a.jt_tau[(size_t)j * a.stride + so] = 0.0;
-            for (int r = 0; r < a.R; ++r) {
-                const size_t o = (size_t)r * a.stride + so;
-                a.jt_violation[o] = 0.0; a.jt_ctrl[o] = 0.0; a.jt_active[o] = 0;
-            }
-        }
+        if (a.walls) wall_fresh(a.wl, a.ndev, a.stride, so);
+        if (a.objects)                              // on start poses count mod OV
+            object_fresh(a.ob, a.ob_pose0 + (size_t)(cnt % a.OV) * a.ob_vstride + (size_t)blockIdx.x * a.nobj * 7 * 64 + lane, a.nobj, a.ng, a.nm, (size_t)a.stride, so);
+        if (a.loads) load_fresh(a.ld, a.ng, (size_t)a.stride, so);
+        if (a.joints) joint_fresh<NJ>(a.jt, a.R, a.stride, so);
     }
     // ---- targets: the whole row back from the snapshot, through the wave's tile; only a wave in which a lane reset touches it ----
     if (!a.init && __any(reset)) {                  // (one wave per block: uniform over the block)

@@ -47,15 +47,24 @@
 
 namespace irlosc {
 
+struct JointState {                 // the rows' per-robot state
+    double* tau;                    // [NJ][stride]
+    double* max_violation; double* ctrl; int32_t* active_ticks;      // [R][stride] each
+};
+// One robot's fresh state of R rows (b: its column): the fills of irlosc_set_joints, written by a reset of episodes (ctrl = 0: an ACTION drive lets go)
+template <int NJ>
+__device__ __forceinline__ void joint_fresh(JointState st, int R, int stride, size_t b) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) st.tau[(size_t)j * stride + b] = 0.0;
+    for (int r = 0; r < R; ++r) { const size_t o = (size_t)r * stride + b; st.max_violation[o] = 0.0; st.ctrl[o] = 0.0; st.active_ticks[o] = 0; }
+}
+
 struct JointArgs {
     double* xside;                  // the tick's exchange block [walk wave][n_compact][64], bias entries in place
     const double* qt;               // the slot's coordinates in the walk's layout [walk wave][2 NJ][64]
     const double* table;            // per_robot: [walk wave][R][8][64], else [R][8]
     const double* gripper_force;    // the action state's gripper_force[stride] of the list in force, or nullptr (no list)
-    double* tau;                    // state [NJ][stride]
-    double* max_violation;          // state [R][stride]
-    double* ctrl;                   // state [R][stride]
-    int32_t* active_ticks;          // state [R][stride]
+    JointState st;
     uint64_t armed;                 // bit r: row r is an ACTION drive whose device is the active device of the list in force
     int32_t B, R, per_robot, stride;
     uint8_t kind[IRLOSC_MAX_JOINT_ROWS], ja[IRLOSC_MAX_JOINT_ROWS], jb[IRLOSC_MAX_JOINT_ROWS], source[IRLOSC_MAX_JOINT_ROWS];
@@ -99,8 +108,8 @@ __global__ __launch_bounds__(64) void osc_joint_kernel(const JointArgs a) {
                 const double t_hi = (g_hi > 0.0 && f_hi > 0.0) ? f_hi : 0.0;
                 t = __dsub_rn(t_lo, t_hi);
                 const double g = g_lo > g_hi ? g_lo : g_hi;
-                if (g > 0.0 && g > a.max_violation[so]) a.max_violation[so] = g;
-                if (t != 0.0) a.active_ticks[so] += 1;
+                if (g > 0.0 && g > a.st.max_violation[so]) a.st.max_violation[so] = g;
+                if (t != 0.0) a.st.active_ticks[so] += 1;
             } else if (kind == IRLOSC_JOINT_COUPLE) {
                 const int ha = a.ja[r], hb = a.jb[r];
                 const double qa = gq[(size_t)(2 * ha) * 64], qda = gq[(size_t)(2 * ha + 1) * 64];
@@ -115,28 +124,28 @@ __global__ __launch_bounds__(64) void osc_joint_kernel(const JointArgs a) {
                     t = (ok && fabs(p) <= DMAX) ? p : 0.0;
                 } else {
                     t = ok ? -f : 0.0;
-                    if (fabs(e) > a.max_violation[so]) a.max_violation[so] = fabs(e);
-                    if (ok && f != 0.0) a.active_ticks[so] += 1;
+                    if (fabs(e) > a.st.max_violation[so]) a.st.max_violation[so] = fabs(e);
+                    if (ok && f != 0.0) a.st.active_ticks[so] += 1;
                 }
             } else {                                // IRLOSC_JOINT_DRIVE
                 const double gear = row[0];
                 double ctrl;
                 if (a.source[r] == IRLOSC_JOINT_SRC_CONST) ctrl = row[cs];
                 else {
-                    ctrl = a.ctrl[so];
+                    ctrl = a.st.ctrl[so];
                     if ((a.armed >> r) & 1u) {
                         const double gf = a.gripper_force[b];
                         if (gf != 0.0) ctrl = gf;
                     }
                 }
-                a.ctrl[so] = ctrl;
+                a.st.ctrl[so] = ctrl;
                 const double p = __dmul_rn(gear, ctrl);
                 t = (fabs(ctrl) <= DMAX && fabs(p) <= DMAX) ? p : 0.0;
-                if (t != 0.0) a.active_ticks[so] += 1;
+                if (t != 0.0) a.st.active_ticks[so] += 1;
             }
             tau = i == a.first[j] ? t : __dadd_rn(tau, t);
         }
-        a.tau[(size_t)j * a.stride + b] = tau;
+        a.st.tau[(size_t)j * a.stride + b] = tau;
         if (tau != 0.0) {
             double* bj = col + (size_t)(bias0 + j) * 64;
             *bj = __dsub_rn(*bj, tau);

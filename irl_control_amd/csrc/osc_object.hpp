@@ -26,8 +26,7 @@
 //   4. mates, ascending m, with mated_tick < 0 and the plug free:  target xyz = p_sock + R(q_sock) seat_xyz, quat = q_sock (x) seat_quat;
 //        |p_plug - target|^2 <= tol_xyz^2 and |q_plug . q_target| >= min_abs_dot -> mated_tick = t
 //
-// init = 1 (irlosc_set_objects): pose = the robot's lines of `pose0` (variant 0), rel 0, holder -1, grasp_tick, release_tick and
-// mated_tick -1, was_closed 0; neither the exchange block nor the coordinates are read.
+// init = 1 (irlosc_set_objects): every robot's state fresh on variant 0 of `pose0` (object_fresh); no block or coordinate is read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,17 +42,28 @@ constexpr int OBJ_POSE_ROWS = IRLOSC_MAX_OBJECTS * 7;
 constexpr int OBJ_D_ROWS = 2 * OBJ_POSE_ROWS;
 constexpr int OBJ_I_ROWS = 3 * IRLOSC_MAX_OBJECTS + IRLOSC_MAX_GRIPPERS + IRLOSC_MAX_MATES;
 
+struct ObjectState {          // the objects' per-robot state (the layout above)
+    double* pose; double* rel;                                      // [MAX_OBJECTS 7][stride] each
+    int32_t* holder; int32_t* grasp_tick; int32_t* release_tick;    // [MAX_OBJECTS][stride] each
+    int32_t* was_closed; int32_t* mated_tick;                       // [MAX_GRIPPERS][stride], [MAX_MATES][stride]
+};
+// One robot's fresh object state (b: its column of rows S words apart) on the start poses at p0, the robot's column of a variant's
+// [nobj 7][64] lines: what the init launch of irlosc_set_objects leaves on variant 0, and a reset of episodes on the variant it picks
+__device__ __forceinline__ void object_fresh(ObjectState st, const double* p0, int nobj, int ng, int nm, size_t S, size_t b) {
+    for (int o = 0; o < nobj; ++o) {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) { st.pose[(size_t)(o * 7 + c) * S + b] = p0[(size_t)(o * 7 + c) * 64]; st.rel[(size_t)(o * 7 + c) * S + b] = 0.0; }
+        st.holder[o * S + b] = -1; st.grasp_tick[o * S + b] = -1; st.release_tick[o * S + b] = -1;
+    }
+    for (int g = 0; g < ng; ++g) st.was_closed[g * S + b] = 0;
+    for (int m = 0; m < nm; ++m) st.mated_tick[m * S + b] = -1;
+}
+
 struct ObjectArgs {
     const double* xside;      // the tick's exchange block [walk wave][n_entries][64] (init: not read)
     const double* qt;         // the slot's coordinates in the walk's layout [walk wave][2 n][64] (init: not read)
     const double* pose0;      // init: [walk wave][nobj 7][64], variant 0 of the start poses; else not read
-    double* pose;             // [MAX_OBJECTS 7][stride]
-    double* rel;              // [MAX_OBJECTS 7][stride]
-    int32_t* holder;          // [MAX_OBJECTS][stride] each
-    int32_t* grasp_tick;
-    int32_t* release_tick;
-    int32_t* was_closed;      // [MAX_GRIPPERS][stride]
-    int32_t* mated_tick;      // [MAX_MATES][stride]
+    ObjectState st;
     double sign[IRLOSC_MAX_GRIPPERS], q_close[IRLOSC_MAX_GRIPPERS], q_open[IRLOSC_MAX_GRIPPERS], grip_xyz[IRLOSC_MAX_GRIPPERS][3];
     double radius[IRLOSC_MAX_OBJECTS];
     double seat_xyz[IRLOSC_MAX_MATES][3], seat_quat[IRLOSC_MAX_MATES][4], tol_xyz[IRLOSC_MAX_MATES], min_abs_dot[IRLOSC_MAX_MATES];
@@ -73,20 +83,13 @@ __global__ __launch_bounds__(64) void osc_object_kernel(const ObjectArgs a) {
     const int b = (int)blockIdx.x * 64 + lane;
     if (b >= a.B) return;                           // (no barrier below; idle lanes of a ragged last wave neither load nor store)
     const size_t S = (size_t)a.stride;
-    double* __restrict__ pose = a.pose + b;         // this robot's column: row r at [r S]
-    double* __restrict__ rel = a.rel + b;
-    int32_t* __restrict__ holder = a.holder + b;
     if (a.init) {
-        const double* __restrict__ p0 = a.pose0 + (size_t)blockIdx.x * a.nobj * 7 * 64 + lane;
-        for (int o = 0; o < a.nobj; ++o) {
-#pragma unroll
-            for (int c = 0; c < 7; ++c) { pose[(size_t)(o * 7 + c) * S] = p0[(size_t)(o * 7 + c) * 64]; rel[(size_t)(o * 7 + c) * S] = 0.0; }
-            holder[o * S] = -1; a.grasp_tick[o * S + b] = -1; a.release_tick[o * S + b] = -1;
-        }
-        for (int g = 0; g < a.ng; ++g) a.was_closed[g * S + b] = 0;
-        for (int m = 0; m < a.nm; ++m) a.mated_tick[m * S + b] = -1;
+        object_fresh(a.st, a.pose0 + (size_t)blockIdx.x * a.nobj * 7 * 64 + lane, a.nobj, a.ng, a.nm, S, (size_t)b);
         return;
     }
+    double* __restrict__ pose = a.st.pose + b;      // this robot's column: row r at [r S]
+    double* __restrict__ rel = a.st.rel + b;
+    int32_t* __restrict__ holder = a.st.holder + b;
     const double* __restrict__ xs = a.xside + (size_t)blockIdx.x * a.n_entries * 64 + lane;
     const double* __restrict__ gq = a.qt + (size_t)blockIdx.x * (2 * a.n * 64) + lane;
     // ---- the grippers of the tick: EE pose, R(q_ee), closed / open (compile-time g: registers) ----
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(64) void osc_object_kernel(const ObjectArgs a) {
             if (h != g) continue;
             if (open[g]) {
                 holder[o * S] = -1;
-                a.release_tick[o * S + b] = a.tick;
+                a.st.release_tick[o * S + b] = a.tick;
                 released |= 1u << o;
             } else {
                 double rx[3], rq[4], v[3], q[4];
@@ -148,7 +151,7 @@ __global__ __launch_bounds__(64) void osc_object_kernel(const ObjectArgs a) {
         bool taken = false;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            if (g >= a.ng || taken || !closed[g] || holds[g] || a.was_closed[g * S + b] != 0) continue;
+            if (g >= a.ng || taken || !closed[g] || holds[g] || a.st.was_closed[g * S + b] != 0) continue;
             double gv[3], gp[3];
             mat_vec_rn(R[g], a.grip_xyz[g], gv);
 #pragma unroll
@@ -167,7 +170,7 @@ __global__ __launch_bounds__(64) void osc_object_kernel(const ObjectArgs a) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) rel[(size_t)(o * 7 + 3 + c) * S] = rq[c];
             holder[o * S] = g;
-            a.grasp_tick[o * S + b] = a.tick;
+            a.st.grasp_tick[o * S + b] = a.tick;
             holds[g] = true;
             taken = true;
         }
@@ -175,10 +178,10 @@ __global__ __launch_bounds__(64) void osc_object_kernel(const ObjectArgs a) {
     // ---- 3. the edge detector ----
 #pragma unroll
     for (int g = 0; g < NG; ++g)
-        if (g < a.ng) a.was_closed[g * S + b] = closed[g] ? 1 : 0;
+        if (g < a.ng) a.st.was_closed[g * S + b] = closed[g] ? 1 : 0;
     // ---- 4. mates ----
     for (int m = 0; m < a.nm; ++m) {
-        if (a.mated_tick[m * S + b] >= 0 || holder[a.plug[m] * S] >= 0) continue;
+        if (a.st.mated_tick[m * S + b] >= 0 || holder[a.plug[m] * S] >= 0) continue;
         double pp[3], qp[4], ps[3], qs[4], Rs[3][3], sv[3], tp[3], tq[4];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { pp[c] = pose[(size_t)(a.plug[m] * 7 + c) * S]; ps[c] = pose[(size_t)(a.socket[m] * 7 + c) * S]; }
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(64) void osc_object_kernel(const ObjectArgs a) {
         for (int c = 0; c < 3; ++c) tp[c] = __dadd_rn(ps[c], sv[c]);
         quat_mul_rn(qs, a.seat_quat[m], tq);
         const double dot = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(qp[0], tq[0]), __dmul_rn(qp[1], tq[1])), __dmul_rn(qp[2], tq[2])), __dmul_rn(qp[3], tq[3]));
-        if (obj_dist2(pp, tp) <= __dmul_rn(a.tol_xyz[m], a.tol_xyz[m]) && fabs(dot) >= a.min_abs_dot[m]) a.mated_tick[m * S + b] = a.tick;
+        if (obj_dist2(pp, tp) <= __dmul_rn(a.tol_xyz[m], a.tol_xyz[m]) && fabs(dot) >= a.min_abs_dot[m]) a.st.mated_tick[m * S + b] = a.tick;
     }
 }
 

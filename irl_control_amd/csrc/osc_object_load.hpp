@@ -32,14 +32,26 @@
 
 namespace irlosc {
 
+struct LoadState {            // the loads' per-robot state
+    double* load;             // [MAX_GRIPPERS 6][stride]: what the last tick applied
+    int32_t* carry_ticks;     // [MAX_GRIPPERS][stride]: ticks on which a weight was applied
+};
+// One robot's fresh state of ng grippers (b: its column of rows S words apart): the fills of irlosc_set_object_loads, written by a reset of episodes
+__device__ __forceinline__ void load_fresh(LoadState st, int ng, size_t S, size_t b) {
+    for (int g = 0; g < ng; ++g) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) st.load[(size_t)(g * 6 + c) * S + b] = 0.0;
+        st.carry_ticks[(size_t)g * S + b] = 0;
+    }
+}
+
 struct ObjectLoadArgs {
     double* xside;            // apply: the tick's exchange block [walk wave][n_compact][64], bias entries in place
     void* wrench;             // sense: the feed's wrench of the tick [B][ndev][6], record type, in place
     const double* table;      // per_robot: [walk wave][nobj 4][64], else [nobj][4]
     const double* obj_pose;   // apply: the objects' poses [MAX_OBJECTS 7][stride] (osc_object.hpp: its layout)
     const int32_t* obj_holder;      // apply: [MAX_OBJECTS][stride]
-    double* load;             // state [MAX_GRIPPERS 6][stride]: what the last tick applied
-    int32_t* carry_ticks;     // state [MAX_GRIPPERS][stride]: ticks on which a weight was applied
+    LoadState st;
     double gravity[3];
     int32_t B, ndev, nobj, ng, per_robot, stride;
     int32_t apply;            // 1: apply mode, 0: sense mode (uniform over the launch)
@@ -61,7 +73,7 @@ __global__ __launch_bounds__(64) void osc_object_load_kernel(const ObjectLoadArg
             if (!((a.grippers >> g) & 1u)) continue;
             T* w = (T*)a.wrench + ((size_t)b * a.ndev + a.dev[g]) * 6;
 #pragma unroll
-            for (int c = 0; c < 6; ++c) w[c] = (T)__dsub_rn((double)w[c], a.load[(size_t)(g * 6 + c) * S + b]);
+            for (int c = 0; c < 6; ++c) w[c] = (T)__dsub_rn((double)w[c], a.st.load[(size_t)(g * 6 + c) * S + b]);
         }
         return;
     }
@@ -115,8 +127,8 @@ __global__ __launch_bounds__(64) void osc_object_load_kernel(const ObjectLoadArg
             }
         });
 #pragma unroll
-        for (int c = 0; c < 6; ++c) a.load[(size_t)(g * 6 + c) * S + b] = W[c];      // 5.
-        if (on) a.carry_ticks[(size_t)g * S + b] += 1;
+        for (int c = 0; c < 6; ++c) a.st.load[(size_t)(g * 6 + c) * S + b] = W[c];      // 5.
+        if (on) a.st.carry_ticks[(size_t)g * S + b] += 1;
     }
 }
 

@@ -45,16 +45,22 @@ struct PolicyNet {
     int32_t rows[2];               // rows of the two LDS buffers: layer l reads buffer l & 1 and writes the other
 };
 
+struct PolicyState { float* out; double* grip; };      // the policy's per-robot state besides the plate (PlateState): [n_out][stride], [stride]
+// One robot's fresh outputs (so: its column): what the fills of irlosc_set_policy leave, written by a reset of episodes
+__device__ __forceinline__ void policy_fresh(PolicyState st, int n_out, int stride, size_t so) {
+    for (int c = 0; c < n_out; ++c) st.out[(size_t)c * stride + so] = 0.0f;
+    st.grip[so] = 0.0;
+}
+
 struct PolicyArgs {
-    TeleopArgs t;                  // tgt, pose, inc, the rig, B, ndev, stride: what teleop_follow reads (the stream's other fields: 0)
+    TeleopArgs t;                  // tgt, the plate, inc, the rig, B, ndev, stride: what teleop_follow reads (the stream's other fields: 0)
     PolicyNet net;
     const float* w;                // the packed weights
     const double* qt;              // [walk wave][2 n][64]: entry 2 j = q_j, 2 j + 1 = qd_j
     const double* xside;           // the tick's exchange block [walk wave][n_entries][64]
     const void* wrench;            // [B][ndev][6], record type: the feed's wrench of the tick, or nullptr (no feed: zeros)
     const double* obj_pose;        // [IRLOSC_MAX_OBJECTS 7][stride]
-    float* out;                    // [n_out][stride]
-    double* grip;                  // [stride]
+    PolicyState st;
     float* obs;                    // [B][n_in] row-major, or nullptr (keep_obs == 0)
     uint32_t* flags_any;           // [B] of the rollout call
     double grip_close, grip_open;
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void osc_policy_kernel(const Pol
         k += w;
     }
     if (a.obs_mask & IRLOSC_OBS_PLATE) {
-        for (int c = wv; c < 6; c += POLICY_WAVES) x0[(k + c) * POLICY_XS] = word(a.t.pose[(size_t)c * stride + sc]);
+        for (int c = wv; c < 6; c += POLICY_WAVES) x0[(k + c) * POLICY_XS] = word(a.t.st.pose[(size_t)c * stride + sc]);
         k += 6;
     }
     if (a.obs_mask & IRLOSC_OBS_OBJECT_POSE) {
@@ -205,8 +211,8 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void osc_policy_kernel(const Pol
             }
 #pragma unroll
             for (int c = 0; c < 7; ++c)
-                if (c < a.net.n_out) a.out[(size_t)c * stride + so] = o[c];
-            if (a.net.n_out == 7) a.grip[so] = o[6] > 0.0f ? a.grip_close : a.grip_open;
+                if (c < a.net.n_out) a.st.out[(size_t)c * stride + so] = o[c];
+            if (a.net.n_out == 7) a.st.grip[so] = o[6] > 0.0f ? a.grip_close : a.grip_open;
             teleop_follow(a.t, s_t, lane, so, row, r);
         } else if (valid) a.flags_any[so] |= IRLOSC_FLAG_NONFINITE;
         if (__any(ok) && lane == 0) *s_moved = 1;

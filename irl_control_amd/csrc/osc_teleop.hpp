@@ -30,9 +30,16 @@
 
 namespace irlosc {
 
+struct PlateState { double* pose; };      // the stream's per-robot state (and a policy's), the plate: [6][stride], x y z roll pitch yaw
+// One robot's fresh plate (so: its column) at the origin given: the init launch of irlosc_set_teleop_stream and irlosc_set_policy, a reset of episodes
+__device__ __forceinline__ void plate_fresh(PlateState st, int stride, size_t so, const double origin[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) st.pose[(size_t)c * stride + so] = origin[c];
+}
+
 struct TeleopArgs {
     void* tgt;                // [B][ndev][7] targets of the slot, record type
-    double* pose;             // [6][stride]
+    PlateState st;
     const double* readings;   // per_robot: [walk wave][T * 6][64] (init: the origins [walk wave][6][64]); else not read
     double r[6];              // !per_robot: the tick's reading (init: the origin)
     double inc;
@@ -49,14 +56,14 @@ template <typename T>
 __device__ __forceinline__ void teleop_follow(const TeleopArgs& a, T* s_t, int lane, size_t so, int row, const double r[6]) {
     double p[6];
 #pragma unroll
-    for (int c = 0; c < 6; ++c) p[c] = a.pose[(size_t)c * a.stride + so];
+    for (int c = 0; c < 6; ++c) p[c] = a.st.pose[(size_t)c * a.stride + so];
 #pragma unroll
     for (int c = 0; c < 3; ++c) p[c] = __dadd_rn(p[c], __dmul_rn(a.inc, r[c]));
     p[5] = teleop_wrap(__dsub_rn(p[5], __dmul_rn(a.inc, r[5])));
     p[4] = teleop_wrap(__dsub_rn(p[4], __dmul_rn(a.inc, r[4])));
     p[3] = teleop_wrap(__dadd_rn(p[3], __dmul_rn(a.inc, r[3])));
 #pragma unroll
-    for (int c = 0; c < 6; ++c) a.pose[(size_t)c * a.stride + so] = p[c];
+    for (int c = 0; c < 6; ++c) a.st.pose[(size_t)c * a.stride + so] = p[c];
     // q_p = qx(pitch) (x) qy(roll) (x) qz(yaw)
     const double hx = __dmul_rn(p[4], 0.5), hy = __dmul_rn(p[3], 0.5), hz = __dmul_rn(p[5], 0.5);
     const double cx = cos(hx), sx = sin(hx), cy = cos(hy), sy = sin(hy), cz = cos(hz), sz = sin(hz);
@@ -100,10 +107,7 @@ __global__ __launch_bounds__(64) void osc_teleop_kernel(const TeleopArgs a) {
         for (int c = 0; c < 6; ++c) r[c] = a.per_robot ? a.readings[e0 + (size_t)c * 64] : a.r[c];
     }
     if (a.init) {
-        if (valid) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) a.pose[(size_t)c * a.stride + so] = r[c];
-        }
+        if (valid) plate_fresh(a.st, a.stride, so, r);
         return;
     }
     const int row = a.ndev * 7;

@@ -33,15 +33,29 @@
 
 namespace irlosc {
 
+struct WallState {            // the walls' per-robot state
+    double* force;            // [3][ndev][stride]: what the last tick applied
+    double* max_depth;        // [ndev][stride]: the largest g > 0 seen, or 0
+    int32_t* contact_ticks;   // [ndev][stride]: ticks on which a wall of the device had g > 0
+    int32_t* first_tick;      // [ndev][stride]: the first such tick, or -1
+};
+// One robot's fresh wall state (so: its column): what the fills of irlosc_set_walls leave, written by a reset of episodes
+__device__ __forceinline__ void wall_fresh(WallState st, int ndev, int stride, size_t so) {
+    const size_t plane = (size_t)ndev * stride;
+    for (int d = 0; d < ndev; ++d) {
+        const size_t o = (size_t)d * stride + so;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) st.force[c * plane + o] = 0.0;
+        st.max_depth[o] = 0.0; st.contact_ticks[o] = 0; st.first_tick[o] = -1;
+    }
+}
+
 struct WallArgs {
     double* xside;            // apply: the tick's exchange block [walk wave][n_compact][64], bias entries in place
     const double* qt;         // apply: the slot's coordinates in the walk's layout [walk wave][2 NJ][64] (entry 2 i + 1 = qvel_i)
     void* wrench;             // sense: the feed's wrench of the tick [B][ndev][6], record type, xyz in place
     const double* table;      // per_robot: [walk wave][W][8][64], else [W][8]
-    double* force;            // state [3][ndev][stride]: what the last tick applied
-    double* max_depth;        // state [ndev][stride]: the largest g > 0 seen, or 0
-    int32_t* contact_ticks;   // state [ndev][stride]: ticks on which a wall of the device had g > 0
-    int32_t* first_tick;      // state [ndev][stride]: the first such tick, or -1
+    WallState st;
     int32_t B, ndev, W, per_robot, stride;
     int32_t apply;            // 1: apply mode, 0: sense mode (uniform over the launch)
     int32_t tick;             // apply: the walls' tick
@@ -65,7 +79,7 @@ __global__ __launch_bounds__(64) void osc_wall_kernel(const WallArgs a) {
             const size_t so = (size_t)d * a.stride + b;
             T* w = (T*)a.wrench + ((size_t)b * a.ndev + d) * 6;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) w[c] = (T)__dsub_rn((double)w[c], a.force[c * plane + so]);
+            for (int c = 0; c < 3; ++c) w[c] = (T)__dsub_rn((double)w[c], a.st.force[c * plane + so]);
         }
         return;
     }
@@ -133,11 +147,11 @@ __global__ __launch_bounds__(64) void osc_wall_kernel(const WallArgs a) {
                         });
                     }
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) a.force[c * plane + so] = F[c];
+                    for (int c = 0; c < 3; ++c) a.st.force[c * plane + so] = F[c];
                     if (depth > 0.0) {
-                        if (depth > a.max_depth[so]) a.max_depth[so] = depth;
-                        a.contact_ticks[so] += 1;
-                        if (a.first_tick[so] < 0) a.first_tick[so] = a.tick;
+                        if (depth > a.st.max_depth[so]) a.st.max_depth[so] = depth;
+                        a.st.contact_ticks[so] += 1;
+                        if (a.st.first_tick[so] < 0) a.st.first_tick[so] = a.tick;
                     }
                 }
             }

@@ -10,8 +10,7 @@
 // [ndev][stride]; a per-robot table is [walk wave][dev][w][3][64] (a lane's waypoint: three coalesced loads), a shared one
 // [dev][w][3].  The distance is float64 with every product and sum rounded on its own (no contraction): the host can repeat it.
 //
-// init = 1 (irlosc_set_waypoints): state = (0, 0, -1) for listed devices, (-1, 0, -1) for the others, and waypoint 0 into the
-// targets of every listed device; the exchange block is not read.
+// init = 1 (irlosc_set_waypoints): every device's state fresh (path_fresh), waypoint 0 into the targets of every listed device; no block is read.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,12 +20,15 @@
 
 namespace irlosc {
 
+struct PathState { int32_t* index; uint32_t* arrivals; int32_t* last_tick; };      // the paths' per-robot state: [ndev][stride] each
+// One robot's fresh state of one device (o: its word of the device's plane; W: the device's waypoints, 0: not listed): what the init
+// launch of irlosc_set_waypoints leaves, and a reset of episodes
+__device__ __forceinline__ void path_fresh(PathState st, size_t o, int W) { st.index[o] = W > 0 ? 0 : -1; st.arrivals[o] = 0u; st.last_tick[o] = -1; }
+
 struct WaypointArgs {
     const double* xside;      // the step's exchange block [walk wave][n_entries][64] (init: not read)
     void* tgt;                // [B][ndev][7] targets of the slot, record type: xyz of the listed devices in place
-    int32_t* index;           // [ndev][stride]
-    uint32_t* arrivals;
-    int32_t* last_tick;
+    PathState st;
     const double* table;      // per_robot: [walk wave][ndev][wmax][3][64], else [ndev][wmax][3]
     double thr2[IRLOSC_MAX_DEV];        // threshold^2
     int32_t count[IRLOSC_MAX_DEV];      // W_d (0: no list)
@@ -49,18 +51,14 @@ __global__ __launch_bounds__(64) void osc_waypoint_kernel(const WaypointArgs a) 
     for (int d = 0; d < a.ndev; ++d) {
         const int W = a.count[d];
         const size_t so = (size_t)d * a.stride + b0 + lane;
-        if (a.init && valid) {
-            a.index[so] = W > 0 ? 0 : -1;
-            a.arrivals[so] = 0u;
-            a.last_tick[so] = -1;
-        }
+        if (a.init && valid) path_fresh(a.st, so, W);
         if (W <= 0) continue;                       // (uniform over the launch)
         int idx = 0;
         bool reached = valid;
         if (!a.init) {
             reached = false;
             if (valid) {                            // idle lanes load nothing
-                idx = a.index[so];
+                idx = a.st.index[so];
                 const double* __restrict__ x = a.xside + ((size_t)blockIdx.x * a.n_entries + a.ee0[d]) * 64 + lane;
                 const T* t = s_t + lane * row + d * 7;
                 const double d0 = __dsub_rn(x[0], (double)t[0]), d1 = __dsub_rn(x[64], (double)t[1]), d2 = __dsub_rn(x[128], (double)t[2]);
@@ -68,10 +66,10 @@ __global__ __launch_bounds__(64) void osc_waypoint_kernel(const WaypointArgs a) 
                 reached = idx < W && dist2 < a.thr2[d];                      // NaN: not reached
             }
             if (reached) {
-                a.arrivals[so] += 1u;
-                a.last_tick[so] = a.tick;
+                a.st.arrivals[so] += 1u;
+                a.st.last_tick[so] = a.tick;
                 idx = idx + 1 < W ? idx + 1 : (a.loop[d] ? 0 : W);
-                a.index[so] = idx;
+                a.st.index[so] = idx;
             }
         }
         if (reached) {
