@@ -13,7 +13,11 @@ there (the ACTION drive of the right arm's gripper motor takes grip_close) and s
 It runs with episodes: every `episode_ticks` ticks a robot's plate is put back to its origin and its coordinates to the start, while the
 others go on; the outcome counts are printed.  The arms follow as far as the contact-free plant lets them: reported, not promised.
 
-    python examples/policy_resident_headless.py [--robots 4096] [--episodes 2] [--episode-ticks 300]
+With --std S the servo explores: a Gaussian head of standard deviation S on the six readings (BatchedOSC.set_policy_noise; the grip's
+output stays deterministic) is drawn on the GPU per robot and tick from --seed, and the one rollout runs with a log of every tenth
+tick's sampled action and log-probability: the fleet's mean logp and the spread of the final plate error are printed.
+
+    python examples/policy_resident_headless.py [--robots 4096] [--episodes 2] [--episode-ticks 300] [--std 0.5 --seed 5]
 """
 import argparse
 import os
@@ -49,8 +53,9 @@ def servo_layers(goal=GOAL, k=K, near=NEAR):
     return [(W0, b0), (W1, b1)]
 
 
-def run(robots=16, episodes=2, episode_ticks=300, seed=5, dt=1e-3, damping=0.0, verbose=True):
-    """-> dict(records [B, episodes, 4], dist [B]: |goal - plate| over x y z when the last episode ended, grip [B], ms_per_tick)"""
+def run(robots=16, episodes=2, episode_ticks=300, seed=5, dt=1e-3, damping=0.0, verbose=True, std=0.0):
+    """-> dict(records [B, episodes, 4], dist [B]: |goal - plate| over x y z when the last episode ended, grip [B], ms_per_tick; with
+    std > 0 also logp [S, B]: the log-probabilities of every tenth tick's sampled actions)"""
     lay = synth.make_layout("k13")
     _, gains, _ = synth.make_batch("k13", 1, seed=0)
     osc = BatchedOSC(lay, robots, dtype=np.float64)
@@ -70,7 +75,14 @@ def run(robots=16, episodes=2, episode_ticks=300, seed=5, dt=1e-3, damping=0.0, 
     ticks = episodes * episode_ticks
     t0 = time.perf_counter()
     # the last episode's final tick parks the robot without a reset: its plate is where the servo left it
-    out = osc.rollout(ticks)
+    logp = None
+    if std > 0.0:
+        osc.set_policy_noise([std] * 6 + [0.0], seed=seed)
+        t0 = time.perf_counter()
+        out = osc.rollout_logged(ticks, ("policy_sample",), every=10)
+        logp = out["log"]["policy_sample"][:, :, 7]
+    else:
+        out = osc.rollout(ticks)
     seconds = time.perf_counter() - t0
     st, es = osc.policy_state(), osc.episode_state()
     osc.close()
@@ -84,7 +96,10 @@ def run(robots=16, episodes=2, episode_ticks=300, seed=5, dt=1e-3, damping=0.0, 
               f"(origins up to {np.abs(origin[:, :3] - GOAL[:3]).sum(axis=1).max():.3g} m away)")
         print(f"  hands closing at the end: {int((st['grip'] == grip.FORCE).sum())} of {robots}; robots frozen by the plant at some tick: "
               f"{int((out['flags_any'] & (64 | 1) != 0).sum())}")
-    return dict(records=es["records"], dist=dist, grip=st["grip"], ms_per_tick=seconds * 1e3 / ticks, pose=st["pose"])
+        if logp is not None:
+            print(f"  Gaussian head, std {std:g} on the six readings, seed {seed}: mean logp of the {logp.size} logged samples {logp.mean():.4f}; final "
+                  f"plate error: mean {dist.mean():.3g}, standard deviation {dist.std():.3g} m over the fleet")
+    return dict(records=es["records"], dist=dist, grip=st["grip"], ms_per_tick=seconds * 1e3 / ticks, pose=st["pose"], logp=logp)
 
 
 if __name__ == "__main__":
@@ -92,6 +107,7 @@ if __name__ == "__main__":
     ap.add_argument("--robots", type=int, default=16)
     ap.add_argument("--episodes", type=int, default=2)
     ap.add_argument("--episode-ticks", type=int, default=300)
-    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=5, help="of the start states and origins, and the key of the exploration noise")
+    ap.add_argument("--std", type=float, default=0.0, help="> 0: a Gaussian head of this standard deviation on the six readings")
     a = ap.parse_args()
-    run(a.robots, a.episodes, a.episode_ticks, a.seed)
+    run(a.robots, a.episodes, a.episode_ticks, a.seed, std=a.std)

@@ -545,7 +545,15 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *     irlosc_set_action_motion that answers IRLOSC_ERR_HIP                             no motion, the list stays
  *     whatever ends or replaces the slot's list (irlosc_set_action_list included)      the motion ends
  *     everything else (refs, objects, episodes, uploads, feeds, pushes, walls, rows)   leaves it and its state alone; a reset of
- *                                                                                      episodes keeps a robot's draws */
+ *                                                                                      episodes keeps a robot's draws
+ * A policy's GAUSSIAN HEAD (irlosc_set_policy_noise, "a stochastic policy head" below) is a side description of the policy in the same way:
+ *     irlosc_set_policy_noise with noise == NULL                                       the head ends, the policy stays (deterministic again)
+ *     irlosc_set_policy_noise that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE          nothing changes: the head in force stays, whole
+ *     irlosc_set_policy_noise that succeeds                                            its head replaces the one in force; its state reset
+ *     irlosc_set_policy_noise that answers IRLOSC_ERR_HIP                              no head, the policy stays
+ *     whatever ends or replaces the slot's policy (irlosc_set_policy included)         the head ends
+ *     everything else                                                                  leaves it and its state alone; a reset of episodes
+ *                                                                                      zeroes a robot's act and logp and keeps its draws */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -832,6 +840,47 @@ IRLOSC_API int irlosc_set_policy(irlosc_ctx* ctx, int32_t slot, int32_t B, const
 IRLOSC_API int irlosc_download_policy_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* pose, float* out, double* grip, float* obs,
                                             int32_t* tick);
 
+/* ---- a stochastic policy head: a Gaussian drawn on the device, logged with its log-probability (csrc/osc_policy.hpp, csrc/osc_rng.hpp) --
+ * A GAUSSIAN HEAD with a state-independent standard deviation on the policy in force: the network's output becomes the MEAN, the action
+ * that steers the plate is sampled around it inside the policy kernel, and per robot the device keeps the action taken and its
+ * log-probability under the policy that took it -- what a PPO-style learner reads per tick (the log: IRLOSC_LOG_POLICY_OUT,
+ * IRLOSC_LOG_POLICY_SAMPLE).  A slot without a head launches exactly the kernels it launched before there was one.
+ * THE ARITHMETIC, per robot b on every tick that runs it, which the host can repeat bit for bit (irl_control_amd/policy.py::sample);
+ * mean[c] = the network's output (float, unchanged), d = draws[b] at the start of the tick:
+ *     eps[c] = z[c & 3] of normal4(seed, b, d, c >> 2, stream 1): Box-Muller on both word pairs of the Philox4x32-10 block with counter
+ *              (b, d, c >> 2, 1) under key seed -- z0 = r0 cos, z1 = r0 sin, z2 = r1 cos, z3 = r1 sin, every ln, sin and cos written
+ *              out in correctly rounded operations (action_motion.py::normal4).  Two blocks cover 6 or 7 outputs.  The fourth counter
+ *              word is a STREAM: an action list's target noise (irlosc_set_action_motion) is stream 0, so the two never meet under one seed
+ *     act[c] = std[c] > 0 ? (float)((double) mean[c] + (double) std[c] * eps[c]) : mean[c]
+ *              -- the product and the sum rounded on their own in double (no fma), ONE round-to-nearest cast (beyond float's range: an
+ *              infinity); an output with std == 0 is deterministic by selection, so a mean of -0 keeps its sign
+ *     s = 0;  for c ascending with std[c] > 0:  s = s + eps[c] * eps[c]   (the product rounded, then the sum);   logp = (-0.5 * s) - C
+ *     C = sum over the noisy c, ascending, of ln((double) std[c]), + (m / 2) ln 2 pi, m = their number: computed once by the setter on
+ *              the host (irlosc_download_policy_noise_state hands it back as logp_const)
+ * logp is the density at the UNROUNDED double mean + std eps, not at the float act: recomputing it from act differs by a few 1e-6.
+ * EVERYTHING BEHIND THE NETWORK uses act where the deterministic policy uses out: the clamp, the plate and the followers' targets,
+ * grip = act[6] > 0 ? grip_close : grip_open, and the finite verdict, which now covers the observation, mean and act.  A robot that is
+ * not finite keeps pose, targets, out, grip, act and logp and gets IRLOSC_FLAG_NONFINITE, as before.  `out` keeps its meaning: the
+ * network's output before the clamp -- the mean.
+ * draws[b] COUNTS TICKS, not successful draws: + 1 (mod 2^32) on every tick that runs robot b, finite or not; a rollout over fewer robots
+ * leaves the others' count alone; a reset of episodes zeroes act and logp and KEEPS draws, so every episode explores afresh. */
+typedef struct irlosc_policy_noise {
+    uint64_t seed;         /* the Philox key */
+    int32_t  n_std;        /* must equal n_out of the policy in force (6 or 7) */
+    int32_t  reserved;     /* 0 */
+    float    std[8];       /* std[c], c < n_std: finite, >= 0, at least one > 0; the others 0 */
+} irlosc_policy_noise;
+/* Gives the policy in force on slot `slot` the head; draw0: [B of the policy] draws to start from, or NULL = zeros.  Every argument is
+ * checked before anything is touched.  IRLOSC_ERR_ARG: n_std other than the policy's n_out, a std that is negative or not finite, all
+ * stds 0, a std behind n_std that is not 0, reserved != 0.  IRLOSC_ERR_STATE: the slot has no policy.  On success act = 0, logp = 0,
+ * draws = draw0.  noise == NULL ends the head and nothing else.  The lifetime: "a policy's GAUSSIAN HEAD" above.  Synchronous. */
+IRLOSC_API int irlosc_set_policy_noise(irlosc_ctx* ctx, int32_t slot, const irlosc_policy_noise* noise, const uint32_t* draw0);
+/* act: [B][n_out] float and logp: [B] double as the last tick that ran the robot left them (0 before the first, and behind a reset of
+ * episodes); draws: [B] uint32; logp_const: one double, C above.  Any may be NULL.  IRLOSC_ERR_STATE on a slot without a head, or with
+ * one for fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_policy_noise_state(irlosc_ctx* ctx, int32_t slot, int32_t B, float* act, double* logp, uint32_t* draws,
+                                                  double* logp_const);
+
 /* ---- external pushes on the plant, sensed by the F/T feed: admit_test / force_test inside a rollout (csrc/osc_push.hpp) ------------
  * What examples/headless_loops.py::admit_test_loop does on the host -- xfrc_applied on a gripper body during a window of ticks, the
  * F/T sensors reading the reaction after sim.step() (fakesim.ToyDynamics), the next `generate` yielding to it -- as up to two more
@@ -1000,6 +1049,11 @@ IRLOSC_API int irlosc_download_joint_state(irlosc_ctx* ctx, int32_t slot, int32_
 #define IRLOSC_LOG_OBJECT_POSE 512u /* [R][nobj][8]  FRONT: the action objects as this tick's object kernel left them: x y z qw qx qy qz
                                        and the holder (-1 = free, else the gripper) as a double.  Only on a slot with action objects
                                        (irlosc_set_objects); elsewhere the bit is unknown: irlosc_log_layout_objects, below          */
+#define IRLOSC_LOG_POLICY_OUT    1024u /* [R][n_out]     FRONT: the network's output of this tick (with a Gaussian head: the mean), widened
+                                          to double.  Only on a slot with a policy; elsewhere the bit is unknown                        */
+#define IRLOSC_LOG_POLICY_SAMPLE 2048u /* [R][n_out + 1] FRONT: act[0 .. n_out) of this tick, widened, then logp.  Only on a slot whose
+                                          policy has a Gaussian head (irlosc_set_policy_noise); elsewhere the bit is unknown.  Both show
+                                          what this tick's policy kernel left: a robot it skipped (not finite) repeats its last sample */
 typedef struct irlosc_log {
     uint32_t channels;      /* OR of the above, not 0, no other bit */
     int32_t  every;         /* >= 1: ticks 0, every, 2 every, ... of THIS call are logged (as trace_every counts) */
@@ -1017,6 +1071,12 @@ IRLOSC_API int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int
  * [R][nobj][8].  With nobj == 0 that bit is unknown, as it is to irlosc_log_layout, and the first nine offsets are irlosc_log_layout's. */
 IRLOSC_API int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, uint32_t channels, int32_t R, int64_t offset[10],
                                          int64_t* sample_words);
+/* The same for a slot whose policy has n_out outputs (6 or 7; 0: no policy) and, with sampled == 1, a Gaussian head: twelve offsets, the
+ * eleventh IRLOSC_LOG_POLICY_OUT's plane [R][n_out], the twelfth IRLOSC_LOG_POLICY_SAMPLE's [R][n_out + 1].  With n_out == 0 both bits
+ * are unknown and the first ten offsets are irlosc_log_layout_objects'; with sampled == 0 IRLOSC_LOG_POLICY_SAMPLE is unknown.
+ * IRLOSC_ERR_ARG also for an n_out other than 0, 6, 7 and a sampled other than 0, 1. */
+IRLOSC_API int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, uint32_t channels, int32_t R,
+                                        int64_t offset[12], int64_t* sample_words);
 /* irlosc_rollout_from_q with a log in place of the EE trace: log_host[ceil(ticks / every)][sample_words] (double), one sample per logged
  * tick of the R robots of `robots` (strictly ascending, in [0, B); NULL: all B).  log == NULL is
  * irlosc_rollout_from_q(ctx, slot, B, ticks, 0, NULL, u_host, flags_any_host); robots and log_host are not read then.
@@ -1027,8 +1087,9 @@ IRLOSC_API int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, 
  * when it needs the block again, and at the end.  Ticks keep running while a half is on the link; the rollout waits only where a half
  * would be refilled before it has left.
  * Every argument is checked before anything is enqueued, sizes in 64 bits; after a refusal the slot is exactly as it was: no tick ran.
- *   IRLOSC_ERR_ARG    what irlosc_log_layout_objects refuses for the slot's action objects (none: what irlosc_log_layout refuses, so
- *                     IRLOSC_LOG_OBJECT_POSE on a slot without objects is an unknown bit); every < 1; reserved != 0; robots == NULL with n_robots not 0 or B; robots given with
+ *   IRLOSC_ERR_ARG    what irlosc_log_layout_policy refuses for the slot's action objects, policy and head (none of them: what
+ *                     irlosc_log_layout refuses, so IRLOSC_LOG_OBJECT_POSE on a slot without objects, IRLOSC_LOG_POLICY_OUT on one without
+ *                     a policy and IRLOSC_LOG_POLICY_SAMPLE on one without a Gaussian head are unknown bits); every < 1; reserved != 0; robots == NULL with n_robots not 0 or B; robots given with
  *                     n_robots outside [1, B], not strictly ascending or outside [0, B); log_host NULL; a buffer_bytes != 0 that
  *                     holds fewer than two samples
  *   IRLOSC_ERR_STATE  what irlosc_rollout_from_q refuses; IRLOSC_LOG_WRENCH on a slot without a sensor feed; IRLOSC_LOG_WALL_FORCE on a

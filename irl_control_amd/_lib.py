@@ -44,9 +44,11 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_log_layout", "irlosc_rollout_from_q_logged", "irlosc_set_episodes", "irlosc_download_episode_state",
            "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects",
            "irlosc_set_action_motion", "irlosc_download_action_motion_state", "irlosc_set_object_loads",
-           "irlosc_download_object_load_state", "irlosc_set_policy", "irlosc_download_policy_state"]
+           "irlosc_download_object_load_state", "irlosc_set_policy", "irlosc_download_policy_state",
+           "irlosc_set_policy_noise", "irlosc_download_policy_noise_state", "irlosc_log_layout_policy"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
 LOG_OBJECT_POSE = 512                                    # only on a slot with action objects
+LOG_POLICY_OUT, LOG_POLICY_SAMPLE = 1024, 2048           # only on a slot with a policy / one whose policy has a Gaussian head
 EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED = 1, 2, 4
 MAX_OBJECTS, MAX_GRIPPERS, MAX_MATES = 4, 2, 2
 MAX_EPISODE_RECORDS, MAX_EPISODE_STARTS = 16, 4096
@@ -178,6 +180,11 @@ class ActionMotion(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class PolicyNoise(C.Structure):
+    """struct irlosc_policy_noise (include/irlosc.h): the Gaussian head of the policy in force, irlosc_set_policy_noise."""
+    _fields_ = [("seed", C.c_uint64), ("n_std", C.c_int32), ("reserved", C.c_int32), ("std", C.c_float * 8)]
+
+
 class Cfg(C.Structure):
     _fields_ = [("hip_device", C.c_int32), ("dtype", C.c_int32), ("max_batch", C.c_int32),
                 ("n_slots", C.c_int32), ("n", C.c_int32), ("ndev", C.c_int32),
@@ -262,6 +269,9 @@ def load():
     lib.irlosc_download_targets.argtypes = [vp, i32, i32, vp]
     lib.irlosc_set_policy.argtypes = [vp, i32, i32, C.POINTER(Policy), vp, vp]
     lib.irlosc_download_policy_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    lib.irlosc_set_policy_noise.argtypes = [vp, i32, C.POINTER(PolicyNoise), vp]
+    lib.irlosc_download_policy_noise_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.irlosc_log_layout_policy.argtypes = [i32, i32, i32, i32, i32, C.c_uint32, i32, vp, vp]
     lib.irlosc_set_pushes.argtypes = [vp, i32, i32, C.POINTER(Pushes), vp]
     lib.irlosc_set_walls.argtypes = [vp, i32, i32, C.POINTER(Walls), vp]
     lib.irlosc_download_wall_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]

@@ -104,6 +104,23 @@ def normal3(seed: int, robot, draw, action):
     return z
 
 
+def normal4(seed: int, robot, draw, block, stream):
+    """Four standard normals per robot: Box-Muller on both word pairs of the Philox block of counter (robot, draw, block, stream) --
+    z0 = r0 cos, z1 = r0 sin, z2 = r1 cos, z3 = r1 sin -> [..., 4] float64 (normal4 of csrc/osc_rng.hpp).  The fourth counter word
+    names a stream: normal3 is the first three values of stream 0, a policy's Gaussian head (policy.sample) draws on stream 1."""
+    robot, draw, block, stream = np.broadcast_arrays(*(np.asarray(v, dtype=np.uint32) for v in (robot, draw, block, stream)))
+    ctr = np.stack([robot, draw, block, stream], axis=-1)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    w = philox4x32_10(ctr, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32))
+    z = np.empty(robot.shape + (4,))
+    for p in (0, 1):
+        u = (2.0 * w[..., 2 * p].astype(np.float64) + 1.0) * _INV33
+        r = np.sqrt(-2.0 * ln_rn(u))
+        s, c = sincos_turn_rn(w[..., 2 * p + 1])
+        z[..., 2 * p], z[..., 2 * p + 1] = r * c, r * s
+    return z
+
+
 # ---- the motion as data -------------------------------------------------------------------------------------------------------------
 def action_motion_state(B: int, draw0=None) -> Dict:
     """The per-robot state of a motion as irlosc_set_action_motion resets it: step 0, draws = draw0 (default zeros), origin and goal 0."""

@@ -352,6 +352,14 @@ class BatchedOSC:
         qpos, qvel = self.download_q(slot)
         return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=tr, ticks_run=run)
 
+    def _log_policy(self, slot: int):
+        """(n_out, sampled) of the slot as the library's log sees it: the policy in force (0: none) and whether it has a Gaussian head.
+        Asked of the library: other programs' setters, set_targets and set_model end a policy behind this object's back."""
+        if self._policy[slot] is None or self.lib.irlosc_download_policy_state(self._h, slot, 0, None, None, None, None, None) != 0:
+            return 0, False
+        sampled = self.lib.irlosc_download_policy_noise_state(self._h, slot, 0, None, None, None, None) == 0
+        return self._policy[slot][1], sampled
+
     def _ticks_run(self, slot: int) -> int:
         """The ticks the slot's last rollout call ran: fewer than asked where its episodes exited early (set_episodes, poll_every)."""
         run = C.c_int32(0)
@@ -381,15 +389,16 @@ class BatchedOSC:
             S = -(-ticks // every) if every > 0 and ticks > 0 else 0
             words = 0
             nobj = self._objects[slot][0]
-            if S and R >= 1 and m and not m & ~(rollout_log.ALL | (rollout_log.OBJECT_POSE_BIT if nobj else 0)):
-                words = rollout_log.layout(L.n, L.ndev, m, R, nobj)[1]
+            n_out, sampled = self._log_policy(slot)
+            if S and R >= 1 and m and not m & ~rollout_log.known(nobj, n_out, sampled):
+                words = rollout_log.layout(L.n, L.ndev, m, R, nobj, n_out, sampled)[1]
             buf = np.empty((S, words), dtype=np.float64)
         self._chk(self.lib.irlosc_rollout_from_q_logged(self._h, slot, B, ticks, C.byref(lg) if lg is not None else None, _lib.ptr(idx),
                                                         _lib.ptr(buf), _lib.ptr(u), _lib.ptr(fl)))
         run = self._ticks_run(slot)
         if buf is not None:
             log_ticks = np.arange(0, min(ticks, run) if B else ticks, every, dtype=np.int64)      # (an early exit: the rows of the ticks run)
-            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype, nobj=nobj) if B else {}
+            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype, nobj=nobj, n_out=n_out, sampled=sampled) if B else {}
         qpos, qvel = self.download_q(slot)
         return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=None, log=log, log_ticks=log_ticks, ticks_run=run)
 
@@ -752,6 +761,44 @@ class BatchedOSC:
         desc = _p.to_struct(layers, mask, rig, og.shape[0], increment, clip, keep_obs, grip_dev, grip_close, grip_open)
         self._chk(self.lib.irlosc_set_policy(self._h, slot, B, C.byref(desc), _lib.ptr(_p.weights(layers)), _lib.ptr(og)))
         self._policy[slot] = (n_in, dims[-1], bool(keep_obs))
+
+    def set_policy_noise(self, std, seed: int = 0, draw0=None, slot: int = 0):
+        """A Gaussian head on the slot's policy (irlosc_set_policy_noise; "a stochastic policy head" in include/irlosc.h): the network's
+        output becomes the mean, and per tick and robot the action act[c] = out[c] + std[c] eps[c] is drawn on the GPU -- from `seed`,
+        the robot's index and its count of draws, so repeatable and the same whatever else runs -- and steers the plate (and the grip)
+        in place of out; the robot's log-probability is kept with it (policy_noise_state; the log's policy_sample channel).  `std`:
+        [n_out] float32, >= 0, at least one > 0 (0: that output stays deterministic).  `draw0`: [B] draws to start from (default
+        zeros).  The arithmetic is policy.sample's, bit for bit.  After set_policy, which ends it; std=None clears the head and
+        nothing else."""
+        if std is None:
+            self._chk(self.lib.irlosc_set_policy_noise(self._h, slot, None, None))
+            return
+        sd = np.asarray(std, dtype=np.float32).reshape(-1)
+        if len(sd) > 8:
+            raise ValueError(f"std: expected one entry per output (6 or 7), got {len(sd)}")
+        d = _lib.PolicyNoise()
+        d.seed, d.n_std, d.reserved = int(seed) & 0xFFFFFFFFFFFFFFFF, len(sd), 0
+        for c, v in enumerate(sd):
+            d.std[c] = float(v)
+        d0 = None
+        if draw0 is not None:
+            d0 = np.ascontiguousarray(draw0, dtype=np.uint32)
+            if d0.shape != (self._B[slot],):
+                raise ValueError(f"draw0: expected shape ({self._B[slot]},), got {d0.shape}")
+        self._chk(self.lib.irlosc_set_policy_noise(self._h, slot, C.byref(d), _lib.ptr(d0)))
+
+    def policy_noise_state(self, slot: int = 0):
+        """-> dict(act [B, n_out] float32: the action the last tick that ran the robot took; logp [B]: its log-probability under the
+        head (the density at the unrounded float64 action); draws [B] uint32: the ticks that ran the robot since set_policy_noise, on
+        top of draw0; logp_const: C of logp = -sum(eps^2) / 2 - C).  (irlosc_download_policy_noise_state)"""
+        B = self._B[slot]
+        if self._policy[slot] is None:      # (the library says why)
+            self._chk(self.lib.irlosc_download_policy_noise_state(self._h, slot, B, None, None, None, None))
+        n_out = self._policy[slot][1]
+        act, logp, draws = np.empty((B, n_out), dtype=np.float32), np.empty(B, dtype=np.float64), np.empty(B, dtype=np.uint32)
+        const = C.c_double(0.0)
+        self._chk(self.lib.irlosc_download_policy_noise_state(self._h, slot, B, _lib.ptr(act), _lib.ptr(logp), _lib.ptr(draws), C.byref(const)))
+        return dict(act=act, logp=logp, draws=draws, logp_const=float(const.value))
 
     def clear_policy(self, slot: int = 0):
         """Ends the slot's policy (irlosc_set_policy with desc == NULL); targets and any other program are left alone."""

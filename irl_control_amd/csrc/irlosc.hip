@@ -82,6 +82,14 @@ struct Program {
     int po_nobj = -1;
     DevBuf<float> po_w, po_out, po_obs;
     DevBuf<double> po_grip;
+    // The Gaussian head of the policy in force (irlosc_set_policy_noise): the description (pn), C of logp (pn_const), and its per-robot
+    // state, allocated by the first use for max_batch robots: act [n_out][max_batch], logp [max_batch], draws [max_batch]
+    int noise = 0;             // 1: the policy's ticks launch the NOISE form of its kernel
+    irlosc_policy_noise pn{};
+    double pn_const = 0.0;
+    DevBuf<float> pn_act;
+    DevBuf<double> pn_logp;
+    DevBuf<uint32_t> pn_draws;
     // THE LAYOUT of the state -- the kernels' arguments, the setters' sizes and the downloads all ask here: wp_i in planes of `plane` =
     // ndev x max_batch words; al_i and al_d in rows of Bm = max_batch words (start_xyz: three rows); and their sizes
     int32_t* index(size_t) const { return wp_i; }  int32_t* arrivals(size_t plane) const { return wp_i + plane; }  int32_t* last_tick(size_t plane) const { return wp_i + 2 * plane; }
@@ -95,7 +103,7 @@ struct Program {
     // ... and each kind's state as its kernels and a reset of episodes take it (the structs of osc_action.hpp, osc_waypoint.hpp, osc_teleop.hpp, osc_policy.hpp)
     ListState list_state(size_t Bm) const { return {action(Bm), entered(Bm), grip_left(Bm), finished_tick(Bm), err(Bm), max_vel0(Bm), gripper_force(Bm), start_xyz(Bm)}; }
     MotionState motion_state(size_t Bm) const { return {m_step(Bm), m_draws(Bm), m_origin(Bm), m_goal(Bm)}; }  PlateState plate_state(size_t Bm) const { return {pose(Bm)}; }
-    PathState path_state(size_t plane) const { return {index(plane), (uint32_t*)arrivals(plane), last_tick(plane)}; }  PolicyState policy_state() const { return {po_out, po_grip}; }
+    PathState path_state(size_t plane) const { return {index(plane), (uint32_t*)arrivals(plane), last_tick(plane)}; }  PolicyState policy_state() const { return {po_out, po_grip, noise ? pn_act.get() : nullptr, noise ? pn_logp.get() : nullptr, noise ? pn_draws.get() : nullptr}; }
 
     // Paths of B robots are in force, their state reset by the cycler's init launch (which also wrote waypoint 0 into the targets).
     void paths(int B, const irlosc_waypoints& d) { kind = PATHS; robots = B; tick = 0; wp = d; }
@@ -112,13 +120,16 @@ struct Program {
     void stream(int B, const irlosc_teleop_stream& d, std::vector<double>&& shared) { kind = STREAM; robots = B; tick = 0; ts = d; ts_shared = std::move(shared); }
     // A policy over B robots is in force, their poses at the origins by the stream kernel's init launch, out and grip zero (no target written: the first tick does)
     void policy(int B, const irlosc_policy& d, const irlosc_teleop_stream& rig, const PolicyNet& net, int nobj, const double* origin0) {
-        kind = POLICY; robots = B; tick = 0; po = d; ts = rig; po_net = net; po_nobj = nobj;
+        kind = POLICY; robots = B; tick = 0; po = d; ts = rig; po_net = net; po_nobj = nobj; noise = 0;      // (a new policy has no head)
         for (int i = 0; i < 6; ++i) po_origin0[i] = origin0[i];
     }
     // The reading a stream takes on the tick to come: tick mod T of one that loops, none (-1) once one that does not has ended
     int reading() const { return kind != STREAM ? -1 : ts.loop ? tick % ts.ticks : tick < ts.ticks ? tick : -1; }
     // The program ends: irlosc_set_targets wrote the targets, another program takes them over, the model changed, or its buffers failed.
-    void end() { kind = NONE; robots = 0; tick = 0; refs = 0; motion = 0; }
+    void end() { kind = NONE; robots = 0; tick = 0; refs = 0; motion = 0; noise = 0; }
+    // The policy in force has a Gaussian head, its state on the device / is deterministic again (its head was cleared)
+    void samples(const irlosc_policy_noise& d, double logp_const) { noise = 1; pn = d; pn_const = logp_const; }
+    void exact() { noise = 0; }
     // The program ends if it is of this kind (its own setter cleared it; a list: the gains its copy was made from were replaced): one of the other kind stays whole
     void end(Kind k) { if (kind == k) end(); }
     // A tick of a rollout ran the program's kernel.  (Marked once the whole tick is enqueued: if a launch behind the kernel fails, the
@@ -1871,7 +1882,7 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 // tick, is the slot's to say (Slot::prog).  log: the episode log's sample of this tick (irlosc_rollout_from_q_logged), or nullptr.
 // A logged tick: the ring's sample it fills, the event its first log launch waits for on the tick's stream (the half it starts was still
 // draining: the copy that empties it; else null), and what stays the same over the call -- channels, robots (device, or nullptr: all), layout
-struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };      // (off[9]: OBJECT_POSE, of a slot with objects)
+struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };      // (off[9]: OBJECT_POSE, of a slot with objects; off[10], off[11]: of a slot with a policy)
 struct PlantCall { double* trace; const LogCall* log; };
 
 // The exchange entry of each device's EE pose (its x; y z qw qx qy qz follow): what the rollout's kernels find an EE body by
@@ -1971,6 +1982,7 @@ static PolicyArgs policy_args(const irlosc_ctx* c, const Slot& s, int B, const d
     a.net = p.po_net; a.w = p.po_w; a.qt = s.qt; a.xside = xside; a.wrench = wrench; a.obj_pose = s.objects.state(Bm).pose;
     a.st = p.policy_state(); a.obs = p.po.keep_obs ? p.po_obs.get() : nullptr; a.flags_any = c->dflags_any;
     a.grip_close = p.po.grip_close; a.grip_open = p.po.grip_open; a.clip = p.po.clip; a.obs_mask = p.po.obs;
+    if (p.noise) { a.seed = p.pn.seed; a.logp_const = p.pn_const; for (int i = 0; i < 8; ++i) a.std[i] = p.pn.std[i]; }
     a.n = c->cfg.n; a.n_entries = (int32_t)c->model.fe_xentries; a.nobj = std::max(0, p.po_nobj);
     fill_ee0(c, a.ee0);
     return a;
@@ -2092,6 +2104,7 @@ static LogArgs log_args(const irlosc_ctx* c, const Slot& s, const irlosc_ctx::Ba
     a.qpos = s.qpos; a.qvel = s.qvel; a.xside = bk.xside[0]; a.tgt = s.tgt; a.wrench = wrench; a.u = bk.u[0]; a.flags = bk.flags[0];
     a.wall_force = s.walls.state((size_t)c->cfg.ndev * Bm).force; a.joint_tau = s.joints.state(Bm).tau;
     a.obj_pose = s.objects.state(Bm).pose; a.obj_holder = s.objects.state(Bm).holder; a.nobj = s.objects.count();
+    if (s.prog.kind == Program::POLICY) { const PolicyState po = s.prog.policy_state(); a.po_out = po.out; a.po_act = po.act; a.po_logp = po.logp; a.n_out = s.prog.po.n_out; }
     a.R = lg.R; a.n = c->cfg.n; a.ndev = c->cfg.ndev; a.n_entries = (int32_t)c->model.fe_xentries; a.stride = (int32_t)Bm;
     fill_ee0(c, a.ee0);
     return a;
@@ -2712,10 +2725,14 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     return IRLOSC_OK;
 }
 
-extern "C" int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, uint32_t channels, int32_t R, int64_t offset[10], int64_t* sample_words) {
+extern "C" int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, uint32_t channels, int32_t R, int64_t offset[12],
+                                        int64_t* sample_words) {
     if (!offset || !sample_words) return fail(nullptr, IRLOSC_ERR_ARG, "log: offset and sample_words are required");
     if (nobj < 0 || nobj > IRLOSC_MAX_OBJECTS) return fail(nullptr, IRLOSC_ERR_ARG, "log: nobj=%d out of [0,%d]", nobj, IRLOSC_MAX_OBJECTS);
-    const uint32_t known = (LOG_FRONT | LOG_BACK) & ~(nobj ? 0u : (uint32_t)IRLOSC_LOG_OBJECT_POSE);      // (no objects: no such channel)
+    if (n_out != 0 && n_out != 6 && n_out != 7) return fail(nullptr, IRLOSC_ERR_ARG, "log: n_out=%d must be 0 (no policy), 6 or 7", n_out);
+    if (sampled != 0 && sampled != 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: sampled=%d must be 0 or 1", sampled);
+    const uint32_t known = (LOG_FRONT | LOG_BACK) & ~(nobj ? 0u : (uint32_t)IRLOSC_LOG_OBJECT_POSE)      // (no objects, no policy, no head: no such channel)
+                           & ~(n_out ? 0u : (uint32_t)IRLOSC_LOG_POLICY_OUT) & ~(n_out && sampled ? 0u : (uint32_t)IRLOSC_LOG_POLICY_SAMPLE);
     if (channels == 0 || (channels & ~known)) return fail(nullptr, IRLOSC_ERR_ARG, "log: channels=0x%x must be a non-empty OR of the IRLOSC_LOG_* bits", channels);
     if (R < 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: R=%d must be >= 1", R);
     if (n < 1 || n > IRLOSC_MAX_N) return fail(nullptr, IRLOSC_ERR_ARG, "log: n=%d out of [1,%d]", n, IRLOSC_MAX_N);
@@ -2723,10 +2740,17 @@ extern "C" int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, 
     int64_t words = 0;
     for (int i = 0; i < LOG_CHANNELS; ++i) {
         offset[i] = (channels >> i) & 1u ? words : -1;
-        if ((channels >> i) & 1u) words += (int64_t)R * log_width(i, n, ndev, nobj);
+        if ((channels >> i) & 1u) words += (int64_t)R * log_width(i, n, ndev, nobj, n_out);
     }
     *sample_words = words;
     return IRLOSC_OK;
+}
+
+extern "C" int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, uint32_t channels, int32_t R, int64_t offset[10], int64_t* sample_words) {
+    int64_t off[LOG_CHANNELS];
+    const int rc = irlosc_log_layout_policy(n, ndev, nobj, 0, 0, channels, R, offset ? off : nullptr, sample_words);
+    for (int i = 0; !rc && i < 10; ++i) offset[i] = off[i];
+    return rc;
 }
 
 extern "C" int irlosc_log_layout(int32_t n, int32_t ndev, uint32_t channels, int32_t R, int64_t offset[9], int64_t* sample_words) {
@@ -2749,7 +2773,9 @@ static int log_plan(irlosc_ctx* c, int slot, int B, int ticks, const irlosc_log*
         if (robots[i] < 0 || robots[i] >= B || (i && robots[i] <= robots[i - 1]))
             return fail(c, IRLOSC_ERR_ARG, "log: robots[%d]=%d: the list must be strictly ascending in [0,%d)", i, robots[i], B);
     int64_t words = 0;
-    if (irlosc_log_layout_objects(c->cfg.n, c->cfg.ndev, c->slot[slot].objects.count(), log->channels, R, lr.call.off, &words)) return fail(c, IRLOSC_ERR_ARG, "%s", irlosc_last_error(nullptr));
+    const Program& pg = c->slot[slot].prog;      // (a policy's channels: POLICY_OUT with a policy, POLICY_SAMPLE with its Gaussian head)
+    if (irlosc_log_layout_policy(c->cfg.n, c->cfg.ndev, c->slot[slot].objects.count(), pg.kind == Program::POLICY ? pg.po.n_out : 0, pg.noise, log->channels, R, lr.call.off, &words))
+        return fail(c, IRLOSC_ERR_ARG, "%s", irlosc_last_error(nullptr));
     const uint64_t sb = (uint64_t)words * sizeof(double);      // (R <= max_batch, 170 words a robot at most: far from 2^63)
     if (log->buffer_bytes && log->buffer_bytes / 2 < sb)
         return fail(c, IRLOSC_ERR_ARG, "log: buffer_bytes=%llu holds fewer than two samples of %llu bytes", (unsigned long long)log->buffer_bytes, (unsigned long long)sb);
@@ -3599,6 +3625,58 @@ extern "C" int irlosc_download_policy_state(irlosc_ctx* c, int32_t slot, int32_t
                                          out ? (const int32_t*)p.po_out.get() : nullptr, out ? no * Bm : 0, {{(int32_t*)out, (const int32_t*)p.po_out.get(), no, no, 0, 1}});
     if (!rc) rc = download_state(c, B, grip ? p.po_grip.get() : nullptr, grip ? Bm : 0, {{grip, p.po_grip.get(), 1, 1, 0, 1}}, nullptr, 0, {});      // (synchronises: obs is in)
     return rc;
+}
+
+// ---- the Gaussian head of the policy in force (osc_policy.hpp: the NOISE form; osc_rng.hpp) ---------------------------------------------
+extern "C" int irlosc_set_policy_noise(irlosc_ctx* c, int32_t slot, const irlosc_policy_noise* d, const uint32_t* draw0) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, 0);
+    if (rc) return rc;
+    Program& p = c->slot[slot].prog;
+    if (!d) { p.exact(); return IRLOSC_OK; }
+    if (d->reserved != 0) return fail(c, IRLOSC_ERR_ARG, "policy noise: reserved must be 0");
+    if (d->n_std != 6 && d->n_std != 7) return fail(c, IRLOSC_ERR_ARG, "policy noise: n_std=%d must be 6 or 7", d->n_std);
+    int m = 0;
+    double sum_ln = 0.0;       // C = sum of ln std[c] over the noisy outputs, c ascending, + (m / 2) ln 2 pi
+    for (int i = 0; i < 8; ++i) {
+        const float sd = d->std[i];
+        if (i >= d->n_std) {
+            if (sd != 0.0f) return fail(c, IRLOSC_ERR_ARG, "policy noise: std[%d]=%g behind n_std=%d must be 0", i, (double)sd, d->n_std);      // (a NaN is not 0)
+            continue;
+        }
+        if (!std::isfinite(sd) || sd < 0.0f) return fail(c, IRLOSC_ERR_ARG, "policy noise: std[%d]=%g must be finite and >= 0", i, (double)sd);
+        if (sd > 0.0f) { ++m; sum_ln += std::log((double)sd); }
+    }
+    if (!m) return fail(c, IRLOSC_ERR_ARG, "policy noise: every std is 0 (desc == NULL ends a head)");
+    if (p.kind != Program::POLICY) return fail(c, IRLOSC_ERR_STATE, "slot %d has no policy (irlosc_set_policy)", slot);
+    if (d->n_std != p.po.n_out) return fail(c, IRLOSC_ERR_ARG, "policy noise: n_std=%d, the policy in force has n_out=%d", d->n_std, p.po.n_out);
+    const double logp_const = sum_ln + (0.5 * (double)m) * 1.8378770664093453;      // ln 2 pi
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, B = (size_t)p.robots, act_bytes = 7 * Bm * sizeof(float);
+    p.exact();                 // (none until the new one's state is in its buffers)
+    if (!got(p.pn_act.ensure(act_bytes)) || !got(p.pn_logp.ensure(Bm * sizeof(double))) || !got(p.pn_draws.ensure(Bm * sizeof(uint32_t))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the policy noise of slot %d", slot);
+    rc = setter_upload(c, {{p.pn_act.get(), nullptr, act_bytes, 0}, {p.pn_logp.get(), nullptr, Bm * sizeof(double), 0},
+                           {p.pn_draws.get(), nullptr, Bm * sizeof(uint32_t), 0}, {p.pn_draws.get(), draw0, draw0 ? B * sizeof(uint32_t) : 0, 0}});
+    if (!rc) p.samples(*d, logp_const);
+    return rc;
+}
+
+extern "C" int irlosc_download_policy_noise_state(irlosc_ctx* c, int32_t slot, int32_t B, float* act, double* logp, uint32_t* draws, double* logp_const) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (!rc) rc = check_program(c, slot, B, Program::POLICY);
+    if (rc) return rc;
+    const Program& p = c->slot[slot].prog;
+    if (!p.noise) return fail(c, IRLOSC_ERR_STATE, "slot %d: its policy has no Gaussian head (irlosc_set_policy_noise)", slot);
+    if (logp_const) *logp_const = p.pn_const;
+    if (B == 0) return IRLOSC_OK;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, no = (size_t)p.po.n_out;      // rows [max_batch] on the device -> [B][n_out], [B], [B]
+    if (draws) HIPCHK(c, hipMemcpyAsync(draws, p.pn_draws.get(), (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (logp) HIPCHK(c, hipMemcpyAsync(logp, p.pn_logp.get(), (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return download_state(c, B, nullptr, 0, {}, act ? (const int32_t*)p.pn_act.get() : nullptr, act ? no * Bm : 0,      // (act: float words moved as int32 words; synchronises)
+                          {{(int32_t*)act, (const int32_t*)p.pn_act.get(), no, no, 0, 1}});
 }
 
 extern "C" int irlosc_download_targets(irlosc_ctx* c, int32_t slot, int32_t B, void* tgt_pose) {

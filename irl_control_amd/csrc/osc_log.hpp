@@ -7,7 +7,8 @@
 //       plant has not advanced yet: what the tick's walk read), EE_POSE (the walk's poses in the tick's exchange block), TARGETS and WRENCH
 //       (as the OSC step read them: a list's or a stream's targets of the tick are in, the cycler's move is not), U (the give-up pass has
 //       run: every robot has its torques), FLAGS (the step's word; what the plant adds behind it is not in), OBJECT_POSE (the action
-//       objects as this tick's object kernel left them: seven pose words and the holder as a double, per object).
+//       objects as this tick's object kernel left them: seven pose words and the holder as a double, per object), POLICY_OUT and
+//       POLICY_SAMPLE (the out, act and logp planes of the policy's per-robot state as this tick's policy kernel left them).
 //   BACK, behind the joint rows and directly in front of the plant: WALL_FORCE and JOINT_TAU, the `force` and `tau` planes of the walls'
 //       and rows' per-robot state as this tick's APPLY launches left them.  Launched only where one of the two is asked for.
 //
@@ -33,14 +34,15 @@
 
 namespace irlosc {
 
-constexpr int LOG_CHANNELS = 10;
+constexpr int LOG_CHANNELS = 12;
 constexpr uint32_t LOG_FRONT = IRLOSC_LOG_QPOS | IRLOSC_LOG_QVEL | IRLOSC_LOG_EE_POSE | IRLOSC_LOG_TARGETS | IRLOSC_LOG_WRENCH |
-                               IRLOSC_LOG_U | IRLOSC_LOG_FLAGS | IRLOSC_LOG_OBJECT_POSE;
+                               IRLOSC_LOG_U | IRLOSC_LOG_FLAGS | IRLOSC_LOG_OBJECT_POSE | IRLOSC_LOG_POLICY_OUT | IRLOSC_LOG_POLICY_SAMPLE;
 constexpr uint32_t LOG_BACK = IRLOSC_LOG_WALL_FORCE | IRLOSC_LOG_JOINT_TAU;
 
-// Words per robot of channel bit i (nobj: the action objects of the slot; 0: it has none, and no OBJECT_POSE channel)
-__host__ __device__ inline int log_width(int i, int n, int ndev, int nobj = 0) {
-    return i == 9 ? nobj * 8 : i == 0 || i == 1 || i == 5 || i == 8 ? n : i == 2 || i == 3 ? ndev * 7 : i == 4 ? ndev * 6 : i == 6 ? 1 : ndev * 3;
+// Words per robot of channel bit i (nobj: the action objects of the slot; 0: it has none, and no OBJECT_POSE channel; n_out: the outputs
+// of its policy; 0: it has none, and neither POLICY channel)
+__host__ __device__ inline int log_width(int i, int n, int ndev, int nobj = 0, int n_out = 0) {
+    return i == 10 ? n_out : i == 11 ? n_out + 1 : i == 9 ? nobj * 8 : i == 0 || i == 1 || i == 5 || i == 8 ? n : i == 2 || i == 3 ? ndev * 7 : i == 4 ? ndev * 6 : i == 6 ? 1 : ndev * 3;
 }
 
 struct LogArgs {
@@ -58,8 +60,11 @@ struct LogArgs {
     const double* joint_tau;          // [n][stride]
     const double* obj_pose;           // [IRLOSC_MAX_OBJECTS 7][stride] the action objects' poses (osc_object.hpp) ...
     const int32_t* obj_holder;        // [IRLOSC_MAX_OBJECTS][stride] ... and their holders
+    const float* po_out;              // [n_out][stride] the policy's output (with a Gaussian head: the mean) ...
+    const float* po_act;              // [n_out][stride] ... the sampled action ...
+    const double* po_logp;            // [stride] ... and its log-probability (osc_policy.hpp: PolicyState)
     uint32_t mask;                    // the channels of THIS launch
-    int32_t R, n, ndev, n_entries, stride, nobj;
+    int32_t R, n, ndev, n_entries, stride, nobj, n_out;
     int32_t ee0[IRLOSC_MAX_DEV];      // exchange entry of each device's EE pose (x y z qw qx qy qz follow each other)
 };
 
@@ -139,6 +144,23 @@ __global__ __launch_bounds__(64) void osc_log_kernel(const LogArgs a) {
                 s_t[lane * w + o * 8 + 7] = (double)a.obj_holder[(size_t)o * a.stride + rb];
             }
         store_tile(9, w);
+    }
+    if (a.mask & IRLOSC_LOG_POLICY_OUT) {
+        const int w = a.n_out;
+        if (valid) {
+#pragma unroll 8
+            for (int j = 0; j < w; ++j) s_t[lane * w + j] = (double)a.po_out[(size_t)j * a.stride + rb];
+        }
+        store_tile(10, w);
+    }
+    if (a.mask & IRLOSC_LOG_POLICY_SAMPLE) {
+        const int w = a.n_out + 1;
+        if (valid) {
+#pragma unroll 8
+            for (int j = 0; j < a.n_out; ++j) s_t[lane * w + j] = (double)a.po_act[(size_t)j * a.stride + rb];
+            s_t[lane * w + a.n_out] = a.po_logp[rb];
+        }
+        store_tile(11, w);
     }
 }
 

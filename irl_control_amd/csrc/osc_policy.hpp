@@ -22,12 +22,24 @@
 // A robot whose observation or output holds a non-finite word is skipped in FOLLOW (pose, targets, out, grip stay) and gets
 // IRLOSC_FLAG_NONFINITE in flags_any: a robot is a COLUMN of every product, so its words never meet another robot's.
 // Cost per wave: sum over layers of 4 ceil(out / 16) ceil(in / 4) MFMAs at 32 cycles: the floor profiles/policy_rates.md measures against.
+//
+// The GAUSSIAN HEAD (irlosc_set_policy_noise; the NOISE = true form of the kernel, which only a slot with a head launches): the network's
+// output is the MEAN, the action that steers the plate is act[c] = mean[c] + std[c] eps[c], and the robot's log-probability of it is kept.
+//   DRAW     in front of LAYERS, all four waves, lane = robot: eps[c] = z[c & 3] of Philox block (robot, draws, c >> 2, stream 1)
+//            (osc_rng.hpp: normal4), so two blocks of two Box-Muller pairs cover 6 or 7 outputs -- four equal pieces, one per wave: wave wv
+//            computes block wv >> 1 and of it the pair wv & 1, and leaves its two normals in the eps region [8][64] (double) of LDS behind
+//            the activation buffers.  The draw reads nothing of the network, so its fp64 VALU work is issued where the MFMA pipe is about to
+//            be busy; the barriers of LAYERS stand between its stores and FOLLOW's loads.
+//   FOLLOW   act, logp = -s / 2 - C with s the sum of eps[c]^2 over the noisy outputs (include/irlosc.h: the arithmetic), the verdict on
+//            observation, mean AND act, and everything behind the network on act where the plain form has out.  draws[robot] advances by
+//            one on every tick that runs the robot, finite or not.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/irlosc.h"
 #include "osc_common.hpp"
+#include "osc_rng.hpp"
 #include "osc_teleop.hpp"
 
 namespace irlosc {
@@ -45,11 +57,18 @@ struct PolicyNet {
     int32_t rows[2];               // rows of the two LDS buffers: layer l reads buffer l & 1 and writes the other
 };
 
-struct PolicyState { float* out; double* grip; };      // the policy's per-robot state besides the plate (PlateState): [n_out][stride], [stride]
-// One robot's fresh outputs (so: its column): what the fills of irlosc_set_policy leave, written by a reset of episodes
+// The policy's per-robot state besides the plate (PlateState): out [n_out][stride], grip [stride]; with a Gaussian head (act != nullptr)
+// act [n_out][stride], logp [stride] and draws [stride], the ticks that ran the robot since the head's setter (plus its draw0; mod 2^32)
+struct PolicyState { float* out; double* grip; float* act; double* logp; uint32_t* draws; };
+// One robot's fresh outputs (so: its column): what the fills of irlosc_set_policy and irlosc_set_policy_noise leave, written by a reset of
+// episodes.  draws stays: it counts on across resets, so that every episode explores afresh.
 __device__ __forceinline__ void policy_fresh(PolicyState st, int n_out, int stride, size_t so) {
     for (int c = 0; c < n_out; ++c) st.out[(size_t)c * stride + so] = 0.0f;
     st.grip[so] = 0.0;
+    if (st.act) {
+        for (int c = 0; c < n_out; ++c) st.act[(size_t)c * stride + so] = 0.0f;
+        st.logp[so] = 0.0;
+    }
 }
 
 struct PolicyArgs {
@@ -68,19 +87,25 @@ struct PolicyArgs {
     uint32_t obs_mask;
     int32_t n, n_entries, nobj;
     int32_t ee0[IRLOSC_MAX_DEV];   // exchange entry of each device's EE pose
+    // the Gaussian head (read by the NOISE form alone): the key, std[c] (0: output c is deterministic) and C of logp = -s / 2 - C
+    uint64_t seed;
+    double logp_const;
+    float std[8];
 };
 
 typedef float policy_f32x4 __attribute__((ext_vector_type(4)));
 
-// LDS of a launch: the target tile and the block's verdict word (a 16-byte multiple), then the two activation buffers
+constexpr size_t POLICY_EPS_BYTES = 8 * 64 * sizeof(double);      // the head's eps region [8][64]: 4 KB behind the activation buffers
+
+// LDS of a launch: the target tile and the block's verdict word (a 16-byte multiple), then the two activation buffers, then (a head) the eps region
 template <typename T>
 __host__ __device__ inline size_t policy_tile_bytes(int ndev) { return (((size_t)64 * ndev * 7 * sizeof(T) + 15) & ~(size_t)15) + 16; }
 template <typename T>
-inline size_t policy_lds_bytes(const PolicyNet& n, int ndev) {
-    return policy_tile_bytes<T>(ndev) + (size_t)(n.rows[0] + n.rows[1]) * POLICY_XS * sizeof(float);
+inline size_t policy_lds_bytes(const PolicyNet& n, int ndev, bool noise = false) {
+    return policy_tile_bytes<T>(ndev) + (size_t)(n.rows[0] + n.rows[1]) * POLICY_XS * sizeof(float) + (noise ? POLICY_EPS_BYTES : 0);
 }
 
-template <typename T>
+template <typename T, bool NOISE>
 __global__ __launch_bounds__(64 * POLICY_WAVES) void osc_policy_kernel(const PolicyArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;      // wv: the wave of the block (uniform over a wave)
@@ -149,6 +174,20 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void osc_policy_kernel(const Pol
         for (int idx = threadIdx.x; idx < nvalid * w; idx += 64 * POLICY_WAVES) o[idx] = xb[0][(idx % w) * POLICY_XS + idx / w];
     }
 
+    // ---- DRAW (a head): wave wv the pair wv & 1 of block wv >> 1, lane = robot; an idle lane draws what the block's first robot draws ----
+    double* s_eps = (double*)(xb[1] + (size_t)a.net.rows[1] * POLICY_XS);      // [8][64] (16-byte aligned: every piece in front is)
+    uint32_t drawn = 0;                             // the robot's count of draws at the start of the tick
+    if constexpr (NOISE) {
+        drawn = a.st.draws[sc];
+        const uint32_t ctr[4] = {(uint32_t)sc, drawn, (uint32_t)(wv >> 1), 1u}, key[2] = {(uint32_t)a.seed, (uint32_t)(a.seed >> 32)};
+        uint32_t w[4];
+        philox4x32_10(ctr, key, w);
+        double zc, zs;
+        normal_pair((wv & 1) ? w[2] : w[0], (wv & 1) ? w[3] : w[1], &zc, &zs);
+        s_eps[(2 * wv) * 64 + lane] = zc;           // (rows 4 (wv >> 1) + 2 (wv & 1) and the next: eps[c] = row c)
+        s_eps[(2 * wv + 1) * 64 + lane] = zs;
+    }
+
     // ---- LAYERS: wave wv the output tiles wv, wv + POLICY_WAVES, ... of every layer ----
     const int lr = lane & 15, lq = lane >> 4;
     for (int l = 0; l < a.net.L; ++l) {
@@ -195,24 +234,43 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void osc_policy_kernel(const Pol
     bool ok = false;
     if (wv == 0) {
         const float* __restrict__ y = xb[a.net.L & 1] + lane;
-        float o[7];
+        float o[7], act[7];                         // the network's output (a head: the mean) and what steers the plate
+        double s = 0.0;
 #pragma unroll
         for (int c = 0; c < 7; ++c) {
             o[c] = c < a.net.n_out ? y[c * POLICY_XS] : 0.0f;
             finite = finite & (fabsf(o[c]) <= 3.402823466e38f);
+            act[c] = o[c];
+            if constexpr (NOISE) {
+                if (c < a.net.n_out && a.std[c] > 0.0f) {      // (uniform; an output with std == 0 keeps the mean's bits)
+                    const double eps = s_eps[c * 64 + lane];
+                    act[c] = (float)__dadd_rn((double)o[c], __dmul_rn((double)a.std[c], eps));      // (beyond float's range: an infinity)
+                    s = __dadd_rn(s, __dmul_rn(eps, eps));
+                    finite = finite & (fabsf(act[c]) <= 3.402823466e38f);
+                }
+            }
         }
         ok = valid && finite;
+        if constexpr (NOISE) {
+            if (valid) a.st.draws[so] = drawn + 1u; // a tick that ran the robot, finite or not (mod 2^32)
+        }
         if (ok) {
             double r[6];
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
-                const float v = o[c];
+                const float v = act[c];
                 r[c] = (double)(a.clip > 0.0f ? (v < -a.clip ? -a.clip : v > a.clip ? a.clip : v) : v);
             }
 #pragma unroll
             for (int c = 0; c < 7; ++c)
                 if (c < a.net.n_out) a.st.out[(size_t)c * stride + so] = o[c];
-            if (a.net.n_out == 7) a.st.grip[so] = o[6] > 0.0f ? a.grip_close : a.grip_open;
+            if constexpr (NOISE) {
+#pragma unroll
+                for (int c = 0; c < 7; ++c)
+                    if (c < a.net.n_out) a.st.act[(size_t)c * stride + so] = act[c];
+                a.st.logp[so] = __dsub_rn(__dmul_rn(-0.5, s), a.logp_const);
+            }
+            if (a.net.n_out == 7) a.st.grip[so] = act[6] > 0.0f ? a.grip_close : a.grip_open;
             teleop_follow(a.t, s_t, lane, so, row, r);
         } else if (valid) a.flags_any[so] |= IRLOSC_FLAG_NONFINITE;
         if (__any(ok) && lane == 0) *s_moved = 1;

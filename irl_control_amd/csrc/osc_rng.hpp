@@ -6,6 +6,7 @@
 //                   Random123 constants; integer arithmetic only.
 //   normal3         Box-Muller on one block w0..w3:  u = (2 w0 + 1) / 2^33 in (0, 1),  r = sqrt(-2 ln u),  phi = 2 pi w1 / 2^32,
 //                   z0 = r cos phi, z1 = r sin phi;  the second pair of words gives z2 = r' cos phi'.  |z| <= sqrt(66 ln 2) = 6.76.
+//   normal4         all four values of a block, z3 = r' sin phi', with the fourth counter word as a stream (action_motion.py: normal4)
 // The device's log and sincos are not correctly rounded and differ from the host's, so both are written out here in add, multiply,
 // divide and square root, every one rounded on its own (__dmul_rn and its relatives: no contraction into an fma) and in the order
 // written:
@@ -91,6 +92,28 @@ __device__ __forceinline__ void normal3(uint64_t seed, uint32_t robot, uint32_t 
     const double r1 = __dsqrt_rn(__dmul_rn(-2.0, ln_rn(u1)));
     sincos_turn_rn(w[3], &s, &c);
     z[2] = __dmul_rn(r1, c);
+}
+
+// One Box-Muller pair on the words (wa, wb) of a block: *zc = r cos phi, *zs = r sin phi -- normal3's steps, both values kept
+__device__ __forceinline__ void normal_pair(uint32_t wa, uint32_t wb, double* zc, double* zs) {
+    constexpr double INV33 = 1.0 / 8589934592.0;                // 2^-33
+    double s, c;
+    const double u = __dmul_rn(__dadd_rn(__dmul_rn(2.0, (double)wa), 1.0), INV33);
+    const double r = __dsqrt_rn(__dmul_rn(-2.0, ln_rn(u)));
+    sincos_turn_rn(wb, &s, &c);
+    *zc = __dmul_rn(r, c);
+    *zs = __dmul_rn(r, s);
+}
+
+// Four standard normals of block (robot, draw, block, stream) under key `seed`: both word pairs of the block, z0 = r0 cos, z1 = r0 sin,
+// z2 = r1 cos, z3 = r1 sin.  The fourth counter word names a STREAM: normal3 is stream 0 (its three values are z0, z1, z2 of this block),
+// the policy's Gaussian head draws on stream 1 (osc_policy.hpp), so the two never meet under one seed.
+__device__ __forceinline__ void normal4(uint64_t seed, uint32_t robot, uint32_t draw, uint32_t block, uint32_t stream, double z[4]) {
+    const uint32_t ctr[4] = {robot, draw, block, stream}, key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t w[4];
+    philox4x32_10(ctr, key, w);
+    normal_pair(w[0], w[1], &z[0], &z[1]);
+    normal_pair(w[2], w[3], &z[2], &z[3]);
 }
 
 }  // namespace irlosc

@@ -99,13 +99,61 @@ def observe(mask, channels, plate=None):
     return np.concatenate(parts, axis=1)
 
 
-def policy_tick(pose, obs, layers, rig, inc=teleop.INCREMENT, clip=0.0, grip=None):
+_LN_2PI = 1.8378770664093453
+
+
+def logp_const(std):
+    """C of logp = -s / 2 - C for standard deviations std [n_out] (float32): the sum of ln std[c] over the noisy outputs (std[c] > 0),
+    c ascending, plus (m / 2) ln 2 pi, m their number -- what irlosc_set_policy_noise computes once (to a few ulp: two libm logs)."""
+    sd = np.asarray(std, dtype=F32).astype(np.float64).reshape(-1)
+    c, m = 0.0, 0
+    for v in sd:
+        if v > 0.0:
+            c, m = c + float(np.log(v)), m + 1
+    return c + (0.5 * m) * _LN_2PI
+
+
+def sample(out, std, seed, robot, draw, logp_const):
+    """The Gaussian head of a policy (include/irlosc.h, "a stochastic policy head"; the NOISE form of csrc/osc_policy.hpp), bit for bit:
+    means out [..., n_out] (float32), std [n_out] (float32; 0: that output is deterministic), robot and draw [...] (uint32: the robot's
+    index and its count of draws at the start of the tick), logp_const: C (logp_const(std), or the library's) ->
+    (act [..., n_out] float32, logp [...] float64, eps [..., n_out] float64).  eps[c] = z[c & 3] of action_motion.normal4(seed, robot,
+    draw, c >> 2, stream 1); act[c] = float32(float64(out[c]) + float64(std[c]) * eps[c]) where std[c] > 0, else out[c] itself; logp =
+    (-0.5 * s) - C with s the sum of eps[c]^2 over the noisy outputs, c ascending.  eps of a deterministic output is returned as drawn."""
+    from .action_motion import normal4
+    out = np.asarray(out, dtype=F32)
+    sd = np.asarray(std, dtype=F32).reshape(-1)
+    n_out = out.shape[-1]
+    if len(sd) < n_out:
+        raise ValueError(f"std: expected {n_out} entries, got {len(sd)}")
+    robot, draw = np.broadcast_arrays(np.asarray(robot, dtype=np.uint32), np.asarray(draw, dtype=np.uint32))
+    robot, draw = np.broadcast_to(robot, out.shape[:-1]), np.broadcast_to(draw, out.shape[:-1])
+    z = np.concatenate([normal4(seed, robot, draw, blk, 1) for blk in range((n_out + 3) // 4)], axis=-1)      # [..., 4 blocks]
+    eps = z[..., :n_out]
+    act = out.copy()
+    s = np.zeros(out.shape[:-1])
+    with np.errstate(over="ignore"):
+        for c in range(n_out):
+            if sd[c] > 0:
+                act[..., c] = (out[..., c].astype(np.float64) + np.float64(sd[c]) * eps[..., c]).astype(F32)
+                s = s + eps[..., c] * eps[..., c]
+    return act, (-0.5 * s) - np.float64(logp_const), eps
+
+
+def policy_tick(pose, obs, layers, rig, inc=teleop.INCREMENT, clip=0.0, grip=None, noise=None):
     """One tick of one robot: pose [6] and its observation [n_in] -> (new pose [6], targets [ndev, 7] with NaN where the tick writes
-    nothing, out [n_out] float32, grip force or None).  `grip`: (close, open) of a network with a seventh output."""
+    nothing, out [n_out] float32, grip force or None).  `grip`: (close, open) of a network with a seventh output.
+    `noise`: dict(std, seed, robot, draw, logp_const) of a Gaussian head (sample's arguments): the tick then steers and grips by the
+    sampled action, and -> (new pose, targets, out, grip, act [n_out] float32, logp)."""
     out = mlp(np.asarray(obs, dtype=F32)[None], layers)[0]
-    new, tgt = teleop.stream_step(pose, clamp(out, clip), rig, inc)
-    g = None if grip is None or len(out) < 7 else float(grip[0] if out[6] > 0 else grip[1])
-    return new, tgt, out, g
+    if noise is None:
+        new, tgt = teleop.stream_step(pose, clamp(out, clip), rig, inc)
+        g = None if grip is None or len(out) < 7 else float(grip[0] if out[6] > 0 else grip[1])
+        return new, tgt, out, g
+    act, logp, _ = sample(out, noise["std"], noise["seed"], noise["robot"], noise["draw"], noise["logp_const"])
+    new, tgt = teleop.stream_step(pose, clamp(act, clip), rig, inc)
+    g = None if grip is None or len(out) < 7 else float(grip[0] if act[6] > 0 else grip[1])
+    return new, tgt, out, g, act, float(logp)
 
 
 def weights(layers):

@@ -10,11 +10,24 @@ ALL = (1 << len(CHANNELS)) - 1
 # and the holder as a double.  It is no part of CHANNELS / ALL: those are the channels every slot can log.
 OBJECT_POSE = "object_pose"
 OBJECT_POSE_BIT = 1 << len(CHANNELS)
+# ... and bits 10 and 11, IRLOSC_LOG_POLICY_OUT and IRLOSC_LOG_POLICY_SAMPLE, which only a slot with a policy (n_out > 0 below) and one
+# whose policy has a Gaussian head (sampled) know: [R, n_out] the network's output (the mean), [R, n_out + 1] the sampled action, then logp.
+POLICY_OUT, POLICY_SAMPLE = "policy_out", "policy_sample"
+POLICY_OUT_BIT, POLICY_SAMPLE_BIT = 1 << 10, 1 << 11
+_EXTRA = (OBJECT_POSE, POLICY_OUT, POLICY_SAMPLE)      # bits 9, 10, 11
 MAX_N, MAX_DEV, MAX_OBJECTS = 32, 4, 4
 
 
-def _channels(nobj: int) -> tuple:
+def _channels(nobj: int, n_out: int = 0) -> tuple:
+    """The channel names by bit, up to the last one a slot with nobj action objects and a policy of n_out outputs can have."""
+    if n_out:
+        return CHANNELS + (OBJECT_POSE, POLICY_OUT, POLICY_SAMPLE)
     return CHANNELS + (OBJECT_POSE,) if nobj else CHANNELS
+
+
+def known(nobj: int = 0, n_out: int = 0, sampled: bool = False) -> int:
+    """The OR of the bits a slot with nobj action objects, a policy of n_out outputs (0: none) and, `sampled`, a Gaussian head knows."""
+    return ALL | (OBJECT_POSE_BIT if nobj else 0) | (POLICY_OUT_BIT if n_out else 0) | (POLICY_SAMPLE_BIT if n_out and sampled else 0)
 
 
 def mask(channels) -> int:
@@ -25,11 +38,11 @@ def mask(channels) -> int:
         channels = [channels]
     m = 0
     for name in channels:
-        if name == OBJECT_POSE:
-            m |= OBJECT_POSE_BIT
+        if name in _EXTRA:
+            m |= OBJECT_POSE_BIT << _EXTRA.index(name)
             continue
         if name not in BITS:
-            raise ValueError(f"unknown log channel {name!r}: one of {CHANNELS + (OBJECT_POSE,)}")
+            raise ValueError(f"unknown log channel {name!r}: one of {CHANNELS + _EXTRA}")
         m |= BITS[name]
     return m
 
@@ -37,26 +50,31 @@ def mask(channels) -> int:
 def names(channels) -> tuple:
     """The names of the channels of a mask, in bit order."""
     m = mask(channels)
-    return tuple(name for i, name in enumerate(CHANNELS + (OBJECT_POSE,)) if (m >> i) & 1)
+    return tuple(name for i, name in enumerate(CHANNELS + _EXTRA) if (m >> i) & 1)
 
 
-def shape(name: str, n: int, ndev: int, nobj: int = 0) -> tuple:
+def shape(name: str, n: int, ndev: int, nobj: int = 0, n_out: int = 0) -> tuple:
     """The per-robot shape of a channel: its plane is [R, *shape]."""
     if name == OBJECT_POSE:
         return (nobj, 8)
+    if name in (POLICY_OUT, POLICY_SAMPLE):
+        return (n_out + (name == POLICY_SAMPLE),)
     return {"qpos": (n,), "qvel": (n,), "ee_pose": (ndev, 7), "targets": (ndev, 7), "wrench": (ndev, 6), "u": (n,), "flags": (),
             "wall_force": (ndev, 3), "joint_tau": (n,)}[name]
 
 
-def layout(n: int, ndev: int, channels, R: int, nobj: int = 0):
+def layout(n: int, ndev: int, channels, R: int, nobj: int = 0, n_out: int = 0, sampled: bool = False):
     """-> (offset[9] int64, sample_words) as irlosc_log_layout gives them: where each channel's plane [R][w] starts inside a sample, in
     doubles (-1: not asked for), and the sample's size.  With nobj > 0 (a slot with action objects): offset[10] as
-    irlosc_log_layout_objects gives them, the tenth OBJECT_POSE's.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
+    irlosc_log_layout_objects gives them, the tenth OBJECT_POSE's.  With n_out > 0 (a slot with a policy; `sampled`: with a Gaussian
+    head): offset[12] as irlosc_log_layout_policy gives them.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
     m = mask(channels)
     if not 0 <= nobj <= MAX_OBJECTS:
         raise ValueError(f"nobj={nobj} out of range")
-    chans = _channels(nobj)
-    if m == 0 or m & ~((1 << len(chans)) - 1):
+    if n_out not in (0, 6, 7):
+        raise ValueError(f"n_out={n_out} must be 0, 6 or 7")
+    chans = _channels(nobj, n_out)
+    if m == 0 or m & ~known(nobj, n_out, sampled):
         raise ValueError(f"channels=0x{m:x} must be a non-empty OR of the IRLOSC_LOG_* bits")
     if R < 1 or not 1 <= n <= MAX_N or not 1 <= ndev <= MAX_DEV:
         raise ValueError(f"R={R}, n={n}, ndev={ndev} out of range")
@@ -65,26 +83,29 @@ def layout(n: int, ndev: int, channels, R: int, nobj: int = 0):
     for i, name in enumerate(chans):
         if (m >> i) & 1:
             off[i] = words
-            words += R * int(np.prod(shape(name, n, ndev, nobj), dtype=np.int64))
+            words += R * int(np.prod(shape(name, n, ndev, nobj, n_out), dtype=np.int64))
     return off, words
 
 
-def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64, nobj: int = 0) -> dict:
+def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64, nobj: int = 0, n_out: int = 0, sampled: bool = False) -> dict:
     """The raw log buffer [S, sample_words] (float64) as named arrays [S, R, ...].  u, targets and wrench come back in `dtype` (the
-    context's: the cast undoes the exact widening), flags as uint32, everything else float64."""
-    off, words = layout(n, ndev, channels, R, nobj)
+    context's: the cast undoes the exact widening), flags as uint32, policy_out as float32, everything else float64 (policy_sample: the
+    float32 action widened -- .astype(float32) undoes it -- and logp in its last column)."""
+    off, words = layout(n, ndev, channels, R, nobj, n_out, sampled)
     buf = np.asarray(buf, dtype=np.float64).reshape(-1, words)
     out = {}
-    for i, name in enumerate(_channels(nobj)):
+    for i, name in enumerate(_channels(nobj, n_out)):
         if off[i] < 0:
             continue
-        shp = shape(name, n, ndev, nobj)
+        shp = shape(name, n, ndev, nobj, n_out)
         w = int(np.prod(shp, dtype=np.int64))
         a = buf[:, off[i]:off[i] + R * w].reshape((buf.shape[0], R) + shp)
         if name in ("u", "targets", "wrench"):
             a = a.astype(dtype)
         elif name == "flags":
             a = a.astype(np.uint32)
+        elif name == POLICY_OUT:
+            a = a.astype(np.float32)
         else:
             a = a.copy()
         out[name] = a

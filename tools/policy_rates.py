@@ -5,7 +5,13 @@
     stream         the same fleet on this build: THE ONE CONDITION is that it agrees with `parent_stream` -- a slot without a policy pays nothing
     policy_small   this build, the same fleet under a policy on PLATE alone, 6 -> 64 -> 64 -> 6
     policy_big     this build, a policy on every channel the fleet has (qpos qvel ee_pose targets wrench plate = 116 on k13) -> 128 -> 128 -> 7
+    parent_policy_small, parent_policy_big   with --parent-tree: the two policy fleets on the parent's package and library
+    policy_small_noise, policy_big_noise     this build, the two policy fleets with a Gaussian head (set_policy_noise, every std 0.1): the
+                   NOISE form of the kernel.  Reported as the leg's median minus the median of the same fleet without a head, next to
+                   THE HEAD'S FLOOR: the --head-valu VALU instructions one draw piece adds to a wave (counted from the kernel's listing: the
+                   NOISE = true form minus the NOISE = false form) at 4 cycles each, the fleet's blocks over the chip's SIMDs
     bench_parent, bench   the benchmark's headline (bench.py --gpus 1) in the parent tree and in this one
+--legs a,b,... picks the legs (default: parent_stream, stream, policy_small, policy_big -- the legs of profiles/policy_rates.md).
 Every leg is a child process of its own (a process loads one library), and the legs are INTERLEAVED --rounds times, so that a drift of
 the machine shows up as spread inside every leg, not as a difference between legs.  The policy legs are set against the ARITHMETIC FLOOR
 of their network: sum over layers of 4 ceil(out / 16) ceil(in / 4) instructions v_mfma_f32_16x16x4_f32 per 64 robots at 32 cycles each per
@@ -58,19 +64,26 @@ def fleet(a):
     return osc, lay, np.array(teleop.ORIGIN)
 
 
+def parts(leg):
+    """leg -> (the fleet: "stream" or a name of NETS, on the parent's build, with a Gaussian head)"""
+    parent, noise = leg.startswith("parent_"), leg.endswith("_noise")
+    return leg[len("parent_") if parent else 0:len(leg) - (len("_noise") if noise else 0)], parent, noise
+
+
 def child(a):
     """One leg in this process: -> a JSON line."""
-    if a.leg == "parent_stream":      # the parent's package and library, imported ahead of the examples (which then find it loaded)
+    net, parent, noise = parts(a.leg)
+    if parent:      # the parent's package and library, imported ahead of the examples (which then find it loaded)
         sys.path.insert(0, os.path.abspath(a.parent_tree))
     import irl_control_amd
     from irl_control_amd import _lib, teleop
-    assert (a.leg == "parent_stream") == (os.path.abspath(a.parent_tree or "/nowhere") in os.path.abspath(irl_control_amd.__file__)), irl_control_amd.__file__
+    assert parent == (os.path.abspath(a.parent_tree or "/nowhere") in os.path.abspath(irl_control_amd.__file__)), irl_control_amd.__file__
     import teleop_loops as tl
     osc, lay, origin = fleet(a)
     B, n = a.batch, lay.n
-    if a.leg in NETS:
+    if net in NETS:
         from irl_control_amd import policy
-        obs, hidden, n_out = NETS[a.leg]
+        obs, hidden, n_out = NETS[net]
         n_in = policy.obs_width(policy.obs_mask(obs), n, lay.ndev)
         rng = np.random.default_rng(1)
         dims = (n_in,) + hidden + (n_out,)
@@ -80,6 +93,8 @@ def child(a):
             osc.set_ft_sensors()
             osc.set_sensordata(np.zeros((B, 18)))
         osc.set_policy(layers, obs, origin, clip=60.0, grip_dev=0, grip_close=0.08, grip_open=-0.08)
+        if noise:
+            osc.set_policy_noise(np.full(n_out, 0.1, np.float32), seed=7)
     else:
         osc.set_teleop_stream(teleop.record_readings(tl.space_mouse_stream(5, 256), 256), origin, loop=True)
     u, fl_any = np.empty((B, n)), np.empty(B, np.uint32)
@@ -115,13 +130,17 @@ def main():
     ap.add_argument("--bench-steps", type=int, default=200, help="0: no benchmark legs")
     ap.add_argument("--clock-ghz", type=float, default=2.4)
     ap.add_argument("--md", default=None)
+    ap.add_argument("--legs", default=None, help="comma-separated legs (default: the stream and policy legs)")
+    ap.add_argument("--head-valu", type=int, default=0, help="VALU instructions the head adds to a wave (from the listing): the head's floor")
     ap.add_argument("--leg", default=None, help="(internal) run this one leg")
     a = ap.parse_args()
     if a.leg:
         return child(a)
     regs = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_regs.py"), "policy"], capture_output=True, text=True).stdout.strip()
     print(regs, flush=True)
-    legs = (["parent_stream"] if a.parent_tree else []) + ["stream", "policy_small", "policy_big"]
+    legs = a.legs.split(",") if a.legs else (["parent_stream"] if a.parent_tree else []) + ["stream", "policy_small", "policy_big"]
+    if any(parts(leg)[1] for leg in legs) and not a.parent_tree:
+        raise SystemExit("a parent_* leg needs --parent-tree")
     res = {k: [] for k in legs}
     rows, heads = [], {}
     for r in range(a.rounds):
@@ -143,21 +162,27 @@ def main():
                 heads.setdefault(name, []).append(o)
                 rows.append(f"round {r} {name:14s} " + json.dumps(o))
                 print(rows[-1], flush=True)
-    names = dict(parent_stream="parent commit, stream fleet", stream="this build, stream fleet", policy_small="this build, policy PLATE 6 -> 64 -> 64 -> 6",
-                 policy_big="this build, policy every channel 116 -> 128 -> 128 -> 7")
+    fleets = dict(stream="stream fleet", policy_small="policy PLATE 6 -> 64 -> 64 -> 6", policy_big="policy every channel 116 -> 128 -> 128 -> 7")
     lines = [f"| leg ({a.batch} robots, {a.ticks} ticks per call, {a.rounds} rounds x {a.reps} calls, interleaved) | best ms/tick | ticks/s at best | median | "
-             "spread (max - min) | over the stream fleet (medians) | MFMA floor ms | cost / floor |", "|---|---|---|---|---|---|---|---|"]
-    base = np.median(res["stream"])
+             "spread (max - min) | over the stream fleet / a head: over the same fleet without one (medians) | floor ms (MFMA / a head: its VALU) | cost / floor |",
+             "|---|---|---|---|---|---|---|---|"]
     for leg in legs:
         t = np.array(res[leg])
+        net, parent, noise = parts(leg)
         cost = floor = ratio = ""
-        if leg in NETS:
+        if noise and net in res:      # the head: over the same fleet without one, against the draw's own floor
+            over = np.median(t) - np.median(res[net])
+            fm = -(-(-(-a.batch // 64)) // SIMDS) * a.head_valu * 4 / (a.clock_ghz * 1e9) * 1e3
+            cost, floor, ratio = f"{over:+.4f}", f"{fm:.4f}" if fm else "", f"{over / fm:.1f}" if fm else ""
+        elif net in NETS and not parent and "stream" in res:
             from irl_control_amd import policy, synth
             lay = synth.make_layout("k13")
-            obs, hidden, n_out = NETS[leg]
+            obs, hidden, n_out = NETS[net]
+            base = np.median(res["stream"])
             fm = floor_ms(floor_instructions(policy.obs_width(policy.obs_mask(obs), lay.n, lay.ndev), hidden, n_out), a.batch, a.clock_ghz)
             cost, floor, ratio = f"{np.median(t) - base:+.4f}", f"{fm:.4f}", f"{(np.median(t) - base) / fm:.1f}"
-        lines.append(f"| {names[leg]} | {t.min():.4f} | {1e3 / t.min():.0f} | {np.median(t):.4f} | {t.max() - t.min():.4f} | {cost} | {floor} | {ratio} |")
+        name = ("parent commit, " if parent else "this build, ") + fleets[net] + (" + Gaussian head" if noise else "")
+        lines.append(f"| {name} | {t.min():.4f} | {1e3 / t.min():.0f} | {np.median(t):.4f} | {t.max() - t.min():.4f} | {cost} | {floor} | {ratio} |")
     print("\n".join(lines))
     if a.md:
         with open(a.md, "a") as f:
