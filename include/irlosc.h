@@ -553,7 +553,19 @@ IRLOSC_API int irlosc_download_q(irlosc_ctx* ctx, int32_t slot, int32_t B, doubl
  *     irlosc_set_policy_noise that answers IRLOSC_ERR_HIP                              no head, the policy stays
  *     whatever ends or replaces the slot's policy (irlosc_set_policy included)         the head ends
  *     everything else                                                                  leaves it and its state alone; a reset of episodes
- *                                                                                      zeroes a robot's act and logp and keeps its draws */
+ *                                                                                      zeroes a robot's act and logp and keeps its draws
+ * A REWARD (irlosc_set_reward, "a reward per tick" below) writes no targets and acts on nothing: it READS other parts -- the targets, a
+ * policy's action, the objects and their mates, the feed's wrench -- by name, and none of their setters looks at it.
+ *     irlosc_set_reward with desc == NULL, irlosc_set_model (all slots)                the reward ends
+ *     irlosc_set_reward that answers IRLOSC_ERR_ARG or IRLOSC_ERR_STATE                nothing changes: the reward in force stays, whole
+ *     irlosc_set_reward that succeeds                                                  its reward replaces the one in force; its state reset
+ *     irlosc_set_reward that answers IRLOSC_ERR_HIP                                    no reward
+ *     a part the reward names ends or shrinks (objects, a policy, the feed, targets)   the reward STAYS, and the next rollout call is
+ *                                                                                      refused (IRLOSC_ERR_STATE, with the reason) until the
+ *                                                                                      part is back or the reward is set again or ended
+ *     everything else                                                                  leaves it and its state alone; a reset of episodes
+ *                                                                                      makes a robot's reward state fresh
+ * Only the two rollout entry points run it.  Order of use: the parts, then the reward, then (optionally) the episodes. */
 
 /* ---- waypoint paths on the GPU: the rollout's targets cycle like gain_test's (csrc/osc_waypoint.hpp) ----------------------
  * What examples/headless_loops.py::gain_test_loop does on the host per tick, as one more small kernel of a rollout tick, between
@@ -881,6 +893,98 @@ IRLOSC_API int irlosc_set_policy_noise(irlosc_ctx* ctx, int32_t slot, const irlo
 IRLOSC_API int irlosc_download_policy_noise_state(irlosc_ctx* ctx, int32_t slot, int32_t B, float* act, double* logp, uint32_t* draws,
                                                   double* logp_const);
 
+/* ---- a reward per tick on the device, and a goal that ends an episode (csrc/osc_reward.hpp) ------------------------------------------
+ * What a learner reads next to (observation, action, logp): per tick and robot a REWARD, stated by the caller as a short list of weighted
+ * terms, evaluated by one more small kernel of the tick, accumulated per episode -- plain and discounted -- and, with a GOAL, the
+ * success signal that ends an episode before its timeout (irlosc_set_episodes: end_on_finish).  The kernel runs behind the give-up pass
+ * (u is complete) and directly in front of the log's FRONT launch, so in front of the waypoint cycler and the plant:
+ *     r_t = R(the state tick t observed, the action tick t took);   what that action does shows in r_{t+1}.
+ * It only reads the tick's state and writes its own.  A slot without a reward enqueues exactly the launches it enqueued before.
+ * POINTS -- where a term reads a position and, for ORI, a quaternion (w x y z):
+ *     EE d       words ee0[d] .. + 6 of the tick's exchange block: the pose IRLOSC_LOG_EE_POSE logs for device d
+ *     TARGET d   the slot's target row of device d as the tick's OSC step read it, widened exactly
+ *     OBJECT o   the pose planes of action object o as this tick's object kernel left them
+ *     FIXED p    row p of `points`; it has no orientation
+ * TERMS -- each yields a double v; float64 whatever the context's dtype, EVERY operation rounded on its own, in the order written, no
+ * fma: irl_control_amd/reward.py::reward_tick repeats every bit.
+ *     DIST_SQ(a, b)  dx = a_x - b_x, dy, dz likewise;  s = dx dx;  s = s + dy dy;  s = s + dz dz;  v = s
+ *     DIST(a, b)     v = sqrt(s)
+ *     ORI(a, b)      d = qa_w qb_w;  d = d + qa_x qb_x;  d = d + qa_y qb_y;  d = d + qa_z qb_z;  v = 1 - |d|
+ *     ACT_SQ         s = 0;  for c ascending below n_out:  s = s + (double) act[c] (double) act[c];  v = s      -- act of a Gaussian head,
+ *                    else the policy's out: what this tick's policy kernel left (a robot it skipped repeats its last one)
+ *     U_SQ           s = 0;  for j ascending below n:  s = s + (double) u_j (double) u_j;  v = s      -- the tick's torques behind the give-up pass
+ *     FORCE d        x, y, z = words 0..2 of device d's wrench row as the OSC step read it;  s = x x;  s = s + y y;  s = s + z z;  v = sqrt(s)
+ *     MATED m        v = mated_tick[m] >= 0 ? 1.0 : 0.0
+ *     ONE            v = 1.0
+ * THE TICK, for every robot the call runs (fresh values: r = ret = gret = 0, disc = 1, steps = hold = 0, goal_step = -1):
+ *     r = 0.0;  for i ascending:  r = r + weight_i v_i          (the product rounded, then the sum)
+ *     steps += 1;   ret = ret + r;   gret = gret + disc r;   disc = disc gamma
+ *   with a goal (goal_term >= 0), v the goal term's value of this tick:
+ *     hold = (goal_cmp == 0 ? v <= goal_value : v >= goal_value) ? hold + 1 : 0          (a NaN compares false)
+ *     goal_step = steps, the first time hold >= goal_hold                                 (then it stays until the state is fresh again)
+ * A NON-FINITE REWARD IS STORED AS COMPUTED AND SETS NO FLAG: a robot with a NaN coordinate has a NaN r and ret from then on, never
+ * reaches a goal, and flags_any is what it is without a reward.
+ * EPISODES: with a reward in force that has a goal, and end_on_finish, a robot's episode is also FINISHED on a tick with goal_step >= 0
+ * -- for every program kind, a policy and none included -- and an episode that ends with goal_step >= 0 (finished or timed out) carries
+ * IRLOSC_EPISODE_GOAL in its outcome.  On the ending tick (ret, gret) go into the reward's own ring of IRLOSC_MAX_EPISODE_RECORDS
+ * entries, entry count mod records beside the episode's record, and a reset makes the reward state fresh.  A PARKED robot goes on
+ * accumulating: its records are what count.
+ * NOT OFFERED: exp / tanh shaping (the host cannot repeat them bit for bit: the policy's own rule); per-episode variants of `points`;
+ * a value head. */
+#define IRLOSC_MAX_REWARD_TERMS  8
+#define IRLOSC_MAX_REWARD_POINTS 8
+#define IRLOSC_REWARD_EE      0      /* point kinds */
+#define IRLOSC_REWARD_TARGET  1
+#define IRLOSC_REWARD_OBJECT  2
+#define IRLOSC_REWARD_FIXED   3
+#define IRLOSC_REWARD_DIST_SQ 0      /* term kinds */
+#define IRLOSC_REWARD_DIST    1
+#define IRLOSC_REWARD_ORI     2
+#define IRLOSC_REWARD_ACT_SQ  3
+#define IRLOSC_REWARD_U_SQ    4
+#define IRLOSC_REWARD_FORCE   5
+#define IRLOSC_REWARD_MATED   6
+#define IRLOSC_REWARD_ONE     7
+typedef struct irlosc_reward {
+    int32_t n_terms;                             /* in [1, IRLOSC_MAX_REWARD_TERMS] */
+    int32_t n_points;                            /* P in [0, IRLOSC_MAX_REWARD_POINTS] */
+    int32_t points_per_robot;                    /* 0: one set of P points for the fleet, 1: a set per robot */
+    int32_t goal_term;                           /* -1: no goal; else the term in [0, n_terms) whose value the goal compares */
+    int32_t goal_cmp;                            /* 0: v <= goal_value, 1: v >= goal_value */
+    int32_t goal_hold;                           /* H >= 1: consecutive ticks the comparison has to hold (1 without a goal) */
+    int32_t kind[IRLOSC_MAX_REWARD_TERMS];       /* IRLOSC_REWARD_DIST_SQ .. IRLOSC_REWARD_ONE; entries >= n_terms: 0, as in the arrays below */
+    int32_t a_kind[IRLOSC_MAX_REWARD_TERMS];     /* DIST_SQ, DIST, ORI: point a's kind; every other term: 0 */
+    int32_t a_index[IRLOSC_MAX_REWARD_TERMS];    /* ... and its device, object or row of `points`; FORCE: the device; MATED: the mate; else 0 */
+    int32_t b_kind[IRLOSC_MAX_REWARD_TERMS];     /* DIST_SQ, DIST, ORI: point b; every other term: 0 */
+    int32_t b_index[IRLOSC_MAX_REWARD_TERMS];
+    int32_t reserved[2];                         /* 0 */
+    double  weight[IRLOSC_MAX_REWARD_TERMS];     /* finite */
+    double  gamma;                               /* finite, in [0, 1] */
+    double  goal_value;                          /* finite (0 without a goal) */
+} irlosc_reward;
+/* Gives slot `slot`'s B robots the reward; points: [points_per_robot ? B : 1][P][3] double (NULL with P == 0).  Every argument is checked
+ * before anything is touched; after a refusal the slot is exactly as it was, the reward in force and its state included.
+ *   IRLOSC_ERR_ARG    a field outside its range above; B < 1; a weight, gamma, point or goal_value that is not finite; a kind that does
+ *                     not exist; an index outside the context's devices, IRLOSC_MAX_OBJECTS, IRLOSC_MAX_MATES or the P points; ORI on a FIXED point; a
+ *                     field of a term that does not read it, or of a term >= n_terms, that is not 0; goal_term outside [-1, n_terms);
+ *                     goal_cmp other than 0, 1; goal_hold < 1; points NULL with P > 0; reserved != 0
+ *   IRLOSC_ERR_STATE  a reference to a part the slot does not have for B robots: no model, or a context whose n is not the rollout's;
+ *                     targets for fewer than B robots (asked of every reward: the rollout needs them); OBJECT o with o >= the slot's
+ *                     objects; MATED m with m >= its mates; ACT_SQ without a policy; FORCE d without a sensor feed, or on a device the
+ *                     feed has no force sensor for; episodes in force for more than B robots (their resets write the reward's state)
+ * The two rollout entry points make the SAME state check on every call: a part that was ended under a reward that names it is refused
+ * there with the reason, and the reward stays.  On success the state is fresh (the values above) and the reward's ring is not touched:
+ * the download masks what no episode of the running count has written.  desc == NULL ends the reward; what else ends it: "one writer of the
+ * targets" above.  Buffers are allocated by the first use; IRLOSC_ERR_HIP leaves the slot without a reward.  Synchronous. */
+IRLOSC_API int irlosc_set_reward(irlosc_ctx* ctx, int32_t slot, int32_t B, const irlosc_reward* desc, const double* points);
+/* r, ret, gret: [B] double -- the last tick's reward and the running episode's sums; steps, hold, goal_step: [B] int32; records:
+ * [B][IRLOSC_MAX_EPISODE_RECORDS][2] double, (ret, gret) of ended episodes, entry e of a robot being its episode e' = the largest
+ * e' < count with e' mod records == e, as irlosc_download_episode_state has them -- and ZERO for an entry that no episode ended under this
+ * reward has written (entries >= records or >= count, episodes that ended before the reward was set, a robot the episodes do not cover, a slot without episodes).  Any may be
+ * NULL.  IRLOSC_ERR_STATE on a slot without a reward, or with one for fewer than B robots.  Synchronous. */
+IRLOSC_API int irlosc_download_reward_state(irlosc_ctx* ctx, int32_t slot, int32_t B, double* r, double* ret, double* gret, int32_t* steps,
+                                            int32_t* hold, int32_t* goal_step, double* records);
+
 /* ---- external pushes on the plant, sensed by the F/T feed: admit_test / force_test inside a rollout (csrc/osc_push.hpp) ------------
  * What examples/headless_loops.py::admit_test_loop does on the host -- xfrc_applied on a gripper body during a window of ticks, the
  * F/T sensors reading the reaction after sim.step() (fakesim.ToyDynamics), the next `generate` yielding to it -- as up to two more
@@ -1054,6 +1158,9 @@ IRLOSC_API int irlosc_download_joint_state(irlosc_ctx* ctx, int32_t slot, int32_
 #define IRLOSC_LOG_POLICY_SAMPLE 2048u /* [R][n_out + 1] FRONT: act[0 .. n_out) of this tick, widened, then logp.  Only on a slot whose
                                           policy has a Gaussian head (irlosc_set_policy_noise); elsewhere the bit is unknown.  Both show
                                           what this tick's policy kernel left: a robot it skipped (not finite) repeats its last sample */
+#define IRLOSC_LOG_REWARD      4096u   /* [R][4]         FRONT: r, ret, steps, goal (goal_step >= 0 ? 1 : 0) as this tick's reward kernel left
+                                          them, the last two as doubles.  Only on a slot with a reward (irlosc_set_reward); elsewhere the
+                                          bit is unknown: irlosc_log_layout_reward, below                                                */
 typedef struct irlosc_log {
     uint32_t channels;      /* OR of the above, not 0, no other bit */
     int32_t  every;         /* >= 1: ticks 0, every, 2 every, ... of THIS call are logged (as trace_every counts) */
@@ -1077,6 +1184,11 @@ IRLOSC_API int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, 
  * IRLOSC_ERR_ARG also for an n_out other than 0, 6, 7 and a sampled other than 0, 1. */
 IRLOSC_API int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, uint32_t channels, int32_t R,
                                         int64_t offset[12], int64_t* sample_words);
+/* The same for a slot that, with rewarded == 1, has a reward: thirteen offsets, the thirteenth IRLOSC_LOG_REWARD's plane [R][4].  With
+ * rewarded == 0 that bit is unknown and the first twelve offsets are irlosc_log_layout_policy's (the three functions above keep refusing
+ * it).  IRLOSC_ERR_ARG also for a rewarded other than 0, 1. */
+IRLOSC_API int irlosc_log_layout_reward(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, int32_t rewarded,
+                                        uint32_t channels, int32_t R, int64_t offset[13], int64_t* sample_words);
 /* irlosc_rollout_from_q with a log in place of the EE trace: log_host[ceil(ticks / every)][sample_words] (double), one sample per logged
  * tick of the R robots of `robots` (strictly ascending, in [0, B); NULL: all B).  log == NULL is
  * irlosc_rollout_from_q(ctx, slot, B, ticks, 0, NULL, u_host, flags_any_host); robots and log_host are not read then.
@@ -1087,7 +1199,8 @@ IRLOSC_API int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, i
  * when it needs the block again, and at the end.  Ticks keep running while a half is on the link; the rollout waits only where a half
  * would be refilled before it has left.
  * Every argument is checked before anything is enqueued, sizes in 64 bits; after a refusal the slot is exactly as it was: no tick ran.
- *   IRLOSC_ERR_ARG    what irlosc_log_layout_policy refuses for the slot's action objects, policy and head (none of them: what
+ *   IRLOSC_ERR_ARG    what irlosc_log_layout_reward refuses for the slot's action objects, policy, head and reward (IRLOSC_LOG_REWARD on
+ *                     a slot without a reward is an unknown bit; none of them: what
  *                     irlosc_log_layout refuses, so IRLOSC_LOG_OBJECT_POSE on a slot without objects, IRLOSC_LOG_POLICY_OUT on one without
  *                     a policy and IRLOSC_LOG_POLICY_SAMPLE on one without a Gaussian head are unknown bits); every < 1; reserved != 0; robots == NULL with n_robots not 0 or B; robots given with
  *                     n_robots outside [1, B], not strictly ascending or outside [0, B); log_host NULL; a buffer_bytes != 0 that
@@ -1109,7 +1222,8 @@ IRLOSC_API int irlosc_rollout_from_q_logged(irlosc_ctx* ctx, int32_t slot, int32
  *     a ring of the last `records` ended episodes: start_tick, length (= age), outcome, start index | variant index << 16
  * and judges it on every tick that runs it.  The episode ENDS on that tick when
  *     FINISHED, with end_on_finish:  a LIST: the robot's finished_tick >= 0;  PATHS: every listed device with loop == 0 has index == W_d,
- *                                    and there is such a device;  no program: never
+ *                                    and there is such a device;  no program, a policy: never;  and, whatever the program, on a
+ *                                    slot whose reward has a goal: the robot's goal_step >= 0 (IRLOSC_EPISODE_GOAL, below)
  *     TIMEOUT, with max_ticks > 0:   age == max_ticks.  A robot that finishes on the tick of its timeout is FINISHED.
  * Then its record is written and count += 1, and with max_episodes == 0 || count < max_episodes the robot is RESET, else PARKED: never
  * judged again, it carries on exactly as a finished robot does without episodes.  A reset leaves the robot as the setters' init launches
@@ -1136,6 +1250,9 @@ IRLOSC_API int irlosc_rollout_from_q_logged(irlosc_ctx* ctx, int32_t slot, int32
 #define IRLOSC_EPISODE_TIMEOUT  2
 #define IRLOSC_EPISODE_INSERTED 4             /* OR-ed into the outcome on a slot with mates ("action objects", below): every mate of the
                                                  slot has mated_tick >= 0 on the tick the episode ends -- 5 or 6 in place of 1 or 2 */
+#define IRLOSC_EPISODE_GOAL     8             /* OR-ed into the outcome on a slot whose reward has a goal ("a reward per tick", above): the
+                                                 robot's goal_step >= 0 on the tick the episode ends.  With end_on_finish such an episode is
+                                                 FINISHED on that tick, whatever the program -- a policy's and no program's included */
 #define IRLOSC_MAX_EPISODE_RECORDS 16
 #define IRLOSC_MAX_EPISODE_STARTS  4096       /* start states and pose variants, each */
 typedef struct irlosc_episodes {

@@ -45,11 +45,16 @@ EXPORTS = ["irlosc_abi_version", "irlosc_device_count", "irlosc_create", "irlosc
            "irlosc_set_objects", "irlosc_download_object_state", "irlosc_set_action_refs", "irlosc_log_layout_objects",
            "irlosc_set_action_motion", "irlosc_download_action_motion_state", "irlosc_set_object_loads",
            "irlosc_download_object_load_state", "irlosc_set_policy", "irlosc_download_policy_state",
-           "irlosc_set_policy_noise", "irlosc_download_policy_noise_state", "irlosc_log_layout_policy"]
+           "irlosc_set_policy_noise", "irlosc_download_policy_noise_state", "irlosc_log_layout_policy",
+           "irlosc_set_reward", "irlosc_download_reward_state", "irlosc_log_layout_reward"]
 LOG_QPOS, LOG_QVEL, LOG_EE_POSE, LOG_TARGETS, LOG_WRENCH, LOG_U, LOG_FLAGS, LOG_WALL_FORCE, LOG_JOINT_TAU = (1 << i for i in range(9))
 LOG_OBJECT_POSE = 512                                    # only on a slot with action objects
 LOG_POLICY_OUT, LOG_POLICY_SAMPLE = 1024, 2048           # only on a slot with a policy / one whose policy has a Gaussian head
-EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED = 1, 2, 4
+LOG_REWARD = 4096                                        # only on a slot with a reward
+EPISODE_FINISHED, EPISODE_TIMEOUT, EPISODE_INSERTED, EPISODE_GOAL = 1, 2, 4, 8
+MAX_REWARD_TERMS, MAX_REWARD_POINTS = 8, 8
+REWARD_EE, REWARD_TARGET, REWARD_OBJECT, REWARD_FIXED = 0, 1, 2, 3      # point kinds
+REWARD_DIST_SQ, REWARD_DIST, REWARD_ORI, REWARD_ACT_SQ, REWARD_U_SQ, REWARD_FORCE, REWARD_MATED, REWARD_ONE = range(8)      # term kinds
 MAX_OBJECTS, MAX_GRIPPERS, MAX_MATES = 4, 2, 2
 MAX_EPISODE_RECORDS, MAX_EPISODE_STARTS = 16, 4096
 ABI_VERSION = 3
@@ -185,6 +190,14 @@ class PolicyNoise(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("n_std", C.c_int32), ("reserved", C.c_int32), ("std", C.c_float * 8)]
 
 
+class Reward(C.Structure):
+    """struct irlosc_reward (include/irlosc.h): the weighted terms, the discount and the goal of a slot's reward, irlosc_set_reward."""
+    _fields_ = [("n_terms", C.c_int32), ("n_points", C.c_int32), ("points_per_robot", C.c_int32), ("goal_term", C.c_int32),
+                ("goal_cmp", C.c_int32), ("goal_hold", C.c_int32), ("kind", C.c_int32 * 8), ("a_kind", C.c_int32 * 8),
+                ("a_index", C.c_int32 * 8), ("b_kind", C.c_int32 * 8), ("b_index", C.c_int32 * 8), ("reserved", C.c_int32 * 2),
+                ("weight", C.c_double * 8), ("gamma", C.c_double), ("goal_value", C.c_double)]
+
+
 class Cfg(C.Structure):
     _fields_ = [("hip_device", C.c_int32), ("dtype", C.c_int32), ("max_batch", C.c_int32),
                 ("n_slots", C.c_int32), ("n", C.c_int32), ("ndev", C.c_int32),
@@ -272,6 +285,9 @@ def load():
     lib.irlosc_set_policy_noise.argtypes = [vp, i32, C.POINTER(PolicyNoise), vp]
     lib.irlosc_download_policy_noise_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     lib.irlosc_log_layout_policy.argtypes = [i32, i32, i32, i32, i32, C.c_uint32, i32, vp, vp]
+    lib.irlosc_set_reward.argtypes = [vp, i32, i32, C.POINTER(Reward), vp]
+    lib.irlosc_download_reward_state.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.irlosc_log_layout_reward.argtypes = [i32, i32, i32, i32, i32, i32, C.c_uint32, i32, vp, vp]
     lib.irlosc_set_pushes.argtypes = [vp, i32, i32, C.POINTER(Pushes), vp]
     lib.irlosc_set_walls.argtypes = [vp, i32, i32, C.POINTER(Walls), vp]
     lib.irlosc_download_wall_state.argtypes = [vp, i32, i32, vp, vp, vp, vp]

@@ -360,6 +360,10 @@ class BatchedOSC:
         sampled = self.lib.irlosc_download_policy_noise_state(self._h, slot, 0, None, None, None, None) == 0
         return self._policy[slot][1], sampled
 
+    def _log_reward(self, slot: int) -> bool:
+        """Whether the slot has a reward as the library's log sees it (set_model ends one behind this object's back)."""
+        return self.lib.irlosc_download_reward_state(self._h, slot, 0, None, None, None, None, None, None, None) == 0
+
     def _ticks_run(self, slot: int) -> int:
         """The ticks the slot's last rollout call ran: fewer than asked where its episodes exited early (set_episodes, poll_every)."""
         run = C.c_int32(0)
@@ -390,17 +394,54 @@ class BatchedOSC:
             words = 0
             nobj = self._objects[slot][0]
             n_out, sampled = self._log_policy(slot)
-            if S and R >= 1 and m and not m & ~rollout_log.known(nobj, n_out, sampled):
-                words = rollout_log.layout(L.n, L.ndev, m, R, nobj, n_out, sampled)[1]
+            rewarded = self._log_reward(slot)
+            if S and R >= 1 and m and not m & ~rollout_log.known(nobj, n_out, sampled, rewarded):
+                words = rollout_log.layout(L.n, L.ndev, m, R, nobj, n_out, sampled, rewarded)[1]
             buf = np.empty((S, words), dtype=np.float64)
         self._chk(self.lib.irlosc_rollout_from_q_logged(self._h, slot, B, ticks, C.byref(lg) if lg is not None else None, _lib.ptr(idx),
                                                         _lib.ptr(buf), _lib.ptr(u), _lib.ptr(fl)))
         run = self._ticks_run(slot)
         if buf is not None:
             log_ticks = np.arange(0, min(ticks, run) if B else ticks, every, dtype=np.int64)      # (an early exit: the rows of the ticks run)
-            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype, nobj=nobj, n_out=n_out, sampled=sampled) if B else {}
+            log = rollout_log.split(buf[:len(log_ticks)], L.n, L.ndev, m, R, dtype=self.dtype, nobj=nobj, n_out=n_out, sampled=sampled, rewarded=rewarded) if B else {}
         qpos, qvel = self.download_q(slot)
         return dict(qpos=qpos, qvel=qvel, u=u, flags_any=fl, ee_trace=None, log=log, log_ticks=log_ticks, ticks_run=run)
+
+    # -- the reward of the rollout (irlosc_set_reward / irlosc_download_reward_state) ---------------------------------------------------
+    def set_reward(self, reward, slot: int = 0):
+        """A reward for the slot's robots (irlosc_set_reward; "a reward per tick" in include/irlosc.h), evaluated on the GPU on every
+        rollout tick behind the OSC step: `reward` is a reward.Reward -- up to 8 weighted terms over the tick's EE poses, targets,
+        object poses, fixed points, the policy's action, the torques, the sensed force and the mates -- accumulated per episode plain
+        (ret) and discounted (gret; gamma), optionally with a goal: a term's value compared with goal_value for goal_hold ticks in a
+        row.  With episodes (set_episodes, end_on_finish) a robot that has reached the goal ends its episode, whose outcome carries
+        _lib.EPISODE_GOAL and whose (ret, gret) reward_state keeps.  The log's "reward" channel is [R, 4]: r, ret, steps, goal.  The
+        arithmetic is reward.reward_tick's, bit for bit.  After the parts it names (targets, objects, policy, feed), before
+        set_episodes; reward=None (or clear_reward) ends it and nothing else."""
+        B = self._B[slot]
+        if reward is None:
+            self._chk(self.lib.irlosc_set_reward(self._h, slot, B, None, None))
+            return
+        desc = reward.desc()
+        pts = None
+        if reward.points is not None:
+            pts = np.ascontiguousarray(reward.points, dtype=np.float64)
+            if pts.ndim == 3 and pts.shape[0] != B:
+                raise ValueError(f"points: expected shape (P, 3) or ({B}, P, 3), got {pts.shape}")
+        self._chk(self.lib.irlosc_set_reward(self._h, slot, B, C.byref(desc), _lib.ptr(pts)))
+
+    def clear_reward(self, slot: int = 0):
+        """Ends the slot's reward (irlosc_set_reward with desc == NULL); everything else is left alone."""
+        self.set_reward(None, slot=slot)
+
+    def reward_state(self, slot: int = 0):
+        """-> dict(r: the last tick's reward; ret, gret: the running episode's plain and discounted sums; steps, hold, goal_step (-1:
+        not reached): [B]; records [B, 16, 2]: (ret, gret) of the robot's ended episodes, entry e mod the episodes' `records` as
+        episode_state has them, zero where no episode ended under this reward).  (irlosc_download_reward_state)"""
+        B = self._B[slot]
+        out = dict(r=np.empty(B), ret=np.empty(B), gret=np.empty(B), steps=np.empty(B, np.int32), hold=np.empty(B, np.int32),
+                   goal_step=np.empty(B, np.int32), records=np.empty((B, _lib.MAX_EPISODE_RECORDS, 2)))
+        self._chk(self.lib.irlosc_download_reward_state(self._h, slot, B, *(_lib.ptr(out[k]) for k in ("r", "ret", "gret", "steps", "hold", "goal_step", "records"))))
+        return out
 
     # -- episodes of the rollout (irlosc_set_episodes / irlosc_download_episode_state) ------------------------------------------------
     def set_episodes(self, qpos0, qvel0=None, max_ticks: int = 0, end_on_finish: bool = True, max_episodes: int = 0, poses=None,

@@ -35,6 +35,7 @@
 #include "osc_wall.hpp"
 #include "osc_object_load.hpp"
 #include "osc_joint.hpp"
+#include "osc_reward.hpp"
 #include "osc_log.hpp"
 #include "osc_episode.hpp"
 #include "launchers.hpp"
@@ -234,12 +235,35 @@ struct Loads : PlantForce {
     void set(int B, const irlosc_object_loads& desc) { in_force(B); d = desc; }
 };
 
+// The reward (irlosc_set_reward, osc_reward.hpp): per robot and tick a list of weighted terms over the tick's state, accumulated per episode,
+// with an optional goal.  It writes no targets and acts on nothing; it READS other parts by name, so what it names is checked by its setter
+// and again by every rollout call (check_reward_refs).  Written by set() and end(), and by nothing else.
+struct Reward {
+    irlosc_reward d{};         // the description in force
+    int robots = 0;            // robots it covers (0: none)
+    int per_robot = 0;         // how `table` is laid out (a lone robot's: the shared form)
+    DevBuf<double> table;      // its points (walk_table), grown on demand
+    DevBuf<double> st_d;       // per-robot state, allocated by the first use for max_batch robots: r, ret, gret, disc, the ring
+    DevBuf<int32_t> st_i;      // ... steps, hold, goal_step
+    // Which episodes its ring's entries can stem from: the serial of the episodes in force when it was set (-1: none) and their tick then
+    long ep_serial = -1;
+    int ep_tick0 = 0;
+    // THE LAYOUT of the state (osc_reward.hpp): rows of Bm = max_batch words; the ring [IRLOSC_MAX_EPISODE_RECORDS][2][Bm] behind the doubles
+    static size_t d_words(size_t Bm) { return (size_t)REWARD_D_ROWS * Bm; }  static size_t i_words(size_t Bm) { return (size_t)REWARD_I_ROWS * Bm; }
+    RewardState state(size_t Bm) const { return {st_d, st_d + Bm, st_d + 2 * Bm, st_d + 3 * Bm, st_i, st_i + Bm, st_i + 2 * Bm, st_d + 4 * Bm}; }
+    bool goal() const { return robots && d.goal_term >= 0; }
+    void set(int B, const irlosc_reward& desc, int pr, long serial, int tick0) { robots = B; d = desc; per_robot = pr; ep_serial = serial; ep_tick0 = tick0; }
+    // It ends: its setter cleared it, the model changed, or its buffers failed.
+    void end() { robots = 0; }
+};
+
 // The episodes (irlosc_set_episodes, osc_episode.hpp): per robot the judgement whether its running episode has ended, its record and its
 // reset on the device, and per wave the robots still running for the early exit.  They write no targets but a reset robot's snapshot row,
 // so they are no Program: they live next to one.  Written by laid_out(), set(), end() and ticked(), and by nothing else.
 struct Episodes {
     irlosc_episodes d{};       // the description in force
     int robots = 0, tick = 0;  // robots they cover (0: none); rollout ticks since they came in force
+    long serial = 0;           // counts the settings that came in force (the reward's ring asks which one wrote an entry)
     int starts_per_robot = 0, list_per_robot = 0;      // the layouts of `starts` and of the list's pose table (a lone robot's: the shared one)
     size_t vstride = 0;        // doubles between two variants' tables
     DevBuf<int32_t> st_i;      // per-robot state, allocated by the first use for max_batch robots: count, age, start_tick, the ring
@@ -252,7 +276,7 @@ struct Episodes {
     static size_t i_words(size_t Bm) { return (3 + 4 * (size_t)IRLOSC_MAX_EPISODE_RECORDS) * Bm; }
     // Episodes of B robots are in force: tables, snapshot and reset state on the device.  (They belong to the program in force with them:
     // every transition that ends or replaces it ends them.)
-    void set(int B, const irlosc_episodes& desc) { robots = B; tick = 0; d = desc; }
+    void set(int B, const irlosc_episodes& desc) { robots = B; tick = 0; d = desc; ++serial; }
     // The tables of the episodes to come are laid out like this (ahead of the init launch, which reads them; none are in force meanwhile)
     void laid_out(int starts_pr, int list_pr, size_t vs) { starts_per_robot = starts_pr; list_per_robot = list_pr; vstride = vs; }
     // They end: their setter cleared them, the model changed, the targets or the program they were set on changed, or their buffers failed.
@@ -296,16 +320,17 @@ struct Slot {
     Joints joints;             // what acts on single hinges inside a rollout: stops, couplings, drives
     Objects objects;           // what the grippers carry inside a rollout
     Loads loads;               // what the carried objects weigh (only next to the objects they describe)
+    Reward reward;             // what judges every tick of a rollout (it reads the other parts; none reads it but the episodes and the log)
     Episodes episodes;         // what ends and restarts single robots inside a rollout
     int ticks_run = 0;         // ticks the last rollout call on the slot ran (fewer than asked: an early exit of its episodes)
     // THE SLOT'S ROLLOUT PARTS, listed three times and nowhere else: a new part goes into all three (adding a part).
     // The model changed: what was laid out for the old one ends -- the compact block and the feed, and every part.
-    void model_changed() { drop_block(true); prog.end(); push.end(); walls.end(); joints.end(); objects.end(); loads.end(); episodes.end(); }
+    void model_changed() { drop_block(true); prog.end(); push.end(); walls.end(); joints.end(); objects.end(); loads.end(); reward.end(); episodes.end(); }
     // A whole rollout tick is enqueued (prog_ran: with the program's kernel): every part in force is a tick older.
-    void parts_ticked(bool prog_ran) { if (prog_ran) prog.ticked(); push.ticked(); walls.ticked(); joints.ticked(); objects.ticked(); loads.ticked(); episodes.ticked(); }
+    void parts_ticked(bool prog_ran) { if (prog_ran) prog.ticked(); push.ticked(); walls.ticked(); joints.ticked(); objects.ticked(); loads.ticked(); episodes.ticked(); }      // (the reward keeps no tick: its steps are per robot)
     // The parts whose state a reset of episodes writes, with the robots each covers: episodes cover no more (irlosc_set_episodes)
     struct Cover { int robots; const char* what; };
-    std::array<Cover, 5> reset_covers() const { return {{{prog.robots, "program"}, {walls.robots, "walls"}, {joints.robots, "joint rows"}, {objects.robots, "action objects"}, {loads.robots, "object loads"}}}; }
+    std::array<Cover, 6> reset_covers() const { return {{{prog.robots, "program"}, {walls.robots, "walls"}, {joints.robots, "joint rows"}, {objects.robots, "action objects"}, {loads.robots, "object loads"}, {reward.robots, "reward"}}}; }
 
     // The feed ends: records that bring a wrench of their own were announced, or its description / the model changed.
     void end_feed() { feed = 0; }
@@ -1882,7 +1907,7 @@ static bool fused_ready(irlosc_ctx* c, int n) {
 // tick, is the slot's to say (Slot::prog).  log: the episode log's sample of this tick (irlosc_rollout_from_q_logged), or nullptr.
 // A logged tick: the ring's sample it fills, the event its first log launch waits for on the tick's stream (the half it starts was still
 // draining: the copy that empties it; else null), and what stays the same over the call -- channels, robots (device, or nullptr: all), layout
-struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };      // (off[9]: OBJECT_POSE, of a slot with objects; off[10], off[11]: of a slot with a policy)
+struct LogCall { double* sample; hipEvent_t wait; uint32_t channels; const int32_t* robots; int32_t R; int64_t off[LOG_CHANNELS]; };      // (off[9]: OBJECT_POSE, of a slot with objects; off[10], off[11]: of a slot with a policy; off[12]: of one with a reward)
 struct PlantCall { double* trace; const LogCall* log; };
 
 // The exchange entry of each device's EE pose (its x; y z qw qx qy qz follow): what the rollout's kernels find an EE body by
@@ -2105,9 +2130,70 @@ static LogArgs log_args(const irlosc_ctx* c, const Slot& s, const irlosc_ctx::Ba
     a.wall_force = s.walls.state((size_t)c->cfg.ndev * Bm).force; a.joint_tau = s.joints.state(Bm).tau;
     a.obj_pose = s.objects.state(Bm).pose; a.obj_holder = s.objects.state(Bm).holder; a.nobj = s.objects.count();
     if (s.prog.kind == Program::POLICY) { const PolicyState po = s.prog.policy_state(); a.po_out = po.out; a.po_act = po.act; a.po_logp = po.logp; a.n_out = s.prog.po.n_out; }
+    if (s.reward.robots) { const RewardState rw = s.reward.state(Bm); a.rw_r = rw.r; a.rw_ret = rw.ret; a.rw_steps = rw.steps; a.rw_goal_step = rw.goal_step; }
     a.R = lg.R; a.n = c->cfg.n; a.ndev = c->cfg.ndev; a.n_entries = (int32_t)c->model.fe_xentries; a.stride = (int32_t)Bm;
     fill_ee0(c, a.ee0);
     return a;
+}
+
+// The arguments of the slot's reward kernel over B robots for description d with its points laid out per_robot or not: a tick of the
+// step on bank bk (wrench: the feed's wrench of the tick, or nullptr), or (bk == nullptr) the init launch of irlosc_set_reward
+static RewardArgs reward_args(const irlosc_ctx* c, const Slot& s, int B, const irlosc_reward& d, int per_robot, const irlosc_ctx::Bank* bk, const void* wrench) {
+    const Reward& w = s.reward;
+    const Program& p = s.prog;
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    RewardArgs a;
+    memset(&a, 0, sizeof a);
+    a.st = w.state(Bm);
+    a.B = B; a.n = c->cfg.n; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.init = bk ? 0 : 1;
+    if (!bk) return a;
+    a.xside = bk->xside[0]; a.tgt = s.tgt; a.u = bk->u[0]; a.wrench = wrench;
+    a.obj_pose = s.objects.state(Bm).pose; a.mated_tick = s.objects.state(Bm).mated_tick;
+    if (p.kind == Program::POLICY) { const PolicyState po = p.policy_state(); a.act = po.act ? po.act : po.out; a.n_out = p.po.n_out; }
+    a.points = w.table; a.per_robot = per_robot;
+    for (int i = 0; i < d.n_terms; ++i) {
+        a.weight[i] = d.weight[i]; a.kind[i] = (int8_t)d.kind[i];
+        a.a_kind[i] = (int8_t)d.a_kind[i]; a.a_index[i] = (int8_t)d.a_index[i]; a.b_kind[i] = (int8_t)d.b_kind[i]; a.b_index[i] = (int8_t)d.b_index[i];
+        const bool pts = d.kind[i] == IRLOSC_REWARD_DIST_SQ || d.kind[i] == IRLOSC_REWARD_DIST || d.kind[i] == IRLOSC_REWARD_ORI;
+        if (pts && (d.a_kind[i] == IRLOSC_REWARD_TARGET || d.b_kind[i] == IRLOSC_REWARD_TARGET)) a.need |= REWARD_NEED_TGT;
+        if (d.kind[i] == IRLOSC_REWARD_U_SQ) a.need |= REWARD_NEED_U;
+        if (d.kind[i] == IRLOSC_REWARD_FORCE) a.need |= REWARD_NEED_WRENCH;
+    }
+    a.gamma = d.gamma; a.goal_value = d.goal_value;
+    a.n_terms = d.n_terms; a.P = d.n_points; a.goal_term = d.goal_term; a.goal_cmp = d.goal_cmp; a.goal_hold = d.goal_hold;
+    a.n_entries = (int32_t)c->model.fe_xentries;
+    fill_ee0(c, a.ee0);
+    return a;
+}
+
+// What reward d names, the slot has for B robots: asked by irlosc_set_reward of the description it is given, and by every rollout call of
+// the reward in force (parts come and go behind a reward's back).  IRLOSC_ERR_STATE with the reason.
+static int check_reward_refs(irlosc_ctx* c, int slot, int B, const irlosc_reward& d) {
+    const Slot& s = c->slot[slot];
+    if (!c->model.in_force) return fail(c, IRLOSC_ERR_STATE, "irlosc_set_model has not been called");
+    if (c->cfg.n != plant_joints()) return fail(c, IRLOSC_ERR_STATE, "no reward on this context: the rollout's kernels hold %d joints, n=%d", plant_joints(), c->cfg.n);
+    if (B > std::max(0, s.targets))
+        return fail(c, IRLOSC_ERR_STATE, "slot %d holds targets for %d instances, its reward covers %d: irlosc_set_targets first", slot, std::max(0, s.targets), B);
+    for (int i = 0; i < d.n_terms; ++i) {
+        const int kind = d.kind[i];
+        const bool pts = kind == IRLOSC_REWARD_DIST_SQ || kind == IRLOSC_REWARD_DIST || kind == IRLOSC_REWARD_ORI;
+        for (int h = 0; pts && h < 2; ++h) {
+            const int pk = h ? d.b_kind[i] : d.a_kind[i], pi = h ? d.b_index[i] : d.a_index[i];
+            if (pk == IRLOSC_REWARD_OBJECT && (pi >= s.objects.count() || s.objects.robots < B))
+                return fail(c, IRLOSC_ERR_STATE, "slot %d: term %d of its reward reads action object %d of %d robots, the slot has %d objects of %d (irlosc_set_objects)", slot,
+                            i, pi, B, s.objects.count(), s.objects.robots);
+        }
+        if (kind == IRLOSC_REWARD_MATED && (s.objects.robots < B || d.a_index[i] >= (s.objects.robots ? s.objects.d.n_mates : 0)))
+            return fail(c, IRLOSC_ERR_STATE, "slot %d: term %d of its reward reads mate %d of %d robots, the slot has %d mates of %d (irlosc_set_objects)", slot, i,
+                        d.a_index[i], B, s.objects.robots ? s.objects.d.n_mates : 0, s.objects.robots);
+        if (kind == IRLOSC_REWARD_ACT_SQ && (s.prog.kind != Program::POLICY || s.prog.robots < B))
+            return fail(c, IRLOSC_ERR_STATE, "slot %d: term %d of its reward reads a policy's action of %d robots, the slot has %s (irlosc_set_policy)", slot, i, B,
+                        s.prog.kind == Program::POLICY ? "one for fewer" : "no policy");
+        if (kind == IRLOSC_REWARD_FORCE && (s.feed < B || c->ft_f0[d.a_index[i]] < 0))
+            return fail(c, IRLOSC_ERR_STATE, "slot %d: term %d of its reward reads the sensed force of device %d of %d robots, %s (irlosc_set_sensordata)", slot, i,
+                        d.a_index[i], B, s.feed < B ? "the slot's sensor feed covers fewer" : "the feed has no force sensor for that device");
+    }
+    return IRLOSC_OK;
 }
 
 // The arguments of the slot's episode kernel over B robots: a tick (the program, walls and rows in force on it travel as uniform arguments)
@@ -2146,6 +2232,7 @@ static EpisodeArgs episode_args(const irlosc_ctx* c, const Slot& s, int B, const
         a.ob = o.state(Bm); a.ob_pose0 = o.table; a.ob_vstride = (int64_t)o.vstride;
     }
     if (!init && s.loads.robots) { a.loads = 1; a.ld = s.loads.state(Bm); }
+    if (!init && s.reward.robots) { a.reward = 1; a.goal = s.reward.goal() ? 1 : 0; a.rw = s.reward.state(Bm); }
     a.B = B; a.ndev = c->cfg.ndev; a.stride = (int32_t)Bm; a.S = d.n_starts; a.starts_per_robot = e.starts_per_robot;
     a.max_ticks = d.max_ticks; a.end_on_finish = d.end_on_finish; a.max_episodes = d.max_episodes; a.records = d.records;
     a.tick = e.tick; a.init = init ? 1 : 0;
@@ -2227,8 +2314,9 @@ static int download_state(irlosc_ctx* c, int B, const double* sd, size_t nd, std
 // What a tick of a rollout runs next to its fused step, decided once per tick from the slot (the default: no tick, nothing): the program that writes its
 // targets; the pushes and the walls' devices that act on its plant, and those its sensors read of the tick before (a feed, and the device a sensor); the
 // grippers whose carried object weighs on the plant, and those whose device's sensor reads the weight of the tick before; rows
-// it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on); episodes it has
-struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; bool objects = false; uint32_t load_apply = 0, load_sense = 0; };
+// it has; a stream's reading of the tick (-1: none -- no stream, or one that has ended: no launch, its tick counts on); episodes it has;
+// a reward it has
+struct TickPlan { Program::Kind prog = Program::NONE; uint32_t push_apply = 0, push_sense = 0, wall_apply = 0, wall_sense = 0; bool joints = false; int reading = -1; bool episodes = false; bool objects = false; uint32_t load_apply = 0, load_sense = 0; bool reward = false; };
 static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
     TickPlan tp{s0.prog.kind, s0.push.applied(), s0.feed > 0 ? s0.push.sensed() : 0u, s0.walls.devices(), 0u, s0.joints.robots != 0, s0.prog.reading(), s0.episodes.robots != 0, s0.objects.robots != 0};
     for (int p = 0; tp.push_sense && p < IRLOSC_MAX_PUSHES; ++p)
@@ -2240,6 +2328,7 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
         tp.load_apply |= 1u << g;
         if (s0.feed > 0 && s0.loads.tick > 0 && c->ft_f0[s0.objects.d.dev[g]] >= 0) tp.load_sense |= 1u << g;
     }
+    tp.reward = s0.reward.robots != 0;
     return tp;
 }
 
@@ -2251,6 +2340,9 @@ static TickPlan tick_plan(const irlosc_ctx* c, const Slot& s0) {
 //                   | stream kernel: its targets are this tick's too | policy kernel: likewise, and it reads what the launches above left: the wrench behind
 //                   every SENSE, the objects' poses of this tick]
 //     the OSC kernels (task pass + lane kernel, or row16 FROMQ), the give-up pass (front end over its lists, generic kernel)
+//     [reward: behind the give-up pass, which completes u, and directly in front of log FRONT, which can then log it -- so r_t judges the state
+//                   the tick observed and the action it took: in front of the cycler, which moves the targets, and of the plant; it reads what the
+//                   launches above left (targets, wrench, objects, a policy's action) and writes its own state alone]
 //     [log FRONT (a logged tick): coordinates, EE poses, targets, wrench, u and flags as the step used and left them -- behind the give-up
 //                   pass, which completes u; in front of the cycler, which moves the targets, and of the plant, which moves the
 //                   coordinates and overwrites the block's M entries (the EE entries it leaves alone; the order does not lean on that)]
@@ -2379,6 +2471,7 @@ static int fused_train(irlosc_ctx* c, const int* slots, int n, int B, int k, con
     else HIPCHK(c, (hipError_t)launch_row16_fromq<T>(tr, n, st));      // (task pass + FROMQ kernel; the lane kernel computes the task rows itself)
     HIPCHK(c, (hipError_t)launch_frontend_generic_lists<T>(c->model.dmodel, ga, n, c->model.fe_smem, st));
     HIPCHK(c, (hipError_t)launch_row16_worklist<T>(tr, n, nullptr, st));
+    if (tp.reward) HIPCHK(c, (hipError_t)launch_reward<T>(reward_args(c, s0, B, s0.reward.d, s0.reward.per_robot, &bk, nft ? fts[0].wrench : nullptr), st));
     if (pl && pl->log) {      // the log's front launch; the first into a half of the ring that was draining waits for its copy
         if (pl->log->wait) HIPCHK(c, hipStreamWaitEvent(st, pl->log->wait, 0));
         HIPCHK(c, (hipError_t)launch_log<T>(log_args(c, s0, bk, *pl->log, LOG_FRONT, nft ? fts[0].wrench : nullptr), st));
@@ -2725,14 +2818,16 @@ static int rollout_ticks(irlosc_ctx* c, int slot, int B, int ticks, int every, d
     return IRLOSC_OK;
 }
 
-extern "C" int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, uint32_t channels, int32_t R, int64_t offset[12],
-                                        int64_t* sample_words) {
+extern "C" int irlosc_log_layout_reward(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, int32_t rewarded, uint32_t channels, int32_t R,
+                                        int64_t offset[13], int64_t* sample_words) {
     if (!offset || !sample_words) return fail(nullptr, IRLOSC_ERR_ARG, "log: offset and sample_words are required");
     if (nobj < 0 || nobj > IRLOSC_MAX_OBJECTS) return fail(nullptr, IRLOSC_ERR_ARG, "log: nobj=%d out of [0,%d]", nobj, IRLOSC_MAX_OBJECTS);
     if (n_out != 0 && n_out != 6 && n_out != 7) return fail(nullptr, IRLOSC_ERR_ARG, "log: n_out=%d must be 0 (no policy), 6 or 7", n_out);
     if (sampled != 0 && sampled != 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: sampled=%d must be 0 or 1", sampled);
-    const uint32_t known = (LOG_FRONT | LOG_BACK) & ~(nobj ? 0u : (uint32_t)IRLOSC_LOG_OBJECT_POSE)      // (no objects, no policy, no head: no such channel)
-                           & ~(n_out ? 0u : (uint32_t)IRLOSC_LOG_POLICY_OUT) & ~(n_out && sampled ? 0u : (uint32_t)IRLOSC_LOG_POLICY_SAMPLE);
+    if (rewarded != 0 && rewarded != 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: rewarded=%d must be 0 or 1", rewarded);
+    const uint32_t known = (LOG_FRONT | LOG_BACK) & ~(nobj ? 0u : (uint32_t)IRLOSC_LOG_OBJECT_POSE)      // (no objects, no policy, no head, no reward: no such channel)
+                           & ~(n_out ? 0u : (uint32_t)IRLOSC_LOG_POLICY_OUT) & ~(n_out && sampled ? 0u : (uint32_t)IRLOSC_LOG_POLICY_SAMPLE)
+                           & ~(rewarded ? 0u : (uint32_t)IRLOSC_LOG_REWARD);
     if (channels == 0 || (channels & ~known)) return fail(nullptr, IRLOSC_ERR_ARG, "log: channels=0x%x must be a non-empty OR of the IRLOSC_LOG_* bits", channels);
     if (R < 1) return fail(nullptr, IRLOSC_ERR_ARG, "log: R=%d must be >= 1", R);
     if (n < 1 || n > IRLOSC_MAX_N) return fail(nullptr, IRLOSC_ERR_ARG, "log: n=%d out of [1,%d]", n, IRLOSC_MAX_N);
@@ -2744,6 +2839,14 @@ extern "C" int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, i
     }
     *sample_words = words;
     return IRLOSC_OK;
+}
+
+extern "C" int irlosc_log_layout_policy(int32_t n, int32_t ndev, int32_t nobj, int32_t n_out, int32_t sampled, uint32_t channels, int32_t R, int64_t offset[12],
+                                        int64_t* sample_words) {
+    int64_t off[LOG_CHANNELS];
+    const int rc = irlosc_log_layout_reward(n, ndev, nobj, n_out, sampled, 0, channels, R, offset ? off : nullptr, sample_words);
+    for (int i = 0; !rc && i < 12; ++i) offset[i] = off[i];
+    return rc;
 }
 
 extern "C" int irlosc_log_layout_objects(int32_t n, int32_t ndev, int32_t nobj, uint32_t channels, int32_t R, int64_t offset[10], int64_t* sample_words) {
@@ -2774,7 +2877,8 @@ static int log_plan(irlosc_ctx* c, int slot, int B, int ticks, const irlosc_log*
             return fail(c, IRLOSC_ERR_ARG, "log: robots[%d]=%d: the list must be strictly ascending in [0,%d)", i, robots[i], B);
     int64_t words = 0;
     const Program& pg = c->slot[slot].prog;      // (a policy's channels: POLICY_OUT with a policy, POLICY_SAMPLE with its Gaussian head)
-    if (irlosc_log_layout_policy(c->cfg.n, c->cfg.ndev, c->slot[slot].objects.count(), pg.kind == Program::POLICY ? pg.po.n_out : 0, pg.noise, log->channels, R, lr.call.off, &words))
+    if (irlosc_log_layout_reward(c->cfg.n, c->cfg.ndev, c->slot[slot].objects.count(), pg.kind == Program::POLICY ? pg.po.n_out : 0, pg.noise, c->slot[slot].reward.robots ? 1 : 0, log->channels, R,
+                                 lr.call.off, &words))
         return fail(c, IRLOSC_ERR_ARG, "%s", irlosc_last_error(nullptr));
     const uint64_t sb = (uint64_t)words * sizeof(double);      // (R <= max_batch, 170 words a robot at most: far from 2^63)
     if (log->buffer_bytes && log->buffer_bytes / 2 < sb)
@@ -2842,6 +2946,8 @@ static int rollout_call(irlosc_ctx* c, int32_t slot, int32_t B, int32_t ticks, i
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].joints.robots, "joint rows", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].objects.robots, "action objects", "cover", nullptr);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].loads.robots, "object loads", "cover", nullptr);
+    if (!rc) rc = check_covers(c, slot, B, c->slot[slot].reward.robots, "reward", "covers", nullptr);
+    if (!rc && c->slot[slot].reward.robots) rc = check_reward_refs(c, slot, B, c->slot[slot].reward.d);
     if (!rc) rc = check_covers(c, slot, B, c->slot[slot].episodes.robots, "episodes", "cover", nullptr);
     if (rc) return rc;
     c->slot[slot].ticks_run = B == 0 ? ticks : 0;      // (rollout_ticks says how many were enqueued; an empty batch: all, none of them a launch)
@@ -3691,6 +3797,110 @@ extern "C" int irlosc_download_targets(irlosc_ctx* c, int32_t slot, int32_t B, v
     HIPCHK(c, hipSetDevice(c->cfg.hip_device));
     HIPCHK(c, hipMemcpyAsync(tgt_pose, s.tgt, (size_t)B * c->cfg.ndev * 7 * c->esz, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return IRLOSC_OK;
+}
+
+// ---- the reward of the rollout (osc_reward.hpp) ---------------------------------------------------------------------------------------
+extern "C" int irlosc_set_reward(irlosc_ctx* c, int32_t slot, int32_t B, const irlosc_reward* d, const double* points) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    Slot& s = c->slot[slot];
+    if (!d) { s.reward.end(); return IRLOSC_OK; }
+    const int nd = c->cfg.ndev, P = d->n_points;
+    if (d->n_terms < 1 || d->n_terms > IRLOSC_MAX_REWARD_TERMS) return fail(c, IRLOSC_ERR_ARG, "reward: n_terms=%d out of [1,%d]", d->n_terms, IRLOSC_MAX_REWARD_TERMS);
+    if (P < 0 || P > IRLOSC_MAX_REWARD_POINTS) return fail(c, IRLOSC_ERR_ARG, "reward: n_points=%d out of [0,%d]", P, IRLOSC_MAX_REWARD_POINTS);
+    if (d->points_per_robot != 0 && d->points_per_robot != 1) return fail(c, IRLOSC_ERR_ARG, "reward: points_per_robot=%d must be 0 or 1", d->points_per_robot);
+    if (d->reserved[0] != 0 || d->reserved[1] != 0) return fail(c, IRLOSC_ERR_ARG, "reward: reserved must be 0");
+    if (B < 1) return fail(c, IRLOSC_ERR_ARG, "reward: B=%d must be >= 1", B);
+    if (!std::isfinite(d->gamma) || d->gamma < 0.0 || d->gamma > 1.0) return fail(c, IRLOSC_ERR_ARG, "reward: gamma=%g must be finite and in [0,1]", d->gamma);
+    if (d->goal_term < -1 || d->goal_term >= d->n_terms) return fail(c, IRLOSC_ERR_ARG, "reward: goal_term=%d out of [-1,%d)", d->goal_term, d->n_terms);
+    if (d->goal_cmp != 0 && d->goal_cmp != 1) return fail(c, IRLOSC_ERR_ARG, "reward: goal_cmp=%d must be 0 (<=) or 1 (>=)", d->goal_cmp);
+    if (d->goal_hold < 1) return fail(c, IRLOSC_ERR_ARG, "reward: goal_hold=%d must be >= 1", d->goal_hold);
+    if (!std::isfinite(d->goal_value)) return fail(c, IRLOSC_ERR_ARG, "reward: goal_value is not finite");
+    if (P > 0 && !points) return fail(c, IRLOSC_ERR_ARG, "reward: points is NULL with n_points=%d", P);
+    // a point (kind, index) of term i; quat: the term reads its orientation
+    auto point = [&](int i, const char* which, int kind, int index, bool quat) -> int {
+        if (kind < IRLOSC_REWARD_EE || kind > IRLOSC_REWARD_FIXED) return fail(c, IRLOSC_ERR_ARG, "reward: term %d: %s_kind=%d is no point kind", i, which, kind);
+        const int lim = kind == IRLOSC_REWARD_OBJECT ? IRLOSC_MAX_OBJECTS : kind == IRLOSC_REWARD_FIXED ? P : nd;
+        if (index < 0 || index >= lim) return fail(c, IRLOSC_ERR_ARG, "reward: term %d: %s_index=%d out of [0,%d)", i, which, index, lim);
+        if (quat && kind == IRLOSC_REWARD_FIXED) return fail(c, IRLOSC_ERR_ARG, "reward: term %d: ORI on a FIXED point, which has no orientation", i);
+        return IRLOSC_OK;
+    };
+    for (int i = 0; i < IRLOSC_MAX_REWARD_TERMS; ++i) {
+        const int kind = d->kind[i];
+        if (i >= d->n_terms) {
+            if (kind || d->a_kind[i] || d->a_index[i] || d->b_kind[i] || d->b_index[i] || d->weight[i] != 0.0)      // (a NaN is not 0)
+                return fail(c, IRLOSC_ERR_ARG, "reward: term %d behind n_terms=%d must be all zero", i, d->n_terms);
+            continue;
+        }
+        if (kind < IRLOSC_REWARD_DIST_SQ || kind > IRLOSC_REWARD_ONE) return fail(c, IRLOSC_ERR_ARG, "reward: term %d: kind=%d is no term kind", i, kind);
+        if (!std::isfinite(d->weight[i])) return fail(c, IRLOSC_ERR_ARG, "reward: term %d: its weight is not finite", i);
+        if (kind <= IRLOSC_REWARD_ORI) {
+            if ((rc = point(i, "a", d->a_kind[i], d->a_index[i], kind == IRLOSC_REWARD_ORI)) || (rc = point(i, "b", d->b_kind[i], d->b_index[i], kind == IRLOSC_REWARD_ORI))) return rc;
+            continue;
+        }
+        const int lim = kind == IRLOSC_REWARD_FORCE ? nd : kind == IRLOSC_REWARD_MATED ? IRLOSC_MAX_MATES : 1;      // what a_index names
+        if (d->a_index[i] < 0 || d->a_index[i] >= lim) return fail(c, IRLOSC_ERR_ARG, "reward: term %d: a_index=%d out of [0,%d)", i, d->a_index[i], lim);
+        if (d->a_kind[i] || d->b_kind[i] || d->b_index[i]) return fail(c, IRLOSC_ERR_ARG, "reward: term %d (kind %d) reads no point: a_kind, b_kind and b_index must be 0", i, kind);
+    }
+    const int nbp = d->points_per_robot ? B : 1;
+    for (size_t i = 0; i < (size_t)nbp * P * 3; ++i)
+        if (!std::isfinite(points[i])) return fail(c, IRLOSC_ERR_ARG, "reward: point %zu of robot %zu is not finite", i / 3 % P, i / 3 / P);
+    if ((rc = check_reward_refs(c, slot, B, *d))) return rc;
+    if (s.episodes.robots > B)
+        return fail(c, IRLOSC_ERR_STATE, "slot %d: its episodes cover %d robots, the reward is given for %d (their resets write its state)", slot, s.episodes.robots, B);
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    Reward& w = s.reward;
+    w.end();           // (none until the new one's state is fresh)
+    const int pr = d->points_per_robot && B > 1 && P > 0;
+    const std::vector<double> tab = P > 0 ? walk_table(points, pr ? B : 1, (size_t)P * 3) : std::vector<double>();
+    const size_t Bm = (size_t)c->cfg.max_batch;
+    const bool first = !w.st_d.get();      // (the first use: the ring starts as zeros; later settings leave it alone)
+    if (!got(w.st_d.ensure(w.d_words(Bm) * sizeof(double))) || !got(w.st_i.ensure(w.i_words(Bm) * sizeof(int32_t))) || !got(w.table.reserve(tab.size() * sizeof(double))))
+        return fail(c, IRLOSC_ERR_HIP, "out of device memory for the reward of slot %d", slot);
+    const RewardArgs init = reward_args(c, s, B, *d, pr, nullptr, nullptr);      // (the init launch: reward_fresh for the B robots)
+    rc = setter_upload(c, {{w.table, tab.data(), tab.size() * sizeof(double), 0}, {w.st_d, nullptr, first ? w.d_words(Bm) * sizeof(double) : 0, 0}},
+                       c->cfg.dtype == IRLOSC_F64 ? launch_reward<double> : launch_reward<float>, &init);
+    if (rc) return rc;
+    w.set(B, *d, pr, s.episodes.robots ? s.episodes.serial : -1, s.episodes.tick);
+    return IRLOSC_OK;
+}
+
+extern "C" int irlosc_download_reward_state(irlosc_ctx* c, int32_t slot, int32_t B, double* r, double* ret, double* gret, int32_t* steps, int32_t* hold,
+                                            int32_t* goal_step, double* records) {
+    if (!c) return IRLOSC_ERR_ARG;
+    int rc = check_slot(c, slot, B);
+    if (rc) return rc;
+    const Slot& s = c->slot[slot];
+    rc = check_covers(c, slot, B, s.reward.robots, "reward", "covers", "irlosc_set_reward");
+    if (rc || B == 0) return rc;
+    const Reward& w = s.reward;
+    const Episodes& e = s.episodes;
+    HIPCHK(c, hipSetDevice(c->cfg.hip_device));
+    const size_t Bm = (size_t)c->cfg.max_batch, NR = IRLOSC_MAX_EPISODE_RECORDS;      // rows [max_batch] on the device -> [B], [B][NR][2] for the caller
+    const RewardState st = w.state(Bm);
+    rc = download_state(c, B, w.st_d, w.d_words(Bm), {{r, st.r, 1, 1, 0, 1}, {ret, st.ret, 1, 1, 0, 1}, {gret, st.gret, 1, 1, 0, 1}, {records, st.ring, 2 * NR, 2 * NR, 0, 1}},
+                        w.st_i, w.i_words(Bm), {{steps, st.steps, 1, 1, 0, 1}, {hold, st.hold, 1, 1, 0, 1}, {goal_step, st.goal_step, 1, 1, 0, 1}});
+    if (rc || !records) return rc;
+    // the mask: an entry counts when an episode of the running count, ended under this reward, wrote it -- the episodes were set behind the
+    // reward (every entry below count), or the episode ended on a tick of theirs not before the reward came in force
+    // (per robot: the episodes may cover fewer robots than this download -- the others' entries are zero)
+    const int Be = std::min(B, e.robots);
+    std::vector<int32_t> cnt((size_t)B, 0), ring(Be ? (size_t)Be * 4 * e.d.records : 0);
+    if (Be) {
+        rc = download_state(c, Be, nullptr, 0, {}, e.st_i, e.i_words(Bm), {{cnt.data(), e.count(Bm), 1, 1, 0, 1}, {ring.data(), e.ring(Bm), 4 * (size_t)e.d.records, 4 * (size_t)e.d.records, 0, 1}});
+        if (rc) return rc;
+    }
+    for (size_t b = 0; b < (size_t)B; ++b)
+        for (size_t k = 0; k < NR; ++k) {
+            bool ok = (int)b < Be && (int)k < e.d.records && (int)k < cnt[b];
+            if (ok && e.serial == w.ep_serial) {
+                const int32_t* rec = &ring[(b * e.d.records + k) * 4];
+                ok = rec[0] + rec[1] - 1 >= w.ep_tick0;      // (start_tick + length - 1: the episodes' tick it ended on)
+            }
+            if (!ok) records[(b * NR + k) * 2] = records[(b * NR + k) * 2 + 1] = 0.0;
+        }
     return IRLOSC_OK;
 }
 

@@ -144,6 +144,12 @@ int launch_object_loads(const ObjectLoadArgs& a, hipStream_t st);
 struct JointArgs;
 int launch_joints(const JointArgs& a, hipStream_t st);
 
+// tu_reward.hip -- the reward of a rollout tick whose slot has one (osc_reward.hpp): behind the give-up pass, directly in front of the
+// log's front launch; init mode: the launch of irlosc_set_reward; T = record type (of u, the targets and the wrench)
+struct RewardArgs;
+template <typename T>
+int launch_reward(const RewardArgs& a, hipStream_t st);
+
 // tu_log.hip -- the episode log of a logged rollout tick (osc_log.hpp): the front launch behind the give-up pass, the back launch (the
 // walls' and rows' planes) directly in front of the plant; T = record type (of u, the targets and the wrench)
 struct LogArgs;

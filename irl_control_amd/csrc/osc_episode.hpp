@@ -15,6 +15,9 @@
 //     and the FRESH STATE OF EVERY PART IN FORCE -- list, paths of the listed devices, a policy's plate (on the robot's origin), out and grip,
 //     walls, action objects (on their start poses count mod OV), their loads, joint rows -- each by the fresh function of the part's own header,
 //     which owns the state and its fresh values.  On a slot with mates the record's outcome carries IRLOSC_EPISODE_INSERTED when all of them are mated;
+//   with a REWARD in force (osc_reward.hpp; a.reward, uniform like a.walls) a lane whose episode ends writes (ret, gret) into the reward's own
+//     ring, entry count mod records beside its record, a reset makes the reward state fresh, and where the reward has a GOAL (a.goal) an
+//     episode is also finished by goal_step >= 0 -- whatever the program -- and one that ends with it carries IRLOSC_EPISODE_GOAL;
 //   idle lanes of a ragged last wave neither load nor store.
 // Every wave stores the number of its robots that are not parked into running[walk wave] (a plain store by lane 0): the early exit's input.
 //
@@ -33,6 +36,7 @@
 #include "osc_joint.hpp"
 #include "osc_object.hpp"
 #include "osc_object_load.hpp"
+#include "osc_reward.hpp"
 
 namespace irlosc {
 
@@ -57,7 +61,7 @@ struct EpisodeArgs {
     const void* gains;        // the context's gains, record type: [1 | max_batch][ndev][IRLOSC_GAIN_WORDS]
     PathState wp;             // PATHS (osc_waypoint.hpp)
     const double* wp_table;   // wp_per_robot: [walk wave][ndev][wmax][3][64], else [ndev][wmax][3]
-    // POLICY (osc_policy.hpp): never finished -- its episodes end by max_ticks alone; a reset puts the plate back to the robot's origin
+    // POLICY (osc_policy.hpp): never finished by itself -- its episodes end by max_ticks, or on a reward's goal; a reset puts the plate back to the robot's origin
     PlateState pl;
     const double* pl_origin;  // per robot: [walk wave][6][64]; nullptr: pl_origin0 for the fleet
     double pl_origin0[6];
@@ -71,6 +75,8 @@ struct EpisodeArgs {
     int32_t objects, nobj, ng, nm, OV;
     LoadState ld;             // the carried objects' weight (osc_object_load.hpp)
     int32_t loads, ld_pad;
+    RewardState rw;           // the reward (osc_reward.hpp): reward: one is in force; goal: it has a goal, which ends an episode like a finished program
+    int32_t reward, goal;
     int64_t vstride;
     int32_t wp_count[IRLOSC_MAX_DEV];
     uint8_t wp_loop[IRLOSC_MAX_DEV];
@@ -115,6 +121,8 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
                 }
             fin = some & all;
         }
+        const bool goal = a.goal && a.rw.goal_step[so] >= 0;      // (a.goal: uniform; this tick's reward kernel has judged the tick)
+        if (a.end_on_finish) fin = fin | goal;
         const int age = parked ? age0 : age0 + 1;   // a parked robot is never judged again
         const bool tmo = a.max_ticks > 0 && age == a.max_ticks;
         ends = !parked && (fin | tmo);
@@ -130,7 +138,13 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
                 for (int m = 0; m < a.nm; ++m) all = all & (a.ob.mated_tick[(size_t)m * a.stride + so] >= 0);
                 if (all) outcome |= IRLOSC_EPISODE_INSERTED;
             }
+            if (goal) outcome |= IRLOSC_EPISODE_GOAL;
             r[2 * (size_t)a.stride] = outcome;
+            if (a.reward) {                         // (ret, gret) of the episode, beside its record
+                double* __restrict__ rr = a.rw.ring + ((size_t)(cnt % a.records) * 2) * a.stride + so;
+                rr[0] = a.rw.ret[so];
+                rr[(size_t)a.stride] = a.rw.gret[so];
+            }
             r[3 * (size_t)a.stride] = (cnt % a.S) | ((a.V > 0 ? cnt % a.V : 0) << 16);
             cnt += 1;
             a.count[so] = cnt;
@@ -192,6 +206,7 @@ __global__ __launch_bounds__(64) void osc_episode_kernel(const EpisodeArgs a) {
             object_fresh(a.ob, a.ob_pose0 + (size_t)(cnt % a.OV) * a.ob_vstride + (size_t)blockIdx.x * a.nobj * 7 * 64 + lane, a.nobj, a.ng, a.nm, (size_t)a.stride, so);
         if (a.loads) load_fresh(a.ld, a.ng, (size_t)a.stride, so);
         if (a.joints) joint_fresh<NJ>(a.jt, a.R, a.stride, so);
+        if (a.reward) reward_fresh(a.rw, so);
     }
     // ---- targets: the whole row back from the snapshot, through the wave's tile; only a wave in which a lane reset touches it ----
     if (!a.init && __any(reset)) {                  // (one wave per block: uniform over the block)

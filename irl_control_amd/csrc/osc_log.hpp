@@ -8,7 +8,8 @@
 //       (as the OSC step read them: a list's or a stream's targets of the tick are in, the cycler's move is not), U (the give-up pass has
 //       run: every robot has its torques), FLAGS (the step's word; what the plant adds behind it is not in), OBJECT_POSE (the action
 //       objects as this tick's object kernel left them: seven pose words and the holder as a double, per object), POLICY_OUT and
-//       POLICY_SAMPLE (the out, act and logp planes of the policy's per-robot state as this tick's policy kernel left them).
+//       POLICY_SAMPLE (the out, act and logp planes of the policy's per-robot state as this tick's policy kernel left them), REWARD (r, ret,
+//       steps and goal_step >= 0 of the reward's per-robot state as this tick's reward kernel, the launch in front of this one, left them).
 //   BACK, behind the joint rows and directly in front of the plant: WALL_FORCE and JOINT_TAU, the `force` and `tau` planes of the walls'
 //       and rows' per-robot state as this tick's APPLY launches left them.  Launched only where one of the two is asked for.
 //
@@ -34,15 +35,15 @@
 
 namespace irlosc {
 
-constexpr int LOG_CHANNELS = 12;
+constexpr int LOG_CHANNELS = 13;
 constexpr uint32_t LOG_FRONT = IRLOSC_LOG_QPOS | IRLOSC_LOG_QVEL | IRLOSC_LOG_EE_POSE | IRLOSC_LOG_TARGETS | IRLOSC_LOG_WRENCH |
-                               IRLOSC_LOG_U | IRLOSC_LOG_FLAGS | IRLOSC_LOG_OBJECT_POSE | IRLOSC_LOG_POLICY_OUT | IRLOSC_LOG_POLICY_SAMPLE;
+                               IRLOSC_LOG_U | IRLOSC_LOG_FLAGS | IRLOSC_LOG_OBJECT_POSE | IRLOSC_LOG_POLICY_OUT | IRLOSC_LOG_POLICY_SAMPLE | IRLOSC_LOG_REWARD;
 constexpr uint32_t LOG_BACK = IRLOSC_LOG_WALL_FORCE | IRLOSC_LOG_JOINT_TAU;
 
 // Words per robot of channel bit i (nobj: the action objects of the slot; 0: it has none, and no OBJECT_POSE channel; n_out: the outputs
-// of its policy; 0: it has none, and neither POLICY channel)
+// of its policy; 0: it has none, and neither POLICY channel; bit 12, REWARD, is four words wherever a slot knows it)
 __host__ __device__ inline int log_width(int i, int n, int ndev, int nobj = 0, int n_out = 0) {
-    return i == 10 ? n_out : i == 11 ? n_out + 1 : i == 9 ? nobj * 8 : i == 0 || i == 1 || i == 5 || i == 8 ? n : i == 2 || i == 3 ? ndev * 7 : i == 4 ? ndev * 6 : i == 6 ? 1 : ndev * 3;
+    return i == 12 ? 4 : i == 10 ? n_out : i == 11 ? n_out + 1 : i == 9 ? nobj * 8 : i == 0 || i == 1 || i == 5 || i == 8 ? n : i == 2 || i == 3 ? ndev * 7 : i == 4 ? ndev * 6 : i == 6 ? 1 : ndev * 3;
 }
 
 struct LogArgs {
@@ -63,6 +64,10 @@ struct LogArgs {
     const float* po_out;              // [n_out][stride] the policy's output (with a Gaussian head: the mean) ...
     const float* po_act;              // [n_out][stride] ... the sampled action ...
     const double* po_logp;            // [stride] ... and its log-probability (osc_policy.hpp: PolicyState)
+    const double* rw_r;               // [stride] the reward's r, ret ...
+    const double* rw_ret;
+    const int32_t* rw_steps;          // [stride] ... steps and goal_step (osc_reward.hpp: RewardState)
+    const int32_t* rw_goal_step;
     uint32_t mask;                    // the channels of THIS launch
     int32_t R, n, ndev, n_entries, stride, nobj, n_out;
     int32_t ee0[IRLOSC_MAX_DEV];      // exchange entry of each device's EE pose (x y z qw qx qy qz follow each other)
@@ -161,6 +166,15 @@ __global__ __launch_bounds__(64) void osc_log_kernel(const LogArgs a) {
             s_t[lane * w + a.n_out] = a.po_logp[rb];
         }
         store_tile(11, w);
+    }
+    if (a.mask & IRLOSC_LOG_REWARD) {
+        if (valid) {
+            s_t[lane * 4] = a.rw_r[rb];
+            s_t[lane * 4 + 1] = a.rw_ret[rb];
+            s_t[lane * 4 + 2] = (double)a.rw_steps[rb];
+            s_t[lane * 4 + 3] = a.rw_goal_step[rb] >= 0 ? 1.0 : 0.0;
+        }
+        store_tile(12, 4);
     }
 }
 

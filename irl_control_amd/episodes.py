@@ -8,6 +8,19 @@ Conventions: S start states, V pose variants (0 counts as one: the list's own ta
 import numpy as np
 
 FINISHED, TIMEOUT = 1, 2      # _lib.EPISODE_FINISHED / EPISODE_TIMEOUT
+INSERTED, GOAL = 4, 8         # OR-ed into an outcome: every mate mated / the reward's goal reached (_lib.EPISODE_INSERTED / EPISODE_GOAL)
+
+
+def lengths_from_goal(goal_step, max_ticks, end_on_finish=True):
+    """(lengths, outcomes) of fresh episodes on a slot whose reward has a goal, from the reward's goal_step of a fresh rollout (steps
+    when the goal was reached, so 1-based; < 0: never, any shape): FINISHED | GOAL after goal_step ticks where that is within max_ticks,
+    else TIMEOUT after max_ticks.  Without end_on_finish the goal ends nothing: TIMEOUT after max_ticks, with GOAL where it was reached
+    by then.  max_ticks == 0: no timeout, length 0 = the episode never ends."""
+    g = np.asarray(goal_step, dtype=np.int64)
+    reached = (g >= 1) & ((g <= max_ticks) | (max_ticks == 0))
+    done = bool(end_on_finish) & reached
+    lengths = np.where(done, g, max_ticks)
+    return lengths, (np.where(done, FINISHED, TIMEOUT) | np.where(reached, GOAL, 0)).astype(np.int32)
 
 
 def lengths_from_finish(finish_tick, max_ticks, end_on_finish=True):

@@ -14,20 +14,27 @@ OBJECT_POSE_BIT = 1 << len(CHANNELS)
 # whose policy has a Gaussian head (sampled) know: [R, n_out] the network's output (the mean), [R, n_out + 1] the sampled action, then logp.
 POLICY_OUT, POLICY_SAMPLE = "policy_out", "policy_sample"
 POLICY_OUT_BIT, POLICY_SAMPLE_BIT = 1 << 10, 1 << 11
-_EXTRA = (OBJECT_POSE, POLICY_OUT, POLICY_SAMPLE)      # bits 9, 10, 11
+# ... and bit 12, IRLOSC_LOG_REWARD, which only a slot with a reward (rewarded below) knows: [R, 4] r, ret, steps, goal_step >= 0.
+REWARD = "reward"
+REWARD_BIT = 1 << 12
+_EXTRA = (OBJECT_POSE, POLICY_OUT, POLICY_SAMPLE, REWARD)      # bits 9, 10, 11, 12
 MAX_N, MAX_DEV, MAX_OBJECTS = 32, 4, 4
 
 
-def _channels(nobj: int, n_out: int = 0) -> tuple:
-    """The channel names by bit, up to the last one a slot with nobj action objects and a policy of n_out outputs can have."""
+def _channels(nobj: int, n_out: int = 0, rewarded: bool = False) -> tuple:
+    """The channel names by bit, up to the last one a slot with nobj action objects, a policy of n_out outputs and (rewarded) a reward can have."""
+    if rewarded:
+        return CHANNELS + _EXTRA
     if n_out:
         return CHANNELS + (OBJECT_POSE, POLICY_OUT, POLICY_SAMPLE)
     return CHANNELS + (OBJECT_POSE,) if nobj else CHANNELS
 
 
-def known(nobj: int = 0, n_out: int = 0, sampled: bool = False) -> int:
-    """The OR of the bits a slot with nobj action objects, a policy of n_out outputs (0: none) and, `sampled`, a Gaussian head knows."""
-    return ALL | (OBJECT_POSE_BIT if nobj else 0) | (POLICY_OUT_BIT if n_out else 0) | (POLICY_SAMPLE_BIT if n_out and sampled else 0)
+def known(nobj: int = 0, n_out: int = 0, sampled: bool = False, rewarded: bool = False) -> int:
+    """The OR of the bits a slot with nobj action objects, a policy of n_out outputs (0: none), `sampled`, a Gaussian head and, `rewarded`,
+    a reward knows."""
+    return (ALL | (OBJECT_POSE_BIT if nobj else 0) | (POLICY_OUT_BIT if n_out else 0) | (POLICY_SAMPLE_BIT if n_out and sampled else 0)
+            | (REWARD_BIT if rewarded else 0))
 
 
 def mask(channels) -> int:
@@ -55,6 +62,8 @@ def names(channels) -> tuple:
 
 def shape(name: str, n: int, ndev: int, nobj: int = 0, n_out: int = 0) -> tuple:
     """The per-robot shape of a channel: its plane is [R, *shape]."""
+    if name == REWARD:
+        return (4,)
     if name == OBJECT_POSE:
         return (nobj, 8)
     if name in (POLICY_OUT, POLICY_SAMPLE):
@@ -63,18 +72,19 @@ def shape(name: str, n: int, ndev: int, nobj: int = 0, n_out: int = 0) -> tuple:
             "wall_force": (ndev, 3), "joint_tau": (n,)}[name]
 
 
-def layout(n: int, ndev: int, channels, R: int, nobj: int = 0, n_out: int = 0, sampled: bool = False):
+def layout(n: int, ndev: int, channels, R: int, nobj: int = 0, n_out: int = 0, sampled: bool = False, rewarded: bool = False):
     """-> (offset[9] int64, sample_words) as irlosc_log_layout gives them: where each channel's plane [R][w] starts inside a sample, in
     doubles (-1: not asked for), and the sample's size.  With nobj > 0 (a slot with action objects): offset[10] as
     irlosc_log_layout_objects gives them, the tenth OBJECT_POSE's.  With n_out > 0 (a slot with a policy; `sampled`: with a Gaussian
-    head): offset[12] as irlosc_log_layout_policy gives them.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
+    head): offset[12] as irlosc_log_layout_policy gives them.  With `rewarded` (a slot with a reward): offset[13] as
+    irlosc_log_layout_reward gives them.  Raises ValueError where the library answers IRLOSC_ERR_ARG."""
     m = mask(channels)
     if not 0 <= nobj <= MAX_OBJECTS:
         raise ValueError(f"nobj={nobj} out of range")
     if n_out not in (0, 6, 7):
         raise ValueError(f"n_out={n_out} must be 0, 6 or 7")
-    chans = _channels(nobj, n_out)
-    if m == 0 or m & ~known(nobj, n_out, sampled):
+    chans = _channels(nobj, n_out, rewarded)
+    if m == 0 or m & ~known(nobj, n_out, sampled, rewarded):
         raise ValueError(f"channels=0x{m:x} must be a non-empty OR of the IRLOSC_LOG_* bits")
     if R < 1 or not 1 <= n <= MAX_N or not 1 <= ndev <= MAX_DEV:
         raise ValueError(f"R={R}, n={n}, ndev={ndev} out of range")
@@ -87,14 +97,15 @@ def layout(n: int, ndev: int, channels, R: int, nobj: int = 0, n_out: int = 0, s
     return off, words
 
 
-def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64, nobj: int = 0, n_out: int = 0, sampled: bool = False) -> dict:
+def split(buf, n: int, ndev: int, channels, R: int, dtype=np.float64, nobj: int = 0, n_out: int = 0, sampled: bool = False,
+          rewarded: bool = False) -> dict:
     """The raw log buffer [S, sample_words] (float64) as named arrays [S, R, ...].  u, targets and wrench come back in `dtype` (the
     context's: the cast undoes the exact widening), flags as uint32, policy_out as float32, everything else float64 (policy_sample: the
-    float32 action widened -- .astype(float32) undoes it -- and logp in its last column)."""
-    off, words = layout(n, ndev, channels, R, nobj, n_out, sampled)
+    float32 action widened -- .astype(float32) undoes it -- and logp in its last column; reward: r, ret, steps, goal as doubles)."""
+    off, words = layout(n, ndev, channels, R, nobj, n_out, sampled, rewarded)
     buf = np.asarray(buf, dtype=np.float64).reshape(-1, words)
     out = {}
-    for i, name in enumerate(_channels(nobj, n_out)):
+    for i, name in enumerate(_channels(nobj, n_out, rewarded)):
         if off[i] < 0:
             continue
         shp = shape(name, n, ndev, nobj, n_out)
